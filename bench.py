@@ -8,7 +8,12 @@ For N>1 every rank runs the same per-GPU workload on its own clips (weak
 scaling, clips are independent) and the output maps are exchanged with ONE RCCL
 all-gather per step.  Rank 0 prints one JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times exactly --steps steps (one window) and prints
+the headline.  --dump-outputs DIR also writes what the last timed step returned
+(maps, state) as DIR/<name>.npy.  --full adds the objects below (each can still be
+left out with its --no-* option) and times the headline over three windows.
+
+Extra objects on a --full line:
   roofline      dominant kernel (largest summed device time): algorithmic FLOP/s
                 (or bytes/s) per launch / average launch duration measured with
                 hipEvents on the launch stream, against the MI355X peak.
@@ -29,6 +34,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -175,6 +181,24 @@ def make_clips(C, T, H, W, seed=0):
         g.append(torch.from_numpy(synth.gauss_priors(T, h, w)))
         o.append(torch.from_numpy(synth.ob_priors(T, h, w, seed=seed + c)))
     return torch.stack(xs), [torch.stack(g), torch.stack(o)]
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000
+
+
+def dump_outputs(path, arrays):
+    """Write each output tensor as `path/<name>.npy` in float32.  When they exceed DUMP_BUDGET_BYTES together, each is
+    replaced by the same share of its elements, drawn with a fixed seed (flattened order, indices sorted), so that two
+    builds run with the same arguments still compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = a.size * DUMP_BUDGET_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(host)
 
 
 def kernel_rooflines(eng, prec, iters=5):
@@ -471,7 +495,8 @@ def main():
     ap.add_argument("--clips", type=int, default=0, help="clips per GPU; default 1 on one GPU (BASELINE configs[1]) "
                     "and 8 per GPU when --gpus > 1 (configs[3]: 8 clips/GPU); pass --clips 8 --gpus 1 for the "
                     "matching single-GPU point of a scaling curve")
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each; the median is reported")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps steps each; the median is reported "
+                    "(default 1, with --full 3)")
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--height", type=int, default=360)
     ap.add_argument("--width", type=int, default=640)
@@ -498,7 +523,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: per-kernel "
+                    "rooflines, the CPU oracle baseline and parity, the scaling reference, the reference's shapes and the extras "
+                    "(--no-roofline / --no-cpu-baseline / --no-extra leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the maps and the state the last timed step "
+                    "returned as DIR/<name>.npy (float32; a fixed, seeded sample when they exceed 60 MB together)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_extra = True
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -585,6 +619,10 @@ def main():
     dt = sorted(wins)[len(wins) // 2]
     log("timed region done: %.3f ms/step (windows: %s)" % (dt / args.steps * 1e3,
                                                            ", ".join("%.3f" % (w / args.steps * 1e3) for w in wins)))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the maps (all ranks' after the gather) and the state
+        names = dump_outputs(args.dump_outputs, {"maps": gathered if distributed else last["out"], "state": last["state"]})
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, ", ".join(names)))
     frames = C * T * world * args.steps
     fps = frames / dt
     result = {
@@ -603,7 +641,7 @@ def main():
     }
 
     result["ranks_seen"] = dist.get_world_size() if distributed else 1
-    if pipe is not None:
+    if pipe is not None and args.full:
         pipe.synchronize()
         so, ss = model.forward_clips(x, cb, state)
         result["bit_identical_to_one_at_a_time"] = bool(torch.equal(last["out"], so) and torch.equal(last["state"], ss))

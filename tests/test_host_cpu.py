@@ -518,17 +518,15 @@ def test_reference_style_whole_model_pickle_loads_through_the_shim(tmp_path):
 
 
 def test_mat_reader_and_priors(golden_dir):
-    """The minimal HDF5 reader against the reference's own prior files (when present) and the
+    """The minimal HDF5 reader against the reference's own prior files (copies under tests/golden/) and the
     converted fixtures; the closed-form gaussian priors equal the shipped gauss_priors.mat exactly."""
     from iip_uavsal_saliency_amd import matio, priors
     g_fix = np.load(os.path.join(golden_dir, "gauss_priors.npz"))["PriorMaps"]
     closed = synth.gauss_priors(1, 45, 80)[0].transpose(1, 2, 0)
     assert g_fix.shape == (45, 80, 8) and np.array_equal(closed, g_fix)
-    ref_dir = "/root/reference"
-    if os.path.isdir(ref_dir):
-        for name in ("gauss_priors", "UAV2_ob_priors_train", "AVS1K_ob_priors_train"):
-            a = matio.loadmat(os.path.join(ref_dir, name + ".mat"))["PriorMaps"]
-            assert np.array_equal(a, np.load(os.path.join(golden_dir, name + ".npz"))["PriorMaps"])
+    for name in ("gauss_priors", "UAV2_ob_priors_train", "AVS1K_ob_priors_train"):
+        a = matio.loadmat(os.path.join(golden_dir, name + ".mat"))["PriorMaps"]
+        assert np.array_equal(a, np.load(os.path.join(golden_dir, name + ".npz"))["PriorMaps"])
     cb = priors.get_bias([1, 1, 1], 3, 45, 80, ob_prior_path=os.path.join(golden_dir, "UAV2_ob_priors_train.npz"),
                          device="cpu")
     assert tuple(cb[0].shape) == (3, 8, 45, 80) and tuple(cb[1].shape) == (3, 20, 45, 80)
@@ -685,6 +683,27 @@ def test_bench_gpus_2_on_a_box_without_two_gpus_exits_nonzero():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr and r.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_float32_and_a_seeded_sample_above_the_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every output as DIR/<name>.npy in float32, whole while they fit the budget; above it the
+    same seeded sample on every run (two builds compare element for element) and the files together within the budget."""
+    bench = _bench_module()
+    maps = torch.arange(24, dtype=torch.float16).view(2, 3, 1, 2, 2)
+    state = torch.arange(1000, dtype=torch.float32).view(10, 100)
+    assert bench.dump_outputs(str(tmp_path / "whole"), {"maps": maps, "state": state}) == ["maps", "state"]
+    got = {k: np.load(str(tmp_path / "whole" / (k + ".npy"))) for k in ("maps", "state")}
+    assert got["maps"].dtype == np.float32 and np.array_equal(got["maps"], maps.float().numpy())
+    assert got["state"].dtype == np.float32 and np.array_equal(got["state"], state.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 400)
+    runs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"maps": maps, "state": state})
+        runs.append({k: np.load(str(tmp_path / d / (k + ".npy"))) for k in ("maps", "state")})
+    s = runs[0]["state"]
+    assert s.dtype == np.float32 and 0 < s.size < state.numel() and np.all(np.diff(s) > 0) and np.isin(s, state.numpy()).all()
+    assert sum(a.nbytes for a in runs[0].values()) <= 400
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
 
 
 def test_committed_bench_line_carries_the_contract_fields():

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r5final
 if [ -z "$ONLY_BENCH" ] && [ -z "$ONLY_SET" ]; then rm -rf $O; fi      # ONLY_BENCH=1: just the bench lines again (bench.py changed, kernels did not)
 mkdir -p $O
-B="--no-cpu-baseline --no-extra --no-roofline"
+B="--full --no-cpu-baseline --no-extra --no-roofline"
 run_set() {   # $1 = prec, $2 = clips, $3 = label, $4 = file tag (bench.py _wl_tag), $5 = 1: also the SQ-counter passes, $6... = extra bench arguments
   local P=$1 C=$2 L="$3" T=$4 SQ=$5; shift 5
   cd /tmp && export TMPDIR=/tmp
@@ -44,10 +44,10 @@ want f16x3_c8 && run_set f16x3 8 "bench.py --prec f16x3 --clips 8 (configs[2]: 3
 want f32_c4_720x1280_t16 && run_set f32 4 "bench.py --height 720 --width 1280 --frames 16 --clips 4 --persistent-state 1 (configs[4])" f32_c4_720x1280_t16 0 --height 720 --width 1280 --frames 16 --persistent-state 1 --steps 5 --warmup 2
 fi
 cd $R
-want f32_c1 && python3 bench.py > $O/r5_bench_default.json 2> $O/r5_bench_default.err
-want f32_c1 && python3 bench.py --inflight 2 --no-extra > $O/r5_bench_inflight2.json 2> $O/r5_bench_inflight2.err
-want f32_c8 && python3 bench.py --clips 8 --no-extra --no-cpu-baseline > $O/r5_bench_f32_c8.json 2> $O/r5_bench_f32_c8.err
-want f16x3_c8 && python3 bench.py --prec f16x3 --clips 8 --no-extra --no-cpu-baseline > $O/r5_bench_f16x3_c8.json 2> $O/r5_bench_f16x3_c8.err
-want f16x3_c8 && python3 bench.py --prec f16x3 --no-extra --no-cpu-baseline > $O/r5_bench_f16x3_c1.json 2> $O/r5_bench_f16x3_c1.err
-want f32_c4_720x1280_t16 && python3 bench.py --height 720 --width 1280 --frames 16 --clips 4 --persistent-state 1 --steps 5 --warmup 2 --no-extra --no-cpu-baseline > $O/r5_bench_720p_c4_t16.json 2> $O/r5_bench_720p_c4_t16.err
+want f32_c1 && python3 bench.py --full > $O/r5_bench_default.json 2> $O/r5_bench_default.err
+want f32_c1 && python3 bench.py --full --inflight 2 --no-extra > $O/r5_bench_inflight2.json 2> $O/r5_bench_inflight2.err
+want f32_c8 && python3 bench.py --full --clips 8 --no-extra --no-cpu-baseline > $O/r5_bench_f32_c8.json 2> $O/r5_bench_f32_c8.err
+want f16x3_c8 && python3 bench.py --full --prec f16x3 --clips 8 --no-extra --no-cpu-baseline > $O/r5_bench_f16x3_c8.json 2> $O/r5_bench_f16x3_c8.err
+want f16x3_c8 && python3 bench.py --full --prec f16x3 --no-extra --no-cpu-baseline > $O/r5_bench_f16x3_c1.json 2> $O/r5_bench_f16x3_c1.err
+want f32_c4_720x1280_t16 && python3 bench.py --full --height 720 --width 1280 --frames 16 --clips 4 --persistent-state 1 --steps 5 --warmup 2 --no-extra --no-cpu-baseline > $O/r5_bench_720p_c4_t16.json 2> $O/r5_bench_720p_c4_t16.err
 ls $O
