@@ -89,6 +89,69 @@ DW_DOT = os.environ.get("UAVSAL_DW_DOT", "1") == "1"       # 0: the one-channel 
 _TILE_OVERRIDE = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in os.environ.get("UAVSAL_TILE_OVERRIDE", "").split(",") if "=" in kv}
 
 
+class OpView:
+    """What one operand of a recorded op addresses: images [0, n) of `h x w` pixels, channels [0, c) of rows `ld` floats apart,
+    starting `off` floats into `buf`; image i starts `img` pixels after image i - 1.  `buf` is the tensor, the arena buffer
+    (_ArenaRef), or the name of a caller tensor that `run` binds into the plan ("x", "out", "state_in", ...; Engine.bound).
+    `sp` / `sp_off`: the split shadow (fp16, `[pixel][ld/32][hi 32 | lo 32]`) and the view's first half in it, or None.
+    `nchw`: the operand is a caller-side NCHW tensor ([n, c, h*w] at `off`; `ld` and `img` unused)."""
+    __slots__ = ("buf", "off", "n", "h", "w", "c", "ld", "img", "sp", "sp_off", "nchw")
+
+    def __init__(self, buf, off, n, h, w, c, ld, img, sp=None, sp_off=0, nchw=False):
+        self.buf, self.off, self.n, self.h, self.w, self.c, self.ld, self.img = buf, off, n, h, w, c, ld, img
+        self.sp, self.sp_off, self.nchw = sp, sp_off, nchw
+
+    @staticmethod
+    def of(v: "V", img=None, binds=None) -> "OpView":
+        buf = v.t
+        if binds is not None and isinstance(buf, torch.Tensor) and id(buf) in binds:
+            buf = binds[id(buf)]
+        sp, sp_off = None, 0
+        if v.sp is not None and not isinstance(v.sp, _Fake):
+            pix, ch = divmod(v.coff, v.ld)
+            sp, sp_off = v.sp, pix * 2 * v.ld + (ch // 32) * 64
+        return OpView(buf, v.coff, v.n, v.h, v.w, v.c, v.ld, v.h * v.w if img is None else img, sp, sp_off)
+
+    def __repr__(self):
+        return "OpView(%s+%d, n=%d, %dx%d, c=%d, ld=%d, img=%d%s)" % (
+            getattr(self.buf, "aid", self.buf if isinstance(self.buf, str) else "tensor"), self.off, self.n, self.h, self.w,
+            self.c, self.ld, self.img, ", shadow" if self.sp is not None else "")
+
+
+def read_view(eng, d: OpView, shadow=False, images=None, device=None) -> torch.Tensor:
+    """Operand `d` of `eng`'s plan as float64 NCHW `[n, c, h, w]` (images `images` only, when given), read from the fp32
+    buffer or -- `shadow` -- merged from its split shadow (ops.merge_shadow's arithmetic).  `eng` may be None for views whose
+    `buf` is a tensor.  A copy: later launches do not change it."""
+    if shadow:
+        if d.sp is None:
+            raise ValueError("%r has no split shadow" % (d,))
+        sp = d.sp.reshape(-1)
+        t = sp.as_strided((d.n, d.h, d.w, d.c // 32, 2, 32), (d.img * 2 * d.ld, d.w * 2 * d.ld, 2 * d.ld, 64, 32, 1),
+                          sp.storage_offset() + d.sp_off)
+        if images is not None:
+            t = t[list(images)]
+        t = t.double()
+        t = ((t[..., 0, :] + t[..., 1, :]) / 16.0).reshape(t.shape[0], d.h, d.w, d.c)
+    else:
+        buf = d.buf
+        if isinstance(buf, str):
+            buf = eng.bound(buf)
+        elif isinstance(buf, _ArenaRef):
+            buf = buf.tensor()
+        if buf is None:
+            raise ValueError("%r has no fp32 buffer (shadow only)" % (d,))
+        flat = buf.reshape(-1)
+        if d.nchw:
+            t = flat.as_strided((d.n, d.c, d.h, d.w), (d.c * d.h * d.w, d.h * d.w, d.w, 1), flat.storage_offset() + d.off)
+            t = t if images is None else t[list(images)]
+            return t.to(device=device, dtype=torch.float64)
+        t = flat.as_strided((d.n, d.h, d.w, d.c), (d.img * d.ld, d.w * d.ld, d.ld, 1), flat.storage_offset() + d.off)
+        if images is not None:
+            t = t[list(images)]
+        t = t.double() if t.dtype != torch.uint8 else t
+    return t.permute(0, 3, 1, 2).to(device=device, dtype=torch.float64).contiguous()
+
+
 def _dwproj_patch_waste(h, w):
     return ((h + 7) // 8 * 8) * ((w + 15) // 16 * 16) / float(h * w)
 
@@ -257,6 +320,11 @@ class Engine:
         self._split_want = set()
         self._no_shadow = set()
         self.ops_meta: List[dict] = []
+        # op_args[i]: what op i of the native plan reads and writes (kind, torch modules, epilogue, OpView operands), filled by
+        # the recorders in the recording pass -- Python references only (tests/test_plan_ops_fp64.py checks every launch with it)
+        self.op_args: List[dict] = []
+        self._binds: Dict[int, str] = {}
+        self._bound_t: Dict[str, torch.Tensor] = {}
         self._op_idx: Dict[str, int] = {}
         # launch-loop mode reads the caller's tensors in place and writes straight into fresh outputs
         # (uavsal_plan_patch_ptr); a captured graph replays fixed addresses and keeps the staging copies
@@ -310,7 +378,7 @@ class Engine:
         self._dry = False
         self._lop, self._scr_serial, self._lane_open, self._lane_refs = -1, 0, {}, {}
         self._poison_done = set()
-        self.ops_meta, self.stage_ranges, self.named, self._op_idx = [], {}, {}, {}
+        self.ops_meta, self.stage_ranges, self.named, self._op_idx, self.op_args = [], {}, {}, {}, []
         self.plan = C.c_void_p(self.lib.uavsal_plan_create())
         if not self.plan:
             raise RuntimeError("uavsal_plan_create failed")
@@ -450,6 +518,7 @@ class Engine:
                 cur = lane
             self._op_idx["poison:%s" % (r.aid,)] = len(self.ops_meta)
             self.ops_meta.append(dict(kind="poison", name="poison:%s" % (r.aid,), flops=0.0, bytes=4.0 * r.numel_, lane=lane))
+            self.op_args.append(dict(kind="poison", name="poison:%s" % (r.aid,)))
             d = L.FillDesc()
             d.out, d.n, d.bits = self._arena.data_ptr() + 4 * r.off, r.numel_, 0x7FC00000
             self._add(self.lib.uavsal_plan_add_fill, d, "plan_add_fill")
@@ -581,6 +650,17 @@ class Engine:
         self._lop += 1
         self._op_idx[kw.get("name")] = len(self.ops_meta)       # == index of the op in the native plan
         self.ops_meta.append(kw)
+        self.op_args.append(dict(kind=kw.get("kind"), name=kw.get("name")))
+
+    def _ov(self, v, img=None):
+        return None if v is None else OpView.of(v, img, self._binds)
+
+    def bound(self, name) -> torch.Tensor:
+        """The caller-side tensor an OpView names ("x", "cb0", "cb1", "out", "state_in", "state_out", "cstate_in",
+        "cstate_out"): what `run` bound into the plan last (launch loop), or the staging tensor (graph)."""
+        if self.inplace:
+            return self._bound_t[name]
+        return getattr(self, {"x": "x_in", "cb0": "cb0_in", "cb1": "cb1_in"}.get(name, name))
 
     def _patch(self, name, slot, ptr):
         L.check(self.lib.uavsal_plan_patch_ptr(self.plan, self._op_idx[name], slot, ptr), "plan_patch_ptr(%s)" % name)
@@ -601,6 +681,7 @@ class Engine:
         cout = out.c if cout is None else cout
         n_img = a.n if n_img is None else n_img
         hin, win = a.h, a.w
+        a_in = a
         if dw is not None:
             a = V(a.t, a.n, (hin - 1) // dw[2] + 1, (win - 1) // dw[2] + 1, a.c, a.ld, a.coff)
         hw = a.h * a.w
@@ -697,6 +778,18 @@ class Engine:
         self.ops_meta[-1]["tile"] = tile
         self.ops_meta[-1]["streamk"] = int(self.lib.uavsal_conv_streamk_grid(C.byref(d)))
         self.ops_meta[-1]["dwproj"] = dwproj
+        groups = cout // n_group if n_group else 1
+        ad = self._ov(V(a_in.t, n_img, hin, win, cin + (groups - 1) * cin, a_in.ld, a_in.coff, a_in.sp, a_in.key),
+                      d.a_img_stride)
+        if not split:
+            ad.sp = None
+        od = self._ov(out, d.o_img_stride)
+        if not d.out_split:
+            od.sp = None
+        self.op_args[-1].update(conv=conv, bn=bn, act=act, epi=epi, taps=taps, wslice=wslice, gate_interleave=gate_interleave,
+                                n_group=n_group, dw=dw, prec=pn, split_in=split, cin=cin, cout=cout, a=ad, out=od,
+                                res=self._ov(res, d.r_img_stride), aux=self._ov(aux, d.x_img_stride),
+                                out2=self._ov(out2, d.o_img_stride))
         self._add(self.lib.uavsal_plan_add_conv, d, "plan_add_conv(%s)" % name)
 
     def conv3_wino(self, name, a: V, conv, bn, out: V, act, wslice=None, n_img=None, strides=None, twa=None, gemm_tile=0, r=2,
@@ -717,6 +810,7 @@ class Engine:
         mm = self._scr("WM", pp, mp, 1, cout)
         in_bytes = 4.0 * (sum(sg.n * sg.h * sg.w * sg.c for sg in segs) if segs else n * hw * cin)
         self._meta(kind="wino_in", name=name + ".xin", flops=0.0, bytes=in_bytes + 4.0 * float(pp) * tiles * cin)
+        self.op_args[-1].update(triple=name + ".xout")
         self._touch(a, v, *(segs or ()))
         if not self._dry:
             wi = L.WinoDesc()
@@ -747,6 +841,7 @@ class Engine:
                        bytes=4.0 * pn * (tiles * (cin + cout) + cin * cout), M=pn * mp, K=cin, Nc=cout,
                        direct_flops=2.0 * n * hw * cin * cout * 9 * pn / pp)
             self._touch(v, mm)
+            self.op_args[-1].update(triple=name + ".xout")
             if self._dry:
                 continue
             d = L.ConvDesc()
@@ -779,6 +874,11 @@ class Engine:
                 wo.res, wo.ldr, wo.res_img_stride = xt.ptr, xt.ld, st.get("r", hw)
                 wo.aux, wo.ldx, wo.aux_img_stride = pre.ptr, pre.ld, st.get("x", hw)
                 wo.hprev, wo.ldh, wo.h_img_stride = a.ptr, a.ld, st.get("a", hw)
+            ai = st.get("a", hw)
+            self.op_args[-1].update(kind="wino", triple_first=name + ".xin", conv=conv, bn=bn, act=act, wslice=wslice, r=r, cin=cin,
+                                    cout=cout, a=None if segs else self._ov(a, ai), segs=[self._ov(sg) for sg in segs] if segs else None,
+                                    out=self._ov(out, wo.out_img_stride),
+                                    twa=None if twa is None else (self._ov(twa[0], wo.res_img_stride), self._ov(twa[1], wo.aux_img_stride)))
             self._add(self.lib.uavsal_plan_add_wino_output, wo, "plan_add_wino_output(%s)" % name)
 
     def dw(self, name, a: V, conv, bn, out: V, stride, dilation):
@@ -818,6 +918,8 @@ class Engine:
         d.n_img, d.H, d.W, d.C = a.n, a.h, a.w, c
         d.stride, d.dilation, d.act = stride, dilation, L.ACT_RELU6
         self.ops_meta[-1]["kernel"] = L.DW_KERNEL.get(int(self.lib.uavsal_dw_variant(C.byref(d))), "dw3x3")
+        self.op_args[-1].update(conv=conv, bn=bn, stride=stride, dilation=(tuple(d.dil_groups[:len(conv)]) if grouped else dilation),
+                                a=self._ov(a), out=self._ov(out))
         self._add(self.lib.uavsal_plan_add_dw, d, "plan_add_dw(%s)" % name)
 
     def dw_dot(self, name, a: V, dwc, dwbn, pl, plbn, out: V, act):
@@ -841,6 +943,7 @@ class Engine:
         d.w9c, d.scale, d.bias, d.w2, d.scale2, d.bias2 = (t.data_ptr() for t in (w9, s, b, w2, s2, b2))
         d.out, d.ldo = out.ptr, out.ld
         d.n_img, d.H, d.W, d.C, d.act = a.n, a.h, a.w, c, act
+        self.op_args[-1].update(dw=(dwc, dwbn), conv=pl, bn=plbn, act=act, a=self._ov(a), out=self._ov(out))
         self._add(self.lib.uavsal_plan_add_dw_dot, d, "plan_add_dw_dot(%s)" % name)
 
     def bilinear(self, name, a: V, out: V, src_mod=None, src_div=1):
@@ -855,11 +958,12 @@ class Engine:
         if out.sp is not None:
             d.out_split, d.ldos = out.sp_ptr, 2 * out.ld
         d.src_mod, d.src_div = (out.n if src_mod is None else src_mod), src_div
+        self.op_args[-1].update(a=self._ov(a), out=self._ov(out), src_mod=d.src_mod, src_div=src_div)
         self._add(self.lib.uavsal_plan_add_bilinear, d, "plan_add_bilinear(%s)" % name)
 
-    def layout(self, name, src, dst, n, c, hw, ld, to_nhwc, cpad=0):
+    def layout(self, name, src, dst, n, c, hw, ld, to_nhwc, cpad=0, bind=None):
         """`src` / `dst`: a view (its address is taken once the op is open, so that the arena sees the use at this op) or a raw
-        device address (the caller's boundary tensors)."""
+        device address (the caller's boundary tensors; `bind` = (name, float offset) of that tensor, see Engine.bound)."""
         self._meta(kind="layout", name=name, flops=0.0, bytes=8.0 * n * c * hw)
         self._touch(*(t for t in (src, dst) if isinstance(t, V)))
         if self._dry:
@@ -867,6 +971,9 @@ class Engine:
         d = L.LayoutDesc()
         src_ptr, dst_ptr = (t.ptr if isinstance(t, V) else t for t in (src, dst))
         d.inp, d.out, d.n_img, d.C, d.HW, d.ld, d.to_nhwc, d.Cpad = src_ptr, dst_ptr, n, c, hw, ld, to_nhwc, cpad
+        nhwc = self._ov(dst if to_nhwc else src)
+        nchw = OpView(bind[0], bind[1], n, nhwc.h, nhwc.w, c, c, hw, nchw=True) if bind is not None else None
+        self.op_args[-1].update(to_nhwc=to_nhwc, cpad=cpad, a=nchw if to_nhwc else nhwc, out=nhwc if to_nhwc else nchw)
         self._add(self.lib.uavsal_plan_add_layout, d, "plan_add_layout(%s)" % name)
 
     def fused_block(self, name, x: V, blk, out: V) -> bool:
@@ -933,6 +1040,7 @@ class Engine:
             d.res, d.ldr = x.ptr, x.ld
         d.out, d.ldo = out.ptr, out.ld
         d.n_img, d.H, d.W = x.n, x.h, x.w
+        self.op_args[-1].update(blk=blk, a=self._ov(x), out=self._ov(out), res=self._ov(x) if blk.use_res_connect else None)
         self._add(self.lib.uavsal_plan_add_fused_ir, d, "plan_add_fused_ir(%s)" % name)
         return True
 
@@ -1022,6 +1130,7 @@ class Engine:
             self.cstate_out = torch.empty((self.n_seq, 256, h, w), dtype=torch.float32, device=dev)
             self.out = torch.empty((N, hw), dtype=torch.float32, device=dev)
             self.logits = torch.empty((N, hw), dtype=torch.float32, device=dev) if self.keep_taps else None
+            self._binds = {id(self.out): "out"}
         feats = m.sfnet.features.features
 
         # ---- boundary: state and priors NCHW -> NHWC
@@ -1047,7 +1156,7 @@ class Engine:
         if not self.persistent:          # persistent mode: h0 / c0 ARE the state, staged only on demand (run())
             names = ["state.in"] + (["cstate.in"] if lstm_model else [])
             for nm, src, dst in zip(names, ("state_in", "cstate_in"), (h0, c0)):
-                self.layout(nm, None if self._dry else getattr(self, src).data_ptr(), dst, self.n_seq, 256, hw, 256, 1)
+                self.layout(nm, None if self._dry else getattr(self, src).data_ptr(), dst, self.n_seq, 256, hw, 256, 1, bind=(src, 0))
         self._mark("boundary_in", s0)
 
         # ---- backbone: MobileNetV2 features[0:18] (model_feature.py:62-69)
@@ -1074,6 +1183,9 @@ class Engine:
             d.n_img, d.H, d.W = N, self.H, self.W
             for i in range(3):
                 d.mean[i], d.stdv[i] = synth.IMAGENET_MEAN[i], synth.IMAGENET_STD[i]
+            self.op_args[-1].update(conv=conv0, bn=bn0, u8=self.in_dtype == torch.uint8, mean=tuple(synth.IMAGENET_MEAN),
+                                    stdv=tuple(synth.IMAGENET_STD), a=OpView("x", 0, N, self.H, self.W, 3, 3, 0, nchw=True),
+                                    out=self._ov(x))
             self._add(self.lib.uavsal_plan_add_stem, d, "plan_add_stem")
         tapsrc = {}
         cb = None
@@ -1110,7 +1222,8 @@ class Engine:
                     else:
                         L.check(self.lib.uavsal_plan_set_lane(self.plan, lane), "plan_set_lane") if not self._dry else None
                         self._lane = lane
-                    self.layout(nm + ".in", None if self._dry else getattr(self, src).data_ptr(), dst, Np, c, hw, c, 1)
+                    self.layout(nm + ".in", None if self._dry else getattr(self, src).data_ptr(), dst, Np, c, hw, c, 1,
+                                bind=(src[:3], 0))
                     self.ir_block(nm + ".0", dst, blocks[0], mid)
                     self.ir_block(nm + ".1", mid, blocks[1], cbs.slice(sl, 64))
                     if self.static_priors:      # frame 0 of the net's output -> every frame (same-size resize: an exact copy)
@@ -1256,6 +1369,7 @@ class Engine:
                 d = L.TdiffDesc()
                 d.inp, d.ldi, d.out, d.ldo = r.ptr, 32, dif.ptr, 64
                 d.n_img, d.HW, d.C, d.seq_len = N, hw, 32, self.seq_len
+                self.op_args[-1].update(a=self._ov(r), out=self._ov(dif), seq_len=self.seq_len)
                 self._add(self.lib.uavsal_plan_add_tdiff, d, "plan_add_tdiff")
             if st_lanes == 2:
                 self.fork(6)
@@ -1290,6 +1404,7 @@ class Engine:
                     d = L.TsumDesc()
                     d.inp, d.ldi, d.out, d.ldo = xs.ptr, 320, tsum.ptr, 256
                     d.n_groups, d.T, d.HW, d.C = B, self.ctx_T, hw, 256
+                    self.op_args[-1].update(a=self._ov(xs), out=self._ov(tsum), T=self.ctx_T)
                     self._add(self.lib.uavsal_plan_add_tsum, d, "plan_add_tsum")
                 h2, w2 = _down(h), _down(w)
                 cx1 = self._buf("ctx1", B, h2, w2, 64)
@@ -1343,7 +1458,9 @@ class Engine:
             strides = {"a": hw if t == 0 else Lq * hw, "o": Lq * hw, "r": Lq * hw, "x": Lq * hw}
             # (split-fp16 plans from four clips up: the per-step gate convolution in exact fp32 through Winograd F(4x4) as well -- 1.78x
             # fewer MFMA FLOPs than the direct 3x3 and it beats the split-fp16 implicit GEMM there: 136 vs 160 us per step at eight
-            # clips, 17.89 -> 17.67 ms per eight-clip step; more accurate, never less.  F16X3_WINO_STEPS = 0: the direct split-fp16 step)
+            # clips, 17.89 -> 17.67 ms per eight-clip step.  Not more accurate: per launch at eight clips (tests/test_plan_ops_fp64.py,
+            # teacher-forced against float64) its worst error is 2.0e-6 against 1.0e-6 for the direct split-fp16 step, both well inside
+            # their bounds.  F16X3_WINO_STEPS = 0: the direct split-fp16 step)
             f16_wino = (F16X3_WINO_STEPS and self.prec_name == "f16x3" and not self.prec_overrides and self.n_seq >= 4
                         and bool(getattr(m, "winograd", True)))
             if (self.winograd or f16_wino) and self.winograd_steps and (f16_wino or self._prec_for("twa.step") == "f32"):
@@ -1377,13 +1494,15 @@ class Engine:
                     d = L.CopyDesc()
                     d.inp, d.out = hist.frames(Lq - 1, 1).ptr, keep.ptr
                     d.in_pitch, d.out_pitch, d.row_floats, d.rows = Lq * hw * 256, hw * 256, hw * 256, self.n_seq
+                    self.op_args[-1].update(a=self._ov(hist.frames(Lq - 1, self.n_seq), Lq * hw), out=self._ov(keep))
                     self._add(self.lib.uavsal_plan_add_copy, d, "plan_add_copy")
         else:
             for c in range(self.n_seq):
                 for hist, dst, _ in outs:
                     last = hist.frames(c * Lq + Lq - 1, 1)
                     nm = "%s%d" % (dst.replace("_", "."), c)           # state.out0, cstate.out0, ...
-                    self.layout(nm, last, None if self._dry else getattr(self, dst).data_ptr() + 4 * c * 256 * hw, 1, 256, hw, 256, 0)
+                    self.layout(nm, last, None if self._dry else getattr(self, dst).data_ptr() + 4 * c * 256 * hw, 1, 256, hw, 256, 0,
+                                bind=(dst, c * 256 * hw))
         # error guard: poisons what the caller will see if any kernel of this run set the error word
         self._meta(kind="guard", name="guard", flops=0.0, bytes=0.0)
         if self.persistent:
@@ -1461,6 +1580,7 @@ class Engine:
         dev = self.device
         x = x.reshape(self.x_in.shape).contiguous()
         hold = [x]
+        bound = {"x": x}
         self._patch("features.0", 1 if self.in_dtype == torch.uint8 else 0, x.data_ptr())
         for t, stage, op, on in ((cb0, self.cb0_in, "gauss.in", self.use_priors[0]), (cb1, self.cb1_in, "ob.in", self.use_priors[1])):
             if not on:                  # a prior this model does not have is never read (reference model.py:347-353)
@@ -1470,11 +1590,13 @@ class Engine:
             t = t.reshape(stage.shape).contiguous()
             self._patch(op, 0, t.data_ptr())
             hold.append(t)
+            bound[op[:-3].replace("gauss", "cb0").replace("ob", "cb1")] = t
         out = torch.empty((self.N, self.h * self.w), dtype=torch.float32, device=dev)
         # (the decoder's last launch: ".dwpl" when its depthwise runs inside the projection)
         self._patch("conv_out_st.pl" if "conv_out_st.pl" in self._op_idx else "conv_out_st.dwpl", 1, out.data_ptr())
         self._patch("guard", 0, out.data_ptr())
         hold.append(out)
+        bound["out"] = out
         st = None
         if self.persistent:
             self._stage_state_persistent(state, cstate)
@@ -1491,9 +1613,11 @@ class Engine:
                     self._patch("%s.out%d" % (nm, c), 1, o.data_ptr() + c * per)
                 self._patch("guard", gslot, o.data_ptr())
                 hold += [t, o]
+                bound[nm + "_in"], bound[nm + "_out"] = t, o
                 outs.append(o)
             st = (outs[0], outs[1]) if lstm else outs[0]
         self._hold = hold
+        self._bound_t = bound
         self._bound = True
         return out, st
 
