@@ -132,8 +132,20 @@ class WinoDesc(C.Structure):
                 ("seg_H", C.c_int32 * 3), ("seg_W", C.c_int32 * 3)]
 
 
+SCORE_NSTAT, SCORE_REPS, SCORE_RUN, SCORE_NKEY = 16, 100, 4096, 7
+
+
+class ScoreDesc(C.Structure):
+    _fields_ = [("sal", _f), ("fix_loc", _f), ("fix_map", _f), ("jitter", _f),
+                ("sal_u8", C.c_int32), ("loc_u8", C.c_int32), ("n_frames", C.c_int32), ("n_pix", C.c_int32),
+                ("stats", _f), ("fix_off", _f), ("run_off", _f), ("total_fix", C.c_int64), ("total_runs", C.c_int32),
+                ("nan_rows", C.c_int32), ("samp", _f * 2), ("samp_off", _f * 2), ("n_samp", C.c_int64 * 2),
+                ("ws", _f), ("ws_bytes", C.c_int64),
+                ("out", _f), ("n_keys", C.c_int32), ("keys", C.c_int32 * SCORE_NKEY)]
+
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
-              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc]
+              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc]
 
 # every symbol include/uavsal_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -187,6 +199,9 @@ SYMBOLS = [
     ("uavsal_plan_graph_build", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_graph_launch", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_time", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    ("uavsal_score_workspace_bytes", C.c_int64, [C.POINTER(ScoreDesc)]),
+    ("uavsal_score_stats", C.c_int, [C.POINTER(ScoreDesc), C.c_void_p]),
+    ("uavsal_score_run", C.c_int, [C.POINTER(ScoreDesc), C.c_void_p]),
     ("uavsal_abi_version", C.c_int, []),
     ("uavsal_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_build_info", C.c_char_p, []),

@@ -217,3 +217,106 @@ def ob_priors(n: int, h: int, w: int, channels: int = 20, seed: int = 0) -> np.n
         maps[c] = m / m.max()
     maps = maps.astype(np.float32)[None]
     return np.ascontiguousarray(np.repeat(maps, n, axis=0))
+
+
+# --------------------------------------------------------------------------- scoring data (scores.py)
+
+def synth_salmaps_u8(n: int, height: int, width: int, seed: int = 0) -> np.ndarray:
+    """uint8 saliency maps `[n, H, W]` (what `stream.predict_video` returns): a few drifting gaussian blobs over a
+    weak hashed floor, so the maps are full of ties (quantised) and nowhere all-zero."""
+    ys = (np.arange(height, dtype=np.float64) / max(height - 1, 1))[:, None]
+    xs = (np.arange(width, dtype=np.float64) / max(width - 1, 1))[None, :]
+    par = hash_uniform("salmaps.params", 32, seed)
+    floor = hash_uniform("salmaps.floor", height * width, seed).reshape(height, width)
+    out = np.empty((n, height, width), dtype=np.uint8)
+    for i in range(n):
+        m = 0.05 * floor
+        for b in range(4):
+            cx = (par[b] + 0.011 * (1 + b) * i) % 1.0
+            cy = (par[4 + b] + 0.007 * (2 + b) * i) % 1.0
+            sg = 0.05 + 0.12 * par[8 + b]
+            m = m + (0.3 + 0.7 * par[12 + b]) * np.exp(-((xs - cx) ** 2 + (ys - cy) ** 2) / (2 * sg * sg))
+        out[i] = np.clip(np.rint(m / m.max() * 255.0), 0, 255).astype(np.uint8)
+    return out
+
+
+def synth_fix_points(n: int, height: int, width: int, n_fix: int = 20, seed: int = 0) -> np.ndarray:
+    """uint8 fixation point maps `fixLoc` `[n, H, W]` (0 / 1): `n_fix` hashed positions per frame, drawn towards the
+    centre (positions that coincide merge)."""
+    out = np.zeros((n, height, width), dtype=np.uint8)
+    u = hash_uniform("fixpts.pos", n * n_fix * 4, seed).reshape(n, n_fix, 4)
+    yy = np.clip(((u[..., 0] + u[..., 1]) / 2.0 * height).astype(np.int64), 0, height - 1)
+    xx = np.clip(((u[..., 2] + u[..., 3]) / 2.0 * width).astype(np.int64), 0, width - 1)
+    for i in range(n):
+        out[i, yy[i], xx[i]] = 1
+    return out
+
+
+def synth_fix_maps(fix_pts: np.ndarray, sigma: float = 6.0) -> np.ndarray:
+    """float64 fixation densities `fixMap` `[n, H, W]`: a truncated gaussian of std `sigma` pixels around every point of
+    `fix_pts`, scaled to a maximum of 1 (0 where a frame has no fixation)."""
+    n, h, w = fix_pts.shape
+    r = int(np.ceil(3 * sigma))
+    g1 = np.exp(-np.arange(-r, r + 1, dtype=np.float64) ** 2 / (2 * sigma * sigma))
+    out = np.zeros((n, h + 2 * r, w + 2 * r), dtype=np.float64)
+    k = g1[:, None] * g1[None, :]
+    for i in range(n):
+        for y, x in zip(*np.nonzero(fix_pts[i])):
+            out[i, y:y + 2 * r + 1, x:x + 2 * r + 1] += k
+    out = out[:, r:r + h, r:r + w]
+    mx = out.reshape(n, -1).max(axis=1)
+    out /= np.where(mx > 0, mx, 1.0)[:, None, None]
+    return np.ascontiguousarray(out)
+
+
+def score_edge_batch(height: int = 90, width: int = 160, seed: int = 0):
+    """`(sal_u8, fix_map f64, fix_loc u8)`, 8 frames `[8, H, W]` that cover the edge cases of the reference's metrics:
+    0 ordinary, 1 constant map, 2 all-zero map, 3 no fixation (fixMap and fixLoc zero), 4 a single fixation,
+    5 fixations on tied map values, 6 fixations on the map's 255 and 0 (where the AUC-Judd jitter of 1e-7 survives fp32
+    rounding only next to 0), 7 many fixations (every 7th pixel)."""
+    sal = synth_salmaps_u8(8, height, width, seed)
+    loc = synth_fix_points(8, height, width, 24, seed)
+    sal[1] = 77
+    sal[2] = 0
+    loc[3] = 0
+    loc[4] = 0
+    loc[4, height // 3, width // 5] = 1
+    sal[5, :, : width // 2] = (sal[5, :, : width // 2] // 32) * 32
+    loc[5] = 0
+    loc[5, height // 4: height // 4 + 10: 2, 2: width // 2: 9] = 1
+    s6 = sal[6]
+    s6[height // 2, width // 2] = 255
+    s6[height // 2 + 1, width // 2] = 0
+    s6[0, 0] = 0
+    loc[6] = 0
+    loc[6, height // 2, width // 2] = 1
+    loc[6, height // 2 + 1, width // 2] = 1
+    loc[6, 0, 0] = 1
+    loc[6, 5, 5] = 1
+    loc[7] = 0
+    loc[7].reshape(-1)[::7] = 1
+    fmap = synth_fix_maps(loc, 4.0)
+    return sal, fmap, loc
+
+
+def write_score_tree(root: str, videos, height: int, width: int, methods=("M1",), seed: int = 0) -> None:
+    """A small dataset tree in the layout of the reference's `evalscores_vid_torch` (utils_score_torch.py:473-582):
+    `<root>/maps/<name>_fixMaps.mat` (fixMap float64 `[H,W,1,F]`), `<root>/fixations/maps/<name>_fixPts.mat` (fixLoc
+    uint8) and `<root>/Saliency/<method>/<name>.mat` (salmap uint8).  `videos`: `[(name, n_frames), ...]`; the saliency
+    files of method j hold one frame more than the fixation files for j even (so `nframes = min` matters)."""
+    from . import matio
+    os.makedirs(os.path.join(root, "maps"), exist_ok=True)
+    os.makedirs(os.path.join(root, "fixations", "maps"), exist_ok=True)
+    for v, (name, nf) in enumerate(videos):
+        loc = synth_fix_points(nf, height, width, 12 + 5 * v, seed + 100 + v)
+        if nf > 3:
+            loc[2] = 0                                       # a frame without fixations: a NaN row
+        fmap = synth_fix_maps(loc, 5.0)
+        matio.savemat(os.path.join(root, "maps", name + "_fixMaps.mat"), {"fixMap": fmap.transpose(1, 2, 0)[:, :, None, :]})
+        matio.savemat(os.path.join(root, "fixations", "maps", name + "_fixPts.mat"),
+                      {"fixLoc": loc.transpose(1, 2, 0)[:, :, None, :]})
+        for j, mname in enumerate(methods):
+            sal = synth_salmaps_u8(nf + (1 - j % 2), height, width, seed + 200 + 10 * v + j)
+            d = os.path.join(root, "Saliency", mname)
+            os.makedirs(d, exist_ok=True)
+            matio.savemat(os.path.join(d, name + ".mat"), {"salmap": sal.transpose(1, 2, 0)[:, :, None, :]})

@@ -444,6 +444,45 @@ typedef struct uavsal_guard_desc {
 
 int uavsal_guard(const uavsal_guard_desc* d, uavsal_stream_t stream);
 
+/* ---- saliency scoring: the metrics of the reference's scorer (utils_score_torch.py:17, 53-229) ----------------
+ * One descriptor covers a batch of F frames of N = H*W pixels.  `sal` is uint8 (sal_u8 = 1) or fp32, `fix_loc` uint8
+ * (loc_u8 = 1) or fp32, `fix_map` fp32, all [F][N] dense.  Metric ids are the positions in the reference's keys_order:
+ * 0 AUC_shuffled, 1 NSS, 2 AUC_Judd, 3 AUC_Borji, 4 KLD, 5 SIM, 6 CC.
+ *
+ * uavsal_score_stats: per-frame statistics into stats[F][UAVSAL_SCORE_NSTAT] (double): 0 min / 1 max of the map,
+ *   2 min / 3 max of the map + jitter (= 0 / 1 without jitter), 4 sum of the map, 5 min / 6 max / 7 sum of fix_map,
+ *   8 sum of fix_loc, 9 count of fix_loc > 0.5, 10 count of fix_loc != 0.  The host reads them to draw the random
+ *   samples (the draws stay on the host, in the reference's order).
+ * uavsal_score_run: everything else, after uavsal_score_stats on the same descriptor: out[F][n_keys] (fp32, column k =
+ *   metric keys[k]).  AUC-Judd reads the fixation values gathered into runs of at most UAVSAL_SCORE_RUN: fix_off[F+1]
+ *   is the prefix of the per-frame fixation counts (0 for a frame whose AUC-Judd is NaN), run_off[F+1] the prefix of
+ *   ceil(count / UAVSAL_SCORE_RUN); both device arrays, totals in total_fix / total_runs.  samp[0] (AUC_shuffled) and
+ *   samp[1] (AUC_Borji) hold pixel indices: frame f at samp_off[s][f], UAVSAL_SCORE_REPS rows of n indices
+ *   (n = (samp_off[s][f+1] - samp_off[s][f]) / REPS; n = 0: no draw, the score is NaN).  nan_rows != 0: a frame whose
+ *   map, fix_map or fix_loc is all zero scores NaN everywhere (utils_score_torch.py:565-571).
+ * Scores are bitwise reproducible: no float atomics, fixed reduction orders.
+ */
+#define UAVSAL_SCORE_NSTAT 16
+#define UAVSAL_SCORE_REPS  100
+#define UAVSAL_SCORE_RUN   4096
+#define UAVSAL_SCORE_NKEY  7
+
+typedef struct uavsal_score_desc {
+    const void* sal;  const void* fix_loc;  const float* fix_map;
+    const float* jitter;                  /* [F][N] fp32 term added to the map for AUC-Judd, or NULL */
+    int32_t sal_u8, loc_u8, n_frames, n_pix;
+    double* stats;                        /* [F][UAVSAL_SCORE_NSTAT] */
+    const int64_t* fix_off;  const int64_t* run_off;  int64_t total_fix;  int32_t total_runs;
+    int32_t nan_rows;
+    const int32_t* samp[2];  const int64_t* samp_off[2];  int64_t n_samp[2];
+    void* ws;  int64_t ws_bytes;          /* workspace, uavsal_score_workspace_bytes() */
+    float* out;  int32_t n_keys;  int32_t keys[UAVSAL_SCORE_NKEY];
+} uavsal_score_desc;
+
+int64_t uavsal_score_workspace_bytes(const uavsal_score_desc* d);
+int uavsal_score_stats(const uavsal_score_desc* d, uavsal_stream_t stream);
+int uavsal_score_run(const uavsal_score_desc* d, uavsal_stream_t stream);
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 
@@ -501,7 +540,7 @@ int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_time(uavsal_plan* p, int first, int last, int iters, uavsal_stream_t stream, float* ms);
 
 int uavsal_abi_version(void);
-int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill */
+int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score */
 const char* uavsal_build_info(void);
 
 #ifdef __cplusplus
