@@ -1076,8 +1076,7 @@ int launch_variant(const ConvK& k0, int taps, hipStream_t stream) {
         const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 1>, SMEM, NT));
         // (same K split as the 3x3 tile below: few 64 x 64 tiles, long K -- the 1920 -> 256 ASPP projections at 12x20)
         if (WM * WN == 1 && k.kpart && k.epi == UAVSAL_EPI_AFFINE && (PREC == UAVSAL_PREC_F16X3 || PREC == UAVSAL_PREC_BF16X3)) {
-            static const bool on = [] { const char* e = getenv("UAVSAL_SPLITK_1X1"); return !(e && e[0] == '0'); }();
-            int ksp = on ? UAVSAL_SPLIT_REF_SLOTS_64 / (k.nblk > 0 ? k.nblk : 1) : 1;
+            int ksp = UAVSAL_SPLIT_REF_SLOTS_64 / (k.nblk > 0 ? k.nblk : 1);
             ksp = ksp >= 4 ? 4 : (ksp >= 2 ? 2 : 1);
             while (ksp > 1 && (k.ktiles % ksp || k.ktiles / ksp < 12)) ksp >>= 1;
             if (ksp > 1 && (long long)ksp * k.M * k.Npad * 4 <= k.kpart_bytes && !(k.Cout & 3) && !(k.ldc & 3)) {
@@ -1094,8 +1093,7 @@ int launch_variant(const ConvK& k0, int taps, hipStream_t stream) {
         // steps): split K over 2 or 4 workgroups per tile; the shares' sums meet in splitk_reduce_kernel
         if (WM * WN == 1 && k.kpart && (k.epi == UAVSAL_EPI_TWA || k.epi == UAVSAL_EPI_AFFINE) &&
             (PREC == UAVSAL_PREC_F16X3 || PREC == UAVSAL_PREC_BF16X3)) {
-            static const bool on = [] { const char* e = getenv("UAVSAL_SPLITK_3X3"); return !(e && e[0] == '0'); }();
-            int ksp = on ? UAVSAL_SPLIT_REF_SLOTS_64 / (k.nblk > 0 ? k.nblk : 1) : 1;
+            int ksp = UAVSAL_SPLIT_REF_SLOTS_64 / (k.nblk > 0 ? k.nblk : 1);
             ksp = ksp >= 4 ? 4 : (ksp >= 2 ? 2 : 1);
             while (ksp > 1 && (k.ktiles % (9 * ksp) || k.ktiles / ksp < 18)) ksp >>= 1;
             if (ksp > 1 && (long long)ksp * k.M * k.Npad * 4 <= k.kpart_bytes && !(k.Cout & 3) && !(k.ldc & 3) &&
@@ -1235,8 +1233,7 @@ int launch_h16_dma(const ConvK& k0, int taps, hipStream_t stream) {
 
 // LDS-halo depthwise -> projection (fp32 / split-fp16): which descriptors take it, and the launch
 bool dwproj_eligible(const uavsal_conv_desc* d) {
-    static const bool on = [] { const char* e = getenv("UAVSAL_DWPROJ_LDS"); return !(e && e[0] == '0'); }();
-    return on && d->dw_w9c && (d->prec == UAVSAL_PREC_F32 || d->prec == UAVSAL_PREC_F16X3) && d->taps == 1 &&
+    return d->dw_w9c && (d->prec == UAVSAL_PREC_F32 || d->prec == UAVSAL_PREC_F16X3) && d->taps == 1 &&
            d->dw_stride == 1 && d->Cin % 16 == 0 && d->Cin <= UAVSAL_DWPROJ_MAX_C && d->epi == UAVSAL_EPI_AFFINE;
 }
 
@@ -1298,9 +1295,7 @@ int pick_tile(long long M, int Cout, int prec) {
     // fp32 256 x 128 on 8 waves (tile 7; a quarter fewer operand bytes per FLOP than 128 x 128) is NOT picked
     // automatically.  Isolated (profiles/r2_f32_tile7_probe.log) the 256 -> 1536 expand gains 3 % at 8 frames and
     // 10 % at 64, the 3x3 448 -> 256 conv 7 %; inside the forward the same build is 0.6 % (1 clip) and 1.1 % (8 clips)
-    // SLOWER end to end, two same-box runs each (1444 / 1671 vs 1453 / 1691 frames/s).  UAVSAL_TILE7=1 opts in.
-    static const bool tile7_on = [] { const char* e = getenv("UAVSAL_TILE7"); return e && e[0] == '1'; }();
-    if (tile7_on && prec == UAVSAL_PREC_F32 && Cout % 128 == 0 && ((M + 255) / 256) * (Cout / 128) >= 768) return 7;
+    // SLOWER end to end, two same-box runs each (1444 / 1671 vs 1453 / 1691 frames/s).  A descriptor asks for it by `tile`.
     // Among the tiles that give >= 256 blocks: least padded-N work, the narrower tiles charged 5 / 35 % for
     // their lower efficiency (Cout = 144: 128x64 27.8 us vs 128x128 33.2; 576: 42.2 vs 46.5; 96: 42.2 with
     // 128x128 vs 50.3, same padding; 24: 128x32 19.9 vs 31.1 -- profiles/r1_gemm_probe_v3.log).
@@ -1329,62 +1324,45 @@ static int effective_tile(const uavsal_conv_desc* d) {
     if (tile == 11 && !uavsal_f32_k32_eligible(d, tile)) tile = 4;
     if (tile == 10 && !uavsal_f32_k32_eligible(d, 10)) tile = 8;
     if ((tile == 8 || tile == 9) && !uavsal_f32_k32_eligible(d, tile)) tile = tile == 9 ? 7 : 1;   // full-line K stages
-    // automatic choice: the 128 x 128 launches that do not take the stream-K path move to the kernel with 32-float K
-    // stages (conv_gemm_k32.hip); UAVSAL_K32=0 keeps the 16-float one, UAVSAL_K32=9 picks the 256 x 128 instance
-    // where it still fills the chip
-    // ... and launches with too few tiles for the chip and a long K walk take it with K split over several workgroups
-    // per tile (uavsal_f32_k32_ksplit): the ConvTWA step (UAVSAL_K32_SPLITK=1, the default), every such conv (=2), none (=0)
-    if (d->tile == 0 && tile == 4 && d->prec == UAVSAL_PREC_F32 && d->sk_ws && d->sk_ws_bytes > 65536) {
-        static const int k32_mode = [] { const char* e = getenv("UAVSAL_K32"); return e ? atoi(e) : 1; }();
-        static const int sk_mode = [] { const char* e = getenv("UAVSAL_K32_SPLITK"); return e ? atoi(e) : 1; }();
-        const bool want = sk_mode == 2 ? (d->epi == UAVSAL_EPI_AFFINE || d->epi == UAVSAL_EPI_TWA) : (sk_mode == 1 && d->epi == UAVSAL_EPI_TWA);
-        if (k32_mode && want && uavsal_f32_k32_eligible(d, 8)) {
-            const long long M = (long long)d->H * d->W * d->n_img;
-            const int npad = (d->Cout + 31) / 32 * 32;
-            const int ksp = uavsal_f32_k32_ksplit(((M + 127) / 128) * ((d->Cout + 127) / 128), d->taps * d->Cin / 32);
-            // (tile 10 reduces the shares inside the launch -- the last share to arrive adds them -- and measures 12 us
-            // SLOWER per ConvTWA step than shares + reduce launch: one workgroup per tile reads all the shares)
-            if (ksp > 1 && (long long)ksp * M * npad * 4 <= d->sk_ws_bytes - 65536 && !(d->Cout & 3) && !(d->ldc & 3)) tile = 8;
-        }
+    // automatic choice, fp32: the ConvTWA step (too few tiles for the chip and a long K walk) takes the kernel with 32-float K
+    // stages (conv_gemm_k32.hip) with K split over several workgroups per tile (uavsal_f32_k32_ksplit)
+    if (d->tile == 0 && tile == 4 && d->prec == UAVSAL_PREC_F32 && d->sk_ws && d->sk_ws_bytes > 65536 &&
+        d->epi == UAVSAL_EPI_TWA && uavsal_f32_k32_eligible(d, 8)) {
+        const long long M = (long long)d->H * d->W * d->n_img;
+        const int npad = (d->Cout + 31) / 32 * 32;
+        const int ksp = uavsal_f32_k32_ksplit(((M + 127) / 128) * ((d->Cout + 127) / 128), d->taps * d->Cin / 32);
+        // (tile 10 reduces the shares inside the launch -- the last share to arrive adds them -- and measures 12 us
+        // SLOWER per ConvTWA step than shares + reduce launch: one workgroup per tile reads all the shares)
+        if (ksp > 1 && (long long)ksp * M * npad * 4 <= d->sk_ws_bytes - 65536 && !(d->Cout & 3) && !(d->ldc & 3)) tile = 8;
     }
     // ... and affine convs on the small backbone maps with a long K (the 12x20 projections: at most 160 tiles of 64 x 64,
     // at least 24 stages) take the 64 x 64 instance with K shares over workgroups reduced inside the launch (tile 11):
     // 17.0 / 23.2 / 26.9 / 18.1 us against 19.5 / 26.6 / 32.7 / 25.2 for the stream-K instance (profiles/r3_gemm_k32.md)
     if (d->tile == 0 && tile == 4 && d->prec == UAVSAL_PREC_F32 && d->epi == UAVSAL_EPI_AFFINE && d->sk_ws && d->sk_ws_bytes > 65536) {
-        static const int k32_mode = [] { const char* e = getenv("UAVSAL_K32"); return e ? atoi(e) : 1; }();
-        static const int small_mode = [] { const char* e = getenv("UAVSAL_K32_SMALL"); return e ? atoi(e) : 1; }();
         const long long M = (long long)d->H * d->W * d->n_img;
         const long long tiles64 = ((M + 63) / 64) * ((d->Cout + 63) / 64);
         // (round 4: from 12 stages on -- features.14's projection, K = 576: 16.9 -> 13.9 us; the context prior's, K = 384 on one
         // 12x20 map: 12.9 -> 10.0)
-        if (k32_mode && small_mode && tiles64 <= 160 && d->taps * d->Cin / 32 >= 12 && uavsal_f32_k32_eligible(d, 11) &&
+        if (tiles64 <= 160 && d->taps * d->Cin / 32 >= 12 && uavsal_f32_k32_eligible(d, 11) &&
             d->act != UAVSAL_ACT_SIGMOID && !(d->Cout & 3) && !(d->ldc & 3))
             tile = 11;
     }
     // ... and the short-K expands of the small backbone maps (64 -> 384, 96 -> 576, 160 -> 960 on 23x40 / 12x20: at most one
     // round of 64 x 64 tiles at three workgroups per CU) take it too: 9.6 / 15.9 / 11.4 us against 11.1 / 18.4 / 13.0
     if (d->tile == 0 && tile != 11 && d->prec == UAVSAL_PREC_F32 && d->epi == UAVSAL_EPI_AFFINE && d->taps == 1) {
-        static const int k32_mode = [] { const char* e = getenv("UAVSAL_K32"); return e ? atoi(e) : 1; }();
-        static const int exp_mode = [] { const char* e = getenv("UAVSAL_K32_SMALL_EXPAND"); return e ? atoi(e) : 1; }();
         const long long M = (long long)d->H * d->W * d->n_img;
         const long long tiles64 = ((M + 63) / 64) * ((d->Cout + 63) / 64);
         // (round 4: up to Cin = 256 and two rounds of tiles -- the context prior's expand, 256 -> 1536 on ONE 45x80 map: 40.4 -> 34.2 us)
-        if (k32_mode && exp_mode && M <= 8192 && tiles64 <= 1536 && d->Cout >= 256 && d->Cin >= 64 && d->Cin <= 256 &&
+        if (M <= 8192 && tiles64 <= 1536 && d->Cout >= 256 && d->Cin >= 64 && d->Cin <= 256 &&
             !d->w_group_stride && !d->n_group && uavsal_f32_k32_eligible(d, 11) && d->act != UAVSAL_ACT_SIGMOID && !(d->Cout & 3) && !(d->ldc & 3))
             tile = 11;
     }
-    if (d->tile == 0 && tile == 1 && d->prec == UAVSAL_PREC_F32) {
-        static const int k32_mode = [] { const char* e = getenv("UAVSAL_K32"); return e ? atoi(e) : 1; }();
-        // (K of at least four 32-float stages: at K = 64 the 16-float instance is 1-2 us faster per launch -- three ring
-        // stages against two -- and at K = 32 the launch is store-bound either way)
-        // (UAVSAL_K32_OVER_SK=1: also where the 16-float instance would run stream-K -- experiment knob)
-        static const int over_sk = [] { const char* e = getenv("UAVSAL_K32_OVER_SK"); return e ? atoi(e) : 0; }();
-        if (k32_mode && uavsal_f32_k32_eligible(d, 8) && d->epi == UAVSAL_EPI_AFFINE && d->taps * d->Cin >= 128 &&
-            (over_sk || streamk_plan(d, 1, (d->taps * d->Cin + 15) / 16) == 0)) {
-            const long long M = (long long)d->H * d->W * d->n_img;
-            tile = (k32_mode == 9 && d->Cout % 128 == 0 && ((M + 255) / 256) * (d->Cout / 128) >= 1024) ? 9 : 8;
-        }
-    }
+    // ... and the 128 x 128 launches that do not take the stream-K path move to the 128 x 128 instance with 32-float K stages
+    // (K of at least four 32-float stages: at K = 64 the 16-float instance is 1-2 us faster per launch -- three ring stages
+    // against two -- and at K = 32 the launch is store-bound either way)
+    if (d->tile == 0 && tile == 1 && d->prec == UAVSAL_PREC_F32 && uavsal_f32_k32_eligible(d, 8) && d->epi == UAVSAL_EPI_AFFINE &&
+        d->taps * d->Cin >= 128 && streamk_plan(d, 1, (d->taps * d->Cin + 15) / 16) == 0)
+        tile = 8;
     // ... and a 1x1 whose 128 x 128 tiles are more than one per CU but fewer than the 512 resident slots (the STBlock's
     // 256 -> 256 output conv at one clip: 450 tiles, so most CUs run two and the rest one) takes the 64 x 64 instance: 49.6 -> 46.7 us
     if (d->tile == 0 && tile == 8 && d->prec == UAVSAL_PREC_F32 && d->epi == UAVSAL_EPI_AFFINE && d->taps == 1 && !d->w_group_stride) {

@@ -936,9 +936,6 @@ int launch_k32(const ConvK& k0, int taps, hipStream_t stream) {
         k.ksplit = uavsal_f32_k32_split_ok(k) ? uavsal_f32_k32_ksplit(k.nblk, k.Kpad / 32) : 1;
         if (k.ksplit > 1) {          // (tile, K share) work units, reduced in the launch by the last share to arrive
             k.nblk *= k.ksplit;
-            // UAVSAL_K32_FLAT_REDUCE=launch: the shares are summed by splitk_reduce_kernel instead
-            static const bool by_launch = [] { const char* e = getenv("UAVSAL_K32_FLAT_REDUCE"); return e && e[0] == 'l'; }();
-            if (by_launch) k.sk_flag = nullptr;
             const int cap1 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW, true>));
             const int cap9 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW, true>));
             const int cap = taps == 1 ? cap1 : cap9;
@@ -950,7 +947,6 @@ int launch_k32(const ConvK& k0, int taps, hipStream_t stream) {
                 UAVSAL_LDS_OPTIN((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW, true>), SMEM);
                 hipLaunchKernelGGL((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW, true>), dim3(grid), dim3(NT), SMEM, stream, k);
             }
-            if (!k.sk_flag) { k.nblk /= k.ksplit; return launch_splitk_reduce(k, 1.0f, stream); }
         } else if (taps == 1) {
             const int cap = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW>));
             const int grid = k.nblk < cap ? k.nblk : cap;
@@ -992,9 +988,8 @@ __attribute__((visibility("hidden"))) int uavsal_f32_k32_ksplit(long long tiles,
     if (tiles <= 0 || tiles * 2 > 512) return 1;
     // measured on the ConvTWA step (58 tiles x 72 stages, one clip): 2 / 3 / 4 / 6 / 8 shares = 90 / 68 / 57 / 72 / 62 us
     // (kernel + reduce launch), the 64 x 64 stream-K instance it replaces 65 -- profiles/r3_gemm_k32.md
-    static const int ksp_max = [] { const char* e = getenv("UAVSAL_K32_KSPLIT_MAX"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
     int ksp = (int)(512 / tiles);
-    if (ksp > ksp_max) ksp = ksp_max;
+    if (ksp > 4) ksp = 4;
     while (ksp > 1 && stages / ksp < 6) --ksp;
     return ksp;
 }

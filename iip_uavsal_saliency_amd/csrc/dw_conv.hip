@@ -310,7 +310,7 @@ __global__ __launch_bounds__(NT) void dw3x3_rowclass_kernel(const DwK p) {
     }
 }
 
-// quads per slab of a group: the widest of 64 / 32 / 16 whose largest class stays within `budget` items (0: none does);
+// quads per slab of a group: the widest of 64 / 32 / 16 / 8 whose largest class stays within `budget` items (0: none does);
 // the group's channels must be whole slabs of it
 static inline int rowclass_quads(const DwK& k, int g, long long budget) {
     const int d = k.dgc ? k.dils[g] : k.dil;
@@ -321,7 +321,7 @@ static inline int rowclass_quads(const DwK& k, int g, long long budget) {
     return 0;
 }
 
-static const long long ROWCLASS_ITEMS = [] { const char* e = getenv("UAVSAL_DW_ROWCLASS_ITEMS"); return e ? atoll(e) : 2560LL; }();       // 40 KB of LDS per workgroup: three per CU
+constexpr long long ROWCLASS_ITEMS = 2560;       // 40 KB of LDS per workgroup: three per CU
 
 static inline bool rowclass_fits(const DwK& k) {
     const int groups = k.dgc ? (k.C4 * 4 + k.dgc - 1) / k.dgc : 1;
@@ -330,8 +330,8 @@ static inline bool rowclass_fits(const DwK& k) {
     return true;
 }
 
-template <int NT>
 int launch_rowclass(DwK k, hipStream_t s) {
+    constexpr int NT = 256;
     const int C = k.C4 * 4;
     const int groups = k.dgc ? (C + k.dgc - 1) / k.dgc : 1;
     long long first = 0, most = 0;
@@ -363,8 +363,6 @@ static inline size_t map_lds_bytes(long long px, int cb) { return (size_t)((px *
 // threads per workgroup: 512 where a slab is many rounds of 256 items (the 23x40 map of 720x1280 inputs: 14.4 rounds; two
 // workgroups per CU by LDS either way, twice the waves to cover the store phase: 0.47 -> 0.52 of 8 TB/s at 64 frames)
 static inline int map_lds_threads(const DwK& k, int cb) {
-    static const int nt_forced = [] { const char* e = getenv("UAVSAL_DW_MAP_NT"); return e ? atoi(e) : 0; }();
-    if (nt_forced == 256 || nt_forced == 512 || nt_forced == 1024) return nt_forced;
     return (long long)k.H * k.W * (cb / 4) >= 2048 ? 512 : 256;
 }
 
@@ -375,8 +373,7 @@ int launch_map_lds(DwK k, hipStream_t s) {
     // 512-thread workgroups where a slab is many rounds of 256 items (the 23x40 map of 720x1280 inputs: 14.4): two workgroups per
     // CU by LDS either way, twice the waves to cover the store phase
     const int nt = map_lds_threads(k, CB);
-    if (nt == 1024) hipLaunchKernelGGL((dw3x3_map_lds_kernel<CB, 1024>), dim3((unsigned)(k.n_img * slabs)), dim3(1024), smem, s, k);
-    else if (nt == 512) hipLaunchKernelGGL((dw3x3_map_lds_kernel<CB, 512>), dim3((unsigned)(k.n_img * slabs)), dim3(512), smem, s, k);
+    if (nt == 512) hipLaunchKernelGGL((dw3x3_map_lds_kernel<CB, 512>), dim3((unsigned)(k.n_img * slabs)), dim3(512), smem, s, k);
     else hipLaunchKernelGGL((dw3x3_map_lds_kernel<CB, 256>), dim3((unsigned)(k.n_img * slabs)), dim3(256), smem, s, k);
     return uavsal_launch_status();
 }
@@ -385,8 +382,6 @@ int launch_map_lds(DwK k, hipStream_t s) {
 static inline int map_lds_slab(const DwK& k) {
     const long long px = (long long)k.H * k.W;
     if (map_lds_bytes(px, 16) > 65536) return 0;
-    static const int forced = [] { const char* e = getenv("UAVSAL_DW_MAP_CB"); return e ? atoi(e) : 0; }();
-    if ((forced == 16 || forced == 32 || forced == 64) && map_lds_bytes(px, forced) <= 65536) return forced;
     // 32 channels (30 KB of LDS at 12x20: five workgroups per CU cover each other's load / compute phases) where that still
     // gives every CU a workgroup, else 16.  (64-channel slabs, two workgroups per CU: 78.7 vs 51.9 us at 64 x 12x20 x 1920
     // and 15.1 vs 11.0 us at 8 frames -- round 4)
@@ -399,17 +394,16 @@ static inline int map_lds_slab(const DwK& k) {
 }
 
 // which kernel a descriptor gets: 1 = dw3x3_kernel<1,4,4>, 2 = <1,2,2>, 3 = <2,2,2>, 4 = dw3x3_dilated_kernel,
-// 16 / 32 / 64 = dw3x3_map_lds_kernel<CB> (uavsal_dw_variant adds 512 / 1024 for the instances with that many threads)
+// 16 / 32 = dw3x3_map_lds_kernel<CB> (uavsal_dw_variant adds 512 for the instances with that many threads),
+// 2048 = dw3x3_rowclass_kernel
 static int dw_variant(const DwK& k, int stride, int dilation) {
     if (k.dgc) {              // several dilated branches in one launch: the whole-map kernel (each byte fetched once whatever the dilation)
         const int cb = map_lds_slab(k);
         // a map too big for 32-channel slabs (23x40, the 1/32 level of 720x1280 inputs) would be read and written in half cache
         // lines: by row class instead (measured at 64 frames x 5760 channels, in the plan: 577 vs 652 us, 0.588 vs 0.520 of 8 TB/s;
-        // on the 12x20 map of 360x640 inputs the whole-map kernel wins, 20 vs 26 us at 8 frames and 142 vs 181 at 64).
-        // UAVSAL_DW_ROWCLASS=0 / 1: never / wherever it fits
-        static const int rowclass = [] { const char* e = getenv("UAVSAL_DW_ROWCLASS"); return e ? atoi(e) : -1; }();
+        // on the 12x20 map of 360x640 inputs the whole-map kernel wins, 20 vs 26 us at 8 frames and 142 vs 181 at 64)
         const bool big_map = map_lds_bytes((long long)k.H * k.W, 32) > 65536;
-        if (rowclass != 0 && (rowclass > 0 || big_map) && rowclass_fits(k)) return 2048;
+        if (big_map && rowclass_fits(k)) return 2048;
         return (cb && k.dgc % cb == 0) ? cb : 4;
     }
     // Measured at 8 x 12x20 x 1920 (profiles/r2_dw_small_maps.md): the whole-map LDS kernel wins only while most
@@ -568,9 +562,7 @@ extern "C" int uavsal_dw3x3(const uavsal_dw_desc* d, uavsal_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const int v = dw_variant(k, d->stride, d->dilation);
     switch (v) {
-        case 2048: { static const int nt = [] { const char* e = getenv("UAVSAL_DW_ROWCLASS_NT"); return e ? atoi(e) : 256; }();
-                     return nt == 256 ? launch_rowclass<256>(k, s) : launch_rowclass<512>(k, s); }
-        case 64: return launch_map_lds<64>(k, s);
+        case 2048: return launch_rowclass(k, s);
         case 32: return launch_map_lds<32>(k, s);
         case 16: return launch_map_lds<16>(k, s);
         case 4: {

@@ -44,19 +44,15 @@ namespace {
 // bound by the requests (29 KB per step and workgroup), not by the matrix pipe.  All fragments of the next step are
 // read after the last MFMA and stay in flight across the barrier.
 // Shapes: stride 1, dilation 1, hidden channels % 16 == 0 (host: dwproj_eligible).
-// PWV = 4 (round 4, "producer waves"): four EXTRA waves, one per SIMD, do nothing but the depthwise and the requests; the
-// WAVES_M x WAVES_N MFMA waves do nothing but fragment reads and MFMAs (three waves per SIMD, <= 168 VGPRs each).  The
-// depthwise VALU / LDS work and the request issue then never sit in an MFMA wave's in-order instruction stream.
-template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN, int PWV = 0>
-__global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void dwproj_kernel(const ConvK p) {
+template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 1) void dwproj_kernel(const ConvK p) {
     static_assert(PREC == UAVSAL_PREC_F32 || PREC == UAVSAL_PREC_F16X3, "fp32 or split-fp16");
     constexpr bool H16 = PREC == UAVSAL_PREC_F16X3;
     constexpr int PH = 8, PW = 16, HPITCH = PW + 3, NHSLOT = (PH + 2) * HPITCH;
     constexpr int BM = PH * PW, BN = WAVES_N * WN * 32;
-    constexpr int NW = WAVES_M * WAVES_N, NT = (NW + PWV) * 64;      // NW: MFMA waves; NT: all threads of the workgroup
+    constexpr int NW = WAVES_M * WAVES_N, NT = NW * 64;
     constexpr int KT = 16, DIST = 4;
     constexpr bool TEPI = UAVSAL_DWPROJ_TEPI != 0;
-    static_assert(PWV == 0 || (PWV == 4 && NW == 8), "producer waves: 8 MFMA waves + 4");
     constexpr int E_REQ = (NHSLOT + 15) / 16;         // 12 wave requests of 16 halo slots, then one for the dw weights
     constexpr int W_OFF = E_REQ * 1024;               // [9 taps | scale | bias][16 channels] behind the halo
     constexpr int E_SLOT = W_OFF + 1024, NE = 3;
@@ -101,9 +97,9 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void d
     // walk a row of zeros), LDS target relative to the slot (or -1: the scratch KB)
     const char* rq_ptr[NREQ];
     int rq_lds[NREQ];
-    // wave roles (a 4-wave workgroup: both; with producer waves: waves NW .. NW + 3 have both, the others neither)
-    const bool loader = PWV ? wave_u >= NW : wave_u >= NW - NLW, dw_wave = PWV ? wave_u >= NW : wave_u < 4;
-    const int lw = PWV ? wave_u - NW : wave_u - (NW - NLW);
+    // wave roles (a 4-wave workgroup: both)
+    const bool loader = wave_u >= NW - NLW, dw_wave = wave_u < 4;
+    const int lw = wave_u - (NW - NLW);
 #pragma unroll
     for (int r = 0; r < NREQ; ++r) {
         const int q = lw + (r < E_IT ? r : r - E_IT) * NLW;
@@ -228,12 +224,11 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void d
     // which waves run the depthwise of K step s: all four of a 4-wave workgroup, else waves 0-3 / 4-7 in turn
     // the whole tile walk, instantiated per wave role (depthwise / requests / both): the two roles share no
     // registers beyond the accumulators and fragments
-    auto run = [&](auto role_dw, auto role_ld, auto role_mma) {
-    constexpr bool MMA = decltype(role_mma)::value;
+    auto run = [&](auto role_dw, auto role_ld) {
     f32x16 acc[WM][WN];
     f32x4 af[2][WM], bfr[2][WN];                       // fragments of the K step about to be multiplied
     auto load_frag = [&](const char* at, const char* bt, int u) {
-        if (!pr_frag || !MMA) return;
+        if (!pr_frag) return;
         const int chunk = 2 * u + lh;
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
@@ -295,17 +290,10 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void d
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         if (pr_bar) {
-            if (MMA && (FULL || kt + 1 < nst)) asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" :: "n"(NTAIL) : "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (a producer's last LDS accesses are its A-tile writes)
+            if (FULL || kt + 1 < nst) asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" :: "n"(NTAIL) : "memory");
+            else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
         if (DW && pr_dw && (FULL || kt + 2 < nst)) depthwise(Es + eo_dw, As + ao_dw);
-        if (!MMA) {                  // a producer wave: the requests of step kt + 4, back to back
-            if (LD && (FULL || kt + DIST < nst)) {
-#pragma unroll
-                for (int r = 0; r < NREQ; ++r) issue_one(r, eo_req, bo_req);
-            }
-            return;
-        }
         if (LD && (FULL || kt + DIST < nst)) {
             multiply_half(std::true_type{}, 0, eo_req, bo_req);
             if (H16 ? false : (FULL || kt + 1 < nst)) load_frag(As + ao_frag, Bs + bo_frag, 0);
@@ -324,14 +312,12 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void d
     if (nst > 1) issue_all(E_SLOT, B_SLOT);
     while (true) {
         const int cimg = img, cy0 = y0, cx0 = x0, cn0 = n0, cks = ks;
-        if (MMA) {
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
             for (int j = 0; j < WN; ++j)
 #pragma unroll
                 for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
-        }
         // ---- two lead-in steps: depthwise(0), depthwise(1), fragments of step 0
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // steps 0, 1 landed
         if (2 < nst) issue_all(2 * E_SLOT, 2 * B_SLOT);
@@ -370,50 +356,48 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void d
         // CONSECUTIVE OUTPUT CHANNELS of one pixel (rows = channels (g & 3) + 8 (g >> 2) + 4 lh, column = pixel lr): BN /
         // activation / residual and 16-byte stores straight from registers -- no LDS staging, no barriers.
         if (TEPI) {
-            if (MMA) {
-                const bool part = p.ksplit > 1;
-                const bool vec = !(p.ldc & 3) && !(p.Cout & 3) && !((size_t)p.out & 15) &&
-                                 (!p.res || (!(p.ldr & 3) && !((size_t)p.res & 15)));
-                const int act = part ? UAVSAL_ACT_NONE : p.act;
+            const bool part = p.ksplit > 1;
+            const bool vec = !(p.ldc & 3) && !(p.Cout & 3) && !((size_t)p.out & 15) &&
+                             (!p.res || (!(p.ldr & 3) && !((size_t)p.res & 15)));
+            const int act = part ? UAVSAL_ACT_NONE : p.act;
 #pragma unroll
-                for (int i = 0; i < WM; ++i) {
-                    const int rho = (wm * WM + i) * 32 + lr;            // A-tile row -> pixel (header comment)
-                    const int y = cy0 + 4 * ((rho >> 5) & 1) + ((rho >> 1) & 3);
-                    const int x = cx0 + 8 * (rho >> 6) + 2 * ((rho & 1) + 2 * ((rho >> 4) & 1)) + ((rho >> 3) & 1);
-                    const bool okp = y < p.H && x < p.W;
-                    const long long pix = (long long)y * p.W + x;
+            for (int i = 0; i < WM; ++i) {
+                const int rho = (wm * WM + i) * 32 + lr;            // A-tile row -> pixel (header comment)
+                const int y = cy0 + 4 * ((rho >> 5) & 1) + ((rho >> 1) & 3);
+                const int x = cx0 + 8 * (rho >> 6) + 2 * ((rho & 1) + 2 * ((rho >> 4) & 1)) + ((rho >> 3) & 1);
+                const bool okp = y < p.H && x < p.W;
+                const long long pix = (long long)y * p.W + x;
 #pragma unroll
-                    for (int j = 0; j < WN; ++j)
+                for (int j = 0; j < WN; ++j)
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int gn = cn0 + (wn * WN + j) * 32 + 4 * lh + 8 * q;
-                            f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                            if (part) {
-                                if (okp && gn < p.Npad)
-                                    *reinterpret_cast<f32x4*>(p.kpart + ((size_t)cks * p.M + (size_t)cimg * p.HW + (size_t)pix) * p.Npad + gn) = v;
-                                continue;
-                            }
-                            if (!okp || gn >= p.Cout) continue;
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) {
-                                const bool okn = p.scale != nullptr && gn + c < p.Cout;
-                                const float sc = (okn ? p.scale[gn + c] : 1.f) * (H16 ? F16X3_ACC_SCALE : 1.f);
-                                v[c] = apply_act(fmaf(v[c], sc, okn ? p.bias[gn + c] : 0.f), act);
-                            }
-                            float* o = p.out + ((long long)cimg * p.o_is + pix) * p.ldc + gn;
-                            const float* rs = p.res ? p.res + ((long long)cimg * p.r_is + pix) * p.ldr + gn : nullptr;
-                            if (vec) {
-                                if (rs) v += *reinterpret_cast<const f32x4*>(rs);
-                                *reinterpret_cast<f32x4*>(o) = v;
-                                if (H16 && p.out_sp)     // split shadow for the GEMM that consumes this output
-                                    uavsal_store_split4(p.out_sp + ((long long)cimg * p.o_is + pix) * p.ldos, gn, v);
-                            } else {
-#pragma unroll
-                                for (int c = 0; c < 4; ++c)
-                                    if (gn + c < p.Cout) o[c] = v[c] + (rs ? rs[c] : 0.f);
-                            }
+                    for (int q = 0; q < 4; ++q) {
+                        const int gn = cn0 + (wn * WN + j) * 32 + 4 * lh + 8 * q;
+                        f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+                        if (part) {
+                            if (okp && gn < p.Npad)
+                                *reinterpret_cast<f32x4*>(p.kpart + ((size_t)cks * p.M + (size_t)cimg * p.HW + (size_t)pix) * p.Npad + gn) = v;
+                            continue;
                         }
-                }
+                        if (!okp || gn >= p.Cout) continue;
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            const bool okn = p.scale != nullptr && gn + c < p.Cout;
+                            const float sc = (okn ? p.scale[gn + c] : 1.f) * (H16 ? F16X3_ACC_SCALE : 1.f);
+                            v[c] = apply_act(fmaf(v[c], sc, okn ? p.bias[gn + c] : 0.f), act);
+                        }
+                        float* o = p.out + ((long long)cimg * p.o_is + pix) * p.ldc + gn;
+                        const float* rs = p.res ? p.res + ((long long)cimg * p.r_is + pix) * p.ldr + gn : nullptr;
+                        if (vec) {
+                            if (rs) v += *reinterpret_cast<const f32x4*>(rs);
+                            *reinterpret_cast<f32x4*>(o) = v;
+                            if (H16 && p.out_sp)     // split shadow for the GEMM that consumes this output
+                                uavsal_store_split4(p.out_sp + ((long long)cimg * p.o_is + pix) * p.ldos, gn, v);
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c)
+                                if (gn + c < p.Cout) o[c] = v[c] + (rs ? rs[c] : 0.f);
+                        }
+                    }
             }
         } else {
             float* stg = reinterpret_cast<float*>(Bs + 2 * B_SLOT);
@@ -434,7 +418,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void d
 #pragma unroll
                 for (int w = 0; w < WAVES_M; ++w) {
                     const int pp = w * WM + i;
-                    if (MMA && wm == w) {
+                    if (wm == w) {
 #pragma unroll
                         for (int g = 0; g < 16; ++g) {
                             const int r = (g & 3) + 8 * (g >> 2) + 4 * lh;
@@ -481,24 +465,21 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + PWV) * 64, PWV ? 3 : 1) void d
         if (!has_next) break;
     }
     };
-    if (PWV) {
-        if (dw_wave) run(std::true_type{}, std::true_type{}, std::false_type{});
-        else run(std::false_type{}, std::false_type{}, std::true_type{});
-    } else if (NW == 4) run(std::true_type{}, std::true_type{}, std::true_type{});
-    else if (dw_wave) run(std::true_type{}, std::false_type{}, std::true_type{});
-    else run(std::false_type{}, std::true_type{}, std::true_type{});
+    if (NW == 4) run(std::true_type{}, std::true_type{});
+    else if (dw_wave) run(std::true_type{}, std::false_type{});
+    else run(std::false_type{}, std::true_type{});
 }
 
 
-template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN, int PWV = 0>
+template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN>
 int launch_dwproj_variant(const ConvK& k0, hipStream_t stream) {
-    constexpr int BN = WAVES_N * WN * 32, NT = (WAVES_M * WAVES_N + PWV) * 64;
+    constexpr int BN = WAVES_N * WN * 32, NT = WAVES_M * WAVES_N * 64;
     constexpr int SMEM = 3 * (13 * 1024) + 5 * BN * 64 + 3 * 128 * 64 + 1024;   // E slots, weight panels, A tiles, scratch
     ConvK k = k0;
     k.tiles_n = (k.Cout + BN - 1) / BN;
     k.nblk = (k.M / k.HW) * ((k.H + 7) / 8) * ((k.W + 15) / 16) * k.tiles_n;
-    UAVSAL_LDS_OPTIN((dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN, PWV>), SMEM);
-    const int cap = UAVSAL_PER_DEVICE(resident_grid(dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN, PWV>, SMEM, NT));
+    UAVSAL_LDS_OPTIN((dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>), SMEM);
+    const int cap = UAVSAL_PER_DEVICE(resident_grid(dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>, SMEM, NT));
     // The narrowest outputs (Cout <= 32: the 1536 -> 1 decoder projection) are bound by the serial depthwise /
     // request segments of a K step, not by the matrix pipe, and their 74 KB ring leaves room for two workgroups per
     // CU: when the tiles alone would leave resident slots empty, K is split over 2-4 workgroups per tile (raw partial
@@ -514,16 +495,13 @@ int launch_dwproj_variant(const ConvK& k0, hipStream_t stream) {
     }
     k.nblk *= k.ksplit;
     const int grid = k.nblk < cap ? k.nblk : cap;
-    hipLaunchKernelGGL((dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN, PWV>), dim3(grid), dim3(NT), SMEM, stream, k);
+    hipLaunchKernelGGL((dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>), dim3(grid), dim3(NT), SMEM, stream, k);
     if (k.ksplit > 1) return launch_splitk_reduce(k, PREC == UAVSAL_PREC_F16X3 ? F16X3_ACC_SCALE : 1.0f, stream);
     return uavsal_launch_status();
 }
 
 template <int PREC>
 int launch_dwproj(const ConvK& k, hipStream_t stream) {
-    static const int pw_mode = [] { const char* e = getenv("UAVSAL_DWPROJ_PW"); return e ? atoi(e) : 0; }();
-    if (k.Cout > 128 && ((pw_mode & 1) && PREC == UAVSAL_PREC_F32 || (pw_mode & 2) && PREC == UAVSAL_PREC_F16X3))
-        return launch_dwproj_variant<PREC, 2, 4, 2, 2, 4>(k, stream);   // + 4 producer waves (1: fp32, 2: split-fp16, 3: both)
     if (k.Cout > 128) return launch_dwproj_variant<PREC, 2, 4, 2, 2>(k, stream);   // 128 x 256, 8 waves
     if (k.Cout > 64) return launch_dwproj_variant<PREC, 2, 4, 2, 1>(k, stream);    // 128 x 128, 8 waves
     if (k.Cout > 32) return launch_dwproj_variant<PREC, 4, 2, 1, 1>(k, stream);    // 128 x 64,  8 waves

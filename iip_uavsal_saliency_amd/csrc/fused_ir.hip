@@ -390,8 +390,7 @@ int launch_fused_shape(const uavsal_fused_ir_desc* d, hipStream_t s) {
     constexpr int BTY = 4 * BPT;
     const int Ho = (d->H - 1) / S + 1, Wo = (d->W - 1) / S + 1;
     const long long big = (long long)d->n_img * ((Ho + BTY - 1) / BTY) * ((Wo + 15) / 16);
-    static const long long big_min = [] { const char* e = getenv("UAVSAL_FUSED_BIG_MIN"); return e ? atoll(e) : (long long)UAVSAL_FUSED_BIG_MIN; }();
-    const bool use_big = d->tile == 2 || (d->tile == 0 && BIG_AUTO && big >= big_min);
+    const bool use_big = d->tile == 2 || (d->tile == 0 && BIG_AUTO && big >= UAVSAL_FUSED_BIG_MIN);
     return use_big ? launch_fused<CIN, HID, COUT, S, EXPAND, HCB, 16, BPT>(d, s) : launch_fused<CIN, HID, COUT, S, EXPAND, HCS, 16, 1>(d, s);
 }
 

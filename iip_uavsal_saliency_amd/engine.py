@@ -14,7 +14,6 @@ stream.  PyTorch is used for device memory and streams, not for arithmetic.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, List, Optional
 
 import torch
@@ -64,29 +63,16 @@ class V:
 # projection launches (tools/dwproj_probe.py: 2 x 23 x 41 x 96 loses).  Round 2 had 8 x 45 x 80 x 512 here, which kept the
 # 384-hidden blocks at 45x80 (temporal sub-blocks, prior nets) unfused at one clip: fused they take 29-32 us instead of 44-46
 # (one clip fp32 4.521 -> 4.452 ms, f16x3 3.25 -> 3.19)
-FUSE_DW_MIN_WORK = int(os.environ.get("UAVSAL_FUSE_DW_MIN_WORK", str(1 << 20)))
+FUSE_DW_MIN_WORK = 1 << 20
 # ... and the share of a map's 8 x 16 pixel patches that lies outside the map must be small: the kernel computes whole
 # patches (45x80: 1.07, 23x40: 1.25, 12x20: 2.13).  Eight clips, fp32, features.8-17 on the 23x40 / 12x20 maps: 1259 us fused
 # against 911 us as depthwise + projection launches (features.17 alone 282 vs 128)
-FUSE_DW_MAX_WASTE = float(os.environ.get("UAVSAL_FUSE_DW_MAX_WASTE", "1.15"))
+FUSE_DW_MAX_WASTE = 1.15
 
 
 # the mid-channel fused block kernel (csrc/fused_mid.hip): workgroups (4 x 8 output patches) of a launch for which it is taken
-MID_MIN_WGS = int(os.environ.get("UAVSAL_MID_MIN_WGS", "1"))
-MID_MAX_WGS = int(os.environ.get("UAVSAL_MID_MAX_WGS", "288"))
-
-
-# features[14..17] (12x20 maps at 360x640: 12 launches of 6-22 us, none of them a round of the chip) as two half-batch chains on two lanes
-F16X3_WINO_STEPS = int(os.environ.get("UAVSAL_F16X3_WINO_STEPS", "1"))
-WINO_TAIL_PLANES = int(os.environ.get("UAVSAL_WINO_TAIL_PLANES", "0"))
-WINO_SEG = int(os.environ.get("UAVSAL_WINO_SEG", "0"))         # see the SRF-Net head in Engine._build (measured: not faster, off)
-TAIL_SPLIT = os.environ.get("UAVSAL_TAIL_SPLIT", "0") == "1"
-TAIL_SPLIT_FROM = int(os.environ.get("UAVSAL_TAIL_SPLIT_FROM", "14"))
-TAIL_SPLIT_MAX_FRAMES = int(os.environ.get("UAVSAL_TAIL_SPLIT_MAX_FRAMES", "16"))
-PRIORS_OB_LANE = int(os.environ.get("UAVSAL_PRIORS_OB_LANE", "1"))      # 1: both prior nets on lane 1 (two event operations fewer on the main stream: 4.29 -> 4.26 ms at one clip); 2: a lane each
-ASPP_DW_MERGE = os.environ.get("UAVSAL_ASPP_DW_MERGE", "1") == "1"      # 0: the three dilated ASPP depthwise convs as three launches on three lanes
-DW_DOT = os.environ.get("UAVSAL_DW_DOT", "1") == "1"       # 0: the one-channel projection of conv_out_st as a dwproj GEMM + reduce launch
-_TILE_OVERRIDE = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in os.environ.get("UAVSAL_TILE_OVERRIDE", "").split(",") if "=" in kv}
+MID_MIN_WGS = 1
+MID_MAX_WGS = 288
 
 
 class OpView:
@@ -156,8 +142,7 @@ def _dwproj_patch_waste(h, w):
     return ((h + 7) // 8 * 8) * ((w + 15) // 16 * 16) / float(h * w)
 
 
-BLOCK_CHUNK_BYTES = int(float(os.environ.get("UAVSAL_BLOCK_CHUNK_GB", "6")) * (1 << 30))     # see Engine.ir_block
-ARENA = os.environ.get("UAVSAL_ARENA", "1") == "1"          # 0: one allocation per activation for the life of the plan (rounds 1-4)
+BLOCK_CHUNK_BYTES = 6 << 30                                   # see Engine.ir_block
 ARENA_ALIGN = 1024                                            # floats (4 KB): every arena buffer starts on a page
 
 
@@ -303,19 +288,16 @@ class Engine:
         self.split_mode = (precision == "f16x3" and not self.prec_overrides
                            and (bool(presplit) if presplit is not None else n_seq >= 4))
         # exact-fp32 mode: the dense 3x3 convs (conv_last, the ConvTWA gate conv) as Winograd F(2x2, 3x3)
-        # (model.winograd, default on; UAVSAL_WINOGRAD=0 switches it off, UAVSAL_WINOGRAD_STEPS = 0 / 8 / 11: the per-step
-        # convolutions of the recurrence too, with that GEMM tile)
-        self.winograd = ((precision == "f32" or bool(getattr(model, "prec_overrides", None))) and bool(getattr(model, "winograd", True))
-                         and os.environ.get("UAVSAL_WINOGRAD", "1") != "0")
-        self.winograd_steps = int(os.environ.get("UAVSAL_WINOGRAD_STEPS", "-1"))     # -1: by the number of clips (below)
+        # (model.winograd, default on; the per-step convolutions of the recurrence too)
+        self.winograd = (precision == "f32" or bool(getattr(model, "prec_overrides", None))) and bool(getattr(model, "winograd", True))
         # output tile of the transforms: 2 = F(2x2, 3x3), 4 = F(4x4, 3x3); for the all-frames convs / for the recurrence steps
         # NOTE: with the defaults the arithmetic of "exact fp32" depends on the number of clips in the call -- F(2x2) steps below
         # four clips, F(4x4) (coefficients up to 8, ~20x less accurate per conv, map moves by ~5e-5) from four up -- so the same
         # clip gives maps that differ by ~1e-4 when batched differently (all inside the 5e-4 gate).  `model.winograd_r = 2`
         # (also for the steps) is the strict setting: F(2x2) everywhere, whatever the batch; `model.winograd = False`: direct.
-        self.winograd_r = int(getattr(model, "winograd_r", None) or os.environ.get("UAVSAL_WINOGRAD_R", "4"))
-        self.winograd_step_r = int(getattr(model, "winograd_step_r", None) or (2 if getattr(model, "winograd_r", None) == 2 else 0)
-                                   or os.environ.get("UAVSAL_WINOGRAD_STEP_R", "0"))   # 0: by the number of clips
+        self.winograd_r = int(getattr(model, "winograd_r", None) or 4)
+        self.winograd_step_r = int(getattr(model, "winograd_step_r", None)
+                                   or (2 if getattr(model, "winograd_r", None) == 2 else 0))   # 0: by the number of clips
         self.fuse_blocks = bool(getattr(model, "fuse_blocks", True))
         self._split_want = set()
         self._no_shadow = set()
@@ -337,8 +319,8 @@ class Engine:
         self._lane = 0
         self.plan = None
         # activation arena (liveness-based): see _buf / _touch / _place_arena
-        self.use_arena = ARENA and bool(getattr(model, "arena", True))
-        self.arena_debug = bool(getattr(model, "arena_debug", False)) or os.environ.get("UAVSAL_ARENA_DEBUG", "0") == "1"
+        self.use_arena = bool(getattr(model, "arena", True))
+        self.arena_debug = bool(getattr(model, "arena_debug", False))
         self._refs: Dict[object, _ArenaRef] = {}
         self._arena = None
         self._recording = False
@@ -748,11 +730,9 @@ class Engine:
         # GEMMs on a side lane run beside grid-filling GEMMs of the main lane: the 64 x 64 instance with 32-float K stages
         # needs 32 KB of LDS and 122 VGPRs, so one of its workgroups fits on a CU next to two of the main lane's
         # (64 KB, 155 VGPRs each) instead of waiting for them to retire
-        side_tile = int(os.environ.get("UAVSAL_SIDE_TILE", "11"))      # (5.155 vs 5.17 ms per step, same box, two runs each)
-        if side_tile and self._lane != 0 and pn == "f32" and epi == L.EPI_AFFINE and dw is None and cin % 32 == 0:
-            d.tile = side_tile
-        if name in _TILE_OVERRIDE:           # experiments: UAVSAL_TILE_OVERRIDE="ctx.0.pw=11,ctx.1.pl=11"
-            d.tile = _TILE_OVERRIDE[name]
+        # (5.155 vs 5.17 ms per step, same box, two runs each)
+        if self._lane != 0 and pn == "f32" and epi == L.EPI_AFFINE and dw is None and cin % 32 == 0:
+            d.tile = 11
         if out2 is not None:
             d.out2, d.ld2 = out2.ptr, out2.ld
         if self.stream_k:
@@ -792,13 +772,10 @@ class Engine:
                                 out2=self._ov(out2, d.o_img_stride))
         self._add(self.lib.uavsal_plan_add_conv, d, "plan_add_conv(%s)" % name)
 
-    def conv3_wino(self, name, a: V, conv, bn, out: V, act, wslice=None, n_img=None, strides=None, twa=None, gemm_tile=0, r=2,
-                   segs=None):
+    def conv3_wino(self, name, a: V, conv, bn, out: V, act, wslice=None, n_img=None, strides=None, twa=None, gemm_tile=0, r=2):
         """Dense 3x3 conv (stride 1, padding 1) as Winograd F(r x r, 3x3), exact-fp32 mode only: input transform, ONE GEMM
         launch over the (r + 2)^2 transform planes (per-plane weights), output transform with the epilogue -- 2.25x (r = 2)
-        or 4x (r = 4) fewer MFMA FLOPs than the implicit GEMM (csrc/winograd.hip).  `twa=(x_t, pre_t)`: ConvTWA update in the output transform.
-        `segs`: the input is the channel concatenation of these views, each resized to `a`'s map size inside the input transform
-        when it lives on a smaller map (uavsal_wino_desc.n_seg); `a` then only carries the shape (its `t` is None)."""
+        or 4x (r = 4) fewer MFMA FLOPs than the implicit GEMM (csrc/winograd.hip).  `twa=(x_t, pre_t)`: ConvTWA update in the output transform."""
         cin, cout = a.c, out.c
         n = a.n if n_img is None else n_img
         hw = a.h * a.w
@@ -808,53 +785,38 @@ class Engine:
         st = strides or {}
         v = self._scr("WV", pp, mp, 1, cin)
         mm = self._scr("WM", pp, mp, 1, cout)
-        in_bytes = 4.0 * (sum(sg.n * sg.h * sg.w * sg.c for sg in segs) if segs else n * hw * cin)
-        self._meta(kind="wino_in", name=name + ".xin", flops=0.0, bytes=in_bytes + 4.0 * float(pp) * tiles * cin)
+        self._meta(kind="wino_in", name=name + ".xin", flops=0.0, bytes=4.0 * n * hw * cin + 4.0 * float(pp) * tiles * cin)
         self.op_args[-1].update(triple=name + ".xout")
-        self._touch(a, v, *(segs or ()))
+        self._touch(a, v)
         if not self._dry:
             wi = L.WinoDesc()
-            if segs:
-                assert sum(sg.c for sg in segs) == cin and len(segs) <= 3 and not strides
-                wi.n_seg = len(segs)
-                for i, sg in enumerate(segs):
-                    wi.seg_in[i], wi.seg_ld[i], wi.seg_c[i], wi.seg_H[i], wi.seg_W[i] = sg.ptr, sg.ld, sg.c, sg.h, sg.w
-            else:
-                wi.inp, wi.ldi, wi.in_img_stride = a.ptr, a.ld, st.get("a", hw)
+            wi.inp, wi.ldi, wi.in_img_stride = a.ptr, a.ld, st.get("a", hw)
             wi.out, wi.ldo = v.ptr, cin
             wi.n_img, wi.H, wi.W, wi.C, wi.Mp, wi.R = n, a.h, a.w, cin, mp, r
             self._add(self.lib.uavsal_plan_add_wino_input, wi, "plan_add_wino_input(%s)" % name)
-        # WINO_TAIL_PLANES (experiment): the planes that only fill the GEMM's last, partial round of 128 x 128 tiles (36 planes x
-        # 15 x 2 tiles on 512 resident workgroups = 2.1 rounds) as a second launch on 64 x 64 tiles
-        tail = WINO_TAIL_PLANES if (gemm_tile in (0, 8) and twa is None and pp > WINO_TAIL_PLANES > 0) else 0
-        plane_parts = [(0, pp - tail, gemm_tile, name)] + ([(pp - tail, tail, 11, name + ".tail")] if tail else [])
-        if not self._dry:
             key = ("wino", id(conv), wslice, r)
             if key not in self._wcache:
                 w = conv.weight.detach()
                 if wslice is not None:
                     w = w[:, wslice[0]:wslice[1]]
                 self._wcache[key] = self._dev(P.pack_wino_weight(w, r))
-        wgs = P.roundup(cout, 32) * P.roundup(cin, 32)
-        for (p0, pn, tile_, nm_) in plane_parts:
-            self._meta(kind="conv1", name=nm_, flops=2.0 * pn * tiles * cin * cout,
-                       bytes=4.0 * pn * (tiles * (cin + cout) + cin * cout), M=pn * mp, K=cin, Nc=cout,
-                       direct_flops=2.0 * n * hw * cin * cout * 9 * pn / pp)
-            self._touch(v, mm)
-            self.op_args[-1].update(triple=name + ".xout")
-            if self._dry:
-                continue
+        self._meta(kind="conv1", name=name, flops=2.0 * pp * tiles * cin * cout,
+                   bytes=4.0 * pp * (tiles * (cin + cout) + cin * cout), M=pp * mp, K=cin, Nc=cout,
+                   direct_flops=2.0 * n * hw * cin * cout * 9)
+        self._touch(v, mm)
+        self.op_args[-1].update(triple=name + ".xout")
+        if not self._dry:
             d = L.ConvDesc()
-            d.a, d.lda, d.a_img_stride = v.ptr + 4 * p0 * mp * cin, cin, mp
-            d.w, d.w_group_stride = self._wcache[key].data_ptr() + 4 * p0 * wgs, wgs
-            d.out, d.ldc, d.o_img_stride = mm.ptr + 4 * p0 * mp * cout, cout, mp
-            d.n_img, d.H, d.W, d.Cin, d.Cout, d.taps = pn, mp, 1, cin, cout, 1
-            d.prec, d.act, d.epi, d.tile = L.PREC["f32"], L.ACT_NONE, L.EPI_AFFINE, tile_      # Winograd plans are exact fp32
+            d.a, d.lda, d.a_img_stride = v.ptr, cin, mp
+            d.w, d.w_group_stride = self._wcache[key].data_ptr(), P.roundup(cout, 32) * P.roundup(cin, 32)
+            d.out, d.ldc, d.o_img_stride = mm.ptr, cout, mp
+            d.n_img, d.H, d.W, d.Cin, d.Cout, d.taps = pp, mp, 1, cin, cout, 1
+            d.prec, d.act, d.epi, d.tile = L.PREC["f32"], L.ACT_NONE, L.EPI_AFFINE, gemm_tile      # Winograd plans are exact fp32
             d.err = self._err
             m_ = self.ops_meta[-1]
             m_["split"], m_["tile"], m_["streamk"], m_["dwproj"] = False, int(self.lib.uavsal_conv_tile(C.byref(d))), 0, 0
             m_["prec"] = "f32"
-            self._add(self.lib.uavsal_plan_add_conv, d, "plan_add_conv(%s)" % nm_)
+            self._add(self.lib.uavsal_plan_add_conv, d, "plan_add_conv(%s)" % name)
         self._meta(kind="wino_out", name=name + ".xout", flops=0.0, bytes=4.0 * (float(pp) * tiles * cout + n * hw * cout))
         self._touch(mm, out, *(twa or ()), *((a,) if twa is not None else ()))
         if out.key is not None and self._dry:
@@ -875,9 +837,10 @@ class Engine:
                 wo.aux, wo.ldx, wo.aux_img_stride = pre.ptr, pre.ld, st.get("x", hw)
                 wo.hprev, wo.ldh, wo.h_img_stride = a.ptr, a.ld, st.get("a", hw)
             ai = st.get("a", hw)
+            # (`segs`: the views of a segmented input, uavsal_wino_desc.n_seg -- a form of the ABI the plans do not take, so
+            # always None; the field stays in the record that tests/test_plan_ops_fp64.py reads)
             self.op_args[-1].update(kind="wino", triple_first=name + ".xin", conv=conv, bn=bn, act=act, wslice=wslice, r=r, cin=cin,
-                                    cout=cout, a=None if segs else self._ov(a, ai), segs=[self._ov(sg) for sg in segs] if segs else None,
-                                    out=self._ov(out, wo.out_img_stride),
+                                    cout=cout, a=self._ov(a, ai), segs=None, out=self._ov(out, wo.out_img_stride),
                                     twa=None if twa is None else (self._ov(twa[0], wo.res_img_stride), self._ov(twa[1], wo.aux_img_stride)))
             self._add(self.lib.uavsal_plan_add_wino_output, wo, "plan_add_wino_output(%s)" % name)
 
@@ -1081,7 +1044,7 @@ class Engine:
             e = x
             dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1], seq[2]
         ho, wo = (x.h - 1) // stride + 1, (x.w - 1) // stride + 1
-        if (DW_DOT and out.c == 1 and stride == 1 and dil == 1 and blk.expand_ratio != 1 and not blk.use_res_connect
+        if (out.c == 1 and stride == 1 and dil == 1 and blk.expand_ratio != 1 and not blk.use_res_connect
                 and blk.hidden % 256 == 0 and blk.hidden <= 2048 and self.fuse_dw is not False):
             self.dw_dot(name + ".dwpl", e, dwc, dwbn, pl, plbn, out, final_act)      # a dot product per pixel: bandwidth-bound
             return
@@ -1192,9 +1155,7 @@ class Engine:
         # where the prior nets' side lane forks off: beside features.11-17 while those launches are latency-bound (one round of the
         # chip each: up to two clips of 8 frames; 4.26 -> 4.25 ms at one clip), beside features.5-10 from there on (8 clips: 27.92
         # vs 27.97 ms).  A function of the frame count only
-        priors_at = int(os.environ.get("UAVSAL_PRIORS_AT", "11" if N <= 16 else "5"))
-        tail_halves = TAIL_SPLIT and N >= 2 and N <= TAIL_SPLIT_MAX_FRAMES
-        tail_chain = []
+        priors_at = 11 if N <= 16 else 5
         for i in range(1, 18):
             if i == priors_at:
                 self._mark("backbone.0-%d" % (priors_at - 1), s0)
@@ -1207,51 +1168,33 @@ class Engine:
                 cb = self._buf("cb192", N, h, w, 64 * num_cb) if num_cb else None
                 cbs = self._buf("cb_static", 1, h, w, 128) if self.static_priors else cb
                 self._no_shadow.add("cb_static")
-                forked = set()
-                for lane, nm, src, dst, c, on in (
-                        (1, "gauss", "cb0_in", g0, 8, use_g),
-                        (PRIORS_OB_LANE, "ob", "cb1_in", o0, 20, use_o)):
+                # both nets on lane 1: one fork / join pair (two event operations fewer on the main stream than a lane each:
+                # 4.29 -> 4.26 ms at one clip)
+                self._priors_forked = use_g or use_o
+                if self._priors_forked:
+                    self.fork(1)
+                for nm, src, dst, c, on in (("gauss", "cb0_in", g0, 8, use_g), ("ob", "cb1_in", o0, 20, use_o)):
                     if not on:
                         continue
                     blocks = m.gauss_cb_layer if nm == "gauss" else m.ob_cb_layer
                     mid = self._buf(nm + "1", Np, h, w, 64)
                     sl = cb_off[nm]
-                    if lane not in forked:               # (both nets on lane 1: one fork / join pair)
-                        self.fork(lane)
-                        forked.add(lane)
-                    else:
-                        L.check(self.lib.uavsal_plan_set_lane(self.plan, lane), "plan_set_lane") if not self._dry else None
-                        self._lane = lane
                     self.layout(nm + ".in", None if self._dry else getattr(self, src).data_ptr(), dst, Np, c, hw, c, 1,
                                 bind=(src[:3], 0))
                     self.ir_block(nm + ".0", dst, blocks[0], mid)
                     self.ir_block(nm + ".1", mid, blocks[1], cbs.slice(sl, 64))
                     if self.static_priors:      # frame 0 of the net's output -> every frame (same-size resize: an exact copy)
                         self.bilinear(nm + ".bcast", cbs.slice(sl, 64), cb.slice(sl, 64), src_mod=1)
+                if self._priors_forked:
                     self.main()
-                self._prior_lanes = sorted(forked)
                 self._mark("priors_side", s0)
                 s0 = len(self.ops_meta)
             blk = feats[i]
             ho, wo = (x.h - 1) // blk.stride + 1, (x.w - 1) // blk.stride + 1
             y = self._buf("f%d" % i, N, ho, wo, blk.cout)
-            if tail_halves and i >= TAIL_SPLIT_FROM:
-                # latency-bound launches on the 1/32-scale map (each far below one round of the chip): the two halves of the
-                # frames run as two independent chains, the first on lane 2, the second here (blocks are per-frame arithmetic)
-                tail_chain.append((i, x, blk, y))
-            else:
-                self.ir_block("features.%d" % i, x, blk, y)
+            self.ir_block("features.%d" % i, x, blk, y)
             x = y
             tapsrc[i] = y
-        if tail_chain:
-            n0 = N // 2
-            self.fork(2)
-            for (i, xi, blk, yi) in tail_chain:
-                self.ir_block("features.%d/a" % i, xi.frames(0, n0), blk, yi.frames(0, n0))
-            self.main()
-            for (i, xi, blk, yi) in tail_chain:
-                self.ir_block("features.%d/b" % i, xi.frames(n0, N - n0), blk, yi.frames(n0, N - n0))
-            self.join(2)
         c3, c4, c5 = tapsrc[6], tapsrc[13], tapsrc[17]
         self.named.update(c3=c3, c4=c4, c5=c5)
         self._mark("backbone.%d-17" % priors_at, s0)
@@ -1264,82 +1207,47 @@ class Engine:
         # 1/32 and 1/16 scale maps: spread them over lanes so they fill the chip together
         x5 = self._buf("x5", N, c5.h, c5.w, 256)
         x4 = self._buf("x4", N, c4.h, c4.w, 128)
-        # conv_last reads cat[interpolate(x5), interpolate(x4), conv_lv3(c3)] (model.py:151-156).  Winograd plans: the input
-        # transform reads the three tensors itself and resizes the two small ones on the fly (uavsal_wino_desc.n_seg) -- no resize
-        # launches, no concat buffer (WINO_SEG = 0: the round-4 form; 1: conv_lv4 / conv_lv3 stay on their side lane)
-        wino_last = self.winograd and self._prec_for("conv_last") == "f32"
-        seg_mode = WINO_SEG if wino_last else 0
-        cat = self._buf("srf_cat", N, h, w, 448) if not seg_mode else None
-        lv3 = self._buf("lv3", N, h, w, 64) if seg_mode else cat.slice(384, 64)
+        # conv_last reads cat[interpolate(x5), interpolate(x4), conv_lv3(c3)] (model.py:151-156)
+        cat = self._buf("srf_cat", N, h, w, 448)
         branches = (sf.lv5_aspp2, sf.lv5_aspp3, sf.lv5_aspp4)
-        aspp_lanes = int(os.environ.get("UAVSAL_ASPP_LANES", "1"))
-        fork = self.fork if aspp_lanes else (lambda lane: None)
-        join = self.join if aspp_lanes else (lambda lane: None)
-        aspp_dw_merged = False
-        if int(os.environ.get("UAVSAL_ASPP_MERGE", "1")) and all(b.expand_ratio != 1 for b in branches):
-            # the three dilated branches expand the SAME map with the same shape: one GEMM with their output channels
-            # side by side (320 -> 3 x 1920: 675 tiles instead of three launches of 225 fighting for the chip on three
-            # lanes), then every branch's depthwise + projection on its own lane, reading its slice
-            hid = branches[0].hidden
-            e3 = self._scr("E3", N, c5.h, c5.w, 3 * hid)
-            self.conv("aspp.pw", c5, [b.conv[0][0] for b in branches], [b.conv[0][1] for b in branches], e3, R6)
-            if self.prec_name == "f32" and int(os.environ.get("UAVSAL_ASPP_GROUP", "1")) and hid % 32 == 0:
-                # ... and their three projections (1920 -> 256 each, different inputs) are ONE launch too: output-channel
-                # groups with their own A columns (uavsal_conv_desc.n_group), K shared out over workgroups
-                d3 = self._scr("D3", N, c5.h, c5.w, 3 * hid)
-                if ASPP_DW_MERGE and all(b.stride == 1 for b in branches) and hid % 64 == 0:
-                    # ... and so are their three dilated depthwise convs: channel groups with their own dilation in the whole-map
-                    # kernel (uavsal_dw_desc.dil_group_c).  Three launches on three lanes cost six event operations on the main
-                    # stream (~25 us between aspp.pw and aspp.pl) for ~10 us of overlap
-                    self.dw("aspp.dw", e3, [b.conv[1][0] for b in branches], [b.conv[1][1] for b in branches], d3, 1,
-                            [getattr(b, "dilation", 1) for b in branches])
-                    aspp_dw_merged = True
-                else:
-                    for bi, b in enumerate(branches):
-                        fork(3 + bi)
-                        self.dw("aspp%d.dw" % (bi + 2), e3.slice(bi * hid, hid), b.conv[1][0], b.conv[1][1], d3.slice(bi * hid, hid),
-                                b.stride, getattr(b, "dilation", 1))
-                        self.main()
-                aspp_grouped = d3
-            else:
-                aspp_grouped = None
-                for bi, b in enumerate(branches):
-                    fork(3 + bi)
-                    self.ir_block("aspp%d" % (bi + 2), c5, b, aspp.slice(256 * (bi + 1), 256), expanded=e3.slice(bi * hid, hid))
-                    self.main()
+        # the three dilated branches expand the SAME map with the same shape: one GEMM with their output channels side by side
+        # (320 -> 3 x 1920: 675 tiles instead of three launches of 225 fighting for the chip on three lanes)
+        hid = branches[0].hidden
+        e3 = self._scr("E3", N, c5.h, c5.w, 3 * hid)
+        self.conv("aspp.pw", c5, [b.conv[0][0] for b in branches], [b.conv[0][1] for b in branches], e3, R6)
+        aspp_grouped = self.prec_name == "f32"
+        if aspp_grouped:
+            # fp32: their three dilated depthwise convs are ONE launch too -- channel groups with their own dilation in the
+            # whole-map kernel (uavsal_dw_desc.dil_group_c; three launches on three lanes cost six event operations on the main
+            # stream, ~25 us between aspp.pw and aspp.pl, for ~10 us of overlap) -- and so are their three projections (1920 ->
+            # 256 each, different inputs): output-channel groups with their own A columns (uavsal_conv_desc.n_group), K shared
+            # out over workgroups
+            d3 = self._scr("D3", N, c5.h, c5.w, 3 * hid)
+            self.dw("aspp.dw", e3, [b.conv[1][0] for b in branches], [b.conv[1][1] for b in branches], d3, 1,
+                    [getattr(b, "dilation", 1) for b in branches])
         else:
-            aspp_grouped = None
+            # every branch's depthwise + projection on its own lane, reading its slice
             for bi, b in enumerate(branches):
-                fork(3 + bi)
-                self.ir_block("aspp%d" % (bi + 2), c5, b, aspp.slice(256 * (bi + 1), 256))
+                self.fork(3 + bi)
+                self.ir_block("aspp%d" % (bi + 2), c5, b, aspp.slice(256 * (bi + 1), 256), expanded=e3.slice(bi * hid, hid))
                 self.main()
-        if seg_mode != 2:
-            fork(6)
+        self.fork(6)
         self.conv("conv_lv4", c4, sf.conv_lv4[0], sf.conv_lv4[1], x4, R6)
-        if not seg_mode:
-            self.bilinear("up_c4", x4, cat.slice(256, 128))
-        self.conv("conv_lv3", c3, sf.conv_lv3[0], sf.conv_lv3[1], lv3, R6)
-        if seg_mode != 2:
-            self.main()
+        self.bilinear("up_c4", x4, cat.slice(256, 128))
+        self.conv("conv_lv3", c3, sf.conv_lv3[0], sf.conv_lv3[1], cat.slice(384, 64), R6)
+        self.main()
         self.conv("aspp1", c5, sf.lv5_aspp1[0], sf.lv5_aspp1[1], aspp.slice(0, 256), R6)
-        if not aspp_dw_merged:
-            join(3)
-            join(4)
-            join(5)
-        if aspp_grouped is not None:
-            hid = branches[0].hidden
-            self.conv("aspp.pl", aspp_grouped.slice(0, hid), [b.conv[2] for b in branches], [b.conv[3] for b in branches],
+        if aspp_grouped:
+            self.conv("aspp.pl", d3.slice(0, hid), [b.conv[2] for b in branches], [b.conv[3] for b in branches],
                       aspp.slice(256, 768), NONE, cout=768, n_group=256)
+        else:
+            for lane in (3, 4, 5):
+                self.join(lane)
         self.conv("conv_lv5", aspp, sf.conv_lv5[0], sf.conv_lv5[1], x5, R6)
-        if not seg_mode:
-            self.bilinear("up_c5", x5, cat.slice(0, 256))
-        if seg_mode != 2:
-            join(6)
+        self.bilinear("up_c5", x5, cat.slice(0, 256))
+        self.join(6)
         x = self._buf("sfnet", N, h, w, 256)
-        if seg_mode:
-            self.conv3_wino("conv_last", V(None, N, h, w, 448), sf.conv_last[0], sf.conv_last[1], x, R6, r=self.winograd_r,
-                            segs=[x5, x4, lv3])
-        elif wino_last:
+        if self.winograd and self._prec_for("conv_last") == "f32":
             self.conv3_wino("conv_last", cat, sf.conv_last[0], sf.conv_last[1], x, R6, r=self.winograd_r)
         else:
             self.conv("conv_last", cat, sf.conv_last[0], sf.conv_last[1], x, R6, taps=9)
@@ -1353,15 +1261,13 @@ class Engine:
             r = self._buf("st%d_red" % i, N, h, w, 32)
             dif = self._buf("st%d_dif" % i, N, h, w, 64)
             t1 = self._buf("st%d_te1" % i, N, h, w, 32)
-            # temporal branch (small launches): st_lanes 1 = all of it on lane 6, next to the spatial branch's big GEMMs;
-            # 2 = its first two launches on the main lane (they would otherwise queue behind a grid-filling GEMM for
-            # the whole of it), the rest on lane 6; 0 = no side lane
-            # (round 2, same box, two runs each: 5.26 / 5.25 / 5.22 ms for 1 / 0 / 2.  Round 5, one clip: 4.234 / 4.221 for 2 / 0 --
-            # the fork / join pair costs more than the overlap buys while the spatial branch's GEMMs fill the chip anyway; eight
-            # clips: 27.97-28.10 / 28.31 for 2 / 0.  A function of the frame count only)
-            st_lanes = int(os.environ.get("UAVSAL_ST_LANES", "0" if N <= 8 else "2"))
-            if st_lanes == 1:
-                self.fork(6)
+            # temporal branch (small launches): from nine frames up its first two launches on the main lane (they would
+            # otherwise queue behind a grid-filling GEMM for the whole of it), the rest on lane 6 next to the spatial branch's
+            # big GEMMs; up to eight frames no side lane
+            # (round 2, same box, two runs each: 5.26 / 5.25 / 5.22 ms for all on lane 6 / no lane / this split.  Round 5, one
+            # clip: 4.234 / 4.221 for split / no lane -- the fork / join pair costs more than the overlap buys while the spatial
+            # branch's GEMMs fill the chip anyway; eight clips: 27.97-28.10 / 28.31 for split / no lane)
+            st_lane = N > 8
             self.conv("st%d.reduce" % i, x, te.reduce_conv[0], te.reduce_conv[1], r, R6)
             self._meta(kind="tdiff", name="st%d.tdiff" % i, flops=0.0, bytes=4.0 * N * hw * 96)
             self._touch(r, dif)
@@ -1371,13 +1277,13 @@ class Engine:
                 d.n_img, d.HW, d.C, d.seq_len = N, hw, 32, self.seq_len
                 self.op_args[-1].update(a=self._ov(r), out=self._ov(dif), seq_len=self.seq_len)
                 self._add(self.lib.uavsal_plan_add_tdiff, d, "plan_add_tdiff")
-            if st_lanes == 2:
+            if st_lane:
                 self.fork(6)
             self.ir_block("st%d.sub" % i, dif, te.sub_conv, t1)
-            if st_lanes:
+            if st_lane:
                 self.main()
             self.ir_block("st%d.sp" % i, x, st.stconv_sp.spconv, sp)
-            if st_lanes:
+            if st_lane:
                 self.join(6)
             ssum = self._buf("st%d_sum" % i, N, h, w, 256)
             self.conv("st%d.te_last" % i, t1, te.last_conv[0], te.last_conv[1], ssum, R6, res=sp)   # x_sp + x_te
@@ -1417,8 +1323,8 @@ class Engine:
                     self.bilinear("ctx.up", cx2, cslot, src_mod=B, src_div=1)
                 else:                            # independent clips: frame (c,t) <- clip c
                     self.bilinear("ctx.up", cx2, cslot, src_mod=N, src_div=self.ctx_T)
-            for lane in self._prior_lanes:
-                self.join(lane)
+            if self._priors_forked:
+                self.join(1)
             self.ir_block("fucb", cb, m.fucb_layer[0], fu.slice(256, 64))
             self.named["fust_in_cb"] = fu.slice(256, 64)
             xf = self._buf("prefuse", N, h, w, 256)
@@ -1460,16 +1366,16 @@ class Engine:
             # fewer MFMA FLOPs than the direct 3x3 and it beats the split-fp16 implicit GEMM there: 136 vs 160 us per step at eight
             # clips, 17.89 -> 17.67 ms per eight-clip step.  Not more accurate: per launch at eight clips (tests/test_plan_ops_fp64.py,
             # teacher-forced against float64) its worst error is 2.0e-6 against 1.0e-6 for the direct split-fp16 step, both well inside
-            # their bounds.  F16X3_WINO_STEPS = 0: the direct split-fp16 step)
-            f16_wino = (F16X3_WINO_STEPS and self.prec_name == "f16x3" and not self.prec_overrides and self.n_seq >= 4
+            # their bounds.  `model.winograd = False`: the direct split-fp16 step)
+            f16_wino = (self.prec_name == "f16x3" and not self.prec_overrides and self.n_seq >= 4
                         and bool(getattr(m, "winograd", True)))
-            if (self.winograd or f16_wino) and self.winograd_steps and (f16_wino or self._prec_for("twa.step") == "f32"):
+            if (self.winograd or f16_wino) and (f16_wino or self._prec_for("twa.step") == "f32"):
                 # one clip: 920 tiles of 2x2 fill the chip with 128x128 GEMM tiles; four clips and more: F(4x4) (1.78x
                 # fewer FLOPs, smaller transforms) on 64x64 tiles (measured: 4.54 vs 4.61 ms at one clip, 29.47 vs 28.80 at eight)
                 many = self.n_seq >= 4
                 self.conv3_wino("twa.step%d" % t, a, rc, None, ro.frames(t, self.n_seq), NONE, wslice=(256, 512),
                                 n_img=self.n_seq, strides=strides, twa=(xf.frames(t, self.n_seq), pre.frames(t, self.n_seq)),
-                                gemm_tile=self.winograd_steps if self.winograd_steps > 0 else (11 if many else 8),
+                                gemm_tile=11 if many else 8,
                                 r=self.winograd_step_r or (4 if many else 2))
                 continue
             self.conv("twa.step%d" % t, a, rc, None, ro.frames(t, self.n_seq), NONE, taps=9, wslice=(256, 512),

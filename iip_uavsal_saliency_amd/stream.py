@@ -8,7 +8,6 @@ maps are resized / normalised / quantised by `uavsal_postprocess`."""
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
@@ -34,8 +33,7 @@ def _host_streams(dev, n):
     end up on one queue, and the overlap is gone without a word (measured: 2077 frames/s -> 1851, below the 1888 of the plain
     loop; profiles/r5_experiments.md).  High-priority streams draw from a queue pool of their own, which nothing else in this
     package uses; consecutive ones get different queues."""
-    prio = int(os.environ.get("UAVSAL_HOST_STREAM_PRIORITY", "-1"))
-    return [torch.cuda.Stream(dev, priority=prio) for _ in range(n)]
+    return [torch.cuda.Stream(dev, priority=-1) for _ in range(n)]
 
 
 _CACHE_KEYS = ("_stream_replicas", "_stream_streams", "_stream_copy")

@@ -394,24 +394,18 @@ def test_eight_clips(prec):
     _walk(m, 8, 8, 360, 640, prec, "B " + prec)
 
 
-def test_f16x3_step_forms():
+def test_f16x3_step_forms_via_model_winograd():
     """B / f16x3: the recurrence step as fp32 Winograd F(4x4) (default) and as the direct split-fp16 step
-    (F16X3_WINO_STEPS = 0); both within their bounds, and their accuracy in units of B reported."""
+    (`model.winograd = False`); both within their bounds, and their accuracy in units of B reported."""
     rel = {}
-    old = E.F16X3_WINO_STEPS
-    try:
-        for form, flag in (("wino F(4x4)", 1), ("direct f16x3", 0)):
-            E.F16X3_WINO_STEPS = flag
-            m = _model(8)
-            m._engines.clear()
-            w = _walk(m, 8, 8, 360, 640, "f16x3", "B f16x3 steps=" + form)
-            steps = {k.split(".xout")[0]: v for k, v in w.step_cmp.items()}
-            assert sorted(steps) == ["twa.step%d" % t for t in range(8)], sorted(steps)
-            kinds = {w.eng.op_args[w.eng._op_idx[k + (".xout" if flag else "")]]["kind"] for k in steps}
-            assert kinds == ({"wino"} if flag else {"conv3"}), kinds
-            rel[form] = (max(v[0] for v in steps.values()), max(v[1] for v in steps.values()))
-    finally:
-        E.F16X3_WINO_STEPS = old
+    for form, flag in (("wino F(4x4)", 1), ("direct f16x3", 0)):
+        m = _model(8, winograd=bool(flag))
+        w = _walk(m, 8, 8, 360, 640, "f16x3", "B f16x3 steps=" + form)
+        steps = {k.split(".xout")[0]: v for k, v in w.step_cmp.items()}
+        assert sorted(steps) == ["twa.step%d" % t for t in range(8)], sorted(steps)
+        kinds = {w.eng.op_args[w.eng._op_idx[k + (".xout" if flag else "")]]["kind"] for k in steps}
+        assert kinds == ({"wino"} if flag else {"conv3"}), kinds
+        rel[form] = (max(v[0] for v in steps.values()), max(v[1] for v in steps.values()))
     print("[plan-ops-fp64] B f16x3 twa.step0-7, max |err| and worst err / (direct fp32 bound): %s" % ", ".join(
         "%s %.3g, %.3g" % (k, *v) for k, v in rel.items()))
 
