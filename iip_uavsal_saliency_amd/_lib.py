@@ -143,8 +143,17 @@ class ScoreDesc(C.Structure):
                 ("out", _f), ("n_keys", C.c_int32), ("keys", C.c_int32 * SCORE_NKEY)]
 
 
+LETTERBOX_HWC, LETTERBOX_CHW = 0, 1
+
+
+class LetterboxDesc(C.Structure):
+    _fields_ = [("src", _f), ("dst", _f), ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("img_pitch", C.c_int64),
+                ("n_img", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("R", C.c_int32), ("C", C.c_int32),
+                ("layout", C.c_int32), ("swap_rb", C.c_int32)]
+
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
-              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc]
+              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc]
 
 # every symbol include/uavsal_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -163,6 +172,7 @@ SYMBOLS = [
     ("uavsal_tsum", C.c_int, [C.POINTER(TsumDesc), C.c_void_p]),
     ("uavsal_layout", C.c_int, [C.POINTER(LayoutDesc), C.c_void_p]),
     ("uavsal_postprocess", C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
+    ("uavsal_letterbox_u8", C.c_int, [C.POINTER(LetterboxDesc), C.c_void_p]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),

@@ -331,6 +331,7 @@ extern "C" int uavsal_sizeof_desc(int which) {
         case 12: return (int)sizeof(uavsal_dw_dot_desc);
         case 13: return (int)sizeof(uavsal_fill_desc);
         case 14: return (int)sizeof(uavsal_score_desc);
+        case 15: return (int)sizeof(uavsal_letterbox_desc);
     }
     return UAVSAL_EINVAL;
 }

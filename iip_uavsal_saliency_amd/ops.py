@@ -423,6 +423,65 @@ def postprocess_predictions(maps, H, W):
     return out
 
 
+def letterbox_geometry(h0: int, w0: int, R: int, C: int):
+    """Where `padding()` (reference utils_data.py:321-343) puts an `h0 x w0` frame inside `R x C`:
+    `(new_r, new_c, y0, x0, branch)` -- the frame is resized to `new_r x new_c` and placed with its top-left corner at
+    `(y0, x0)`; `branch` is "cols" when the sides are padded (`h0 / R > w0 / C`, utils_data.py:330-335) and "rows" when top
+    and bottom are (:336-341).  Host arithmetic only.  A picture of zero rows or columns is an error, as it is in cv2."""
+    h0, w0, R, C = int(h0), int(w0), int(R), int(C)
+    if min(h0, w0, R, C) <= 0:
+        raise RuntimeError("letterbox_geometry: sizes must be positive, got %r" % ((h0, w0, R, C),))
+    if h0 / R > w0 / C:
+        new_r, new_c, branch = R, (w0 * R) // h0, "cols"
+    else:
+        new_r, new_c, branch = (h0 * C) // w0, C, "rows"
+    if new_r <= 0 or new_c <= 0:
+        raise RuntimeError("letterbox_geometry: a %dx%d frame has no picture inside %dx%d (%dx%d)" % (h0, w0, R, C, new_r, new_c))
+    return new_r, new_c, (R - new_r) // 2, (C - new_c) // 2, branch
+
+
+def letterbox_frames(frames, H, W, layout="HWC", bgr=False):
+    """Device version of the caller's pre-processing (`padding` per frame and the channel swap of preprocess_videos,
+    reference utils_data.py:255-287, 321-343): source-size uint8 frames `[F, H0, W0, 3]` (`layout="HWC"`, what a decoder
+    yields) or `[F, 3, H0, W0]` (`"CHW"`) on the device -> uint8 `[F, 3, H, W]`, resized with cv2's 8-bit INTER_LINEAR
+    rule and centred between zero bars; `bgr=True` swaps channels 0 and 2 on the way (cv2 decodes to BGR, the model reads
+    RGB).  A slice along the first dimension, rows longer than the picture (`buf[..., :W0, :]`) and any byte offset are
+    read in place.  One launch on the current stream, no synchronisation."""
+    lib = L.load()
+    if not torch.is_tensor(frames) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise RuntimeError("expected uint8 cuda frames [F,H0,W0,3] (layout='HWC') or [F,3,H0,W0] (layout='CHW')")
+    if layout not in ("HWC", "CHW"):
+        raise RuntimeError("layout must be 'HWC' or 'CHW', got %r" % (layout,))
+    F = frames.shape[0]
+    if layout == "HWC":
+        _, h0, w0, c = frames.shape
+        st = frames.stride()
+        dense = (st[3] == 1 or c == 1) and (st[2] == 3 or w0 == 1)
+        row, plane, img = (st[1] if h0 > 1 else 3 * w0), 0, st[0]
+    else:
+        _, c, h0, w0 = frames.shape
+        st = frames.stride()
+        dense = st[3] == 1 or w0 == 1
+        row = st[2] if h0 > 1 else w0
+        plane, img = st[1], st[0]
+    if c != 3:
+        raise RuntimeError("expected 3 channels in dimension %d of %s frames, got shape %r" % (
+            3 if layout == "HWC" else 1, layout, tuple(frames.shape)))
+    letterbox_geometry(h0, w0, H, W)
+    if F == 0:
+        return torch.empty((0, 3, H, W), dtype=torch.uint8, device=frames.device)
+    if not dense or row < (3 * w0 if layout == "HWC" else w0):
+        raise RuntimeError("frames are not a %s buffer (or a slice of one): strides %r" % (layout, tuple(st)))
+    out = torch.empty((F, 3, H, W), dtype=torch.uint8, device=frames.device)
+    d = L.LetterboxDesc()
+    d.src, d.dst = frames.data_ptr(), out.data_ptr()
+    d.row_pitch, d.plane_pitch, d.img_pitch = row, plane, (img if F > 1 else 0)
+    d.n_img, d.h0, d.w0, d.R, d.C = F, h0, w0, H, W
+    d.layout, d.swap_rb = (L.LETTERBOX_HWC if layout == "HWC" else L.LETTERBOX_CHW), int(bool(bgr))
+    L.check(lib.uavsal_letterbox_u8(C.byref(d), _stream(frames)), "uavsal_letterbox_u8")
+    return out
+
+
 def lstm_step(x_t, h_prev, c_prev, weight, prec="f32"):
     """One ConvLSTM step (reference model_convlstm.py:111-126, bias=False) from NHWC tensors and the
     reference-layout weight [4*hid, in+hid, 3, 3]: returns (h_t, c_t).  The x half of the conv is

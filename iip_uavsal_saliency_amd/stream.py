@@ -4,7 +4,9 @@ normalises each group of `batch_size * time_dims` frames on the host, copies it 
 `model(x, cb, state)`, copies the maps back and resizes them one by one with cv2.  Here the
 caller hands over the uint8 RGB frames as a tensor (decoding is out of scope: no video codec in
 this image); normalisation happens inside the stem kernel, the state never leaves HBM, and the
-maps are resized / normalised / quantised by `uavsal_postprocess`."""
+maps are resized / normalised / quantised by `uavsal_postprocess`.  With `model_size` the frames are
+the decoder's source-size ones and `uavsal_letterbox_u8` letterboxes them on the device first
+(preprocess_videos / padding, utils_data.py:255-287, 321-343)."""
 from __future__ import annotations
 
 import math
@@ -43,29 +45,43 @@ class _Groups:
     """The groups of a video as device tensors.  Frames already on the device are sliced; frames in host memory (what a decoder
     hands over, Demo_Test.py:78-85) are uploaded group by group on a copy stream of their own, `ahead` groups in front of the
     one being launched, so that the copy of group k + 1 runs under the launches of group k instead of in front of the whole
-    video (pinned memory: asynchronous; pageable memory: the host thread stages it, the GPU keeps computing)."""
+    video (pinned memory: asynchronous; pageable memory: the host thread stages it, the GPU keeps computing).
+    `letterbox=(R, C, layout, bgr)`: the frames are source-size (Demo_Test.py:72-74 hands them to preprocess_videos); each group
+    is letterboxed to `R x C` by one `ops.letterbox_frames` launch on the copy stream -- behind its upload for host frames -- so
+    that the launch runs under the previous groups instead of between two of them on a compute stream.  A group's source-size
+    staging buffer goes back to the allocator as soon as that launch is enqueued: it was allocated, written and read on the copy
+    stream only, whose order protects its reuse."""
 
-    def __init__(self, model, frames_u8, group, steps, dev, ahead=2):
+    def __init__(self, model, frames_u8, group, steps, dev, ahead=2, letterbox=None):
         self.frames, self.group, self.steps, self.dev, self.ahead = frames_u8, group, steps, dev, ahead
         self.host = not frames_u8.is_cuda
+        self.letterbox = letterbox
+        self.side = self.host or letterbox is not None
         self.pending = {}
-        if self.host:
+        if self.side:
             cs = model.__dict__.get("_stream_copy")
             if cs is None or cs.device != torch.device(dev):
                 cs = model.__dict__["_stream_copy"] = _host_streams(dev, 1)[0]
             self.copy_stream = cs
+            if not self.host:
+                cs.wait_stream(torch.cuda.current_stream(dev))      # device frames were produced on the caller's stream
 
     def _fetch(self, i):
         if i < self.steps and i not in self.pending:
             with torch.cuda.stream(self.copy_stream):
-                t = self.frames[i * self.group:(i + 1) * self.group].to(self.dev, non_blocking=True)
+                t = self.frames[i * self.group:(i + 1) * self.group]
+                if self.host:
+                    t = t.to(self.dev, non_blocking=True)
+                if self.letterbox is not None:
+                    R, C, layout, bgr = self.letterbox
+                    t = ops.letterbox_frames(t, R, C, layout=layout, bgr=bgr)
                 ev = torch.cuda.Event()
                 ev.record(self.copy_stream)
             self.pending[i] = (t, ev)
 
     def get(self, i, stream=None):
         """Group `i`, ready on `stream` (default: the current one)."""
-        if not self.host:
+        if not self.side:
             return self.frames[i * self.group:(i + 1) * self.group]
         for k in range(i, i + 1 + self.ahead):
             self._fetch(k)
@@ -141,11 +157,19 @@ def _predict_overlapped(model, groups, gauss_prior, ob_prior, steps, dev):
 def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_prior: torch.Tensor,
                   batch_size: int = 4, out_size: Optional[tuple] = None, return_maps: bool = False,
                   persistent_state: bool = True, out_path: Optional[str] = None, save_frames: Optional[int] = None,
-                  overlap: Optional[bool] = None):
+                  overlap: Optional[bool] = None, model_size: Optional[tuple] = None, frame_layout: str = "CHW",
+                  bgr: bool = False):
     """`frames_u8` uint8 `[F,3,H,W]` RGB (already letterboxed to the model size, as
     preprocess_videos does, utils_data.py:255-287) on the device, or in host memory (pinned for asynchronous copies): host
     frames are uploaded group by group on a copy stream, two groups ahead of the launches (`_Groups`), `gauss_prior` `[8,h,w]`, `ob_prior` `[20,h,w]`
     float32 (one map set, repeated per frame like get_bias, Demo_Test.py:14-27).
+    `model_size=(R, C)`: `frames_u8` are the decoded SOURCE-size frames instead -- `[F,3,H0,W0]`, or `[F,H0,W0,3]` with
+    `frame_layout="HWC"` (what cv2's `VideoCapture` yields; `bgr=True` for its channel order) -- and each group is letterboxed to
+    `R x C` on the device before it reaches the model (`ops.letterbox_frames`: `padding()` and the channel swap of
+    preprocess_videos, utils_data.py:269-270, 321-343; cv2's 8-bit INTER_LINEAR rule restated, not checked against cv2 itself);
+    `out_size` then defaults to `(H0, W0)`, the reference's loop (Demo_Test.py:65-91).  Device and host frames both work; the
+    letterbox launch of a group runs on the copy stream, behind the group's upload and ahead of the model's launches.  With
+    `model_size=None` (default) `frame_layout` and `bgr` must be left alone and nothing changes.
     Frames beyond the last full `time_dims` chunk are dropped (Demo_Test.py:68-70); groups of
     `batch_size * time_dims` frames are pushed through `model.forward` with the state carried
     (Demo_Test.py:75-86).  Returns uint8 `[F', H_out, W_out]` on the device (the reference's
@@ -166,7 +190,20 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
     frames_u8 = frames_u8[:keep]
     if frames_u8.is_cuda and frames_u8.device != torch.device(dev):
         frames_u8 = frames_u8.to(dev)
-    H, W = frames_u8.shape[2:]
+    letterbox = None
+    if model_size is None:
+        if frame_layout != "CHW" or bgr:
+            raise RuntimeError("frame_layout / bgr describe source-size frames: pass model_size=(R, C) with them")
+        H, W = frames_u8.shape[2:]
+    else:
+        if frame_layout not in ("CHW", "HWC") or frames_u8.dim() != 4 or frames_u8.dtype != torch.uint8:
+            raise RuntimeError("model_size needs uint8 frames [F,3,H0,W0] (frame_layout='CHW') or [F,H0,W0,3] ('HWC')")
+        H, W = (frames_u8.shape[2:] if frame_layout == "CHW" else frames_u8.shape[1:3])      # the source size
+        if frames_u8.shape[1 if frame_layout == "CHW" else 3] != 3:
+            raise RuntimeError("expected 3 channels, got %s frames of shape %r" % (frame_layout, tuple(frames_u8.shape)))
+        R, C = int(model_size[0]), int(model_size[1])
+        ops.letterbox_geometry(H, W, R, C)                # a degenerate picture raises here, before anything is launched
+        letterbox = (R, C, frame_layout, bool(bgr))
     out_size = out_size or (H, W)
     group = batch_size * T
     steps = math.ceil(count_bs / batch_size)
@@ -182,7 +219,7 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
         if overlap and not applies:
             raise RuntimeError("overlap=True needs persistent_state=True, the launch-loop plan and at least two whole groups of "
                                "batch_size * time_dims frames")
-        groups = _Groups(model, frames_u8, group, steps, dev)
+        groups = _Groups(model, frames_u8, group, steps, dev, letterbox=letterbox)
         first = 0
         if overlap:
             maps, state = _predict_overlapped(model, groups, gauss_prior.to(dev), ob_prior.to(dev), whole, dev)

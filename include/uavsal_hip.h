@@ -405,6 +405,35 @@ typedef struct uavsal_post_desc {
 int uavsal_postprocess(const uavsal_post_desc* d, uavsal_stream_t stream);
 
 /*
+ * Input letterboxing of the caller, replacing per frame `padding(img, shape_r, shape_c, 3)` (utils_data.py:321-343,
+ * called from preprocess_videos, :255-287) and the BGR -> RGB swap behind it (`ims[:, :, :, [2, 1, 0]]`, :269-270):
+ * a source-size uint8 frame h0 x w0 is resized with cv2.resize's 8-bit INTER_LINEAR rule (fixed point, 11-bit
+ * weights; csrc/letterbox.hip states it) to R x new_c (if h0 / R > w0 / C: new_c = w0 * R / h0, placed at column
+ * (C - new_c) / 2) or to new_r x C (new_r = h0 * C / w0, placed at row (R - new_r) / 2); everything outside is 0.
+ * The library computes the geometry.  cv2 was not available to pin the rule: it is pinned by known answers that
+ * follow from it (tests/letterbox_ref.py), not by outputs of cv2.
+ * src: layout UAVSAL_LETTERBOX_HWC = interleaved [n_img, h0, w0, 3] (what a decoder produces) or UAVSAL_LETTERBOX_CHW
+ * = planar [n_img, 3, h0, w0]; a row is dense, rows are row_pitch bytes apart, planes plane_pitch (planar only),
+ * images img_pitch: a slice of a larger buffer works and no alignment is required (the kernel reads the 16-byte
+ * aligned ranges that enclose each row).  swap_rb != 0: output plane 0 is source channel 2 and the other way round.
+ * dst: [n_img, 3, R, C] uint8 planar, dense -- what uavsal_stem_desc.in_u8 reads.  ONE launch, bars included; no
+ * allocation, no synchronisation.  UAVSAL_ESHAPE: a degenerate picture (new_r or new_c = 0), pitches smaller than
+ * what they separate, n_img > 65535, or source rows too long for the LDS staging (8 C + 6 w0 bytes + padding
+ * above 160 KB).
+ */
+#define UAVSAL_LETTERBOX_HWC 0
+#define UAVSAL_LETTERBOX_CHW 1
+
+typedef struct uavsal_letterbox_desc {
+    const uint8_t* src;  uint8_t* dst;
+    int64_t row_pitch, plane_pitch, img_pitch;     /* bytes */
+    int32_t n_img, h0, w0, R, C;
+    int32_t layout, swap_rb;
+} uavsal_letterbox_desc;
+
+int uavsal_letterbox_u8(const uavsal_letterbox_desc* d, uavsal_stream_t stream);
+
+/*
  * Strided row copy, device to device: `rows` rows of `row_floats` contiguous floats (a multiple of 4),
  * row r read at in + r*in_pitch and written at out + r*out_pitch (pitches in floats).  Used by the
  * persistent-state mode to carry h_last (NHWC, last frame of every clip of the ConvTWA history, which
@@ -540,7 +569,7 @@ int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_time(uavsal_plan* p, int first, int last, int iters, uavsal_stream_t stream, float* ms);
 
 int uavsal_abi_version(void);
-int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score */
+int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score,15 letterbox */
 const char* uavsal_build_info(void);
 
 #ifdef __cplusplus
