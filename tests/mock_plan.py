@@ -35,6 +35,44 @@ class MockLib:
         return getattr(self.real, name)
 
 
+HOST_ALIGN = 256        # bytes: what the device allocator guarantees at least (torch's host allocator: 64)
+
+
+class _AlignedTorch:
+    """The engine's `torch` while a plan is recorded on the host: allocations start on HOST_ALIGN bytes, as every device
+    allocation does.  The library's shape queries read the ADDRESSES of a descriptor too (a split shadow must start on 128
+    bytes: `split_eligible`, csrc/conv_gemm.hip), so on a 64-byte host pointer a GEMM whose input exists only as a shadow was
+    refused -- "its input only exists as a split shadow but the GEMM is not eligible" -- for a plan the device records fine.
+    Nothing recorded is ever launched, so `empty` / `full` leave the memory untouched (a shadow of a big plan is gigabytes)."""
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+    @staticmethod
+    def _alloc(shape, dtype, device, zero=False):
+        if torch.device(device if device is not None else "cpu").type != "cpu":
+            raise RuntimeError("mock_plan records on the host")
+        shape = (int(shape),) if isinstance(shape, int) else tuple(int(s) for s in shape)
+        n = 1
+        for s in shape:
+            n *= s
+        item = torch.empty(0, dtype=dtype).element_size()
+        raw = torch.empty(n * item + HOST_ALIGN, dtype=torch.uint8)
+        skip = -raw.data_ptr() % HOST_ALIGN
+        t = raw[skip:skip + n * item].view(dtype).view(shape)
+        assert t.data_ptr() % HOST_ALIGN == 0
+        return t.zero_() if zero else t
+
+    def empty(self, shape, dtype=torch.float32, device=None):
+        return self._alloc(shape, dtype, device)
+
+    def zeros(self, shape, dtype=torch.float32, device=None):
+        return self._alloc(shape, dtype, device, zero=True)
+
+    def full(self, shape, value, dtype=torch.float32, device=None):
+        return self._alloc(shape, dtype, device)
+
+
 class _NoDevice:
     def __init__(self, d):
         pass
@@ -49,12 +87,12 @@ class _NoDevice:
 def record(model, **kw):
     """(engine, mock library) of a plan recorded on the CPU (activations in host memory, nothing launched)."""
     mock = MockLib(L.load())
-    orig_load, orig_dev = L.load, torch.cuda.device
-    L.load, torch.cuda.device = (lambda: mock), _NoDevice
+    orig_load, orig_dev, orig_torch = L.load, torch.cuda.device, E.torch
+    L.load, torch.cuda.device, E.torch = (lambda: mock), _NoDevice, _AlignedTorch()
     try:
         eng = E.Engine(model, "cpu", plan_only=True, **kw)       # sizing pass + placement ...
         eng.plan_only = False                                   # ... then the recording pass against the stubs
         eng._init_on_device(True, resume=True)
     finally:
-        L.load, torch.cuda.device = orig_load, orig_dev
+        L.load, torch.cuda.device, E.torch = orig_load, orig_dev, orig_torch
     return eng, mock

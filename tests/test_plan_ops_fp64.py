@@ -12,12 +12,17 @@ NaN-filled); in f16x3 plans every output split shadow equals its fp32 output and
 passes from the merged shadow and from the fp32 values; in the headline f32 plan three deliberately wrong references (an input
 channel dropped, the last input row zeroed, one output channel's bias left out) must be rejected on a fixed list of ops.
 A Winograd triple (input transform, plane GEMM, output transform) is checked as one launch: its input and its output.
+
+`test_dispatch_cover` walks the configurations of `plan_census.WALKS` the same way: together with the cases above they reach every
+dispatch signature (kernel instance x edge path, tests/plan_census.py) of the model sizes in `plan_census.DOMAIN`; the first op of
+every signature that no earlier walk visits carries the wrong references too.
 """
 import time
 
 import pytest
 import torch
 
+import plan_census as PC
 import plan_ref64 as R
 from iip_uavsal_saliency_amd import engine as E
 from iip_uavsal_saliency_amd import synth
@@ -74,6 +79,13 @@ class Walk:
         self.checked = 0
         self.mut_results = {}
         self.shadow_out = self.shadow_in = 0
+        self.sampled = []               # ops checked on a sample of their images
+
+    def _imgs(self, name, d, n=None):
+        imgs = _images(d, n)
+        if len(imgs) < (d.n if n is None else n):
+            self.sampled.append(name)
+        return imgs
 
     def _finite(self, name, *ts):
         for t in ts:
@@ -152,7 +164,7 @@ class Walk:
     def op_conv1(self, i, last, rec):
         eng, name = self.eng, rec["name"]
         ad, od = rec["a"], rec["out"]
-        imgs = _images(od if rec.get("dw") is None else ad)
+        imgs = self._imgs(name, od if rec.get("dw") is None else ad)
         a_fp = _rd(eng, ad, imgs) if ad.buf is not None else None
         a_sh = _rd(eng, ad, imgs, shadow=True) if rec.get("split_in") else None
         res = _rd(eng, rec["res"], imgs) if rec["res"] is not None else None
@@ -180,7 +192,7 @@ class Walk:
     def op_wino(self, i, last, rec):
         eng, name = self.eng, rec["name"]
         od = rec["out"]
-        imgs = _images(od)
+        imgs = self._imgs(name, od)
         if rec["segs"]:
             parts = []
             for sg in rec["segs"]:
@@ -207,7 +219,7 @@ class Walk:
     def op_dw(self, i, last, rec):
         eng, name = self.eng, rec["name"]
         ad, od = rec["a"], rec["out"]
-        imgs = _images(ad)
+        imgs = self._imgs(name, ad)
         a = _rd(eng, ad, imgs)
         self._finite(name, a)
         self.launch(i, last)
@@ -223,7 +235,7 @@ class Walk:
 
     def op_dw_dot(self, i, last, rec):
         eng, name = self.eng, rec["name"]
-        imgs = _images(rec["a"])
+        imgs = self._imgs(name, rec["a"])
         a = _rd(eng, rec["a"], imgs)
         self._finite(name, a)
         self.launch(i, last)
@@ -233,7 +245,7 @@ class Walk:
 
     def op_fused_ir(self, i, last, rec):
         eng, name = self.eng, rec["name"]
-        imgs = _images(rec["a"])
+        imgs = self._imgs(name, rec["a"])
         a = _rd(eng, rec["a"], imgs)
         self._finite(name, a)
         self.launch(i, last)
@@ -243,7 +255,7 @@ class Walk:
 
     def op_stem(self, i, last, rec):
         eng, name = self.eng, rec["name"]
-        imgs = _images(rec["out"])
+        imgs = self._imgs(name, rec["out"])
         x = _rd(eng, rec["a"], imgs)
         self._finite(name, x)
         self.launch(i, last)
@@ -254,7 +266,7 @@ class Walk:
     def op_bilinear(self, i, last, rec):
         eng, name = self.eng, rec["name"]
         od = rec["out"]
-        imgs = _images(od)
+        imgs = self._imgs(name, od)
         x = _rd(eng, rec["a"])
         self._finite(name, x)
         self.launch(i, last)
@@ -276,7 +288,7 @@ class Walk:
     def op_tsum(self, i, last, rec):
         eng, name = self.eng, rec["name"]
         od, T = rec["out"], rec["T"]
-        groups = _images(od)
+        groups = self._imgs(name, od)
         x = _rd(eng, rec["a"], [g * T + t for g in groups for t in range(T)])
         self._finite(name, x)
         self.launch(i, last)
@@ -304,7 +316,7 @@ class Walk:
 
 # ------------------------------------------------------------------------------------------------------------- configs
 def _inputs(N, H, W, seed=0, u8=False, t0=0):
-    h, w = H // 8, W // 8
+    h, w = (E._down(E._down(E._down(n))) for n in (H, W))      # the engine's 1/8-scale map (sizes that are no multiple of 8 round up)
     f = synth.synth_frames_u8(N, H, W, seed, t0)
     x = torch.from_numpy(f if u8 else synth.normalize_frames(f)).cuda()
     cb0 = torch.from_numpy(synth.gauss_priors(N, h, w)).cuda()
@@ -330,10 +342,16 @@ def _engine(m, C, T, H, W, prec, static=False, u8=False):
                      static_priors=static)
 
 
-def _walk(m, C, T, H, W, prec, tag, static=False, u8=False, calls=1, mutations=None):
+def _walk(m, C, T, H, W, prec, tag, static=False, u8=False, calls=1, mutations=None, rand_state=False):
+    """`mutations`: {op name: wrong references}, or a function of the engine that returns it; `rand_state`: the call starts from
+    a non-zero recurrent state (with the zero state the first step's h operand is all zeros, and so is any mutation of it)."""
     eng = _engine(m, C, T, H, W, prec, static, u8)
     lstm = getattr(m, "rnn_type", "twa") == "lstm"
     state = cstate = None
+    if rand_state:
+        state = (0.5 * torch.rand((C, 256, eng.h, eng.w), generator=torch.Generator().manual_seed(1))).cuda()
+    if callable(mutations):
+        mutations = mutations(eng)
     x, cb0, cb1 = _inputs(C * T, H, W, 0, u8)
     for call in range(calls - 1):                          # earlier calls run whole; the last is walked
         eng.run(x, cb0, cb1, state, cstate=cstate)
@@ -437,3 +455,66 @@ def test_big_maps():
     """F: 720x1280, 4 clips x 16 frames (row-class depthwise, big maps; ops checked on a sample of their images)."""
     m = _model(16)
     _walk(m, 4, 16, 720, 1280, "f32", "F f32")
+
+
+# ------------------------------------------------------------------------------------------------ the dispatch-signature cover
+SPATIAL = ("conv3", "wino", "dw", "dw_dot", "fused_ir", "stem")          # kinds whose output pixel reads a 3x3 neighbourhood
+HAS_BIAS = ("dw", "dw_dot", "fused_ir", "stem")                          # kinds that always end in a folded BatchNorm
+
+
+def _wrong_refs_for(rec):
+    """The wrong references an op carries: always `chan`; `row` when the kind has spatial support; `bias` when it has a bias.
+    (layout / copy are compared bit for bit: any wrong reference is rejected by construction, none is tried.)"""
+    k = rec["kind"]
+    if k in ("layout", "copy"):
+        return ()
+    muts = ["chan"]
+    if k in SPATIAL or (k == "conv1" and rec.get("dw") is not None):
+        muts.append("row")
+    if k in HAS_BIAS or (k in ("conv1", "conv3", "wino") and rec.get("bn") is not None):
+        muts.append("bias")
+    return tuple(muts)
+
+
+def _cover_mutations(eng, dev_sigs, new):
+    """{op name: wrong references} for the first op of every signature in `new` (a part of a Winograd triple: the triple)."""
+    by_op, seen = {}, set()
+    for i, name, sig in dev_sigs:
+        if sig not in new or sig in seen:
+            continue
+        seen.add(sig)
+        key = eng.op_args[i].get("triple", name)
+        by_op[key] = _wrong_refs_for(eng.op_args[eng._op_idx[key]])
+    assert seen == set(new), set(new) - seen
+    return by_op
+
+
+@pytest.mark.parametrize("cfg", PC.WALKS, ids=lambda c: "%dx%d-%dx%d-%s" % c[:5])
+def test_dispatch_cover(cfg):
+    """One entry of `plan_census.WALKS`: the plan walked like every other; the engine built on the device has every dispatch
+    signature the CPU census recorded for this configuration; the first op of every signature that neither the cases above nor
+    an earlier entry visits rejects its wrong references; ops are checked on a sample of their images only where the census
+    says so (an operand above IMG_BUDGET: tests/test_plan_census_cpu.py holds which entries may have such ops)."""
+    C, T, H, W, prec, variant = cfg
+    assert variant == "" and PC.IMG_BUDGET == IMG_BUDGET
+    cpu, new = PC.config_signatures(cfg), PC.new_signatures(cfg)
+    assert new, "%s reaches nothing new" % (cfg,)
+    got = {}
+
+    def mutations(eng):
+        dev = PC.plan_signatures(eng)
+        missing = cpu - {s for _, _, s in dev}
+        assert not missing, "the plan built on the device lacks signatures the CPU census recorded: %s" % sorted(missing, key=str)
+        got.update(_cover_mutations(eng, dev, new))
+        return got
+
+    tag = "cover %dx%d %dx%d %s" % (H, W, C, T, prec)
+    w = _walk(_model(T), C, T, H, W, prec, tag, mutations=mutations, rand_state=True)
+    expect = sum(len(v) for v in got.values())
+    assert len(w.mut_results) == expect and all(r > 1.0 for r in w.mut_results.values())
+    assert sorted(w.sampled) == sorted(PC.config_sampled(cfg)), (w.sampled, PC.config_sampled(cfg))
+    exact = sum(1 for v in got.values() if not v)
+    print("[plan-ops-fp64] %s: %d new signatures on %d ops (%d of them bit-exact copies); %d wrong references rejected%s; "
+          "%d ops sampled%s" % (tag, len(new), len(got), exact, len(w.mut_results),
+                                 ", smallest err/bound %.3g (%s %s)" % (min(w.mut_results.values()), *min(w.mut_results, key=w.mut_results.get))
+                                 if w.mut_results else "", len(w.sampled), " (%s ...)" % ", ".join(w.sampled[:3]) if w.sampled else ""))
