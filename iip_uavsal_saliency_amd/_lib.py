@@ -152,8 +152,17 @@ class LetterboxDesc(C.Structure):
                 ("layout", C.c_int32), ("swap_rb", C.c_int32)]
 
 
+class OverlayDesc(C.Structure):
+    _fields_ = [("frames", _f), ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("img_pitch", C.c_int64),
+                ("map", _f), ("map_img_pitch", C.c_int64), ("fix", _f), ("lut", _f),
+                ("out", _f), ("ws", _f), ("ws_bytes", C.c_int64),
+                ("n_img", C.c_int32), ("layout", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32),
+                ("map_h", C.c_int32), ("map_w", C.c_int32), ("fix_h", C.c_int32), ("fix_w", C.c_int32),
+                ("mid_h", C.c_int32), ("mid_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32)]
+
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
-              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc]
+              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc]
 
 # every symbol include/uavsal_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -173,6 +182,8 @@ SYMBOLS = [
     ("uavsal_layout", C.c_int, [C.POINTER(LayoutDesc), C.c_void_p]),
     ("uavsal_postprocess", C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
     ("uavsal_letterbox_u8", C.c_int, [C.POINTER(LetterboxDesc), C.c_void_p]),
+    ("uavsal_overlay_workspace_bytes", C.c_int64, [C.POINTER(OverlayDesc)]),
+    ("uavsal_overlay_u8", C.c_int, [C.POINTER(OverlayDesc), C.c_void_p]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),

@@ -18,6 +18,7 @@
 // thread produces four adjacent output pixels of all three planes from LDS bytes: one dword store per plane.  Rows
 // and columns of the bars are written as zeros by the same launch.
 #include "common.h"
+#include "resize_u8.h"
 
 namespace {
 
@@ -34,17 +35,6 @@ struct LbK {
     int col_bytes, seg_pitch;          // LDS: column table, then the row segments
     double sy, sx;                     // n_in / n_out per axis
 };
-
-// source index and the two 11-bit weights of output index d
-__device__ __forceinline__ void lb_tap(int d, double scale, int n_in, int& s, int& c0, int& c1) {
-    float f = (float)__dsub_rn(__dmul_rn((double)d + 0.5, scale), 0.5);
-    s = (int)floorf(f);
-    f = __fsub_rn(f, (float)s);
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= n_in - 1) { s = n_in - 1; f = 0.f; }
-    c1 = (int)rintf(__fmul_rn(f, 2048.f));
-    c0 = (int)rintf(__fmul_rn(__fsub_rn(1.f, f), 2048.f));
-}
 
 __global__ __launch_bounds__(kThreads) void letterbox_u8_kernel(const LbK p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lb_lds[];
@@ -107,10 +97,7 @@ __global__ __launch_bounds__(kThreads) void letterbox_u8_kernel(const LbK p) {
                         if (e[j].x < 0) continue;
                         const int xa = e[j].x * ps, xb = min(e[j].x + 1, p.w0 - 1) * ps;
                         const int a0 = e[j].y & 0xffff, a1 = e[j].y >> 16;
-                        const int t0 = r0[xa] * a0 + r0[xb] * a1;
-                        const int t1 = r1[xa] * a0 + r1[xb] * a1;
-                        int v = ((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16);
-                        v = min((v + 2) >> 2, 255);
+                        const int v = lb_mix(r0[xa], r0[xb], r1[xa], r1[xb], a0, a1, b0, b1);
                         w[pl] |= (unsigned)v << (8 * j);
                     }
                 }

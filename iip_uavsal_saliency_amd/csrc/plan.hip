@@ -332,6 +332,7 @@ extern "C" int uavsal_sizeof_desc(int which) {
         case 13: return (int)sizeof(uavsal_fill_desc);
         case 14: return (int)sizeof(uavsal_score_desc);
         case 15: return (int)sizeof(uavsal_letterbox_desc);
+        case 16: return (int)sizeof(uavsal_overlay_desc);
     }
     return UAVSAL_EINVAL;
 }

@@ -158,7 +158,7 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
                   batch_size: int = 4, out_size: Optional[tuple] = None, return_maps: bool = False,
                   persistent_state: bool = True, out_path: Optional[str] = None, save_frames: Optional[int] = None,
                   overlap: Optional[bool] = None, model_size: Optional[tuple] = None, frame_layout: str = "CHW",
-                  bgr: bool = False):
+                  bgr: bool = False, overlay=None):
     """`frames_u8` uint8 `[F,3,H,W]` RGB (already letterboxed to the model size, as
     preprocess_videos does, utils_data.py:255-287) on the device, or in host memory (pinned for asynchronous copies): host
     frames are uploaded group by group on a copy stream, two groups ahead of the launches (`_Groups`), `gauss_prior` `[8,h,w]`, `ob_prior` `[20,h,w]`
@@ -179,7 +179,14 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
     group (`_predict_overlapped`); same maps, bit for bit, 1833 -> 2006 frames/s on a 192-frame video at 360x640 in groups of 8.
     None (default): whenever it applies -- resident state, launch-loop plans, at least two whole groups (a shorter last group
     follows them on its own plan, taking over the state); True: insist (raises where it does not apply); False: the reference's
-    one-after-the-other loop."""
+    one-after-the-other loop.
+    `overlay`: True, or a dict of `fix=` (the video's `fixLoc` maps `[F,Hf,Wf]`, drawn when given), `colormap=`, `sink=`,
+    `group=`, `host=` (see `vis.visual_video`), with `model_size`: the source frames and the fresh maps go through
+    `vis.visual_video` on the device -- the reference driver's third call, `visual_vid(..., with_color=1)`
+    (Demo_Test.py:130); device frames are read in place, host frames are uploaded a second time, group by group (the
+    source-size staging of the forward is gone by then) -- and the overlay frames `[F', out_h, out_w, 3]` (None with a sink) are returned as the last
+    element beside the maps.  They carry the channel order of the source frames: for RGB frames (`bgr=False`) the colour
+    table, which is BGR, is flipped.  None (default): nothing changes."""
     dev = next(model.parameters()).device
     T = model.time_dims
     F = frames_u8.shape[0]
@@ -204,6 +211,8 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
         R, C = int(model_size[0]), int(model_size[1])
         ops.letterbox_geometry(H, W, R, C)                # a degenerate picture raises here, before anything is launched
         letterbox = (R, C, frame_layout, bool(bgr))
+    if overlay is not None and overlay is not False and model_size is None:
+        raise RuntimeError("overlay needs the source-size frames: pass model_size=(R, C) with it")
     out_size = out_size or (H, W)
     group = batch_size * T
     steps = math.ceil(count_bs / batch_size)
@@ -242,6 +251,19 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
     sal = ops.postprocess_predictions(maps, out_size[0], out_size[1])
     if out_path is not None:
         save_salmap(out_path, sal, save_frames)
+    if overlay is not None and overlay is not False:
+        from . import vis
+        kw = dict(overlay) if isinstance(overlay, dict) else {}
+        unknown = set(kw) - {"fix", "colormap", "sink", "group", "host"}
+        if unknown:
+            raise RuntimeError("overlay: unknown keys %r" % sorted(unknown))
+        cmap = kw.pop("colormap", None)
+        if not bgr:
+            cmap = vis.JET_BGR if cmap is None else cmap
+            cmap = torch.as_tensor(cmap.copy() if hasattr(cmap, "copy") else cmap).reshape(256, 3).flip(1)
+        fix = kw.pop("fix", None)
+        over = vis.visual_video(frames_u8, sal, fix=fix, with_fix=fix is not None, layout=frame_layout, colormap=cmap, **kw)
+        return (sal, maps, over) if return_maps else (sal, over)
     return (sal, maps) if return_maps else sal
 
 

@@ -434,6 +434,37 @@ typedef struct uavsal_letterbox_desc {
 int uavsal_letterbox_u8(const uavsal_letterbox_desc* d, uavsal_stream_t stream);
 
 /*
+ * Heat-map overlay frames of the reference's visualisation: the coloured path of `visual_vid` (utils_vis.py:103-212,
+ * with_color=1, with and without with_fix) and `heatmap_overlay` / `visual_img` (:34-101) as the case without resizes.
+ * Per frame: the BGR uint8 frame h0 x w0 and the uint8 map map_h x map_w go to mid_h x mid_w with cv2.resize's 8-bit
+ * INTER_LINEAR rule (the rule of uavsal_letterbox_u8; the identity at equal sizes), map_color = lut[map],
+ * o = 0.8 * (1 - m ** 0.8) * img + m * map_color with img, m, map_color normalised by their per-frame maxima (in double,
+ * EPS = 2.2204e-16), o goes to out_h x out_w with cv2.resize's float INTER_LINEAR rule (half-pixel centres in double cast
+ * to float32, float32 weights, products and sums in double, horizontal pass then vertical), the nonzero pixels of the
+ * frame's fixation map are scattered to the output size (resize_fixation, :16-31), dilated 5x5 and set to 1, and
+ * o / max(o) * 255 is clipped, rounded half to even and stored as interleaved BGR uint8 [n_img][out_h][out_w][3].
+ * A frame the reference leaves undefined (max(o) == 0 or max(map_color) == 0: 0 / 0) is written as zeros.
+ * csrc/overlay.hip states the rules line by line; neither resize rule was checked against cv2 itself.
+ * frames: layout / row_pitch / plane_pitch / img_pitch as in uavsal_letterbox_desc: any byte offset; the channel
+ * order is kept (BGR in, BGR out).  map: dense [n_img][map_h][map_w] images map_img_pitch bytes apart, any byte offset.
+ * fix: NULL, or dense uint8 [n_img][fix_h][fix_w] (nonzero = a fixation), any byte offset.  lut: [256][3] uint8 BGR.
+ * ws: uavsal_overlay_workspace_bytes(d) bytes, 256-byte aligned; the call clears what it needs cleared.
+ * UAVSAL_ESHAPE: rows longer than the LDS staging allows (or more than 65535 frames).  Mid / out sizes are the caller's:
+ * the visual_vid geometry is host arithmetic (vis.visual_geometry).  Bitwise reproducible: integer atomics only.
+ */
+typedef struct uavsal_overlay_desc {
+    const uint8_t* frames;  int64_t row_pitch, plane_pitch, img_pitch;     /* bytes */
+    const uint8_t* map;  int64_t map_img_pitch;
+    const uint8_t* fix;  const uint8_t* lut;
+    uint8_t* out;  void* ws;  int64_t ws_bytes;
+    int32_t n_img, layout, h0, w0, map_h, map_w, fix_h, fix_w;
+    int32_t mid_h, mid_w, out_h, out_w;
+} uavsal_overlay_desc;
+
+int64_t uavsal_overlay_workspace_bytes(const uavsal_overlay_desc* d);
+int uavsal_overlay_u8(const uavsal_overlay_desc* d, uavsal_stream_t stream);
+
+/*
  * Strided row copy, device to device: `rows` rows of `row_floats` contiguous floats (a multiple of 4),
  * row r read at in + r*in_pitch and written at out + r*out_pitch (pitches in floats).  Used by the
  * persistent-state mode to carry h_last (NHWC, last frame of every clip of the ConvTWA history, which
@@ -569,7 +600,7 @@ int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_time(uavsal_plan* p, int first, int last, int iters, uavsal_stream_t stream, float* ms);
 
 int uavsal_abi_version(void);
-int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score,15 letterbox */
+int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score,15 letterbox,16 overlay */
 const char* uavsal_build_info(void);
 
 #ifdef __cplusplus
