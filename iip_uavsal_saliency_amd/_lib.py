@@ -161,8 +161,25 @@ class OverlayDesc(C.Structure):
                 ("mid_h", C.c_int32), ("mid_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32)]
 
 
+class GazeDesc(C.Structure):
+    _fields_ = [("fix_map", _f), ("map_row_pitch", C.c_int64), ("map_col_pitch", C.c_int64), ("map_img_pitch", C.c_int64),
+                ("fix_loc", _f), ("loc_row_pitch", C.c_int64), ("loc_col_pitch", C.c_int64), ("loc_img_pitch", C.c_int64),
+                ("out", _f), ("flags", _f),
+                ("n_img", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+LOSS_NSTAT = 16
+LOSS_FU_WEIGHTS, LOSS_KL_WEIGHTS = (10.0, -2.0, -1.0), (10.0, 0.0, 0.0)      # loss_functions.py:37-50
+
+
+class LossDesc(C.Structure):
+    _fields_ = [("pred", _f), ("truth", _f), ("stats", _f), ("out", _f), ("grad_out", _f), ("grad", _f),
+                ("n_img", C.c_int32), ("n_pix", C.c_int32),
+                ("w_kl", C.c_double), ("w_cc", C.c_double), ("w_nss", C.c_double)]
+
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
-              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc]
+              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc]
 
 # every symbol include/uavsal_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -184,6 +201,9 @@ SYMBOLS = [
     ("uavsal_letterbox_u8", C.c_int, [C.POINTER(LetterboxDesc), C.c_void_p]),
     ("uavsal_overlay_workspace_bytes", C.c_int64, [C.POINTER(OverlayDesc)]),
     ("uavsal_overlay_u8", C.c_int, [C.POINTER(OverlayDesc), C.c_void_p]),
+    ("uavsal_gaze_prepare", C.c_int, [C.POINTER(GazeDesc), C.c_void_p]),
+    ("uavsal_loss_fu", C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
+    ("uavsal_loss_fu_grad", C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),

@@ -333,6 +333,8 @@ extern "C" int uavsal_sizeof_desc(int which) {
         case 14: return (int)sizeof(uavsal_score_desc);
         case 15: return (int)sizeof(uavsal_letterbox_desc);
         case 16: return (int)sizeof(uavsal_overlay_desc);
+        case 17: return (int)sizeof(uavsal_gaze_desc);
+        case 18: return (int)sizeof(uavsal_loss_desc);
     }
     return UAVSAL_EINVAL;
 }

@@ -482,6 +482,51 @@ def letterbox_frames(frames, H, W, layout="HWC", bgr=False):
     return out
 
 
+def _gaze_view(t, name, layout):
+    """`t` as a `[F, H0, W0]` view (no copy) of uint8 fixation data in one of the layouts the callers hold:
+    `[F,H0,W0]`, or the .mat layouts `[H0,W0,1,F]` / `[H0,W0,F]` (`layout="HWF"`; a 4-d tensor is always the former)."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8:
+        raise RuntimeError("prepare_gaze: %s must be a uint8 cuda tensor" % name)
+    if t.dim() == 4:
+        if t.shape[2] != 1:
+            raise RuntimeError("prepare_gaze: a 4-d %s is the .mat layout [H0,W0,1,F], got %r" % (name, tuple(t.shape)))
+        return t[:, :, 0, :].permute(2, 0, 1)
+    if t.dim() != 3 or layout not in (None, "FHW", "HWF"):
+        raise RuntimeError("prepare_gaze: %s must be [F,H0,W0], [H0,W0,F] (layout='HWF') or [H0,W0,1,F]" % name)
+    return t.permute(2, 0, 1) if layout == "HWF" else t
+
+
+def prepare_gaze(fix_map_u8, fix_loc_u8, h, w, layout=None):
+    """Device version of the `val` / `train` ground truth of the reference (`preprocess_vidmaps` + `preprocess_vidfixs`,
+    utils_data.py:229-253, concatenated at Demo_Train_Test.py:114): source-size uint8 `fixMap` and `fixLoc` of a video ->
+    `(y_gaze, has_gaze)`, `y_gaze` float32 `[F,2,h,w]` -- channel 0 `padding(fixMap, h, w, 1)` (cv2's 8-bit INTER_LINEAR rule
+    as restated for `letterbox_frames`, values 0..255), channel 1 `padding_fixation(fixLoc, h, w)` -- and `has_gaze` bool
+    `[F,2]` = `np.any(y_gaze, axis=(2, 3))` (the skip test of Demo_Train_Test.py:125).  Both inputs are read in place as
+    `[F,H0,W0]`, `[H0,W0,1,F]` or (`layout="HWF"`) `[H0,W0,F]`, with any strides.  One zero fill and one launch on the
+    current stream, no synchronisation."""
+    lib = L.load()
+    m, l = _gaze_view(fix_map_u8, "fix_map", layout), _gaze_view(fix_loc_u8, "fix_loc", layout)
+    if m.shape != l.shape or m.device != l.device:
+        raise RuntimeError("prepare_gaze: fix_map %r and fix_loc %r differ" % (tuple(m.shape), tuple(l.shape)))
+    F, h0, w0 = m.shape
+    h, w = int(h), int(w)
+    letterbox_geometry(h0, w0, h, w)
+    nbytes = F * 2 * h * w * 4
+    buf = torch.zeros(nbytes + 2 * F, dtype=torch.uint8, device=m.device)        # the maps and, behind them, the flags
+    y = buf[:nbytes].view(torch.float32).view(F, 2, h, w)
+    flags = buf[nbytes:].view(F, 2)
+    if F == 0:
+        return y, flags.view(torch.bool)
+    d = L.GazeDesc()
+    d.fix_map, d.fix_loc = m.data_ptr(), l.data_ptr()
+    d.map_img_pitch, d.map_row_pitch, d.map_col_pitch = m.stride()
+    d.loc_img_pitch, d.loc_row_pitch, d.loc_col_pitch = l.stride()
+    d.out, d.flags = y.data_ptr(), flags.data_ptr()
+    d.n_img, d.h0, d.w0, d.h, d.w = F, h0, w0, h, w
+    L.check(lib.uavsal_gaze_prepare(C.byref(d), _stream(m)), "uavsal_gaze_prepare")
+    return y, flags.view(torch.bool)
+
+
 def lstm_step(x_t, h_prev, c_prev, weight, prec="f32"):
     """One ConvLSTM step (reference model_convlstm.py:111-126, bias=False) from NHWC tensors and the
     reference-layout weight [4*hid, in+hid, 3, 3]: returns (h_t, c_t).  The x half of the conv is

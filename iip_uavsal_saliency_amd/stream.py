@@ -267,6 +267,101 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
     return (sal, maps) if return_maps else sal
 
 
+def validation_groups(n_frames, time_dims, batch_size, has_gaze):
+    """The groups of the reference's loop over one video (Demo_Train_Test.py:111-126) as `[(first, last, run), ...]`: the
+    video is cut to `(n_frames // time_dims) * time_dims` frames, a group is `batch_size * time_dims` frames (the last one
+    may be shorter), and a group runs only if every frame of it has a non-zero fixation map AND a fixation
+    (`np.any(y_gaze, axis=(2, 3)).all()`).  `has_gaze`: `[F,2]` booleans (rows beyond the cut are ignored)."""
+    count_bs = int(n_frames) // int(time_dims)
+    keep = count_bs * time_dims
+    group = batch_size * time_dims
+    steps = math.ceil(count_bs / batch_size)
+    out = []
+    for i in range(steps):
+        a, b = i * group, min((i + 1) * group, keep)
+        out.append((a, b, all(bool(has_gaze[f][0]) and bool(has_gaze[f][1]) for f in range(a, b))))
+    return out
+
+
+def validation_aggregates(losses):
+    """The reference's bookkeeping for one video from its per-group losses (NaN = a skipped group):
+    `video_mean` = `video_loss / bs_steps`, the sum over the groups that ran divided by ALL groups, skipped ones included
+    (Demo_Train_Test.py:147, 153); `run_loss` and `num_step`, this video's share of the epoch's `run_loss / num_step`
+    (:148-149, 155).  Sums are Python floats added in group order, as `loss.data.item()` is there."""
+    video_loss, num_step = 0.0, 0
+    for v in losses:
+        v = float(v)
+        if not math.isnan(v):
+            video_loss += v
+            num_step += 1
+    return {"video_mean": video_loss / len(losses), "run_loss": video_loss, "num_step": num_step}
+
+
+@torch.no_grad()
+def validate_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_prior: torch.Tensor,
+                   fix_map: torch.Tensor, fix_loc: torch.Tensor, batch_size: int = 4, model_size: Optional[tuple] = None,
+                   frame_layout: str = "CHW", bgr: bool = False, gaze_layout: Optional[str] = None, criterion=None,
+                   prepare=None):
+    """The inner loop of the reference's `val` phase for one video (Demo_Train_Test.py:105-153, `model.eval()`, no
+    gradient): forward, criterion and gaze ground truth on the device.  `frames_u8`, `gauss_prior`, `ob_prior`,
+    `batch_size`, `model_size`, `frame_layout`, `bgr` as in `predict_video`; `fix_map` / `fix_loc` the video's source-size
+    uint8 `fixMap` / `fixLoc` in any layout `ops.prepare_gaze` reads (`gaze_layout` is its `layout`).
+    Kept from the reference: the video is cut to whole `time_dims` chunks (of the shortest of frames, maps and fixations);
+    groups are `batch_size * time_dims` frames, the last one shorter; a group in which a frame lacks a non-zero map or a
+    fixation is skipped BEFORE its forward, so the carried state does not advance over it; the maps stay in 0..255; the
+    video's mean divides by all groups.  Groups run one after the other through `model(...)`.
+    The ground truth of the whole video is prepared by one call up front and its flags are the only thing the host waits
+    for; the forwards and the loss launches are then queued without synchronisation and the losses come back in one copy.
+    Returns a dict: `losses` float32 `[groups]` on the host (NaN for a skipped group), `groups_run`, `video_mean`,
+    `run_loss`, `num_step` (see `validation_aggregates`).
+    `criterion` (default `losses.loss_fu`) and `prepare` (default `ops.prepare_gaze`) may be replaced."""
+    from . import losses as _losses
+    criterion = criterion or _losses.loss_fu
+    prepare = prepare or ops.prepare_gaze
+    dev = next(model.parameters()).device
+    T = model.time_dims
+    letterbox = None
+    if model_size is None:
+        if frame_layout != "CHW" or bgr:
+            raise RuntimeError("frame_layout / bgr describe source-size frames: pass model_size=(R, C) with them")
+    else:
+        if frame_layout not in ("CHW", "HWC") or frames_u8.dim() != 4 or frames_u8.dtype != torch.uint8:
+            raise RuntimeError("model_size needs uint8 frames [F,3,H0,W0] (frame_layout='CHW') or [F,H0,W0,3] ('HWC')")
+        R, C = int(model_size[0]), int(model_size[1])
+        h0, w0 = (frames_u8.shape[2:] if frame_layout == "CHW" else frames_u8.shape[1:3])
+        ops.letterbox_geometry(h0, w0, R, C)              # a degenerate picture raises here, before anything is launched
+        letterbox = (R, C, frame_layout, bool(bgr))
+    # the output size of the model is the size of its prior maps (shape_r_out x shape_c_out, Demo_Train_Test.py:64, 105-106)
+    y_gaze, has_gaze = prepare(fix_map.to(dev), fix_loc.to(dev), gauss_prior.shape[-2], gauss_prior.shape[-1], gaze_layout)
+    n_frames = min(frames_u8.shape[0], y_gaze.shape[0])                 # Demo_Train_Test.py:109
+    if (n_frames // T) * T < 2:
+        raise RuntimeError("need at least one full chunk of time_dims >= 2 frames")
+    groups = validation_groups(n_frames, T, batch_size, has_gaze.cpu().tolist())     # the one wait for the device
+    gauss_prior, ob_prior = gauss_prior.to(dev), ob_prior.to(dev)
+    lstm = getattr(model, "rnn_type", "twa") == "lstm"
+    state, ran = None, []
+    for a, b, run in groups:
+        if not run:
+            continue
+        x = frames_u8[a:b]
+        if x.device != torch.device(dev):
+            x = x.to(dev, non_blocking=True)
+        if letterbox is not None:
+            x = ops.letterbox_frames(x, letterbox[0], letterbox[1], layout=letterbox[2], bgr=letterbox[3])
+        n = b - a
+        cb = [gauss_prior.unsqueeze(0).expand(n, -1, -1, -1), ob_prior.unsqueeze(0).expand(n, -1, -1, -1)]
+        out, st = model(x, cb, state)
+        state = [(st[0].detach(), st[1].detach())] if lstm else [st[0].detach()]
+        ran.append(criterion(out, y_gaze[a:b]).reshape(()))
+    vals = torch.stack(ran).cpu().tolist() if ran else []                # the one copy back
+    per_group = torch.full((len(groups),), float("nan"), dtype=torch.float32)
+    for i, v in zip([i for i, g in enumerate(groups) if g[2]], vals):
+        per_group[i] = v
+    res = {"losses": per_group, "groups_run": len(ran)}
+    res.update(validation_aggregates(per_group.tolist()))
+    return res
+
+
 class RequestPipeline:
     """Independent requests (clips of DIFFERENT videos: no carried state between them) kept `streams` deep in
     flight: request k runs on host stream k % streams through its own handle on the model (`_inflight_replicas`: same weights,

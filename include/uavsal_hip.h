@@ -543,6 +543,62 @@ int64_t uavsal_score_workspace_bytes(const uavsal_score_desc* d);
 int uavsal_score_stats(const uavsal_score_desc* d, uavsal_stream_t stream);
 int uavsal_score_run(const uavsal_score_desc* d, uavsal_stream_t stream);
 
+/* ---- training criterion and gaze ground truth: the pieces of the reference's `val` phase around the forward ----------
+ * (Demo_Train_Test.py:87-156; csrc/loss.hip states the rules line by line)
+ *
+ * uavsal_gaze_prepare: y_gaze [n_img][2][h][w] fp32 from the source-size uint8 fixMap / fixLoc of a video, replacing per
+ * frame `padding(fixMap, h, w, 1)` and `padding_fixation(fixLoc, h, w)` (utils_data.py:229-253, 321-385).
+ *   channel 0: the map resized with cv2.resize's 8-bit INTER_LINEAR rule (csrc/resize_u8.h, the rule of
+ *     uavsal_letterbox_u8 with its geometry), centred between zero bars; values stay 0..255.
+ *   channel 1: every non-zero source pixel (r, c) writes 1 at (rint(r * rows / h0), rint(c * cols / w0)) of the picture
+ *     area (rows x cols, the letterbox geometry; product and rint in double, an index equal to rows / cols pulled in by
+ *     one); with h0 == h and w0 == w the source VALUES are copied instead (utils_data.py:366-367 returns the input).
+ *   flags [n_img][2] uint8: 1 where a channel of a frame holds a non-zero (np.any(y_gaze, axis=(2, 3))).
+ * Both sources are read in place: element (img, r, c) at base + img * img_pitch + r * row_pitch + c * col_pitch bytes, any
+ * non-negative pitches (so [F,H0,W0] and the .mat layouts [H0,W0,1,F] / [H0,W0,F] are views).  The caller zeroes `out`
+ * and `flags` on the stream first; ONE launch; writers of one cell all store the same value: no atomics.
+ * UAVSAL_ESHAPE: a degenerate picture, or n_img > 65535.
+ */
+typedef struct uavsal_gaze_desc {
+    const uint8_t* fix_map;  int64_t map_row_pitch, map_col_pitch, map_img_pitch;     /* bytes */
+    const uint8_t* fix_loc;  int64_t loc_row_pitch, loc_col_pitch, loc_img_pitch;
+    float* out;  uint8_t* flags;
+    int32_t n_img, h0, w0, h, w;
+} uavsal_gaze_desc;
+
+int uavsal_gaze_prepare(const uavsal_gaze_desc* d, uavsal_stream_t stream);
+
+/*
+ * The criterion of the reference (loss_functions.py:43-50, 64-86): per frame, on pred [B][1][h][w] and truth [B][2][h][w]
+ * (channel 0 the fixation map, channel 1 the fixation points), dense fp32,
+ *   kl  = sum t' * log(t' / (p' + EPS) + EPS),  t' = t / (sum t + EPS),  p' = p / (sum p + EPS)
+ *   cc  = r1 / (r2 + EPS) of the standardised maps ((x - mean) / (std + EPS), unbiased std)
+ *   nss = sum(f * p_std) / (sum f + EPS)
+ * and out[0..2] = their means over the B frames, out[3] = w_kl * out[0] + w_cc * out[1] + w_nss * out[2]: (10, -2, -1) is
+ * loss_fu, (10, 0, 0) loss_kl.  Everything is accumulated in double and rounded to fp32 once.
+ * uavsal_loss_fu: one workgroup per frame writes stats[B][UAVSAL_LOSS_NSTAT] (double: 0 kl, 1 cc, 2 nss, 3 sum p,
+ *   4 mean p, 5 mean t, 6 sum (p - mean)^2, 7 sum (t - mean)^2, 8 sum (t - mean)(p - mean), 9 sum f (p - mean), 10 sum f,
+ *   11 sum A p' with A = d kl / d p', 12 sum t), then a second one-wave launch takes the means over the frames in a
+ *   fixed order: no float atomics, two runs are bit-identical.  No allocation, no synchronisation.
+ * uavsal_loss_fu_grad: grad [B][1][h][w] = *grad_out * d out[3] / d pred from pred, truth and the saved stats, one pass
+ *   over the pixels, ONE launch.  `grad_out` is a device scalar (autograd's incoming gradient).  A term whose weight
+ *   is 0 is left out.  A frame of constant predictions has std 0: its cc / nss gradient is NaN, as in the reference.
+ * UAVSAL_ESHAPE: fewer than 2 pixels per frame.
+ */
+#define UAVSAL_LOSS_NSTAT 16
+
+typedef struct uavsal_loss_desc {
+    const float* pred;  const float* truth;
+    double* stats;                        /* [B][UAVSAL_LOSS_NSTAT] */
+    float* out;                           /* [4] (forward) */
+    const float* grad_out;  float* grad;  /* (backward) */
+    int32_t n_img, n_pix;
+    double w_kl, w_cc, w_nss;
+} uavsal_loss_desc;
+
+int uavsal_loss_fu(const uavsal_loss_desc* d, uavsal_stream_t stream);
+int uavsal_loss_fu_grad(const uavsal_loss_desc* d, uavsal_stream_t stream);
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 
@@ -600,7 +656,7 @@ int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_time(uavsal_plan* p, int first, int last, int iters, uavsal_stream_t stream, float* ms);
 
 int uavsal_abi_version(void);
-int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score,15 letterbox,16 overlay */
+int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score,15 letterbox,16 overlay,17 gaze,18 loss */
 const char* uavsal_build_info(void);
 
 #ifdef __cplusplus
