@@ -1,10 +1,9 @@
 """Host side of the HIP path: turns a `UAVSal` parameter tree into a native launch plan.
 
 Built once per (device, clip count, sequence length, frame size, precision):
-  1. folds every BatchNorm and packs every conv weight (packing.py), uploads them;
+  1. folds every BatchNorm and packs every conv weight, uploads them (weights.py, packing.py);
   2. lays the NHWC fp32 activation buffers out in HBM (concatenations become channel
-     slices of one wider buffer; the two 6x-expanded hidden tensors of an inverted
-     residual block live in two scratch buffers shared by all blocks);
+     slices of one wider buffer; buffers share one arena by liveness: arena.py);
   3. records every kernel launch of reference `UAVSal.forward` (model.py:341-375) into a
      `uavsal_plan` (C ABI, include/uavsal_hip.h) that is then replayed natively --
      as a launch loop or as one captured hipGraph.
@@ -19,8 +18,10 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib as L
-from . import packing as P
 from . import synth
+from .arena import ARENA_ALIGN, Arena, _ArenaRef, arena_conflict, plan_arena      # (the planner's names stay importable from here)
+from .packing import conv_weight_layout, roundup
+from .weights import WeightCache
 
 
 def _down(n: int) -> int:
@@ -143,84 +144,6 @@ def _dwproj_patch_waste(h, w):
 
 
 BLOCK_CHUNK_BYTES = 6 << 30                                   # see Engine.ir_block
-ARENA_ALIGN = 1024                                            # floats (4 KB): every arena buffer starts on a page
-
-
-class _ArenaRef:
-    """An activation's place in the engine's arena: `numel` floats at `off`, live over the recorded ops [first, last]
-    (positions on the main lane's timeline; a use on a side lane counts from that lane's fork to its join).  Stands where a
-    tensor stood in `V.t`, so every view of the buffer shares it; `data_ptr()` refuses to hand out an address outside the
-    live range while a plan is being recorded -- a recorder that forgot to declare a use fails there, at build time."""
-    __slots__ = ("eng", "aid", "numel_", "off", "first", "last", "pinned", "lkey", "lfirst", "llast")
-
-    def __init__(self, eng, aid, numel):
-        self.eng, self.aid, self.numel_ = eng, aid, int(numel)
-        self.off, self.first, self.last, self.pinned = None, None, None, False
-        # lkey: (lane, index of its fork) while every use so far was recorded on that lane between that fork and its join
-        # (its launches are then ordered among themselves on one stream: [lfirst, llast] in recording order), else "mixed"
-        self.lkey, self.lfirst, self.llast = None, None, None
-
-    def numel(self):
-        return self.numel_
-
-    def data_ptr(self):
-        e = self.eng
-        if e._dry:
-            return 0
-        lo, hi = (self.lfirst, self.llast) if isinstance(self.lkey, tuple) else (self.first, self.last)
-        if e._recording and not self.pinned and not (lo <= e._lop <= hi):
-            raise RuntimeError("arena: %r is addressed by op %d outside its live range [%d, %d] -- a recorder did not declare "
-                               "this use (Engine._touch)" % (self.aid, e._lop, lo, hi))
-        return e._arena.data_ptr() + 4 * self.off
-
-    def tensor(self):
-        return self.eng._arena[self.off:self.off + self.numel_]
-
-
-def arena_conflict(a, b):
-    """Are two buffers `(numel, first, last[, lane key, lane first, lane last])` ever live together?  [first, last] are positions
-    on the main lane's timeline (a side-lane use counts from the fork to the join); two buffers used ONLY on the same side lane
-    between the same fork and join are ordered by that lane's stream, so for them the recording-order ranges decide."""
-    if a[2] < b[1] or b[2] < a[1]:
-        return False
-    if len(a) > 3 and len(b) > 3 and a[3] is not None and a[3] == b[3] and isinstance(a[3], tuple):
-        return not (a[5] < b[4] or b[5] < a[4])
-    return True
-
-
-def plan_arena(bufs, align=ARENA_ALIGN):
-    """Offsets for buffers `[(numel, first, last[, lane key, lane first, lane last]), ...]` such that two buffers that are ever
-    live together (`arena_conflict`) never overlap: biggest first, each at the lowest aligned offset free of every already-placed
-    buffer it conflicts with.  Returns (offsets, total floats, lower bound = the largest sum of sizes live at one main-lane position)."""
-    order = sorted(range(len(bufs)), key=lambda i: (-bufs[i][0], bufs[i][1]))
-    placed, offs = [], [0] * len(bufs)
-    rnd = lambda n: (n + align - 1) // align * align
-    for i in order:
-        n, f, l = bufs[i][:3]
-        busy = sorted((o, o + rnd(bufs[j][0])) for (o, j) in placed if arena_conflict(bufs[i], bufs[j]))
-        at = 0
-        for lo, hi in busy:
-            if at + rnd(n) <= lo:
-                break
-            at = max(at, hi)
-        offs[i] = at
-        placed.append((at, i))
-    total = max([o + rnd(bufs[j][0]) for (o, j) in placed], default=0)
-    # lower bound: at a main-lane position, everything live there -- of the buffers that are private to one side lane only the
-    # largest set that is live together in that lane's own order
-    events = sorted(set(b[1] for b in bufs))
-    bound = 0
-    for t in events:
-        live = [b for b in bufs if b[1] <= t <= b[2]]
-        tot = sum(rnd(b[0]) for b in live if not (len(b) > 3 and isinstance(b[3], tuple)))
-        lanes = {}
-        for b in live:
-            if len(b) > 3 and isinstance(b[3], tuple):
-                lanes.setdefault(b[3], []).append(b)
-        for grp in lanes.values():
-            tot += max(sum(rnd(c[0]) for c in grp if c[4] <= u <= c[5]) for u in set(c[4] for c in grp))
-        bound = max(bound, tot)
-    return offs, total, bound
 
 
 class Engine:
@@ -271,7 +194,8 @@ class Engine:
         self.w = _down(_down(_down(W)))
         self._keep: List[torch.Tensor] = []        # buffers kept alive
         # packed device weights, keyed by (kind, id(module), ...): one copy per model, shared by its engines
-        self._wcache: Dict[tuple, object] = wcache if wcache is not None else {}
+        self.weights = WeightCache(self.device, wcache if wcache is not None else {})
+        self.lstm = getattr(model, "rnn_type", "twa") == "lstm"      # the recurrence: ConvLSTM, else ConvTWA
         # persistent-state mode: the recurrent state lives in `hprev` (NHWC) across calls, see run()
         self.persistent = bool(persistent)
         # f16x3: tensors that an eligible GEMM consumes are ALSO kept as split shadows (hi/lo fp16 planes) written
@@ -318,39 +242,44 @@ class Engine:
         self._scratch: Dict[tuple, torch.Tensor] = {}
         self._lane = 0
         self.plan = None
-        # activation arena (liveness-based): see _buf / _touch / _place_arena
+        # activation arena (liveness-based, arena.py): see _buf / _size
         self.use_arena = bool(getattr(model, "arena", True))
         self.arena_debug = bool(getattr(model, "arena_debug", False))
-        self._refs: Dict[object, _ArenaRef] = {}
-        self._arena = None
-        self._recording = False
-        self._lop = -1                        # logical op index (poison fills of the debug mode do not count)
-        self._lane_open: Dict[int, int] = {}
-        self._lane_refs: Dict[int, set] = {}
-        self._scr_serial = 0
-        self.arena_stats: Dict[str, float] = {}
+        self.arena = Arena()
         # everything below allocates on, or creates native objects for, the CURRENT device (the plan's error word, its
         # `done` event, workspaces, occupancy queries): make that the engine's device, whatever the caller's is
         if self.plan_only:
-            self._dry = self._recording = True
-            self._build()
-            self._close_lanes()
-            if self.use_arena:
-                self._place_arena()
+            self._size()
             return
         with torch.cuda.device(self.device):
             self._init_on_device(use_lanes)
 
+    _arena = property(lambda self: self.arena.buf)              # the pool (one float32 tensor)
+    arena_stats = property(lambda self: self.arena.stats)
+    TAP_NAMES = ("c3", "c4", "c5", "sfnet", "st0", "st1", "fust_in_cb", "prefuse", "rnn")
+
+    def _size(self):
+        """Pass 1: sizes the shared scratch and lays the arena out (nothing allocated, nothing recorded)."""
+        self._dry = True
+        self._build()
+        self.arena.close(len(self.ops_meta))
+        if self.use_arena:       # (what `tap` reads back after the run stays live to the end)
+            taps = [self.named[k].t for k in self.TAP_NAMES if k in self.named] if self.keep_taps else []
+            self._arena_floats = self.arena.place(len(self.ops_meta), [t for t in taps if isinstance(t, _ArenaRef)])
+
+    def arena_layout(self):
+        """[(buffer id, offset, floats, first op, last op, lane key, first / last op in recording order)], by offset."""
+        return self.arena.layout()
+
     def _init_on_device(self, use_lanes, resume=False):
-        # pass 1 sizes the shared scratch and the arena, pass 2 records the launches (`resume`: pass 1 already ran -- plan_only)
+        # pass 1, then pass 2 records the launches (`resume`: pass 1 already ran -- plan_only)
         if not resume:
-            self._dry = True
-            self._recording = True
-            self._build()
-            self._close_lanes()
+            self._size()
         self._split_want -= self._no_shadow
-        if self.use_arena and (not resume or self._arena is None):
-            self._place_arena()
+        if self.use_arena:
+            self.arena.buf = torch.empty(max(self._arena_floats, 4), dtype=torch.float32, device=self.device)
+            if self.arena_debug:
+                self.arena.buf.fill_(float("nan"))
         for k, need in self._scratch_need.items():
             # (the Winograd V planes are zero-filled once: their padding rows are multiplied by the GEMM, never read back)
             alloc = torch.zeros if k[0] == "WV" else torch.empty
@@ -358,8 +287,7 @@ class Engine:
                                      device=self.device)
         self._lane = 0
         self._dry = False
-        self._lop, self._scr_serial, self._lane_open, self._lane_refs = -1, 0, {}, {}
-        self._poison_done = set()
+        self.arena.begin(dry=False)
         self.ops_meta, self.stage_ranges, self.named, self._op_idx, self.op_args = [], {}, {}, {}, []
         self.plan = C.c_void_p(self.lib.uavsal_plan_create())
         if not self.plan:
@@ -367,7 +295,7 @@ class Engine:
         self._err = self.lib.uavsal_plan_error_word(self.plan)
         self._build()
         self._flush_poison(final=True)
-        self._recording = False
+        self.arena.recording = False
         self.use_lanes = bool(use_lanes)
         L.check(self.lib.uavsal_plan_enable_lanes(self.plan, 1 if self.use_lanes else 0), "plan_enable_lanes")
         self._graph_ready = False
@@ -388,7 +316,7 @@ class Engine:
         sp = None
         numel = n * h * w * c
         if self.use_arena and not pinned:
-            t = self._ref(name, numel)
+            t = self.arena.ref(name, numel)
         elif self._dry:
             t = _Fake()
         else:
@@ -406,95 +334,13 @@ class Engine:
             self.named[name] = v
         return v
 
-    # ---- activation arena -------------------------------------------------------------------------------------------
-    def _ref(self, aid, numel) -> _ArenaRef:
-        if self._dry:
-            if aid in self._refs:
-                raise RuntimeError("arena: buffer %r declared twice" % (aid,))
-            r = self._refs[aid] = _ArenaRef(self, aid, numel)
-            return r
-        r = self._refs.get(aid)
-        if r is None or r.numel_ != int(numel):
-            raise RuntimeError("arena: buffer %r of the recording pass was not (or differently) declared in the sizing pass" % (aid,))
-        return r
-
-    def _touch(self, *vs):
-        """Declare that the op being recorded (the last `_meta`) reads or writes these views.  Sizing pass: grows the live
-        range of their arena buffers -- on a side lane from the lane's fork (it may start right there) to, at its join, the
-        join (it may still be running until then)."""
-        if not self._dry:
-            return
-        for v in vs:
-            r = getattr(v, "t", None) if v is not None else None
-            if not isinstance(r, _ArenaRef):
-                continue
-            lo = hi = self._lop
-            key = "main"
-            if self._lane != 0:
-                lo = self._lane_open.get(self._lane, lo)
-                self._lane_refs.setdefault(self._lane, set()).add(r)
-                key = (self._lane, self._lane_open.get(self._lane, -1))
-            r.first = lo if r.first is None else min(r.first, lo)
-            r.last = hi if r.last is None else max(r.last, hi)
-            r.lkey = key if r.lkey in (None, key) else "mixed"
-            r.lfirst = self._lop if r.lfirst is None else min(r.lfirst, self._lop)
-            r.llast = self._lop if r.llast is None else max(r.llast, self._lop)
-
-    def _close_lanes(self):
-        for lane in list(self._lane_refs):          # (a lane the plan never joined: live to the end)
-            for r in self._lane_refs.pop(lane):
-                r.last = max(r.last, len(self.ops_meta))
-        self._lane_open = {}
-
-    TAP_NAMES = ("c3", "c4", "c5", "sfnet", "st0", "st1", "fust_in_cb", "prefuse", "rnn")
-
-    def _place_arena(self):
-        refs = list(self._refs.values())
-        last_op = len(self.ops_meta)
-        for r in refs:
-            if r.first is None:                      # declared, never used by an op: keep it addressable for the whole plan
-                r.first, r.last, r.lkey, r.lfirst, r.llast = 0, last_op, "mixed", 0, last_op
-        if self.keep_taps:                           # read back after the run (Engine.tap)
-            for k in self.TAP_NAMES:
-                v = self.named.get(k)
-                if v is not None and isinstance(v.t, _ArenaRef):
-                    v.t.last, v.t.lkey = last_op, "mixed"
-        offs, total, bound = plan_arena([(r.numel_, r.first, r.last, r.lkey, r.lfirst, r.llast) for r in refs])
-        for r, o in zip(refs, offs):
-            r.off = o
-        self.arena_stats = {"arena_mb": total * 4 / 1e6, "live_bound_mb": bound * 4 / 1e6,
-                            "unshared_mb": sum(r.numel_ for r in refs) * 4 / 1e6, "buffers": len(refs)}
-        if self.plan_only:
-            return
-        self._arena = torch.empty(max(total, 4), dtype=torch.float32, device=self.device)
-        if self.arena_debug:
-            self._arena.fill_(float("nan"))
-
-    def arena_layout(self):
-        """[(buffer id, offset, floats, first op, last op, lane key, first / last op in recording order)] of the arena, by offset
-        (engine.arena_conflict takes `t[2:]`)."""
-        return sorted(((r.aid, r.off, r.numel_, r.first, r.last, r.lkey, r.lfirst, r.llast) for r in self._refs.values()),
-                      key=lambda t: (t[1], t[3]))
-
     def _flush_poison(self, final=False):
         """Debug mode: once the op that ends a buffer's live range has been recorded -- and before anything of the next op,
-        a fork included -- the range is filled with NaN on the main lane, so a use after release cannot go unnoticed."""
+        a fork included -- the range is filled with NaN (on the lane Arena.due names), so a use after release cannot go unnoticed."""
         if not (self.arena_debug and self.use_arena) or self._dry:
             return
-        def end_of(r):          # last logical op that may touch the buffer
-            return r.llast if isinstance(r.lkey, tuple) else r.last
-        due = [r for r in self._refs.values() if r not in self._poison_done and not r.pinned
-               and (final or end_of(r) < self._lop + 1)]
-        if not due:
-            return
         cur = self._lane
-        for r in sorted(due, key=lambda r_: r_.off):
-            self._poison_done.add(r)
-            if final and end_of(r) >= self._lop:     # still live at the end of the plan (taps, the history the state is read from)
-                continue
-            # a buffer private to a side lane is released in that lane's own order: its fill goes on that lane (while the lane is
-            # open: behind its last launch there, in front of whatever the lane runs next), everything else on the main lane
-            lane = r.lkey[0] if isinstance(r.lkey, tuple) and self._lane_open.get(r.lkey[0]) == r.lkey[1] else 0
+        for r, lane in self.arena.due(final):
             if lane != cur:
                 L.check(self.lib.uavsal_plan_set_lane(self.plan, lane), "plan_set_lane")
                 cur = lane
@@ -502,7 +348,7 @@ class Engine:
             self.ops_meta.append(dict(kind="poison", name="poison:%s" % (r.aid,), flops=0.0, bytes=4.0 * r.numel_, lane=lane))
             self.op_args.append(dict(kind="poison", name="poison:%s" % (r.aid,)))
             d = L.FillDesc()
-            d.out, d.n, d.bits = self._arena.data_ptr() + 4 * r.off, r.numel_, 0x7FC00000
+            d.out, d.n, d.bits = self.arena.buf.data_ptr() + 4 * r.off, r.numel_, 0x7FC00000
             self._add(self.lib.uavsal_plan_add_fill, d, "plan_add_fill")
         if cur != self._lane:
             L.check(self.lib.uavsal_plan_set_lane(self.plan, self._lane), "plan_set_lane")
@@ -538,8 +384,7 @@ class Engine:
         same addresses, concurrent lanes never do).  Without: one pool per (kind, lane)."""
         numel = n * h * w * c
         if self.use_arena:
-            self._scr_serial += 1
-            return V(self._ref((kind, self._scr_serial), numel), n, h, w, c)
+            return V(self.arena.scratch(kind, numel), n, h, w, c)
         key = (kind, self._lane)
         if self._dry:
             self._scratch_need[key] = max(self._scratch_need.get(key, 0), numel)
@@ -551,67 +396,26 @@ class Engine:
         """Following ops (until `main()`) go to `lane`, which starts after everything recorded on
         lane 0 so far."""
         self._meta(kind="sync", name="fork%d" % lane, flops=0.0, bytes=0.0)
-        self._lane_open.setdefault(lane, self._lop)
+        self.arena.fork(lane)
         if not self._dry:
             r = self.lib.uavsal_plan_add_fork(self.plan, lane)
             if r < 0:
                 L.check(r, "plan_add_fork")
             L.check(self.lib.uavsal_plan_set_lane(self.plan, lane), "plan_set_lane")
-        self._lane = lane
+        self._lane = self.arena.lane = lane
 
     def main(self):
         if not self._dry:
             L.check(self.lib.uavsal_plan_set_lane(self.plan, 0), "plan_set_lane")
-        self._lane = 0
+        self._lane = self.arena.lane = 0
 
     def join(self, lane):
         self._meta(kind="sync", name="join%d" % lane, flops=0.0, bytes=0.0)
-        for r_ in self._lane_refs.pop(lane, ()):          # what ran on the lane may have been running until here
-            r_.last = max(r_.last, self._lop)
-        self._lane_open.pop(lane, None)
+        self.arena.join(lane)
         if not self._dry:
             r = self.lib.uavsal_plan_add_join(self.plan, lane)
             if r < 0:
                 L.check(r, "plan_add_join")
-
-    def _dev(self, t: torch.Tensor) -> torch.Tensor:
-        return t.contiguous().to(self.device)      # kept alive by the weight cache
-
-    def _affine(self, bn, cout):
-        if isinstance(bn, (list, tuple)):        # several convs of the same input as ONE GEMM: outputs side by side
-            key = ("bn",) + tuple(id(b_) for b_ in bn) + (cout,)
-            if key not in self._wcache:
-                parts = [P.fold_bn(b_) for b_ in bn]
-                s, b = torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
-                n = P.roundup(cout, 32)
-                self._wcache[key] = (self._dev(P.pad_vec(s, n, 1.0)), self._dev(P.pad_vec(b, n, 0.0)))
-            return self._wcache[key]
-        key = ("bn", id(bn), cout)
-        if key not in self._wcache:
-            s, b = P.fold_bn(bn)
-            n = P.roundup(cout, 32)
-            self._wcache[key] = (self._dev(P.pad_vec(s, n, 1.0)), self._dev(P.pad_vec(b, n, 0.0)))
-        return self._wcache[key]
-
-    def _convw(self, conv, sl=None, gate_interleave=0, natural=False, dwproj=False, k32=False, prec_name=None):
-        """`natural`: the pre-split LDS-DMA path takes the weights as [K step][Cout][hi 32 | lo 32] ('f16x3i');
-        `dwproj`: the split-fp16 depthwise -> projection kernel takes [K step of 16][Cout][hi 16 | lo 16] ('f16x3j');
-        `k32`: fp32 kernels with 32-float K stages (tiles 8 / 9; differs from 'f32' for 3x3 weights only)."""
-        prec_name = prec_name or self.prec_name
-        layout = "f16x3i" if natural else ("f16x3j" if dwproj and prec_name == "f16x3" else prec_name)
-        multi = isinstance(conv, (list, tuple))
-        if k32 and layout == "f32" and (conv[0] if multi else conv).weight.shape[-1] == 3:
-            layout = "f32k32"
-        key = ("w",) + (tuple(id(c_) for c_ in conv) if multi else (id(conv),)) + (sl, layout, gate_interleave)
-        if key not in self._wcache:
-            w = torch.cat([c_.weight.detach() for c_ in conv], 0) if multi else conv.weight.detach()
-            if sl is not None:
-                w = w[:, sl[0]:sl[1]]
-            if gate_interleave:      # ConvLSTM: row g*hid + c  ->  4*c + g  (gates i,f,o,g adjacent)
-                hid = gate_interleave
-                w = w.reshape(4, hid, *w.shape[1:]).permute(1, 0, 2, 3, 4).reshape(4 * hid, *w.shape[1:])
-            self._wcache[key] = self._dev(P.pack_conv_weight(w, layout))
-        return self._wcache[key]
 
     def _prec_for(self, name) -> str:
         best, val = -1, self.prec_name
@@ -629,7 +433,7 @@ class Engine:
     # ------------------------------------------------------------------ op recorders
     def _meta(self, **kw):
         self._flush_poison()
-        self._lop += 1
+        self.arena.lop += 1
         self._op_idx[kw.get("name")] = len(self.ops_meta)       # == index of the op in the native plan
         self.ops_meta.append(kw)
         self.op_args.append(dict(kind=kw.get("kind"), name=kw.get("name")))
@@ -674,7 +478,7 @@ class Engine:
             byts = 4.0 * n_img * (hin * win * cin + hw * cout) + 4.0 * cin * (cout + 11)
         self._meta(kind="conv%d" % (3 if taps == 9 else 1), name=name, flops=flops, bytes=byts,
                    M=n_img * hw, K=cin * taps, Nc=cout)
-        self._touch(a, out, res, aux, out2)
+        self.arena.touch(a, out, res, aux, out2)
         # split shadows (f16x3): can this launch write one for its output / read its input pre-split?
         shadow_out = False
         if self.split_mode:
@@ -700,16 +504,12 @@ class Engine:
         if out.sp is not None and shadow_out:
             d.out_split, d.ldos = out.sp_ptr, 2 * out.ld
         if dw is not None:
-            key = ("dw", id(dw[0]))
-            if key not in self._wcache:
-                s_, b_ = P.fold_bn(dw[1])
-                self._wcache[key] = (self._dev(P.pack_dw_weight(dw[0].weight)), self._dev(s_), self._dev(b_))
-            w9, s_, b_ = self._wcache[key]
+            w9, s_, b_ = self.weights.depthwise(dw[0], dw[1])
             d.dw_w9c, d.dw_scale, d.dw_bias = w9.data_ptr(), s_.data_ptr(), b_.data_ptr()
             d.dw_stride, d.dw_Hin, d.dw_Win = dw[2], hin, win
             self.ops_meta[-1]["fused_dw"] = True
         if bn is not None:
-            s, b = self._affine(bn, cout)
+            s, b = self.weights.affine(bn, cout)
             d.scale, d.bias = s.data_ptr(), b.data_ptr()
         else:
             d.scale, d.bias = None, None
@@ -751,8 +551,8 @@ class Engine:
             raise RuntimeError("%s: its input only exists as a split shadow but the GEMM is not eligible" % name)
         dwproj = int(self.lib.uavsal_conv_dwproj(C.byref(d)))
         tile = int(self.lib.uavsal_conv_tile(C.byref(d)))
-        d.w = self._convw(conv, wslice, gate_interleave, natural=split, dwproj=dwproj != 0, k32=tile in (8, 9, 10, 11),
-                          prec_name=pn).data_ptr()
+        ksize = (conv[0] if isinstance(conv, (list, tuple)) else conv).weight.shape[-1]
+        d.w = self.weights.conv(conv, wslice, gate_interleave, conv_weight_layout(pn, split, dwproj != 0, tile, ksize)).data_ptr()
         self.ops_meta[-1]["prec"] = pn
         self.ops_meta[-1]["split"] = split
         self.ops_meta[-1]["tile"] = tile
@@ -781,34 +581,28 @@ class Engine:
         hw = a.h * a.w
         tiles = n * ((a.h + r - 1) // r) * ((a.w + r - 1) // r)
         pp = (r + 2) * (r + 2)
-        mp = P.roundup(tiles, 128)
+        mp = roundup(tiles, 128)
         st = strides or {}
         v = self._scr("WV", pp, mp, 1, cin)
         mm = self._scr("WM", pp, mp, 1, cout)
         self._meta(kind="wino_in", name=name + ".xin", flops=0.0, bytes=4.0 * n * hw * cin + 4.0 * float(pp) * tiles * cin)
         self.op_args[-1].update(triple=name + ".xout")
-        self._touch(a, v)
+        self.arena.touch(a, v)
         if not self._dry:
             wi = L.WinoDesc()
             wi.inp, wi.ldi, wi.in_img_stride = a.ptr, a.ld, st.get("a", hw)
             wi.out, wi.ldo = v.ptr, cin
             wi.n_img, wi.H, wi.W, wi.C, wi.Mp, wi.R = n, a.h, a.w, cin, mp, r
             self._add(self.lib.uavsal_plan_add_wino_input, wi, "plan_add_wino_input(%s)" % name)
-            key = ("wino", id(conv), wslice, r)
-            if key not in self._wcache:
-                w = conv.weight.detach()
-                if wslice is not None:
-                    w = w[:, wslice[0]:wslice[1]]
-                self._wcache[key] = self._dev(P.pack_wino_weight(w, r))
         self._meta(kind="conv1", name=name, flops=2.0 * pp * tiles * cin * cout,
                    bytes=4.0 * pp * (tiles * (cin + cout) + cin * cout), M=pp * mp, K=cin, Nc=cout,
                    direct_flops=2.0 * n * hw * cin * cout * 9)
-        self._touch(v, mm)
+        self.arena.touch(v, mm)
         self.op_args[-1].update(triple=name + ".xout")
         if not self._dry:
             d = L.ConvDesc()
             d.a, d.lda, d.a_img_stride = v.ptr, cin, mp
-            d.w, d.w_group_stride = self._wcache[key].data_ptr(), P.roundup(cout, 32) * P.roundup(cin, 32)
+            d.w, d.w_group_stride = self.weights.wino(conv, wslice, r).data_ptr(), roundup(cout, 32) * roundup(cin, 32)
             d.out, d.ldc, d.o_img_stride = mm.ptr, cout, mp
             d.n_img, d.H, d.W, d.Cin, d.Cout, d.taps = pp, mp, 1, cin, cout, 1
             d.prec, d.act, d.epi, d.tile = L.PREC["f32"], L.ACT_NONE, L.EPI_AFFINE, gemm_tile      # Winograd plans are exact fp32
@@ -818,7 +612,7 @@ class Engine:
             m_["prec"] = "f32"
             self._add(self.lib.uavsal_plan_add_conv, d, "plan_add_conv(%s)" % name)
         self._meta(kind="wino_out", name=name + ".xout", flops=0.0, bytes=4.0 * (float(pp) * tiles * cout + n * hw * cout))
-        self._touch(mm, out, *(twa or ()), *((a,) if twa is not None else ()))
+        self.arena.touch(mm, out, *(twa or ()), *((a,) if twa is not None else ()))
         if out.key is not None and self._dry:
             self._no_shadow.add(out.key)            # the output transform does not write split shadows
         if not self._dry:
@@ -827,7 +621,7 @@ class Engine:
             wo.out, wo.ldo, wo.out_img_stride = out.ptr, out.ld, st.get("o", hw)
             wo.n_img, wo.H, wo.W, wo.C, wo.Mp, wo.R = n, a.h, a.w, cout, mp, r
             if bn is not None:
-                s_, b_ = self._affine(bn, cout)
+                s_, b_ = self.weights.affine(bn, cout)
                 wo.scale, wo.bias = s_.data_ptr(), b_.data_ptr()
             wo.act, wo.epi = act, L.EPI_AFFINE
             if twa is not None:
@@ -850,20 +644,11 @@ class Engine:
         byts = 4.0 * a.n * c * (a.h * a.w + ho * wo) + 4.0 * 9 * c + 4.0 * 2 * c
         self._meta(kind="dw", name=name, flops=2.0 * 9 * a.n * ho * wo * c, bytes=byts, stride=stride,
                    dil=dilation if not isinstance(dilation, (list, tuple)) else tuple(dilation), patches44=a.n * ((ho + 3) // 4) * ((wo + 3) // 4) * (c // 4))
-        self._touch(a, out)
+        self.arena.touch(a, out)
         if self._dry:
             return
         grouped = isinstance(conv, (list, tuple))      # several dilated branches of one map: channel groups with their own dilation
-        key = ("dw",) + tuple(id(c_) for c_ in conv) if grouped else ("dw", id(conv))
-        if key not in self._wcache:
-            if grouped:
-                parts = [P.fold_bn(b_) for b_ in bn]
-                self._wcache[key] = (self._dev(torch.cat([P.pack_dw_weight(c_.weight) for c_ in conv], 1)),
-                                     self._dev(torch.cat([p_[0] for p_ in parts])), self._dev(torch.cat([p_[1] for p_ in parts])))
-            else:
-                s, b = P.fold_bn(bn)
-                self._wcache[key] = (self._dev(P.pack_dw_weight(conv.weight)), self._dev(s), self._dev(b))
-        w9, s, b = self._wcache[key]
+        w9, s, b = self.weights.depthwise(conv, bn)
         d = L.DwDesc()
         if grouped:
             d.dil_group_c = c // len(conv)
@@ -891,16 +676,10 @@ class Engine:
         c = a.c
         self._meta(kind="dw_dot", name=name, flops=2.0 * 10 * a.n * a.h * a.w * c, bytes=4.0 * a.n * a.h * a.w * (c + 1) + 4.0 * 12 * c,
                    stride=1, dil=1, kernel="dw3x3_dot_kernel<4, 4>")
-        self._touch(a, out)
+        self.arena.touch(a, out)
         if self._dry:
             return
-        key = ("dwdot", id(dwc), id(pl))
-        if key not in self._wcache:
-            s, b = P.fold_bn(dwbn)
-            s2, b2 = P.fold_bn(plbn)
-            self._wcache[key] = (self._dev(P.pack_dw_weight(dwc.weight)), self._dev(s), self._dev(b),
-                                 self._dev(pl.weight.detach().float().reshape(-1)), self._dev(s2.reshape(1)), self._dev(b2.reshape(1)))
-        w9, s, b, w2, s2, b2 = self._wcache[key]
+        w9, s, b, w2, s2, b2 = self.weights.dw_dot(dwc, dwbn, pl, plbn)
         d = L.DwDotDesc()
         d.inp, d.ldi = a.ptr, a.ld
         d.w9c, d.scale, d.bias, d.w2, d.scale2, d.bias2 = (t.data_ptr() for t in (w9, s, b, w2, s2, b2))
@@ -911,7 +690,7 @@ class Engine:
 
     def bilinear(self, name, a: V, out: V, src_mod=None, src_div=1):
         self._meta(kind="bilinear", name=name, flops=0.0, bytes=4.0 * out.n * out.h * out.w * out.c * 2)
-        self._touch(a, out)
+        self.arena.touch(a, out)
         if self._dry:
             return
         d = L.BilinearDesc()
@@ -928,7 +707,7 @@ class Engine:
         """`src` / `dst`: a view (its address is taken once the op is open, so that the arena sees the use at this op) or a raw
         device address (the caller's boundary tensors; `bind` = (name, float offset) of that tensor, see Engine.bound)."""
         self._meta(kind="layout", name=name, flops=0.0, bytes=8.0 * n * c * hw)
-        self._touch(*(t for t in (src, dst) if isinstance(t, V)))
+        self.arena.touch(*(t for t in (src, dst) if isinstance(t, V)))
         if self._dry:
             return
         d = L.LayoutDesc()
@@ -942,7 +721,6 @@ class Engine:
     def fused_block(self, name, x: V, blk, out: V) -> bool:
         """The whole inverted-residual block as ONE launch (uavsal_fused_ir: the expanded tensors stay in LDS),
         where an instance exists -- the bandwidth-bound small-channel blocks features[1..7].  False = not taken."""
-        seq = blk.conv
         if not self.fuse_blocks or getattr(blk, "dilation", 1) != 1:
             return False
         d = L.FusedIrDesc()
@@ -969,33 +747,14 @@ class Engine:
                    # what the matrix pipe executes in the mid kernel: every 4 x 8 patch expands its whole 6 x 10 halo (64 MFMA
                    # rows) and projects 32 rows, edge patches included
                    **({"flops_executed": 2.0 * wgs * blk.hidden * (64 * x.c + 32 * out.c)} if natural else {}))
-        self._touch(x, out)
+        self.arena.touch(x, out)
         if out.key is not None:
             self._no_shadow.add(out.key)            # this kernel does not write split shadows
         if self._dry:
             return True
-        if blk.expand_ratio != 1:
-            pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
-        else:
-            pw, pwbn, dwc, dwbn, pl, plbn = None, None, seq[0][0], seq[0][1], seq[1], seq[2]
-        key = ("fused", id(dwc), natural)
-        if key not in self._wcache:
-            ws = {}
-            if pw is not None:
-                s_, b_ = P.fold_bn(pwbn)
-                w1 = pw.weight.detach().float().cpu().reshape(blk.hidden, x.c)
-                ws["w1"] = self._dev((w1 if natural else w1.t()).contiguous())
-                ws["s1"], ws["b1"] = self._dev(s_), self._dev(b_)
-            s_, b_ = P.fold_bn(dwbn)
-            ws["wd"], ws["sd"], ws["bd"] = self._dev(P.pack_dw_weight(dwc.weight)), self._dev(s_), self._dev(b_)
-            s_, b_ = P.fold_bn(plbn)
-            w2 = pl.weight.detach().float().cpu().reshape(out.c, blk.hidden)
-            ws["w2"] = self._dev((w2 if natural else w2.t()).contiguous())
-            ws["s2"], ws["b2"] = self._dev(s_), self._dev(b_)
-            self._wcache[key] = ws
-        ws = self._wcache[key]
+        ws = self.weights.fused_block(blk, natural)
         d.inp, d.ldi = x.ptr, x.ld
-        if pw is not None:
+        if "w1" in ws:
             d.w1, d.scale1, d.bias1 = ws["w1"].data_ptr(), ws["s1"].data_ptr(), ws["b1"].data_ptr()
         d.wd, d.scale_d, d.bias_d = ws["wd"].data_ptr(), ws["sd"].data_ptr(), ws["bd"].data_ptr()
         d.w2, d.scale2, d.bias2 = ws["w2"].data_ptr(), ws["s2"].data_ptr(), ws["b2"].data_ptr()
@@ -1013,8 +772,6 @@ class Engine:
         `expanded`: the block's expanded tensor already exists (several blocks' expands run as one GEMM)."""
         if expanded is None and final_act == L.ACT_NONE and self.fused_block(name, x, blk, out):
             return
-        seq = blk.conv
-        stride, dil = blk.stride, getattr(blk, "dilation", 1)
         # a block whose expanded tensor would be bigger than BLOCK_CHUNK_BYTES runs in chunks of whole frames (the block is
         # per-frame arithmetic; the launches stay many rounds of the chip): the arena's peak is set by the biggest E, not by
         # the layer count -- 720x1280 x 64 frames: fucbst's 7.1 GB E in two halves, peak 16.97 -> ~13 GB
@@ -1102,8 +859,8 @@ class Engine:
         # buffers written by kernels that do not produce split shadows
         self._no_shadow.update(("h0", "c0", "gauss_in", "ob_in", "f0", "ctx_sum", "lstm_pre", "lstm_c", "twa_pre"))
         self._no_shadow.update("st%d_dif" % i for i in range(len(m.st_layer)))
-        lstm_model = getattr(m, "rnn_type", "twa") == "lstm"
-        c0 = self._buf("c0", self.n_seq, h, w, 256, pinned=self.persistent) if lstm_model else None
+        lstm = self.lstm
+        c0 = self._buf("c0", self.n_seq, h, w, 256, pinned=self.persistent) if lstm else None
         Np = 1 if self.static_priors else N
         # which priors this model has (reference model.py:281-324: a disabled prior has no net, and with none at all the two
         # fusion blocks do not exist either); enabled priors keep the reference's concat order gauss | observed | context
@@ -1117,7 +874,7 @@ class Engine:
         g0 = self._buf("gauss_in", Np, h, w, 8) if use_g else None
         o0 = self._buf("ob_in", Np, h, w, 20) if use_o else None
         if not self.persistent:          # persistent mode: h0 / c0 ARE the state, staged only on demand (run())
-            names = ["state.in"] + (["cstate.in"] if lstm_model else [])
+            names = ["state.in"] + (["cstate.in"] if lstm else [])
             for nm, src, dst in zip(names, ("state_in", "cstate_in"), (h0, c0)):
                 self.layout(nm, None if self._dry else getattr(self, src).data_ptr(), dst, self.n_seq, 256, hw, 256, 1, bind=(src, 0))
         self._mark("boundary_in", s0)
@@ -1128,14 +885,10 @@ class Engine:
         x = self._buf("f0", N, H1, W1, 32)
         self._meta(kind="stem", name="features.0", flops=2.0 * 27 * 32 * N * H1 * W1,
                    bytes=(4.0 if self.in_dtype == torch.float32 else 1.0) * N * 3 * self.H * self.W + 4.0 * N * H1 * W1 * 32)
-        self._touch(x)
+        self.arena.touch(x)
         if not self._dry:
             conv0, bn0 = feats[0][0], feats[0][1]
-            key = ("stem", id(conv0))
-            if key not in self._wcache:
-                s, b = P.fold_bn(bn0)
-                self._wcache[key] = (self._dev(P.pack_stem_weight(conv0.weight)), self._dev(s), self._dev(b))
-            ws, ss, bs = self._wcache[key]
+            ws, ss, bs = self.weights.stem(conv0, bn0)
             d = L.StemDesc()
             if self.in_dtype == torch.uint8:
                 d.inp, d.in_u8 = None, self.x_in.data_ptr()
@@ -1270,7 +1023,7 @@ class Engine:
             st_lane = N > 8
             self.conv("st%d.reduce" % i, x, te.reduce_conv[0], te.reduce_conv[1], r, R6)
             self._meta(kind="tdiff", name="st%d.tdiff" % i, flops=0.0, bytes=4.0 * N * hw * 96)
-            self._touch(r, dif)
+            self.arena.touch(r, dif)
             if not self._dry:
                 d = L.TdiffDesc()
                 d.inp, d.ldi, d.out, d.ldo = r.ptr, 32, dif.ptr, 64
@@ -1305,7 +1058,7 @@ class Engine:
                 B = N // self.ctx_T
                 tsum = self._buf("ctx_sum", B, h, w, 256)
                 self._meta(kind="tsum", name="ctx.sum", flops=0.0, bytes=4.0 * (N + B) * hw * 256)
-                self._touch(xs, tsum)
+                self.arena.touch(xs, tsum)
                 if not self._dry:
                     d = L.TsumDesc()
                     d.inp, d.ldi, d.out, d.ldo = xs.ptr, 320, tsum.ptr, 256
@@ -1336,7 +1089,6 @@ class Engine:
         rc = m.rnn.cell_list[0].rnn_conv
         Lq = self.seq_len
         ro = self._buf("rnn", N, h, w, 256)
-        lstm = getattr(m, "rnn_type", "twa") == "lstm"
         if lstm:
             pre = self._buf("lstm_pre", N, h, w, 1024)      # W[:, :256] * x_t for all t, rows 4*c+gate
             self.conv("lstm.wx", xf, rc, None, pre, NONE, taps=9, wslice=(0, 256), gate_interleave=256)
@@ -1395,7 +1147,7 @@ class Engine:
             # h_last of every clip (NHWC rows of the history) -> the resident state buffer, one strided copy
             for hist, _, keep in outs:
                 self._meta(kind="copy", name="state.keep", flops=0.0, bytes=8.0 * self.n_seq * 256 * hw)
-                self._touch(hist, keep)
+                self.arena.touch(hist, keep)
                 if not self._dry:
                     d = L.CopyDesc()
                     d.inp, d.out = hist.frames(Lq - 1, 1).ptr, keep.ptr
@@ -1412,7 +1164,7 @@ class Engine:
         # error guard: poisons what the caller will see if any kernel of this run set the error word
         self._meta(kind="guard", name="guard", flops=0.0, bytes=0.0)
         if self.persistent:
-            self._touch(h0, c0)
+            self.arena.touch(h0, c0)
         if not self._dry:
             bufs = [(self.out.data_ptr(), self.out.numel())]
             if self.persistent:
@@ -1546,7 +1298,7 @@ class Engine:
     def run(self, x, cb0, cb1, state=None, taps: Optional[dict] = None, cstate=None):
         if x.dtype != self.in_dtype:
             raise RuntimeError("engine built for %s frames, got %s" % (self.in_dtype, x.dtype))
-        lstm = getattr(self.model, "rnn_type", "twa") == "lstm"
+        lstm = self.lstm
         with torch.cuda.device(self.device):
             self.check(wait=False)               # a previous asynchronous run that is over by now
             if self.inplace:
@@ -1579,7 +1331,7 @@ class Engine:
             if taps is not None:
                 if not self.keep_taps:
                     raise RuntimeError("engine was built without taps")
-                for k in ("c3", "c4", "c5", "sfnet", "st0", "st1", "fust_in_cb", "prefuse", "rnn"):
+                for k in self.TAP_NAMES:
                     if k in self.named:          # (no "fust_in_cb" in a model without priors)
                         taps[k] = self.tap(k)
                 taps["logits"] = self.logits.clone().view(self.N, 1, self.h, self.w)
@@ -1602,7 +1354,7 @@ class Engine:
         the head of group k + 1 overlaps the tail of group k (Demo_Test.py:75-86 runs them back to back)."""
         if not (self.persistent and self.inplace):
             raise RuntimeError("run_streamed needs the resident-state launch-loop plan (model.persistent_state = True, no graph)")
-        lstm = getattr(self.model, "rnn_type", "twa") == "lstm"
+        lstm = self.lstm
         with torch.cuda.device(self.device):
             self.check(wait=False)
             out, _ = self._bind_in_place(x, cb0, cb1, self.h_view, self.c_view, lstm)      # (resident views: nothing is staged)

@@ -34,6 +34,24 @@ def roundup(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+# uavsal_conv_tile numbers of the fp32 GEMM instances with 32-float K stages (csrc/conv_gemm_k32.hip)
+K32_TILES = (8, 9, 10, 11)
+
+
+def conv_weight_layout(prec: str, split: bool, dwproj: bool, tile: int, ksize: int) -> str:
+    """The `pack_conv_weight` layout for a GEMM launch of precision `prec`, from what the library answers for its descriptor:
+    `split` (uavsal_conv_uses_split: the pre-split LDS-DMA path), `dwproj` (uavsal_conv_dwproj: the depthwise -> projection
+    kernel) and `tile` (uavsal_conv_tile); `ksize` = 1 or 3, the conv's kernel size.  (The 32-float-K instances need
+    Cin % 32 == 0, and for 1x1 weights of such a Cin 'f32k32' and 'f32' are the same bytes: only 3x3 weights take the name.)"""
+    if split:
+        return "f16x3i"
+    if dwproj and prec == "f16x3":
+        return "f16x3j"
+    if prec == "f32" and tile in K32_TILES and ksize == 3:
+        return "f32k32"
+    return prec
+
+
 def pack_conv_weight(w: torch.Tensor, prec: str) -> torch.Tensor:
     """`w` [Cout, Cin, kh, kw] (kh=kw in {1,3}) -> packed byte tensor (uint8, 1-D) in the layout
     `uavsal_conv_gemm` expects for `prec` in {'f32','bf16','bf16x3','f16x3'}, or 'f32k32': fp32 for the kernels

@@ -1,0 +1,106 @@
+"""Packed device weights of a model: BatchNorm folded, weights in the layouts of packing.py, uploaded once and remembered.
+
+`WeightCache(device, store)` wraps the dictionary a model keeps per device (`model._wshared[device]`); the dictionary stays
+the store, so every engine of the model -- whatever its precision -- and every replica share one copy, and dropping the
+dictionary drops the weights.  One method per kind of parameter set; each is the only place where that kind's key is built
+and its tensors are made.  Keys carry `id(module)`: an entry holds that module's parameters as they were when it was packed
+(`model.invalidate_engines()` after an edit)."""
+import torch
+
+from . import packing as P
+
+
+def _seq(x):
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
+def _ids(mods):
+    return tuple(id(m) for m in mods)
+
+
+def _folded(bns):
+    """(scale, bias) of BatchNorms whose channels lie side by side."""
+    parts = [P.fold_bn(b) for b in bns]
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
+def _weight(convs, wslice):
+    w = torch.cat([c.weight.detach() for c in convs], 0)
+    return w if wslice is None else w[:, wslice[0]:wslice[1]]
+
+
+class WeightCache:
+    def __init__(self, device, store):
+        self.device, self.store = torch.device(device), store
+
+    def _get(self, key, make):
+        if key not in self.store:
+            self.store[key] = make()
+        return self.store[key]
+
+    def _up(self, *ts):
+        return tuple(t.contiguous().to(self.device) for t in ts)      # kept alive by the store
+
+    def affine(self, bn, cout):
+        """(scale, bias) of one BatchNorm or a list (several convs of the same input as ONE GEMM: outputs side by side), padded
+        to `roundup(cout, 32)` with the identity."""
+        bns, n = _seq(bn), P.roundup(cout, 32)
+
+        def make():
+            s, b = _folded(bns)
+            return self._up(P.pad_vec(s, n, 1.0), P.pad_vec(b, n, 0.0))
+        return self._get(("bn",) + _ids(bns) + (cout,), make)
+
+    def conv(self, conv, wslice, gate_interleave, layout):
+        """The weights of one conv or a list (output channels side by side), input channels `wslice` = (first, end) of them,
+        packed for `layout` (packing.conv_weight_layout).  `gate_interleave` = hidden size of a ConvLSTM whose gate rows are
+        interleaved: row g * hid + c -> 4 * c + g (gates i, f, o, g adjacent)."""
+        convs = _seq(conv)
+
+        def make():
+            w = _weight(convs, wslice)
+            if gate_interleave:
+                w = w.reshape(4, gate_interleave, *w.shape[1:]).permute(1, 0, 2, 3, 4).reshape(w.shape)
+            return self._up(P.pack_conv_weight(w, layout))[0]
+        return self._get(("w",) + _ids(convs) + (wslice, layout, gate_interleave), make)
+
+    def wino(self, conv, wslice, r):
+        """The Winograd F(r x r, 3x3) filter transform of a dense 3x3 conv (input channels `wslice`)."""
+        return self._get(("wino", id(conv), wslice, r), lambda: self._up(P.pack_wino_weight(_weight([conv], wslice), r))[0])
+
+    def depthwise(self, conv, bn):
+        """(tap-major weights, scale, bias) of a depthwise 3x3 + BatchNorm, or of a list of them as channel groups.  The
+        standalone launch and the depthwise inside a projection GEMM's loader share the entry."""
+        convs = _seq(conv)
+        return self._get(("dw",) + _ids(convs), lambda: self._up(torch.cat([P.pack_dw_weight(c.weight) for c in convs], 1),
+                                                                *_folded(_seq(bn))))
+
+    def dw_dot(self, dwc, dwbn, pl, plbn):
+        """Depthwise 3x3 + BatchNorm -> projection to ONE channel + BatchNorm: (w9, scale, bias, w2, scale2, bias2)."""
+        return self._get(("dwdot", id(dwc), id(pl)), lambda: self._up(
+            P.pack_dw_weight(dwc.weight), *P.fold_bn(dwbn), pl.weight.detach().float().reshape(-1),
+            *(t.reshape(1) for t in P.fold_bn(plbn))))
+
+    def fused_block(self, blk, natural):
+        """An inverted-residual block for the one-launch kernels: {w1, s1, b1 (with an expand conv), wd, sd, bd, w2, s2, b2}.
+        The 1x1 weights are [Cin][Cout], or -- `natural` (csrc/fused_mid.hip) -- as the module holds them, [Cout][Cin]."""
+        seq = list(blk.conv)
+        pw, pwbn = (None, None) if blk.expand_ratio == 1 else (seq[0][0], seq.pop(0)[1])
+        dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1], seq[2]
+
+        def mat(conv):
+            w = conv.weight.detach().float().cpu().reshape(conv.weight.shape[:2])
+            return w if natural else w.t()
+
+        def make():
+            ws = {}
+            if pw is not None:
+                ws["w1"], ws["s1"], ws["b1"] = self._up(mat(pw), *P.fold_bn(pwbn))
+            ws["wd"], ws["sd"], ws["bd"] = self._up(P.pack_dw_weight(dwc.weight), *P.fold_bn(dwbn))
+            ws["w2"], ws["s2"], ws["b2"] = self._up(mat(pl), *P.fold_bn(plbn))
+            return ws
+        return self._get(("fused", id(dwc), natural), make)
+
+    def stem(self, conv, bn):
+        """(weights [27, 32], scale, bias) of the stem conv + BatchNorm."""
+        return self._get(("stem", id(conv)), lambda: self._up(P.pack_stem_weight(conv.weight), *P.fold_bn(bn)))

@@ -1,5 +1,5 @@
 """Record a launch plan WITHOUT a device: the library's shape queries are the real ones (they need no GPU), the plan-recording
-entry points are stubs that count the ops and keep the fill descriptors.  Lets the CPU suite run the engine's second pass --
+entry points are stubs that count the ops and keep what they were handed (`MockLib.calls`).  Lets the CPU suite run the engine's second pass --
 where every activation address is handed out by the arena and checked against the buffer's declared live range."""
 import torch
 
@@ -11,6 +11,9 @@ class MockLib:
     def __init__(self, real):
         self.real, self.n, self.fills, self.lanes = real, 0, [], []
         self.cur_lane = 0
+        # (entry point, arguments) of every recording call in order: a copy of the descriptor for the ops that take one, the
+        # plain arguments for guard / fork / join / set_lane / patch_ptr (tools/plan_fingerprint.py)
+        self.calls = []
 
     def __getattr__(self, name):
         if name.startswith("uavsal_plan_add_"):
@@ -18,19 +21,29 @@ class MockLib:
                 if name == "uavsal_plan_add_fill":
                     d = a[0]._obj
                     self.fills.append((self.n, int(d.out), int(d.n), self.cur_lane))
+                if name in ("uavsal_plan_add_guard", "uavsal_plan_add_fork", "uavsal_plan_add_join"):
+                    self.calls.append((name, a))
+                else:
+                    self.calls.append((name, type(a[0]._obj).from_buffer_copy(a[0]._obj)))
                 self.n += 1
                 return self.n - 1
             return add
         if name == "uavsal_plan_set_lane":
             def set_lane(plan, lane):
                 self.cur_lane = lane
+                self.calls.append((name, (lane,)))
                 return 0
             return set_lane
+        if name == "uavsal_plan_patch_ptr":
+            def patch_ptr(plan, *a):
+                self.calls.append((name, a))
+                return 0
+            return patch_ptr
         if name == "uavsal_plan_create":
             return lambda: 1
         if name == "uavsal_plan_error_word":
             return lambda p: 4096
-        if name in ("uavsal_plan_enable_lanes", "uavsal_plan_destroy", "uavsal_plan_patch_ptr"):
+        if name in ("uavsal_plan_enable_lanes", "uavsal_plan_destroy"):
             return lambda *a: 0
         return getattr(self.real, name)
 

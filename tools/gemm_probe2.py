@@ -29,7 +29,7 @@ def run(hw, n_img, cin, cout, taps, tile, split=True, act=1, iters=20, prec="f16
     d.prec, d.act, d.epi, d.tile = L.PREC[prec], act, 0, tile
     d.w = 1 << 20
     uses = int(lib.uavsal_conv_uses_split(C.byref(d))) == 1
-    wp = P.pack_conv_weight(wt, "f16x3i" if uses else prec).to(dev)
+    wp = P.pack_conv_weight(wt, P.conv_weight_layout(prec, uses, False, int(lib.uavsal_conv_tile(C.byref(d))), wt.shape[-1])).to(dev)
     d.w = wp.data_ptr()
     plan = C.c_void_p(lib.uavsal_plan_create())
     lib.uavsal_plan_add_conv(plan, C.byref(d))

@@ -56,7 +56,7 @@ def run(hw, n_img, cin, cout, taps, tile, iters=20, launches_only=0, act=1, stam
     h, w = hw
     a = torch.rand((n_img * h * w, cin), device=dev) * 2 - 1
     wt = (torch.rand((cout, cin, 3 if taps == 9 else 1, 3 if taps == 9 else 1)) - 0.5) * 0.1
-    wp = P.pack_conv_weight(wt, "f32k32" if tile in (8, 9, 10, 11) else "f32").to(dev)
+    wp = P.pack_conv_weight(wt, P.conv_weight_layout("f32", False, False, tile, wt.shape[-1])).to(dev)
     out = torch.empty((n_img * h * w, cout), device=dev)
     s = torch.ones(P.roundup(cout, 32), device=dev)
     b = torch.zeros(P.roundup(cout, 32), device=dev)
@@ -117,7 +117,7 @@ def parts():
     names = {1: "full", 101: "no store", 116: "no epilogue", 102: "no MFMA", 104: "no DMA", 108: "no frag reads",
              106: "no MFMA, no DMA", 110: "no MFMA, no frag", 126: "K loop: DMA only", 124: "K loop: MFMA+frag only (no DMA, no epi)"}
     for sh in (((45, 80), 8, 256, 1536, 1), ((45, 80), 64, 256, 1536, 1), ((45, 80), 8, 4096, 1536, 1)):
-        for tile in (8, 9, 10, 11):
+        for tile in P.K32_TILES:
             for act, nm in names.items():
                 ms, tf = run(*sh, tile, act=act)
                 print("parts n=%d K=%d N=%d tile=%d %-42s %8.1f us" % (sh[1], sh[2], sh[3], tile, nm, ms * 1e3), flush=True)
