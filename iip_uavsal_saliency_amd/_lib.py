@@ -236,6 +236,10 @@ SYMBOLS = [
     ("uavsal_plan_enable_lanes", C.c_int, [C.c_void_p, C.c_int]),
     ("uavsal_plan_size", C.c_int, [C.c_void_p]),
     ("uavsal_plan_run", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("uavsal_plan_group_mark", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("uavsal_plan_group_enable", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("uavsal_plan_group_launches", C.c_int, [C.c_void_p, C.c_int]),
+    ("uavsal_plan_last_launches", C.c_int, [C.c_void_p]),
     ("uavsal_plan_graph_build", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_graph_launch", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_time", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),

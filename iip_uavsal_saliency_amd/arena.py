@@ -11,10 +11,11 @@ class _ArenaRef:
     (positions on the main lane's timeline; a use on a side lane counts from that lane's fork to its join).  Stands where a
     tensor stood in `V.t`, so every view of the buffer shares it; `data_ptr()` refuses to hand out an address outside the
     live range while a plan is being recorded -- a recorder that forgot to declare a use fails there, at build time."""
-    __slots__ = ("arena", "aid", "numel_", "off", "first", "last", "lkey", "lfirst", "llast")
+    __slots__ = ("arena", "aid", "numel_", "off", "first", "last", "lkey", "lfirst", "llast", "pinned")
 
     def __init__(self, arena, aid, numel):
         self.arena, self.aid, self.numel_ = arena, aid, int(numel)
+        self.pinned = False                   # outlives the call: a range of its own, never poisoned (Arena.pin)
         self.off, self.first, self.last = None, None, None
         # lkey: (lane, index of its fork) while every use so far was recorded on that lane between that fork and its join
         # (its launches are then ordered among themselves on one stream: [lfirst, llast] in recording order), else "mixed"
@@ -118,6 +119,14 @@ class Arena:
         self._serial += 1
         return self.ref((kind, self._serial), numel)
 
+    def pin(self, r):
+        """`r` outlives a call (sizing pass): what it holds after one run is read by later runs that do not write it again (the
+        output of the prior nets while the caller's priors stay the same).  `place` gives it a range that no other buffer ever
+        gets, whatever the live ranges say, and `due` never names it for a poison fill."""
+        if not isinstance(r, _ArenaRef) or r.arena is not self:
+            raise RuntimeError("arena: only a buffer of this arena can be pinned")
+        r.pinned = True
+
     def touch(self, *vs):
         """Declare that the op being recorded reads or writes these views.  Sizing pass: grows the live range of their arena
         buffers -- on a side lane from the lane's fork (it may start right there) to, at its join, the join (it may still
@@ -168,8 +177,21 @@ class Arena:
         offs, total, bound = plan_arena([(r.numel_, r.first, r.last, r.lkey, r.lfirst, r.llast) for r in refs])
         for r, o in zip(refs, offs):
             r.off = o
+        # a pinned buffer's range is its own: where other buffers share the range the planner gave it (by liveness they may),
+        # it moves to a range of its own behind the pool; where nobody does -- the concatenated prior maps of the real plans --
+        # it stays.  Everything else stays exactly where the planner put it: pinning changes no other address
+        rnd = lambda n: (n + ARENA_ALIGN - 1) // ARENA_ALIGN * ARENA_ALIGN
+        shared = total
+        for r in refs:
+            if r.pinned:
+                r.last, r.lkey = n_ops, "mixed"          # (what it holds is still wanted after the plan's last op)
+                if any(q is not r and q.off < r.off + rnd(r.numel_) and r.off < q.off + rnd(q.numel_) for q in refs):
+                    r.off = total
+                    total += rnd(r.numel_)
         self.stats = {"arena_mb": total * 4 / 1e6, "live_bound_mb": bound * 4 / 1e6,
-                      "unshared_mb": sum(r.numel_ for r in refs) * 4 / 1e6, "buffers": len(refs)}
+                      "unshared_mb": sum(r.numel_ for r in refs) * 4 / 1e6, "buffers": len(refs),
+                      "pinned_mb": sum(rnd(r.numel_) for r in refs if r.pinned) * 4 / 1e6,
+                      "pinned_extra_mb": (total - shared) * 4 / 1e6}
         return total
 
     def layout(self):
@@ -183,7 +205,7 @@ class Arena:
         last one) -- every buffer once, when the op that ends its live range has been recorded; by offset.  A buffer private to
         a side lane is released in that lane's own order: its fill goes on that lane (while the lane is open: behind its last
         launch there, in front of whatever the lane runs next), everything else on the main lane."""
-        due = [r for r in self.refs.values() if r not in self._poisoned and (final or r.end() < self.lop + 1)]
+        due = [r for r in self.refs.values() if r not in self._poisoned and not r.pinned and (final or r.end() < self.lop + 1)]
         self._poisoned.update(due)
         # (still live at the end of the plan -- taps, the history the state is read from: no fill)
         return [(r, r.lkey[0] if isinstance(r.lkey, tuple) and self._lane_open.get(r.lkey[0]) == r.lkey[1] else 0)

@@ -11,6 +11,7 @@ namespace {
 enum OpKind { OP_CONV = 0, OP_DW, OP_STEM, OP_BILINEAR, OP_TDIFF, OP_TSUM, OP_LAYOUT, OP_GUARD, OP_COPY, OP_FUSED_IR, OP_FORK, OP_JOIN,
               OP_WINO_IN, OP_WINO_OUT, OP_DW_DOT, OP_FILL };
 constexpr int MAX_LANES = 8;
+constexpr int MAX_GROUPS = 32;
 
 // Lanes: lane 0 is the caller's stream; lanes 1..7 are private streams on which independent
 // branches of the forward (prior nets, ASPP branches, the temporal branch of an STBlock) run
@@ -20,6 +21,7 @@ constexpr int MAX_LANES = 8;
 struct Op {
     int kind;
     int lane;
+    int group;      // -1, or the group (uavsal_plan_group_mark) whose switch decides whether a run issues this op
     union {
         uavsal_conv_desc conv;
         uavsal_dw_desc dw;
@@ -73,6 +75,10 @@ struct uavsal_plan {
     int32_t* err_host_dev = nullptr;      // its device address
     hipEvent_t done = nullptr;
     bool ran = false;
+    // groups of ops that a run can leave out (uavsal_plan_group_mark / _enable): bit g set = group g is skipped
+    uint32_t groups_off = 0;
+    int last_launches = 0;                // ops that launched in the most recent run (its ranges added up; an op may be >1 kernel)
+    int graph_launches = 0;               // ... that the captured graph holds
 };
 
 extern "C" uavsal_plan* uavsal_plan_create(void) { return new (std::nothrow) uavsal_plan(); }
@@ -97,7 +103,7 @@ extern "C" int uavsal_plan_add_guard(uavsal_plan* p, float* b0, int64_t n0, floa
     if (!p) return UAVSAL_EINVAL;
     if (p->exec) return UAVSAL_ESTATE;
     if (!ensure_error_words(p)) return UAVSAL_ESTATE;
-    Op op; op.kind = OP_GUARD; op.lane = 0;
+    Op op; op.kind = OP_GUARD; op.lane = 0; op.group = -1;
     op.u.guard.err = p->err_dev; op.u.guard.host_err = p->err_host_dev;
     op.u.guard.buf[0] = b0; op.u.guard.n[0] = n0;
     op.u.guard.buf[1] = b1; op.u.guard.n[1] = n1;
@@ -156,7 +162,7 @@ extern "C" int uavsal_plan_enable_lanes(uavsal_plan* p, int on) {
 static int add_sync(uavsal_plan* p, int kind, int lane) {
     if (!p || lane < 1 || lane >= MAX_LANES) return UAVSAL_EINVAL;
     if (p->exec) return UAVSAL_ESTATE;
-    Op op; op.kind = kind; op.lane = lane;
+    Op op; op.kind = kind; op.lane = lane; op.group = -1;
     p->ops.push_back(op);
     return (int)p->ops.size() - 1;
 }
@@ -167,7 +173,7 @@ extern "C" int uavsal_plan_add_join(uavsal_plan* p, int lane) { return add_sync(
     extern "C" int fn(uavsal_plan* p, const T* d) {                      \
         if (!p || !d) return UAVSAL_EINVAL;                              \
         if (p->exec) return UAVSAL_ESTATE;                               \
-        Op op; op.kind = KIND; op.lane = p->cur_lane; op.u.field = *d;   \
+        Op op; op.kind = KIND; op.lane = p->cur_lane; op.group = -1; op.u.field = *d; \
         p->ops.push_back(op);                                            \
         return (int)p->ops.size() - 1;                                   \
     }
@@ -221,17 +227,47 @@ extern "C" int uavsal_plan_patch_ptr(uavsal_plan* p, int op, int slot, void* ptr
 
 extern "C" int uavsal_plan_size(const uavsal_plan* p) { return p ? (int)p->ops.size() : UAVSAL_EINVAL; }
 
-extern "C" int uavsal_plan_run(uavsal_plan* p, int first, int last, uavsal_stream_t stream) {
-    if (!p) return UAVSAL_EINVAL;
+extern "C" int uavsal_plan_group_mark(uavsal_plan* p, int group, int first, int last) {
+    if (!p || group < 0 || group >= MAX_GROUPS || first < 0 || last > (int)p->ops.size() || first >= last) return UAVSAL_EINVAL;
+    if (p->exec) return UAVSAL_ESTATE;
+    for (int i = first; i < last; ++i)
+        if (p->ops[i].group >= 0 && p->ops[i].group != group) return UAVSAL_EINVAL;     // an op belongs to one group
+    for (int i = first; i < last; ++i) p->ops[i].group = group;
+    return 0;
+}
+
+extern "C" int uavsal_plan_group_enable(uavsal_plan* p, int group, int on) {
+    if (!p || group < 0 || group >= MAX_GROUPS) return UAVSAL_EINVAL;
+    const uint32_t bit = 1u << group;
+    if (((p->groups_off & bit) == 0) == (on != 0)) return 0;
+    if (p->exec) return UAVSAL_ESTATE;     // a captured graph replays the ops it was captured with
+    if (on) p->groups_off &= ~bit; else p->groups_off |= bit;
+    return 0;
+}
+
+extern "C" int uavsal_plan_group_launches(const uavsal_plan* p, int group) {
+    if (!p || group < 0 || group >= MAX_GROUPS) return UAVSAL_EINVAL;
+    int n = 0;
+    for (const Op& op : p->ops) n += op.group == group && op.kind != OP_FORK && op.kind != OP_JOIN;
+    return n;
+}
+
+extern "C" int uavsal_plan_last_launches(const uavsal_plan* p) { return p ? p->last_launches : UAVSAL_EINVAL; }
+
+// ops [first, last); `masked`: leave out the ops of switched-off groups -- kernels, fork / join event operations and all.
+// *launched += ops that launched
+static int run_range(uavsal_plan* p, int first, int last, uavsal_stream_t stream, bool masked, int* launched) {
     const int n = (int)p->ops.size();
     if (last < 0 || last > n) last = n;
     if (first < 0 || first > last) return UAVSAL_EINVAL;
     // lanes are honoured only when the whole plan runs; a sub-range (per-op timing) is launched flat
     const bool lanes = p->lanes_on && first == 0 && last == n;
+    const uint32_t off = masked ? p->groups_off : 0u;
     hipStream_t main_s = (hipStream_t)stream;
     if (p->events.size() < p->ops.size()) p->events.resize(p->ops.size(), nullptr);
     for (int i = first; i < last; ++i) {
         const Op& op = p->ops[i];
+        if (op.group >= 0 && ((off >> op.group) & 1u)) continue;
         if (op.kind == OP_FORK || op.kind == OP_JOIN) {
             if (!lanes) continue;
             // (side lanes on high-priority queues, hipStreamCreateWithPriority: the whole step takes 8.8 ms instead of 4.5)
@@ -250,6 +286,7 @@ extern "C" int uavsal_plan_run(uavsal_plan* p, int first, int last, uavsal_strea
         if (lanes && op.lane > 0 && !p->side[op.lane]) return UAVSAL_ESTATE;    // op on a lane that was never forked
         const int e = run_op(op, s);
         if (e) return e;
+        ++*launched;
     }
     if (last == n) {       // the run that ends the plan (its guard op) -- whole, or the second part of a run issued in two ranges
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -261,6 +298,12 @@ extern "C" int uavsal_plan_run(uavsal_plan* p, int first, int last, uavsal_strea
         }
     }
     return 0;
+}
+
+extern "C" int uavsal_plan_run(uavsal_plan* p, int first, int last, uavsal_stream_t stream) {
+    if (!p) return UAVSAL_EINVAL;
+    if (first == 0) p->last_launches = 0;       // (a run issued in two ranges: the second adds to the first)
+    return run_range(p, first, last, stream, true, &p->last_launches);
 }
 
 extern "C" int uavsal_plan_graph_build(uavsal_plan* p, uavsal_stream_t stream) {
@@ -278,6 +321,7 @@ extern "C" int uavsal_plan_graph_build(uavsal_plan* p, uavsal_stream_t stream) {
     e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
     if (e != hipSuccess) { hipGraphDestroy(g); return (int)e; }
     p->graph = g; p->exec = ex;
+    p->graph_launches = p->last_launches;
     return 0;
 }
 
@@ -289,6 +333,7 @@ extern "C" int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream) 
         e = hipEventRecord(p->done, (hipStream_t)stream);
         if (e == hipSuccess) p->ran = true;
     }
+    if (e == hipSuccess) p->last_launches = p->graph_launches;
     return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -298,9 +343,10 @@ extern "C" int uavsal_plan_time(uavsal_plan* p, int first, int last, int iters, 
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess) return (int)hipGetLastError();
     if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return (int)hipGetLastError(); }
-    int r = 0;
+    int r = 0, launched = 0;
     hipEventRecord(e0, s);
-    for (int i = 0; i < iters && !r; ++i) r = uavsal_plan_run(p, first, last, stream);
+    // (a per-op microbenchmark: it times every op it is asked for, whatever the groups' switches say)
+    for (int i = 0; i < iters && !r; ++i) r = run_range(p, first, last, stream, false, &launched);
     hipEventRecord(e1, s);
     hipError_t e = hipEventSynchronize(e1);
     float t = 0.f;

@@ -12,6 +12,7 @@ stream.  PyTorch is used for device memory and streams, not for arithmetic.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, List, Optional
 
@@ -145,6 +146,11 @@ def _dwproj_patch_waste(h, w):
 
 BLOCK_CHUNK_BYTES = 6 << 30                                   # see Engine.ir_block
 
+# the two prior nets: everything recorded on their side lane, with its fork and its join, is one group of the native plan
+# (uavsal_plan_group_mark) that a run leaves out while the caller's prior tensors are the ones the nets last ran on
+PRIOR_LANE = 1
+PRIOR_GROUP = 0
+
 
 class Engine:
     def __init__(self, model, device, n_seq, seq_len, H, W, ctx_T, ctx_mode="tile",
@@ -242,6 +248,15 @@ class Engine:
         self._scratch: Dict[tuple, torch.Tensor] = {}
         self._lane = 0
         self.plan = None
+        # prior cache (see _prior_gate): the native ops of the prior group, whether the group is marked / switched off in the
+        # plan, the record of the run that last executed it (`_prior_rec`: sig, hold, bound, confirmed) and the record the
+        # call in progress is putting together (`_prior_new`: sig, hold, bound; None when the call is not to be remembered)
+        self._prior_ops: List[int] = []
+        self._groups_marked = False
+        self._prior_off = False
+        self._prior_rec = None
+        self._prior_new = None
+        self.prior_group_launches = 0
         # activation arena (liveness-based, arena.py): see _buf / _size
         self.use_arena = bool(getattr(model, "arena", True))
         self.arena_debug = bool(getattr(model, "arena_debug", False))
@@ -289,6 +304,7 @@ class Engine:
         self._dry = False
         self.arena.begin(dry=False)
         self.ops_meta, self.stage_ranges, self.named, self._op_idx, self.op_args = [], {}, {}, {}, []
+        self._prior_ops, self._groups_marked, self._prior_off, self._prior_rec, self._prior_new = [], False, False, None, None
         self.plan = C.c_void_p(self.lib.uavsal_plan_create())
         if not self.plan:
             raise RuntimeError("uavsal_plan_create failed")
@@ -345,6 +361,8 @@ class Engine:
                 L.check(self.lib.uavsal_plan_set_lane(self.plan, lane), "plan_set_lane")
                 cur = lane
             self._op_idx["poison:%s" % (r.aid,)] = len(self.ops_meta)
+            if lane == PRIOR_LANE:
+                self._prior_ops.append(len(self.ops_meta))
             self.ops_meta.append(dict(kind="poison", name="poison:%s" % (r.aid,), flops=0.0, bytes=4.0 * r.numel_, lane=lane))
             self.op_args.append(dict(kind="poison", name="poison:%s" % (r.aid,)))
             d = L.FillDesc()
@@ -395,7 +413,7 @@ class Engine:
     def fork(self, lane):
         """Following ops (until `main()`) go to `lane`, which starts after everything recorded on
         lane 0 so far."""
-        self._meta(kind="sync", name="fork%d" % lane, flops=0.0, bytes=0.0)
+        self._meta(kind="sync", name="fork%d" % lane, flops=0.0, bytes=0.0, group_lane=lane)
         self.arena.fork(lane)
         if not self._dry:
             r = self.lib.uavsal_plan_add_fork(self.plan, lane)
@@ -410,7 +428,7 @@ class Engine:
         self._lane = self.arena.lane = 0
 
     def join(self, lane):
-        self._meta(kind="sync", name="join%d" % lane, flops=0.0, bytes=0.0)
+        self._meta(kind="sync", name="join%d" % lane, flops=0.0, bytes=0.0, group_lane=lane)
         self.arena.join(lane)
         if not self._dry:
             r = self.lib.uavsal_plan_add_join(self.plan, lane)
@@ -434,6 +452,8 @@ class Engine:
     def _meta(self, **kw):
         self._flush_poison()
         self.arena.lop += 1
+        if kw.pop("group_lane", self._lane) == PRIOR_LANE:      # (a fork / join belongs to the lane it names)
+            self._prior_ops.append(len(self.ops_meta))
         self._op_idx[kw.get("name")] = len(self.ops_meta)       # == index of the op in the native plan
         self.ops_meta.append(kw)
         self.op_args.append(dict(kind=kw.get("kind"), name=kw.get("name")))
@@ -921,6 +941,12 @@ class Engine:
                 cb = self._buf("cb192", N, h, w, 64 * num_cb) if num_cb else None
                 cbs = self._buf("cb_static", 1, h, w, 128) if self.static_priors else cb
                 self._no_shadow.add("cb_static")
+                # what the prior nets leave behind outlives the call: a later call with the same prior tensors does not run
+                # them again (_prior_gate), so nothing else may ever be placed on these ranges (the `ctx` slice of cb192 is
+                # still rewritten by every call; split shadows are allocations of their own anyway)
+                if self.use_arena and self._dry and (use_g or use_o):
+                    for v_ in {id(cb.t): cb.t, id(cbs.t): cbs.t}.values():
+                        self.arena.pin(v_)
                 # both nets on lane 1: one fork / join pair (two event operations fewer on the main stream than a lane each:
                 # 4.29 -> 4.26 ms at one clip)
                 self._priors_forked = use_g or use_o
@@ -1185,8 +1211,88 @@ class Engine:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    # ---- prior cache: the prior nets run once per prior tensor, not once per call ------------------------------------------
+    def _mark_groups(self):
+        """Hands the prior group to the native plan (once, before the plan first runs): every op recorded on the prior lane,
+        its fork and its join -- as ranges of consecutive ops."""
+        if self._groups_marked:
+            return
+        self._groups_marked = True
+        ops = sorted(self._prior_ops)
+        i = 0
+        while i < len(ops):
+            j = i
+            while j + 1 < len(ops) and ops[j + 1] == ops[j] + 1:
+                j += 1
+            L.check(self.lib.uavsal_plan_group_mark(self.plan, PRIOR_GROUP, ops[i], ops[j] + 1), "plan_group_mark")
+            i = j + 1
+        self.prior_group_launches = int(self.lib.uavsal_plan_group_launches(self.plan, PRIOR_GROUP)) if ops else 0
+
+    def _prior_sig(self, srcs):
+        """What identifies the caller's prior tensors of a call: per used prior the tensor object (of a view: its base, with
+        the view's address, shape and strides) and torch's version counter, which every in-place operation on the tensor or on
+        any view of it advances.  None when a tensor has no version counter (inference tensors): such a call is never cached."""
+        sig = []
+        for t, on in zip(srcs, self.use_priors[:2]):
+            if not on:
+                continue
+            try:
+                base = t._base if t._base is not None else t
+                sig.append((base, t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version))
+            except RuntimeError:
+                return None
+        return sig
+
+    def drop_prior_record(self):
+        """Forget the run the prior nets' output in the arena comes from: the next call runs them again."""
+        self._prior_rec = None
+
+    def _prior_gate(self, srcs) -> bool:
+        """May this call leave the prior group out?  Only if a completed, error-free run of this plan executed the group on the
+        very tensors `srcs` names -- same objects, same version -- since the plan was built (its output then still stands in the
+        pinned buffers, Arena.pin).  Sets the group's switch in the native plan accordingly; the call's launches then go
+        inside `_prior_launches`, which closes it."""
+        self._mark_groups()
+        self._prior_new = None
+        if not self._prior_ops:
+            return False
+        skip = False
+        sig = self._prior_sig(srcs) if (self.inplace and bool(getattr(self.model, "cache_priors", True))) else None
+        rec = self._prior_rec
+        if sig is not None and rec is not None and len(rec["sig"]) == len(sig) and all(
+                a[0] is b[0] and a[1:] == b[1:] for a, b in zip(rec["sig"], sig)):
+            if not rec["confirmed"]:
+                self.check(wait=True)           # (raises, and drops the record, if that run reported a device error)
+            skip = self._prior_rec is not None
+        if not skip:
+            self._prior_rec = None              # replaced once this run is launched
+            self._prior_new = None if sig is None else dict(sig=sig, hold=[], bound={})
+        if skip != self._prior_off:
+            L.check(self.lib.uavsal_plan_group_enable(self.plan, PRIOR_GROUP, 0 if skip else 1), "plan_group_enable")
+            self._prior_off = skip
+        return skip
+
+    @contextlib.contextmanager
+    def _prior_launches(self):
+        """Around the launches of a call that went through `_prior_gate`: once they are all issued, the tensors the prior group
+        ran on become the record (with the contiguous forms the plan reads, which must stay alive while they may be bound);
+        if issuing them fails there is no record at all."""
+        try:
+            yield
+        except Exception:
+            self._prior_rec = self._prior_new = None
+            raise
+        if self._prior_new is not None:
+            self._prior_rec = dict(self._prior_new, confirmed=False)
+            self._prior_new = None
+
+    def last_launches(self) -> int:
+        """Plan ops that launched in the most recent run of the plan (an op with a split-K reduction is two kernels, one op)."""
+        return int(self.lib.uavsal_plan_last_launches(self.plan))
+
     def launch(self):
         """Launch the recorded plan once on torch's current stream (no staging, no sync)."""
+        self._mark_groups()
         if self.use_graph:
             # the legacy default stream cannot be captured: capture and replay on a private
             # stream, fenced against torch's current stream on both sides
@@ -1231,17 +1337,21 @@ class Engine:
                 stage.data_ptr(), buf.ptr, self.n_seq, 256, self.h * self.w, 256, 1, 0)
             L.check(self.lib.uavsal_layout(C.byref(d), self._stream()), "uavsal_layout(state)")
 
-    def _bind_in_place(self, x, cb0, cb1, state, cstate, lstm):
+    def _bind_in_place(self, x, cb0, cb1, state, cstate, lstm, skip_priors=False):
         """Point the plan at the caller's tensors and at freshly allocated outputs (no staging copies, no
         clones).  Non-contiguous inputs are made contiguous first; everything bound is kept referenced until
-        the next call."""
+        the next call.  `skip_priors`: the prior group is left out of this run, its input slots stay as the run
+        that last executed it left them (the record keeps those tensors alive)."""
         dev = self.device
         x = x.reshape(self.x_in.shape).contiguous()
         hold = [x]
         bound = {"x": x}
         self._patch("features.0", 1 if self.in_dtype == torch.uint8 else 0, x.data_ptr())
+        if skip_priors:
+            hold += self._prior_rec["hold"]
+            bound.update(self._prior_rec["bound"])
         for t, stage, op, on in ((cb0, self.cb0_in, "gauss.in", self.use_priors[0]), (cb1, self.cb1_in, "ob.in", self.use_priors[1])):
-            if not on:                  # a prior this model does not have is never read (reference model.py:347-353)
+            if not on or skip_priors:   # a prior this model does not have is never read (reference model.py:347-353)
                 continue
             if self.static_priors:      # (zero frame stride, checked by the model: frame 0 is every frame)
                 t = t[:1]
@@ -1249,6 +1359,9 @@ class Engine:
             self._patch(op, 0, t.data_ptr())
             hold.append(t)
             bound[op[:-3].replace("gauss", "cb0").replace("ob", "cb1")] = t
+            if self._prior_new is not None:
+                self._prior_new["hold"].append(t)
+                self._prior_new["bound"][op[:-3].replace("gauss", "cb0").replace("ob", "cb1")] = t
         out = torch.empty((self.N, self.h * self.w), dtype=torch.float32, device=dev)
         # (the decoder's last launch: ".dwpl" when its depthwise runs inside the projection)
         self._patch("conv_out_st.pl" if "conv_out_st.pl" in self._op_idx else "conv_out_st.dwpl", 1, out.data_ptr())
@@ -1295,17 +1408,21 @@ class Engine:
         else:
             self.cstate_in.copy_(cstate.reshape(self.cstate_in.shape))
 
-    def run(self, x, cb0, cb1, state=None, taps: Optional[dict] = None, cstate=None):
+    def run(self, x, cb0, cb1, state=None, taps: Optional[dict] = None, cstate=None, prior_src=None):
+        """`prior_src`: the caller's own prior tensor objects when `cb0` / `cb1` are forms the model derived from them (a
+        reshape): the prior cache goes by the caller's objects."""
         if x.dtype != self.in_dtype:
             raise RuntimeError("engine built for %s frames, got %s" % (self.in_dtype, x.dtype))
         lstm = self.lstm
         with torch.cuda.device(self.device):
             self.check(wait=False)               # a previous asynchronous run that is over by now
+            skip = self._prior_gate(prior_src if prior_src is not None else (cb0, cb1))
             if self.inplace:
-                out, st = self._bind_in_place(x, cb0, cb1, state, cstate, lstm)
+                out, st = self._bind_in_place(x, cb0, cb1, state, cstate, lstm, skip)
             else:
                 self.stage_inputs(x, cb0, cb1, state, cstate)
-            self.launch()
+            with self._prior_launches():
+                self.launch()
             if self.sync_errors:
                 self.check(wait=True)
             if not self._first_run_verified and self.split_mode:
@@ -1357,19 +1474,21 @@ class Engine:
         lstm = self.lstm
         with torch.cuda.device(self.device):
             self.check(wait=False)
-            out, _ = self._bind_in_place(x, cb0, cb1, self.h_view, self.c_view, lstm)      # (resident views: nothing is staged)
+            skip = self._prior_gate((cb0, cb1))
+            out, _ = self._bind_in_place(x, cb0, cb1, self.h_view, self.c_view, lstm, skip)      # (resident views: nothing is staged)
             split = self.state_split()
-            L.check(self.lib.uavsal_plan_run(self.plan, 0, split, self._stream()), "plan_run(head)")
-            cur = torch.cuda.current_stream(self.device)
-            if prev_done is not None:
-                cur.wait_event(prev_done)
-            for name in ("h0", "c0") if lstm else ("h0",):
-                mine = self.named[name].t
-                if reset:
-                    mine.zero_()
-                elif prev is not None and prev is not self:
-                    mine.copy_(prev.named[name].t)
-            L.check(self.lib.uavsal_plan_run(self.plan, split, -1, self._stream()), "plan_run(tail)")
+            with self._prior_launches():
+                L.check(self.lib.uavsal_plan_run(self.plan, 0, split, self._stream()), "plan_run(head)")
+                cur = torch.cuda.current_stream(self.device)
+                if prev_done is not None:
+                    cur.wait_event(prev_done)
+                for name in ("h0", "c0") if lstm else ("h0",):
+                    mine = self.named[name].t
+                    if reset:
+                        mine.zero_()
+                    elif prev is not None and prev is not self:
+                        mine.copy_(prev.named[name].t)
+                L.check(self.lib.uavsal_plan_run(self.plan, split, -1, self._stream()), "plan_run(tail)")
         return out
 
     def check(self, wait=True):
@@ -1377,7 +1496,10 @@ class Engine:
         `wait=False` only looks when that run is known to have finished."""
         code = self.lib.uavsal_plan_status(self.plan, 1 if wait else 0)
         if code == 0:
+            if wait and self._prior_rec is not None:
+                self._prior_rec["confirmed"] = True      # the run that executed the prior group is over, without an error
             return
+        self._prior_rec = None       # (the prior nets' GEMMs may be what failed: never reuse their output)
         if code == -5:
             # a piece published after its owner gave up would be consumed by the next launch: start clean
             torch.cuda.synchronize(self.device)

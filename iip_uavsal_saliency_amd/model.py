@@ -194,6 +194,13 @@ class UAVSal(nn.Module):
         # reference's caller repeats one prior file over all frames, utils_data.py:466-467, 601-602): the two prior nets run on
         # one frame instead of on every frame.  Decided from the strides, never from the values; False: always per frame.
         self.dedupe_priors = True
+        # The two prior nets read nothing but the caller's prior tensors and their own weights, and the reference's caller builds
+        # those tensors once per video (Demo_Test.py:14-27, 49, 85).  True: a plan runs them only when a prior tensor is not the
+        # one it last ran them on -- another tensor object, or the same one modified in place since (torch's version counter) --
+        # and otherwise reads what they left in the arena.  Bit-identical maps.  Writes that bypass the version counter (a raw
+        # kernel through `data_ptr()`, `tensor.data`) are NOT seen: call `invalidate_priors()` after those.  False: every call
+        # runs them.
+        self.cache_priors = True
         # Activations of a plan live in ONE arena per plan, placed by liveness (first / last use over the recorded launches; a
         # use on a side lane counts from the lane's fork to its join): memory per call follows the largest set of tensors that
         # is live at once, not the number of layers (720x1280, 4 x 16 frames: 14.7 GB instead of 42.6).  False: one allocation
@@ -276,6 +283,13 @@ class UAVSal(nn.Module):
         self._wversion = None
 
     invalidate_engines = _drop_engines
+
+    def invalidate_priors(self):
+        """The next call of every plan of this model (and of the handles the streaming drivers keep on it) runs the prior nets
+        again, whatever tensors it is given: for prior tensors that were written behind torch's back (see `cache_priors`)."""
+        for m in [self] + list(self.__dict__.get("_stream_replicas") or []):
+            for eng in list(m._engines.values()):
+                eng.drop_prior_record()
 
     def _weights_version(self):
         return sum(t._version for t in self._wtensors)
@@ -407,6 +421,7 @@ class UAVSal(nn.Module):
         static = self.dedupe_priors and self._static(cb0, cb1, 2)
         eng = self._engine(x.device, C, T, H, W, "clip", taps is not None, x.dtype, sync_default=False, static_priors=static)
         h, w = eng.h, eng.w
+        src = (cb0, cb1)                          # (the prior cache goes by the caller's objects, not by the reshaped forms)
         cb0 = None if cb0 is None else cb0.reshape(C * T, *cb0.shape[2:])
         cb1 = None if cb1 is None else cb1.reshape(C * T, *cb1.shape[2:])
         self._check_cb(cb0, cb1, C * T, h, w)
@@ -415,7 +430,7 @@ class UAVSal(nn.Module):
             states, cst = states                 # (h [C,256,h,w], c [C,256,h,w])
         if states is not None and tuple(states.shape) != (C, 256, h, w):
             raise RuntimeError("states must be [C, 256, h, w]")
-        out, state = eng.run(x.reshape(C * T, 3, H, W), cb0, cb1, states, taps, cstate=cst)
+        out, state = eng.run(x.reshape(C * T, 3, H, W), cb0, cb1, states, taps, cstate=cst, prior_src=src)
         if self.rnn_type == "lstm":
             return out.view(C, T, 1, h, w), (state[0].view(C, 256, h, w), state[1].view(C, 256, h, w))
         return out.view(C, T, 1, h, w), state.view(C, 256, h, w)

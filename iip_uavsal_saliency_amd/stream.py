@@ -230,15 +230,18 @@ def predict_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_
                                "batch_size * time_dims frames")
         groups = _Groups(model, frames_u8, group, steps, dev, letterbox=letterbox)
         first = 0
+        # on the device once, not per group: the groups then hand over views of the SAME tensors, which the model's prior
+        # cache recognises (model.cache_priors: the prior nets run once per video and plan)
+        gauss_prior, ob_prior = gauss_prior.to(dev), ob_prior.to(dev)
         if overlap:
-            maps, state = _predict_overlapped(model, groups, gauss_prior.to(dev), ob_prior.to(dev), whole, dev)
+            maps, state = _predict_overlapped(model, groups, gauss_prior, ob_prior, whole, dev)
             first = whole
         for i in range(first, steps):
             x = groups.get(i)
             n = x.shape[0]
             # one map set for every frame, handed over as a zero-stride view: the model runs its prior nets once per call
             # (model.dedupe_priors) instead of once per frame
-            cb = [gauss_prior.to(dev).unsqueeze(0).expand(n, -1, -1, -1), ob_prior.to(dev).unsqueeze(0).expand(n, -1, -1, -1)]
+            cb = [gauss_prior.unsqueeze(0).expand(n, -1, -1, -1), ob_prior.unsqueeze(0).expand(n, -1, -1, -1)]
             out, st = model(x, cb, state)
             # persistent mode: st[0] is a view of the engine's state buffer (valid until the next call, which
             # recognises it by address); a shorter last group runs on another plan, which loads it as a tensor

@@ -646,13 +646,27 @@ int uavsal_plan_size(const uavsal_plan* p);
  * launched flat on `stream`.  A run that reaches the end of the plan -- whole, or the second of two ranges (the streaming driver issues
  * everything in front of the recurrence, waits for the previous group's state, then the rest) -- is the one uavsal_plan_status reports on. */
 int uavsal_plan_run(uavsal_plan* p, int first, int last, uavsal_stream_t stream);
+/* Groups of ops that a run can leave out -- work whose inputs did not change since the run that last did it and whose
+ * outputs are still in place (the engine's prior nets).  group_mark: ops [first, last) belong to `group` (0..31); a group
+ * that runs on a side lane takes its fork and its join with it, and several calls may add ranges to one group (the join
+ * is usually recorded later than the branch).  group_enable(on = 0): runs leave the group out entirely -- its kernels and
+ * its fork / join event operations; nothing of it needs patch_ptr then -- until it is enabled again.  Holds for whole
+ * runs, sub-ranges and the capture; only the per-op timer below ignores the switch.  A captured graph holds the ops it
+ * was captured with: once it is built, marking and CHANGING a switch return UAVSAL_ESTATE.
+ * group_launches: plan ops of the group that launch (everything but its fork / join).  last_launches: plan ops that
+ * launched in the most recent run (a run issued as two ranges: both; a graph launch: what was captured).  Both count
+ * ops, not kernels: an op may issue more than one kernel (a GEMM with a split-K reduction is two). */
+int uavsal_plan_group_mark(uavsal_plan* p, int group, int first, int last);
+int uavsal_plan_group_enable(uavsal_plan* p, int group, int on);
+int uavsal_plan_group_launches(const uavsal_plan* p, int group);
+int uavsal_plan_last_launches(const uavsal_plan* p);
 /* capture the whole plan into a hipGraph once, then replay it */
 int uavsal_plan_graph_build(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
 
 /* ---- device timing on the launch stream (hipEvent) and introspection --------------- */
 /* run ops [first,last) `iters` times on `stream`, return average ms per iteration in *ms
- * (hipEventRecord on `stream` around the loop, hipEventSynchronize on the stop event). */
+ * (hipEventRecord on `stream` around the loop, hipEventSynchronize on the stop event).  Switched-off groups are timed too. */
 int uavsal_plan_time(uavsal_plan* p, int first, int last, int iters, uavsal_stream_t stream, float* ms);
 
 int uavsal_abi_version(void);
