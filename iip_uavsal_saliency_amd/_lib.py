@@ -5,6 +5,7 @@ launch fails, a RuntimeError is raised.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -47,6 +48,26 @@ class ConvDesc(C.Structure):
                 ("out_split", _f), ("ldos", C.c_int32),
                 ("err", _f), ("sk_spin_limit", C.c_int32), ("sk_debug_drop", C.c_int32),
                 ("w_group_stride", C.c_int64), ("n_group", C.c_int32), ("a_group_off", C.c_int32)]
+
+
+ROUTE_PRESPLIT, ROUTE_DWPROJ, ROUTE_STREAMK, ROUTE_K32, ROUTE_F32_DMA, ROUTE_STAGED = 1, 2, 3, 4, 5, 6
+REDUCE_NONE, REDUCE_LAUNCH, REDUCE_IN_LAUNCH = 0, 1, 2
+
+
+class ConvRoute(C.Structure):
+    """uavsal_conv_route: what uavsal_conv_gemm runs for a descriptor (include/uavsal_hip.h)."""
+    _fields_ = [("family", C.c_int32), ("tile", C.c_int32), ("dwproj", C.c_int32), ("streamk", C.c_int32),
+                ("ksplit", C.c_int32), ("reduce", C.c_int32)]
+
+
+Route = collections.namedtuple("Route", [f for f, _ in ConvRoute._fields_])
+
+
+def conv_route(lib, d: ConvDesc) -> Route:
+    """The route of `d`, asked once (no launch; pointers may be dummies with the real alignment)."""
+    r = ConvRoute()
+    check(lib.uavsal_conv_route_of(C.byref(d), C.byref(r)), "uavsal_conv_route_of")
+    return Route(*(int(getattr(r, f)) for f in Route._fields))
 
 
 class DwDesc(C.Structure):
@@ -179,11 +200,12 @@ class LossDesc(C.Structure):
 
 
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
-              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc]
+              FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
 # every symbol include/uavsal_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("uavsal_conv_gemm", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
+    ("uavsal_conv_route_of", C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvRoute)]),
     ("uavsal_conv_tile", C.c_int, [C.POINTER(ConvDesc)]),
     ("uavsal_conv_uses_split", C.c_int, [C.POINTER(ConvDesc)]),
     ("uavsal_conv_dwproj", C.c_int, [C.POINTER(ConvDesc)]),

@@ -34,6 +34,7 @@
 #include "common.h"
 
 #include "conv_gemm_common.h"
+#include "conv_route.h"
 
 namespace {
 
@@ -1051,9 +1052,6 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_gemm_h16_dma_k
     }
 }
 
-// K-split decisions count work units against a FIXED number of workgroup slots (two per CU of a 256-CU part), not against
-// what the occupancy query returns on the device at hand: the number of shares, hence the fp32 summation order, is a
-// function of the shape only (same results on every SKU / partition mode)
 template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN>
 int launch_variant(const ConvK& k0, int taps, hipStream_t stream) {
     constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
@@ -1061,52 +1059,15 @@ int launch_variant(const ConvK& k0, int taps, hipStream_t stream) {
     constexpr int SMEM = 2 * NPAN * (BM + BN) * 64;
     constexpr int NT = WAVES_M * WAVES_N * 64;
     ConvK k = k0;
-    const int tiles_m = (k.M + BM - 1) / BM;
     k.tiles_n = (k.Cout + BN - 1) / BN;
-    k.nblk = tiles_m * k.tiles_n;
-    if (taps == 1 && k.dw_w) {
-        if constexpr (WM * WN <= 4) {      // the fused producer is not built for the 256 x 256 tile
-            const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 1, true>, SMEM, NT));
-            const int grid = k.nblk < cap ? k.nblk : cap;
-            hipLaunchKernelGGL((conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 1, true>), dim3(grid), dim3(NT), SMEM, stream, k);
-        } else {
-            return UAVSAL_ESHAPE;
-        }
-    } else if (taps == 1) {
-        const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 1>, SMEM, NT));
-        // (same K split as the 3x3 tile below: few 64 x 64 tiles, long K -- the 1920 -> 256 ASPP projections at 12x20)
-        if (WM * WN == 1 && k.kpart && k.epi == UAVSAL_EPI_AFFINE && (PREC == UAVSAL_PREC_F16X3 || PREC == UAVSAL_PREC_BF16X3)) {
-            int ksp = UAVSAL_SPLIT_REF_SLOTS_64 / (k.nblk > 0 ? k.nblk : 1);
-            ksp = ksp >= 4 ? 4 : (ksp >= 2 ? 2 : 1);
-            while (ksp > 1 && (k.ktiles % ksp || k.ktiles / ksp < 12)) ksp >>= 1;
-            if (ksp > 1 && (long long)ksp * k.M * k.Npad * 4 <= k.kpart_bytes && !(k.Cout & 3) && !(k.ldc & 3)) {
-                k.ksplit = ksp;
-                k.nblk *= ksp;
-            }
-        }
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        hipLaunchKernelGGL((conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 1>), dim3(grid), dim3(NT), SMEM, stream, k);
-        if (k.ksplit > 1) return launch_splitk_reduce(k, PREC == UAVSAL_PREC_F16X3 ? F16X3_ACC_SCALE : 1.0f, stream);
-    } else {
-        const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 9>, SMEM, NT));
-        // 64 x 64 tile with fewer tiles than CUs-worth of slots and a long K walk (the ConvTWA step: 228 tiles x 72 K
-        // steps): split K over 2 or 4 workgroups per tile; the shares' sums meet in splitk_reduce_kernel
-        if (WM * WN == 1 && k.kpart && (k.epi == UAVSAL_EPI_TWA || k.epi == UAVSAL_EPI_AFFINE) &&
-            (PREC == UAVSAL_PREC_F16X3 || PREC == UAVSAL_PREC_BF16X3)) {
-            int ksp = UAVSAL_SPLIT_REF_SLOTS_64 / (k.nblk > 0 ? k.nblk : 1);
-            ksp = ksp >= 4 ? 4 : (ksp >= 2 ? 2 : 1);
-            while (ksp > 1 && (k.ktiles % (9 * ksp) || k.ktiles / ksp < 18)) ksp >>= 1;
-            if (ksp > 1 && (long long)ksp * k.M * k.Npad * 4 <= k.kpart_bytes && !(k.Cout & 3) && !(k.ldc & 3) &&
-                (k.epi != UAVSAL_EPI_TWA || (!(k.ldx & 3) && !(k.lda & 3) && !(k.ldr & 3)))) {
-                k.ksplit = ksp;
-                k.nblk *= ksp;
-            }
-        }
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        hipLaunchKernelGGL((conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 9>), dim3(grid), dim3(NT), SMEM, stream, k);
-        if (k.ksplit > 1) return launch_splitk_reduce(k, PREC == UAVSAL_PREC_F16X3 ? F16X3_ACC_SCALE : 1.0f, stream);
+    k.nblk = ((k.M + BM - 1) / BM) * k.tiles_n * k.ksplit;
+    if (k.dw_w) {
+        if constexpr (WM * WN <= 4)      // the fused producer is not built for the 256 x 256 tile
+            return launch_resident<conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 1, true>, SMEM, NT>(k, stream);
+        return UAVSAL_ESHAPE;
     }
-    return uavsal_launch_status();
+    return then_reduce(launch_taps<conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 1>, conv_gemm_kernel<PREC, WAVES_M, WAVES_N, WM, WN, 9>,
+                                   SMEM, NT>(k, taps, stream), k, PREC == UAVSAL_PREC_F16X3 ? F16X3_ACC_SCALE : 1.0f, stream);
 }
 
 // stream-K is used when whole-tile scheduling would leave part of the chip idle in the last round;
@@ -1164,19 +1125,10 @@ int launch_f32_dma(const ConvK& k0, int taps, hipStream_t stream) {
     constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32, NT = WAVES_M * WAVES_N * 64;
     constexpr int SMEM = S * NKP * (BM + BN) * 64;
     ConvK k = k0;
-    const int tiles_m = (k.M + BM - 1) / BM;
     k.tiles_n = (k.Cout + BN - 1) / BN;
-    k.nblk = tiles_m * k.tiles_n;
-    if (taps == 1) {
-        const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_f32_dma_kernel<WAVES_M, WAVES_N, WM, WN, 1, S, NKP>, SMEM, NT));
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        hipLaunchKernelGGL((conv_gemm_f32_dma_kernel<WAVES_M, WAVES_N, WM, WN, 1, S, NKP>), dim3(grid), dim3(NT), SMEM, stream, k);
-    } else {
-        const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_f32_dma_kernel<WAVES_M, WAVES_N, WM, WN, 9, S, NKP>, SMEM, NT));
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        hipLaunchKernelGGL((conv_gemm_f32_dma_kernel<WAVES_M, WAVES_N, WM, WN, 9, S, NKP>), dim3(grid), dim3(NT), SMEM, stream, k);
-    }
-    return uavsal_launch_status();
+    k.nblk = ((k.M + BM - 1) / BM) * k.tiles_n;
+    return launch_taps<conv_gemm_f32_dma_kernel<WAVES_M, WAVES_N, WM, WN, 1, S, NKP>,
+                       conv_gemm_f32_dma_kernel<WAVES_M, WAVES_N, WM, WN, 9, S, NKP>, SMEM, NT>(k, taps, stream);
 }
 
 int launch_f32(const ConvK& k, int taps, int tile, hipStream_t stream) {
@@ -1218,17 +1170,8 @@ int launch_h16_dma(const ConvK& k0, int taps, hipStream_t stream) {
     ConvK k = k0;
     k.tiles_n = (k.Cout + BN - 1) / BN;
     k.nblk = ((k.M + BM - 1) / BM) * k.tiles_n;
-
-    if (taps == 1) {
-        const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_h16_dma_kernel<WAVES_M, WAVES_N, WM, WN, 1, S>, SMEM, NT));
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        hipLaunchKernelGGL((conv_gemm_h16_dma_kernel<WAVES_M, WAVES_N, WM, WN, 1, S>), dim3(grid), dim3(NT), SMEM, stream, k);
-    } else {
-        const int cap = UAVSAL_PER_DEVICE(resident_grid(conv_gemm_h16_dma_kernel<WAVES_M, WAVES_N, WM, WN, 9, S>, SMEM, NT));
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        hipLaunchKernelGGL((conv_gemm_h16_dma_kernel<WAVES_M, WAVES_N, WM, WN, 9, S>), dim3(grid), dim3(NT), SMEM, stream, k);
-    }
-    return uavsal_launch_status();
+    return launch_taps<conv_gemm_h16_dma_kernel<WAVES_M, WAVES_N, WM, WN, 1, S>, conv_gemm_h16_dma_kernel<WAVES_M, WAVES_N, WM, WN, 9, S>,
+                       SMEM, NT>(k, taps, stream);
 }
 
 // LDS-halo depthwise -> projection (fp32 / split-fp16): which descriptors take it, and the launch
@@ -1316,59 +1259,59 @@ int pick_tile(long long M, int Cout, int prec) {
 
 }  // namespace
 
-static int effective_tile(const uavsal_conv_desc* d) {
+// The block tile: the descriptor's own or pick_tile's, then a ladder of rules whose ORDER is behaviour.  `*sk1` receives the
+// stream-K grid of tile 1 when a rule had to ask for it (else stays -1), so that conv_route does not ask again.
+static int route_tile(const uavsal_conv_desc* d, int* sk1) {
+    using namespace uavsal_route;
     if (d->w_group_stride) return d->tile == 11 ? 11 : 8;    // per-image weights: the instances with 32-float K stages, 128 x 128 or 64 x 64
     if (d->n_group) return 11;                               // output-channel groups with their own inputs: the 64 x 64 instance
     int tile = (d->tile >= 1 && d->tile <= 11) ? d->tile
-                                             : pick_tile((long long)d->H * d->W * d->n_img, d->Cout, d->prec);
-    if (tile == 11 && !uavsal_f32_k32_eligible(d, tile)) tile = 4;
-    if (tile == 10 && !uavsal_f32_k32_eligible(d, 10)) tile = 8;
-    if ((tile == 8 || tile == 9) && !uavsal_f32_k32_eligible(d, tile)) tile = tile == 9 ? 7 : 1;   // full-line K stages
+                                             : pick_tile(rows(d), d->Cout, d->prec);
+    if (tile == 11 && !k32_eligible(d, tile)) tile = 4;
+    if (tile == 10 && !k32_eligible(d, 10)) tile = 8;
+    if ((tile == 8 || tile == 9) && !k32_eligible(d, tile)) tile = tile == 9 ? 7 : 1;   // full-line K stages
     // automatic choice, fp32: the ConvTWA step (too few tiles for the chip and a long K walk) takes the kernel with 32-float K
-    // stages (conv_gemm_k32.hip) with K split over several workgroups per tile (uavsal_f32_k32_ksplit)
+    // stages (conv_gemm_k32.hip) with K split over several workgroups per tile (k32_share_count)
     if (d->tile == 0 && tile == 4 && d->prec == UAVSAL_PREC_F32 && d->sk_ws && d->sk_ws_bytes > 65536 &&
-        d->epi == UAVSAL_EPI_TWA && uavsal_f32_k32_eligible(d, 8)) {
-        const long long M = (long long)d->H * d->W * d->n_img;
-        const int npad = (d->Cout + 31) / 32 * 32;
-        const int ksp = uavsal_f32_k32_ksplit(((M + 127) / 128) * ((d->Cout + 127) / 128), d->taps * d->Cin / 32);
+        d->epi == UAVSAL_EPI_TWA && k32_eligible(d, 8)) {
+        const int ksp = k32_share_count(tiles(d, 128, 128), d->taps * d->Cin / 32);
         // (tile 10 reduces the shares inside the launch -- the last share to arrive adds them -- and measures 12 us
         // SLOWER per ConvTWA step than shares + reduce launch: one workgroup per tile reads all the shares)
-        if (ksp > 1 && (long long)ksp * M * npad * 4 <= d->sk_ws_bytes - 65536 && !(d->Cout & 3) && !(d->ldc & 3)) tile = 8;
+        // (this rule's own room check -- `ksp` shares, any workspace alignment -- is looser than the launch's, k32_shares:
+        // profiles/conv_route.md lists it)
+        if (ksp > 1 && (long long)ksp * rows(d) * npad(d) * 4 <= d->sk_ws_bytes - 65536 && !(d->Cout & 3) && !(d->ldc & 3)) tile = 8;
     }
     // ... and affine convs on the small backbone maps with a long K (the 12x20 projections: at most 160 tiles of 64 x 64,
     // at least 24 stages) take the 64 x 64 instance with K shares over workgroups reduced inside the launch (tile 11):
     // 17.0 / 23.2 / 26.9 / 18.1 us against 19.5 / 26.6 / 32.7 / 25.2 for the stream-K instance (profiles/r3_gemm_k32.md)
     if (d->tile == 0 && tile == 4 && d->prec == UAVSAL_PREC_F32 && d->epi == UAVSAL_EPI_AFFINE && d->sk_ws && d->sk_ws_bytes > 65536) {
-        const long long M = (long long)d->H * d->W * d->n_img;
-        const long long tiles64 = ((M + 63) / 64) * ((d->Cout + 63) / 64);
+        const long long tiles64 = tiles(d, 64, 64);
         // (round 4: from 12 stages on -- features.14's projection, K = 576: 16.9 -> 13.9 us; the context prior's, K = 384 on one
         // 12x20 map: 12.9 -> 10.0)
-        if (tiles64 <= 160 && d->taps * d->Cin / 32 >= 12 && uavsal_f32_k32_eligible(d, 11) &&
+        if (tiles64 <= 160 && d->taps * d->Cin / 32 >= 12 && k32_eligible(d, 11) &&
             d->act != UAVSAL_ACT_SIGMOID && !(d->Cout & 3) && !(d->ldc & 3))
             tile = 11;
     }
     // ... and the short-K expands of the small backbone maps (64 -> 384, 96 -> 576, 160 -> 960 on 23x40 / 12x20: at most one
     // round of 64 x 64 tiles at three workgroups per CU) take it too: 9.6 / 15.9 / 11.4 us against 11.1 / 18.4 / 13.0
     if (d->tile == 0 && tile != 11 && d->prec == UAVSAL_PREC_F32 && d->epi == UAVSAL_EPI_AFFINE && d->taps == 1) {
-        const long long M = (long long)d->H * d->W * d->n_img;
-        const long long tiles64 = ((M + 63) / 64) * ((d->Cout + 63) / 64);
+        const long long M = rows(d), tiles64 = tiles(d, 64, 64);
         // (round 4: up to Cin = 256 and two rounds of tiles -- the context prior's expand, 256 -> 1536 on ONE 45x80 map: 40.4 -> 34.2 us)
         if (M <= 8192 && tiles64 <= 1536 && d->Cout >= 256 && d->Cin >= 64 && d->Cin <= 256 &&
-            !d->w_group_stride && !d->n_group && uavsal_f32_k32_eligible(d, 11) && d->act != UAVSAL_ACT_SIGMOID && !(d->Cout & 3) && !(d->ldc & 3))
+            !d->w_group_stride && !d->n_group && k32_eligible(d, 11) && d->act != UAVSAL_ACT_SIGMOID && !(d->Cout & 3) && !(d->ldc & 3))
             tile = 11;
     }
     // ... and the 128 x 128 launches that do not take the stream-K path move to the 128 x 128 instance with 32-float K stages
     // (K of at least four 32-float stages: at K = 64 the 16-float instance is 1-2 us faster per launch -- three ring stages
     // against two -- and at K = 32 the launch is store-bound either way)
-    if (d->tile == 0 && tile == 1 && d->prec == UAVSAL_PREC_F32 && uavsal_f32_k32_eligible(d, 8) && d->epi == UAVSAL_EPI_AFFINE &&
-        d->taps * d->Cin >= 128 && streamk_plan(d, 1, (d->taps * d->Cin + 15) / 16) == 0)
+    if (d->tile == 0 && tile == 1 && d->prec == UAVSAL_PREC_F32 && k32_eligible(d, 8) && d->epi == UAVSAL_EPI_AFFINE &&
+        d->taps * d->Cin >= 128 && (*sk1 = streamk_plan(d, 1, (d->taps * d->Cin + 15) / 16)) == 0)
         tile = 8;
     // ... and a 1x1 whose 128 x 128 tiles are more than one per CU but fewer than the 512 resident slots (the STBlock's
     // 256 -> 256 output conv at one clip: 450 tiles, so most CUs run two and the rest one) takes the 64 x 64 instance: 49.6 -> 46.7 us
     if (d->tile == 0 && tile == 8 && d->prec == UAVSAL_PREC_F32 && d->epi == UAVSAL_EPI_AFFINE && d->taps == 1 && !d->w_group_stride) {
-        const long long M = (long long)d->H * d->W * d->n_img;
-        const long long tiles128 = ((M + 127) / 128) * ((d->Cout + 127) / 128);
-        if (tiles128 > 256 && tiles128 < 512 && d->Cin >= 128 && d->Cout <= 256 && uavsal_f32_k32_eligible(d, 11) &&
+        const long long tiles128 = tiles(d, 128, 128);
+        if (tiles128 > 256 && tiles128 < 512 && d->Cin >= 128 && d->Cout <= 256 && k32_eligible(d, 11) &&
             d->act != UAVSAL_ACT_SIGMOID && !(d->Cout & 3) && !(d->ldc & 3))
             tile = 11;
     }
@@ -1383,6 +1326,45 @@ static int effective_tile(const uavsal_conv_desc* d) {
     return tile;
 }
 
+
+// THE route of a descriptor (uavsal_conv_route, uavsal_hip.h): family in the order below, tile, K shares.  Computed once per
+// launch and once per query; nothing else calls the predicates above.  Returns 0, or the status uavsal_conv_gemm gives a
+// descriptor that passed its argument checks and that no kernel takes (the route is filled in either way).
+static int conv_route(const uavsal_conv_desc* d, uavsal_conv_route* r) {
+    using namespace uavsal_route;
+    int sk1 = -1;
+    const int tile = route_tile(d, &sk1);
+    *r = uavsal_conv_route{0, tile, 0, 0, 1, UAVSAL_REDUCE_NONE};
+    int status = 0;
+    if (d->w_group_stride && !((tile == 8 || tile == 11) && k32_eligible(d, tile) && d->epi == UAVSAL_EPI_AFFINE && !d->a_split))
+        status = UAVSAL_ESHAPE;
+    else if (d->n_group < 0 || (d->n_group && !(k32_eligible(d, 11) && !d->a_split && !d->out_split)))
+        status = UAVSAL_ESHAPE;
+    const int ktiles = d->prec == UAVSAL_PREC_F32 ? (d->taps * d->Cin + 15) / 16 : (d->taps * d->Cin + 31) / 32;
+    if (split_eligible(d, tile)) {
+        r->family = UAVSAL_ROUTE_PRESPLIT;
+        return status;
+    }
+    if (dwproj_eligible(d)) {
+        r->family = UAVSAL_ROUTE_DWPROJ;
+        r->dwproj = d->Cout > 128 ? 256 : (d->Cout > 64 ? 128 : (d->Cout > 32 ? 64 : 32));
+        r->ksplit = dwproj_shares(d);
+    } else if ((r->streamk = tile == 1 && sk1 >= 0 ? sk1 : streamk_plan(d, tile, ktiles)) > 0) {
+        r->family = UAVSAL_ROUTE_STREAMK;
+    } else if (tile >= 8 && tile <= 11) {
+        r->family = UAVSAL_ROUTE_K32;
+        r->ksplit = tile == 11 ? k32s_shares(d) : k32_shares(d, tile);
+    } else if (d->prec == UAVSAL_PREC_F32 && !d->dw_w9c) {
+        r->family = UAVSAL_ROUTE_F32_DMA;
+    } else {      // (fp32 with the fused producer needs register staging too)
+        r->family = UAVSAL_ROUTE_STAGED;
+        r->ksplit = staged_shares(d, tile, ktiles);
+    }
+    if (r->ksplit > 1) r->reduce = r->family == UAVSAL_ROUTE_K32 && tile >= 10 ? UAVSAL_REDUCE_IN_LAUNCH : UAVSAL_REDUCE_LAUNCH;
+    if (!status && r->family != UAVSAL_ROUTE_DWPROJ && !d->a) status = UAVSAL_EINVAL;     // pre-split operands given but the shape is not eligible
+    return status;
+}
+
 extern "C" long long uavsal_streamk_workspace_bytes(void) {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -1391,27 +1373,22 @@ extern "C" long long uavsal_streamk_workspace_bytes(void) {
     return 65536 + G * 128 * 128 * 4;
 }
 
-extern "C" int uavsal_conv_streamk_grid(const uavsal_conv_desc* d) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return 0;
-    const int tile = uavsal_conv_tile(d);
-    const int KT = d->prec == UAVSAL_PREC_F32 ? 16 : 32;
-    return tile > 0 ? streamk_plan(d, tile, (d->taps * d->Cin + KT - 1) / KT) : 0;
+extern "C" int uavsal_conv_route_of(const uavsal_conv_desc* d, uavsal_conv_route* r) {
+    if (!d || !r || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0) return UAVSAL_EINVAL;
+    (void)conv_route(d, r);
+    return 0;
 }
 
-extern "C" int uavsal_conv_tile(const uavsal_conv_desc* d) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0) return UAVSAL_EINVAL;
-    return effective_tile(d);
+// single fields of the route (the last three are 0 without a positive Cin, as they always were)
+static uavsal_conv_route route_or_none(const uavsal_conv_desc* d, bool need_cin) {
+    uavsal_conv_route r = {};
+    if (d && (!need_cin || d->Cin > 0)) (void)uavsal_conv_route_of(d, &r);
+    return r;
 }
-
-extern "C" int uavsal_conv_uses_split(const uavsal_conv_desc* d) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return 0;
-    return split_eligible(d, effective_tile(d)) ? 1 : 0;
-}
-
-extern "C" int uavsal_conv_dwproj(const uavsal_conv_desc* d) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || !dwproj_eligible(d)) return 0;
-    return d->Cout > 128 ? 256 : (d->Cout > 64 ? 128 : (d->Cout > 32 ? 64 : 32));
-}
+extern "C" int uavsal_conv_tile(const uavsal_conv_desc* d) { const int t = route_or_none(d, false).tile; return t ? t : UAVSAL_EINVAL; }
+extern "C" int uavsal_conv_uses_split(const uavsal_conv_desc* d) { return route_or_none(d, true).family == UAVSAL_ROUTE_PRESPLIT; }
+extern "C" int uavsal_conv_dwproj(const uavsal_conv_desc* d) { return route_or_none(d, true).dwproj; }
+extern "C" int uavsal_conv_streamk_grid(const uavsal_conv_desc* d) { return route_or_none(d, true).streamk; }
 
 extern "C" int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t stream) {
     if (!d || !d->w || !d->out) return UAVSAL_EINVAL;
@@ -1426,8 +1403,10 @@ extern "C" int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t strea
     if (d->out_split && ((d->ldos & 63) || d->ldos < 2 * d->Cout || ((uintptr_t)d->out_split & 127)))
         return UAVSAL_EALIGN;
     if (d->out_split && d->prec != UAVSAL_PREC_F16X3) return UAVSAL_ESHAPE;   // only those kernels carry the store
+    uavsal_conv_route r;
+    const int route_status = conv_route(d, &r);
     if (d->out_split) {  // the shadow is written by the vector epilogue only
-        const int t = effective_tile(d);
+        const int t = r.tile;
         const bool twa_vec = d->epi == UAVSAL_EPI_TWA && (t == 3 || t == 4) && !(d->ldx & 3) && !(d->lda & 3) &&
                              uavsal_aligned16(d->aux);
         const bool vec = (d->epi == UAVSAL_EPI_AFFINE || twa_vec) && d->act != UAVSAL_ACT_SIGMOID && !(d->ldc & 3) &&
@@ -1478,49 +1457,41 @@ extern "C" int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t strea
     k.act = d->act; k.epi = d->epi;
     k.contig = ((k.a_is == HW || k.dw_w) && k.o_is == HW && k.r_is == HW && k.x_is == HW) ? 1 : 0;
     k.tiles_n = 0; k.nblk = 0;
-    k.sk_part = nullptr; k.sk_flag = nullptr; k.err = nullptr; k.ksplit = 1; k.kpart = nullptr; k.kpart_bytes = 0;
+    k.sk_part = nullptr; k.sk_flag = nullptr; k.err = nullptr; k.ksplit = r.ksplit; k.kpart = nullptr; k.kpart_bytes = 0;
     k.sk_spin = d->sk_spin_limit > 0 ? d->sk_spin_limit : (1 << 22);
     k.sk_drop = d->sk_debug_drop;
-    const int tile = effective_tile(d);
-    hipStream_t s = (hipStream_t)stream;
     k.w_gs = d->w_group_stride;
-    if (k.w_gs && !((tile == 8 || tile == 11) && uavsal_f32_k32_eligible(d, tile) && d->epi == UAVSAL_EPI_AFFINE && !d->a_split))
-        return UAVSAL_ESHAPE;
     k.ngrp = d->n_group; k.a_goff = d->a_group_off;
-    if (d->n_group < 0 || (k.ngrp && !(uavsal_f32_k32_eligible(d, 11) && !d->a_split && !d->out_split))) return UAVSAL_ESHAPE;
     k.a_sp = (const _Float16*)d->a_split; k.ldas = d->ldas;
     k.out_sp = (_Float16*)d->out_split; k.ldos = d->ldos;
-    if (split_eligible(d, tile)) return launch_h16(k, d->taps, tile, s);
-    // K-split workspace: the partial-tile area of the caller's stream-K workspace (launches on one lane are ordered)
-    if (d->sk_ws && uavsal_aligned16(d->sk_ws) && d->sk_ws_bytes > 65536) {
+    if (route_status) return route_status;
+    hipStream_t s = (hipStream_t)stream;
+    const bool t1 = d->taps == 1;
+    if (r.family != UAVSAL_ROUTE_PRESPLIT && uavsal_route::kpart_room(d)) {      // the K shares' partial sums
         k.kpart = (float*)((char*)d->sk_ws + 65536);
         k.kpart_bytes = d->sk_ws_bytes - 65536;
     }
-    if (dwproj_eligible(d))
-        return uavsal_launch_dwproj(k, d->prec, s);
-    if (!d->a) return UAVSAL_EINVAL;             // pre-split operands given but the shape is not eligible
-    {
-        const int G = streamk_plan(d, tile, k.ktiles);
-        if (G > 0) {
+    switch (r.family) {
+        case UAVSAL_ROUTE_PRESPLIT: return launch_h16(k, d->taps, r.tile, s);
+        case UAVSAL_ROUTE_DWPROJ: return uavsal_launch_dwproj(k, d->prec, r.dwproj, s);
+        case UAVSAL_ROUTE_STREAMK:
             // workspace: 64 KB of flags (one per workgroup + a "wait gave up" word), then the partial tiles
             k.sk_flag = (int*)d->sk_ws;
             k.sk_part = (float*)((char*)d->sk_ws + 65536);
             k.err = d->err ? d->err : (int*)d->sk_ws + UAVSAL_SK_ERR_WORD;
-            const bool t1 = d->taps == 1;
-            if (tile == 1) return t1 ? SkBig::launch<1>(k, G, s) : SkBig::launch<9>(k, G, s);
-            if (tile == 3) return t1 ? SkThin::launch<1>(k, G, s) : SkThin::launch<9>(k, G, s);
-            return t1 ? SkSmall::launch<1>(k, G, s) : SkSmall::launch<9>(k, G, s);
-        }
-    }
-    if (tile >= 8 && tile <= 11) {
-        if (k.kpart) k.sk_flag = (int*)d->sk_ws + UAVSAL_SK_TICKET_BASE;       // per-tile ticket counters of the K-split launch: their own region
-        return uavsal_launch_f32_k32(k, d->taps, tile, s);
+            if (r.tile == 1) return t1 ? SkBig::launch<1>(k, r.streamk, s) : SkBig::launch<9>(k, r.streamk, s);
+            if (r.tile == 3) return t1 ? SkThin::launch<1>(k, r.streamk, s) : SkThin::launch<9>(k, r.streamk, s);
+            return t1 ? SkSmall::launch<1>(k, r.streamk, s) : SkSmall::launch<9>(k, r.streamk, s);
+        case UAVSAL_ROUTE_K32:
+            if (k.kpart) k.sk_flag = (int*)d->sk_ws + UAVSAL_SK_TICKET_BASE;       // per-tile ticket counters of the K-split launch: their own region
+            return uavsal_launch_f32_k32(k, d->taps, r.tile, s);
+        case UAVSAL_ROUTE_F32_DMA: return launch_f32(k, d->taps, r.tile, s);
+        default: break;
     }
     switch (d->prec) {
-        case UAVSAL_PREC_F32:    // the fused producer needs register staging: use the generic kernel
-            return k.dw_w ? launch_prec<UAVSAL_PREC_F32>(k, d->taps, tile, s) : launch_f32(k, d->taps, tile, s);
-        case UAVSAL_PREC_BF16X3: return launch_prec<UAVSAL_PREC_BF16X3>(k, d->taps, tile, s);
-        case UAVSAL_PREC_F16X3: return launch_prec<UAVSAL_PREC_F16X3>(k, d->taps, tile, s);
-        default: return launch_prec<UAVSAL_PREC_BF16>(k, d->taps, tile, s);
+        case UAVSAL_PREC_F32: return launch_prec<UAVSAL_PREC_F32>(k, d->taps, r.tile, s);
+        case UAVSAL_PREC_BF16X3: return launch_prec<UAVSAL_PREC_BF16X3>(k, d->taps, r.tile, s);
+        case UAVSAL_PREC_F16X3: return launch_prec<UAVSAL_PREC_F16X3>(k, d->taps, r.tile, s);
+        default: return launch_prec<UAVSAL_PREC_BF16>(k, d->taps, r.tile, s);
     }
 }

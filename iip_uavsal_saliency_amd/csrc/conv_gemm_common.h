@@ -39,12 +39,13 @@ struct ConvK {
 
 }  // namespace uavsal_gemm
 
-// conv_gemm_k32.hip: fp32 LDS-DMA GEMM with 128-byte (32-float) K stages; tile = 8 (128 x 128) or 9 (256 x 128)
+// The launchers of the other translation units.  Which of them runs, with which tile and how many K shares per tile
+// (k.ksplit), is decided before they are called (conv_route.h): a launcher derives nothing from the shape.
+// conv_gemm_k32.hip: fp32 LDS-DMA GEMM with 128-byte (32-float) K stages; tile = 8 .. 11
 int uavsal_launch_f32_k32(const uavsal_gemm::ConvK& k, int taps, int tile, hipStream_t stream);
-bool uavsal_f32_k32_eligible(const uavsal_conv_desc* d, int tile);
-int uavsal_f32_k32_ksplit(long long tiles, int stages);
-// dwproj.hip: depthwise 3x3 + BN + ReLU6 -> 1x1 projection in one launch (LDS halo tile), fp32 / split-fp16
-int uavsal_launch_dwproj(const uavsal_gemm::ConvK& k, int prec, hipStream_t stream);
+// dwproj.hip: depthwise 3x3 + BN + ReLU6 -> 1x1 projection in one launch (LDS halo tile), fp32 / split-fp16;
+// `bn` = its output-channel tile (uavsal_conv_route.dwproj)
+int uavsal_launch_dwproj(const uavsal_gemm::ConvK& k, int prec, int bn, hipStream_t stream);
 
 namespace {
 using uavsal_gemm::ConvK;
@@ -313,8 +314,6 @@ int launch_splitk_reduce(const ConvK& k, float acc_scale, hipStream_t stream) {
 #define UAVSAL_SK_STREAMK_MAX UAVSAL_SK_TICKET_BASE
 #define UAVSAL_SK_TICKET_MAX (UAVSAL_SK_ERR_WORD - UAVSAL_SK_TICKET_BASE)
 static_assert(UAVSAL_SK_TICKET_BASE + UAVSAL_SK_TICKET_MAX <= UAVSAL_SK_ERR_WORD, "ticket indices stay below the fallback error word");
-#define UAVSAL_SPLIT_REF_SLOTS 512          /* dwproj_kernel's narrow instance: two workgroups per CU */
-#define UAVSAL_SPLIT_REF_SLOTS_64 1024      /* the register-staged 64 x 64 tiles (32 KB of LDS): four per CU */
 
 // resident workgroups per CU for one kernel instantiation (cached; queried once, outside any capture)
 template <typename K>
@@ -324,6 +323,27 @@ int resident_grid(K kernel, int smem, int threads = 256) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, smem) != hipSuccess || per_cu <= 0) per_cu = 1;
     return per_cu * cus;
+}
+
+// One launch of a persistent-tile kernel over k.nblk work units: grid = min(k.nblk, what is resident of THIS instance on
+// this device).  Templated on the kernel itself, not on its type: every GEMM kernel has the same function-pointer type,
+// and the per-device memos of UAVSAL_PER_DEVICE / UAVSAL_LDS_OPTIN are statics of the instantiation.  OPTIN: the instance
+// needs more than 64 KB of dynamic LDS (asked for before the occupancy query, which depends on it).
+template <auto Kernel, int SMEM, int NT, bool OPTIN = false>
+int launch_resident(const ConvK& k, hipStream_t stream) {
+    if constexpr (OPTIN) UAVSAL_LDS_OPTIN(Kernel, SMEM);
+    const int cap = UAVSAL_PER_DEVICE(resident_grid(Kernel, SMEM, NT));
+    hipLaunchKernelGGL(Kernel, dim3(k.nblk < cap ? k.nblk : cap), dim3(NT), SMEM, stream, k);
+    return uavsal_launch_status();
+}
+// ... of the 1x1 or the 3x3 instance of a kernel
+template <auto Kernel1, auto Kernel9, int SMEM, int NT, bool OPTIN = false>
+int launch_taps(const ConvK& k, int taps, hipStream_t stream) {
+    return taps == 1 ? launch_resident<Kernel1, SMEM, NT, OPTIN>(k, stream) : launch_resident<Kernel9, SMEM, NT, OPTIN>(k, stream);
+}
+// ... followed, when K was split into shares that meet in a launch of their own, by that launch
+inline int then_reduce(int launched, const ConvK& k, float acc_scale, hipStream_t stream) {
+    return launched || k.ksplit <= 1 ? launched : launch_splitk_reduce(k, acc_scale, stream);
 }
 
 }  // namespace

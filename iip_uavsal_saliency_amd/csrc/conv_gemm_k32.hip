@@ -17,7 +17,7 @@
 //     `s_waitcnt vmcnt(0)` drain on gfx950 (no back-off barrier), which is what kept the older kernel's three-stage
 //     ring from ever being more than one stage ahead.
 //   * fragments of K sub-step u + 1 are read while sub-step u multiplies.
-// Eligible: fp32, Cin % 32 == 0, Cin <= 4096, no fused depthwise producer (host: uavsal_f32_k32_eligible).
+// Eligible: fp32, Cin % 32 == 0, Cin <= 4096, no fused depthwise producer (host: k32_eligible, conv_route.h).
 #define UAVSAL_EPI_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #include "conv_gemm_common.h"
 
@@ -900,169 +900,35 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_f32_k32s_kernel(const ConvK 
     }
 }
 
-// may this launch split K?  (a) the gates every in-launch reduction needs: ticket region and partial area there, an epilogue
-// the reducing share carries, vector alignment, tile count inside the ticket region; (b) partial area large enough for 8 shares
-// of the unpadded output (the 128 x 128 kernels; the 64 x 64 kernel sizes its own <= 4 whole-tile shares).
-// The number of shares itself is uavsal_f32_k32_ksplit(tiles, stages).
-bool uavsal_f32_k32_split_gates(const ConvK& k) {
-    if (!k.kpart || !k.sk_flag || (k.epi != UAVSAL_EPI_AFFINE && k.epi != UAVSAL_EPI_TWA) || k.act == UAVSAL_ACT_SIGMOID) return false;
-    if (k.nblk <= 0 || k.nblk >= UAVSAL_SK_TICKET_MAX) return false;
-    if ((k.Cout & 3) || (k.ldc & 3) || ((size_t)k.out & 15)) return false;
-    if (k.res && ((k.ldr & 3) || ((size_t)k.res & 15))) return false;
-    if (k.epi == UAVSAL_EPI_TWA && ((k.ldx & 3) || (k.lda & 3) || !k.res || !k.aux || ((size_t)k.aux & 15))) return false;
-    return true;
-}
-bool uavsal_f32_k32_split_ok(const ConvK& k) {
-    return uavsal_f32_k32_split_gates(k) && 8LL * k.M * k.Npad * 4 <= k.kpart_bytes;
-}
-
+// k.ksplit (conv_route.h: k32_shares / k32s_shares) workgroups share the K loop of a tile.  FLAT (tile 10): the last share to
+// arrive adds them inside the launch; else (tiles 8 / 9) they meet in splitk_reduce_kernel.
 template <int WAVES_M, int WAVES_N, int MINW, bool FLAT = false>
 int launch_k32(const ConvK& k0, int taps, hipStream_t stream) {
     constexpr int BM = WAVES_M * 64, BN = WAVES_N * 64, NT = WAVES_M * WAVES_N * 64;
     constexpr int SMEM = 2 * (BM + BN) * 128 + (FLAT ? 32 * BN * 4 : 0);
     ConvK k = k0;
     k.tiles_n = (k.Cout + BN - 1) / BN;
-    k.nblk = ((k.M + BM - 1) / BM) * k.tiles_n;
-    k.ksplit = 1;
-    auto cap_of = [](auto kernel) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        int per_cu = 0, cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, NT, SMEM) != hipSuccess || per_cu <= 0) per_cu = 1;
-        return per_cu * cus;
-    };
+    k.nblk = ((k.M + BM - 1) / BM) * k.tiles_n * k.ksplit;
     if constexpr (FLAT) {
-        k.ksplit = uavsal_f32_k32_split_ok(k) ? uavsal_f32_k32_ksplit(k.nblk, k.Kpad / 32) : 1;
-        if (k.ksplit > 1) {          // (tile, K share) work units, reduced in the launch by the last share to arrive
-            k.nblk *= k.ksplit;
-            const int cap1 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW, true>));
-            const int cap9 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW, true>));
-            const int cap = taps == 1 ? cap1 : cap9;
-            const int grid = k.nblk < cap ? k.nblk : cap;
-            if (taps == 1) {
-                UAVSAL_LDS_OPTIN((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW, true>), SMEM);
-                hipLaunchKernelGGL((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW, true>), dim3(grid), dim3(NT), SMEM, stream, k);
-            } else {
-                UAVSAL_LDS_OPTIN((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW, true>), SMEM);
-                hipLaunchKernelGGL((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW, true>), dim3(grid), dim3(NT), SMEM, stream, k);
-            }
-        } else if (taps == 1) {
-            const int cap = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW>));
-            const int grid = k.nblk < cap ? k.nblk : cap;
-            UAVSAL_LDS_OPTIN((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW>), SMEM);
-            hipLaunchKernelGGL((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW>), dim3(grid), dim3(NT), SMEM, stream, k);
-        } else {
-            const int cap = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW>));
-            const int grid = k.nblk < cap ? k.nblk : cap;
-            UAVSAL_LDS_OPTIN((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW>), SMEM);
-            hipLaunchKernelGGL((conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW>), dim3(grid), dim3(NT), SMEM, stream, k);
-        }
+        if (k.ksplit > 1)          // (tile, K share) work units
+            return launch_taps<conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW, true>,
+                               conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW, true>, SMEM, NT, true>(k, taps, stream);
+        return launch_taps<conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW>, conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 9, MINW>,
+                           SMEM, NT, true>(k, taps, stream);
     } else {
-        const int cap1 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 1, MINW>));
-        const int cap9 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 9, MINW>));
-        const int cap = taps == 1 ? cap1 : cap9;
-        // Too few tiles for the chip and a long K walk (the ConvTWA step: 58 tiles x 72 stages; the 12x20 / 23x40 maps of
-        // the backbone tail): K is split over up to 8 workgroups per tile, the shares meet in splitk_reduce_kernel
-        // (fixed order, no atomics).  The split is a function of the shape and of fixed constants only (512 workgroup
-        // slots = two per CU of a 256-CU part), not of the device the launch happens to run on.
-        k.ksplit = uavsal_f32_k32_split_ok(k) ? uavsal_f32_k32_ksplit(k.nblk, k.Kpad / 32) : 1;
-        k.nblk *= k.ksplit;
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        if (taps == 1) {
-            UAVSAL_LDS_OPTIN((conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 1, MINW>), SMEM);
-            hipLaunchKernelGGL((conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 1, MINW>), dim3(grid), dim3(NT), SMEM, stream, k);
-        } else {
-            UAVSAL_LDS_OPTIN((conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 9, MINW>), SMEM);
-            hipLaunchKernelGGL((conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 9, MINW>), dim3(grid), dim3(NT), SMEM, stream, k);
-        }
-        if (k.ksplit > 1) return launch_splitk_reduce(k, 1.0f, stream);
+        return then_reduce(launch_taps<conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 1, MINW>, conv_gemm_f32_k32_kernel<WAVES_M, WAVES_N, 9, MINW>,
+                                       SMEM, NT, true>(k, taps, stream), k, 1.0f, stream);
     }
-    return uavsal_launch_status();
 }
 
-}  // namespace
-
-// K shares per tile for `tiles` 128 x 128 tiles with `stages` 32-float K stages each (1: no split)
-__attribute__((visibility("hidden"))) int uavsal_f32_k32_ksplit(long long tiles, int stages) {
-    if (tiles <= 0 || tiles * 2 > 512) return 1;
-    // measured on the ConvTWA step (58 tiles x 72 stages, one clip): 2 / 3 / 4 / 6 / 8 shares = 90 / 68 / 57 / 72 / 62 us
-    // (kernel + reduce launch), the 64 x 64 stream-K instance it replaces 65 -- profiles/r3_gemm_k32.md
-    int ksp = (int)(512 / tiles);
-    if (ksp > 4) ksp = 4;
-    while (ksp > 1 && stages / ksp < 6) --ksp;
-    return ksp;
-}
-
-__attribute__((visibility("hidden"))) bool uavsal_f32_k32_eligible(const uavsal_conv_desc* d, int tile) {
-    if (tile < 8 || tile > 11) return false;
-    if (d->w_group_stride && ((tile != 8 && tile != 11) || d->taps != 1 || (((long long)d->H * d->W) & 127))) return false;
-    if (d->n_group && (tile != 11 || d->taps != 1 || d->w_group_stride || d->epi != UAVSAL_EPI_AFFINE || (d->n_group & 63) ||
-                       d->Cout % d->n_group || d->a_group_off < d->Cin || (d->a_group_off & 3) ||
-                       (long long)d->lda < (long long)(d->Cout / d->n_group - 1) * d->a_group_off + d->Cin)) return false;
-    if (d->prec != UAVSAL_PREC_F32 || d->dw_w9c || d->epi == UAVSAL_EPI_LSTM) return false;
-    if (tile == 11 && d->epi == UAVSAL_EPI_TWA && ((d->ldx & 3) || (d->lda & 3) || (d->ldc & 3) || (d->Cout & 3))) return false;
-    if ((d->Cin % 32) || d->Cin > UAVSAL_DWPROJ_MAX_C) return false;
-    if (tile == 10) {      // the flat-pipeline kernel carries the vector affine epilogue; with K split (few tiles, long K,
-                           // workspace given) the reducing share also does the ConvTWA update
-        const bool al = d->act != UAVSAL_ACT_SIGMOID && !(d->ldc & 3) && !(d->Cout & 3) && uavsal_aligned16(d->out) &&
-                        (!d->res || (!(d->ldr & 3) && uavsal_aligned16(d->res)));
-        const long long M = (long long)d->H * d->W * d->n_img;
-        const int npad = (d->Cout + 31) / 32 * 32;
-        const bool split = d->sk_ws && uavsal_aligned16(d->sk_ws) && d->sk_ws_bytes - 65536 >= 8LL * M * npad * 4 &&
-                           uavsal_f32_k32_ksplit(((M + 127) / 128) * ((d->Cout + 127) / 128), d->taps * d->Cin / 32) > 1;
-        if (split) {
-            if (!al || (d->epi != UAVSAL_EPI_AFFINE && d->epi != UAVSAL_EPI_TWA)) return false;
-            if (d->epi == UAVSAL_EPI_TWA && ((d->ldx & 3) || (d->lda & 3) || !d->res || !d->aux || !uavsal_aligned16(d->aux))) return false;
-        } else if (!(al && d->epi == UAVSAL_EPI_AFFINE && d->scale && d->bias)) {
-            return false;
-        }
-    }
-    return d->taps == 1 || d->taps == 9;
-}
-
-namespace {
-// 64 x 64 tiles; K shares per tile (<= 4) when the workspace is there and the tiles alone leave most of the chip idle:
-// shares = the count that brings the work units to about two per CU of a 256-CU part (a function of the shape only)
+// 64 x 64 tiles (tile 11, 32 KB of LDS: no opt-in); K shares are reduced in the launch
 int launch_k32s(const ConvK& k0, int taps, hipStream_t stream) {
     constexpr int SMEM = 2 * (64 + 64) * 128;
     ConvK k = k0;
     k.tiles_n = (k.Cout + 63) / 64;
-    k.nblk = ((k.M + 63) / 64) * k.tiles_n;
-    const int stages = k.Kpad / 32;
-    int ksp = 1;
-    if (uavsal_f32_k32_split_gates(k)) {
-        ksp = (int)(1024 / (k.nblk > 0 ? k.nblk : 1));
-        if (ksp > 4) ksp = 4;
-        while (ksp > 1 && stages / ksp < 4) --ksp;
-        if (ksp < 1) ksp = 1;
-        if ((long long)k.nblk * ksp * 64 * 64 * 4 > k.kpart_bytes) ksp = 1;
-    }
-    k.ksplit = ksp;
-    auto cap_of = [](auto kernel) {
-        int per_cu = 0, cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, SMEM) != hipSuccess || per_cu <= 0) per_cu = 1;
-        return per_cu * cus;
-    };
-    if (ksp > 1) {
-        k.nblk *= ksp;
-        const int cap1 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32s_kernel<1, true>));
-        const int cap9 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32s_kernel<9, true>));
-        const int cap = taps == 1 ? cap1 : cap9;
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        if (taps == 1) hipLaunchKernelGGL((conv_gemm_f32_k32s_kernel<1, true>), dim3(grid), dim3(256), SMEM, stream, k);
-        else hipLaunchKernelGGL((conv_gemm_f32_k32s_kernel<9, true>), dim3(grid), dim3(256), SMEM, stream, k);
-    } else {
-        const int cap1 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32s_kernel<1, false>));
-        const int cap9 = UAVSAL_PER_DEVICE(cap_of(conv_gemm_f32_k32s_kernel<9, false>));
-        const int cap = taps == 1 ? cap1 : cap9;
-        const int grid = k.nblk < cap ? k.nblk : cap;
-        if (taps == 1) hipLaunchKernelGGL((conv_gemm_f32_k32s_kernel<1, false>), dim3(grid), dim3(256), SMEM, stream, k);
-        else hipLaunchKernelGGL((conv_gemm_f32_k32s_kernel<9, false>), dim3(grid), dim3(256), SMEM, stream, k);
-    }
-    return uavsal_launch_status();
+    k.nblk = ((k.M + 63) / 64) * k.tiles_n * k.ksplit;
+    if (k.ksplit > 1) return launch_taps<conv_gemm_f32_k32s_kernel<1, true>, conv_gemm_f32_k32s_kernel<9, true>, SMEM, 256>(k, taps, stream);
+    return launch_taps<conv_gemm_f32_k32s_kernel<1, false>, conv_gemm_f32_k32s_kernel<9, false>, SMEM, 256>(k, taps, stream);
 }
 }  // namespace
 

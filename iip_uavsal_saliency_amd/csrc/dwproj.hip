@@ -478,39 +478,22 @@ int launch_dwproj_variant(const ConvK& k0, hipStream_t stream) {
     ConvK k = k0;
     k.tiles_n = (k.Cout + BN - 1) / BN;
     k.nblk = (k.M / k.HW) * ((k.H + 7) / 8) * ((k.W + 15) / 16) * k.tiles_n;
-    UAVSAL_LDS_OPTIN((dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>), SMEM);
-    const int cap = UAVSAL_PER_DEVICE(resident_grid(dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>, SMEM, NT));
-    // The narrowest outputs (Cout <= 32: the 1536 -> 1 decoder projection) are bound by the serial depthwise /
-    // request segments of a K step, not by the matrix pipe, and their 74 KB ring leaves room for two workgroups per
-    // CU: when the tiles alone would leave resident slots empty, K is split over 2-4 workgroups per tile (raw partial
-    // sums into the caller's workspace, summed in a fixed order by dwproj_reduce_kernel): 96 -> 72 us fp32, 88 -> 64
-    // f16x3 for 8 x 45 x 80 x 1536 -> 1.  The 64-wide instance gains nothing (81 vs 77 us: one workgroup per CU by
-    // registers in fp32, and 7 MB of partial sums to re-read), so it is not split.
-    k.ksplit = 1;
-    if (BN <= 32 && k.kpart) {
-        int ksp = UAVSAL_SPLIT_REF_SLOTS / (k.nblk > 0 ? k.nblk : 1);
-        if (ksp > 4) ksp = 4;
-        while (ksp > 1 && (k.Cin / 16) / ksp < 12) --ksp;
-        if (ksp > 1 && (long long)ksp * k.M * k.Npad * 4 <= k.kpart_bytes) k.ksplit = ksp;
-    }
-    k.nblk *= k.ksplit;
-    const int grid = k.nblk < cap ? k.nblk : cap;
-    hipLaunchKernelGGL((dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>), dim3(grid), dim3(NT), SMEM, stream, k);
-    if (k.ksplit > 1) return launch_splitk_reduce(k, PREC == UAVSAL_PREC_F16X3 ? F16X3_ACC_SCALE : 1.0f, stream);
-    return uavsal_launch_status();
+    k.nblk *= k.ksplit;      // (conv_route.h: dwproj_shares; the narrowest instance only)
+    return then_reduce(launch_resident<dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>, SMEM, NT, true>(k, stream), k,
+                       PREC == UAVSAL_PREC_F16X3 ? F16X3_ACC_SCALE : 1.0f, stream);
 }
 
 template <int PREC>
-int launch_dwproj(const ConvK& k, hipStream_t stream) {
-    if (k.Cout > 128) return launch_dwproj_variant<PREC, 2, 4, 2, 2>(k, stream);   // 128 x 256, 8 waves
-    if (k.Cout > 64) return launch_dwproj_variant<PREC, 2, 4, 2, 1>(k, stream);    // 128 x 128, 8 waves
-    if (k.Cout > 32) return launch_dwproj_variant<PREC, 4, 2, 1, 1>(k, stream);    // 128 x 64,  8 waves
-    return launch_dwproj_variant<PREC, 4, 1, 1, 1>(k, stream);                     // 128 x 32,  4 waves
+int launch_dwproj(const ConvK& k, int bn, hipStream_t stream) {
+    if (bn == 256) return launch_dwproj_variant<PREC, 2, 4, 2, 2>(k, stream);   // 128 x 256, 8 waves
+    if (bn == 128) return launch_dwproj_variant<PREC, 2, 4, 2, 1>(k, stream);   // 128 x 128, 8 waves
+    if (bn == 64) return launch_dwproj_variant<PREC, 4, 2, 1, 1>(k, stream);    // 128 x 64,  8 waves
+    return launch_dwproj_variant<PREC, 4, 1, 1, 1>(k, stream);                  // 128 x 32,  4 waves
 }
 
 
 }  // namespace
 
-int uavsal_launch_dwproj(const uavsal_gemm::ConvK& k, int prec, hipStream_t stream) {
-    return prec == UAVSAL_PREC_F32 ? launch_dwproj<UAVSAL_PREC_F32>(k, stream) : launch_dwproj<UAVSAL_PREC_F16X3>(k, stream);
+int uavsal_launch_dwproj(const uavsal_gemm::ConvK& k, int prec, int bn, hipStream_t stream) {
+    return prec == UAVSAL_PREC_F32 ? launch_dwproj<UAVSAL_PREC_F32>(k, bn, stream) : launch_dwproj<UAVSAL_PREC_F16X3>(k, bn, stream);
 }

@@ -381,6 +381,7 @@ extern "C" int uavsal_sizeof_desc(int which) {
         case 16: return (int)sizeof(uavsal_overlay_desc);
         case 17: return (int)sizeof(uavsal_gaze_desc);
         case 18: return (int)sizeof(uavsal_loss_desc);
+        case 19: return (int)sizeof(uavsal_conv_route);
     }
     return UAVSAL_EINVAL;
 }

@@ -394,7 +394,7 @@ class Engine:
             d.res, d.ldr, d.r_img_stride = P_, (cout if ldr is None else ldr), h * w
         d.n_img, d.H, d.W, d.Cin, d.Cout, d.taps = n_img, h, w, cin, cout, taps
         d.prec, d.act, d.epi, d.tile = self.prec, act, L.EPI_AFFINE, 0
-        return int(self.lib.uavsal_conv_uses_split(C.byref(d))) == 1
+        return L.conv_route(self.lib, d).family == L.ROUTE_PRESPLIT
 
     def _scr(self, kind, n, h, w, c) -> V:
         """Scratch for the expanded tensors of an inverted-residual block and the Winograd planes.  With the arena: an
@@ -446,7 +446,7 @@ class Engine:
         d = L.ConvDesc()
         d.n_img, d.H, d.W, d.Cout, d.prec, d.epi, d.tile = n_img, h, w, cout, self.prec, epi, 0
         d.out = 1 << 20
-        return int(self.lib.uavsal_conv_tile(C.byref(d)))
+        return L.conv_route(self.lib, d).tile
 
     # ------------------------------------------------------------------ op recorders
     def _meta(self, **kw):
@@ -566,17 +566,16 @@ class Engine:
         d.sk_spin_limit, d.sk_debug_drop = self._sk_debug      # test hooks (model._sk_debug), normally (0, 0)
         # weights last: their 16-bit packing depends on which kernel the descriptor selects
         d.w = 1 << 20
-        split = int(self.lib.uavsal_conv_uses_split(C.byref(d))) == 1
+        route = L.conv_route(self.lib, d)
+        split, dwproj, tile = route.family == L.ROUTE_PRESPLIT, route.dwproj, route.tile
         if a.t is None and not split:
             raise RuntimeError("%s: its input only exists as a split shadow but the GEMM is not eligible" % name)
-        dwproj = int(self.lib.uavsal_conv_dwproj(C.byref(d)))
-        tile = int(self.lib.uavsal_conv_tile(C.byref(d)))
         ksize = (conv[0] if isinstance(conv, (list, tuple)) else conv).weight.shape[-1]
         d.w = self.weights.conv(conv, wslice, gate_interleave, conv_weight_layout(pn, split, dwproj != 0, tile, ksize)).data_ptr()
         self.ops_meta[-1]["prec"] = pn
         self.ops_meta[-1]["split"] = split
         self.ops_meta[-1]["tile"] = tile
-        self.ops_meta[-1]["streamk"] = int(self.lib.uavsal_conv_streamk_grid(C.byref(d)))
+        self.ops_meta[-1]["streamk"] = route.streamk
         self.ops_meta[-1]["dwproj"] = dwproj
         groups = cout // n_group if n_group else 1
         ad = self._ov(V(a_in.t, n_img, hin, win, cin + (groups - 1) * cin, a_in.ld, a_in.coff, a_in.sp, a_in.key),
@@ -628,7 +627,7 @@ class Engine:
             d.prec, d.act, d.epi, d.tile = L.PREC["f32"], L.ACT_NONE, L.EPI_AFFINE, gemm_tile      # Winograd plans are exact fp32
             d.err = self._err
             m_ = self.ops_meta[-1]
-            m_["split"], m_["tile"], m_["streamk"], m_["dwproj"] = False, int(self.lib.uavsal_conv_tile(C.byref(d))), 0, 0
+            m_["split"], m_["tile"], m_["streamk"], m_["dwproj"] = False, L.conv_route(self.lib, d).tile, 0, 0
             m_["prec"] = "f32"
             self._add(self.lib.uavsal_plan_add_conv, d, "plan_add_conv(%s)" % name)
         self._meta(kind="wino_out", name=name + ".xout", flops=0.0, bytes=4.0 * (float(pp) * tiles * cout + n * hw * cout))

@@ -69,12 +69,14 @@ def _empty_shadow(n, h, w, c, device):
 
 
 def conv_gemm(x, weight, scale=None, bias=None, act=L.ACT_NONE, res=None, out=None, prec="f32", tile=0, dw=None,
-              stream_k=False, sk_spin_limit=0, sk_debug_drop=0, split_in=False, split_out=False, n_group=0, _stale_streamk_flags=False):
+              stream_k=False, sk_spin_limit=0, sk_debug_drop=0, split_in=False, split_out=False, n_group=0, _stale_streamk_flags=False,
+              route=None):
     """Dense 1x1 / 3x3 conv (+ folded BN, activation, residual).  `weight` [Cout,Cin,k,k] (cpu or cuda).
     `n_group`: several 1x1 convs of different inputs as one launch -- `x` holds the inputs side by side ([.., groups * Cin]),
     `weight` [groups * n_group, Cin, 1, 1] the stacked weights (uavsal_conv_desc.n_group / a_group_off).
     `dw=(w[C,1,3,3], scale[C], bias[C], stride)`: x is the expanded tensor and the depthwise 3x3 + BN + ReLU6
-    in front of this 1x1 conv is computed inside the GEMM's loader (fused inverted-residual tail)."""
+    in front of this 1x1 conv is computed inside the GEMM's loader (fused inverted-residual tail).
+    `route`: a dict that receives the fields of the launch's route (uavsal_conv_route: family, tile, ksplit, ...)."""
     lib = L.load()
     ap, lda, n, hin, win, cin = _nhwc_view(x)
     stride = dw[3] if dw is not None else 1
@@ -125,12 +127,13 @@ def conv_gemm(x, weight, scale=None, bias=None, act=L.ACT_NONE, res=None, out=No
         if _stale_streamk_flags:        # test hook: what a stream-K wait that gave up earlier on this lane leaves behind
             ws[:4 * L.SK_TICKET_BASE].view(torch.int32).fill_(1)
     d.w = 1 << 20
-    uses_split = int(lib.uavsal_conv_uses_split(C.byref(d))) == 1
+    rt = L.conv_route(lib, d)
+    if route is not None:
+        route.update(rt._asdict())
+    uses_split = rt.family == L.ROUTE_PRESPLIT
     if split_in and not uses_split:
         raise RuntimeError("this shape / tile does not take the pre-split path")
-    dwproj = int(lib.uavsal_conv_dwproj(C.byref(d))) != 0
-    wp = P.pack_conv_weight(weight, P.conv_weight_layout(prec, uses_split, dwproj, int(lib.uavsal_conv_tile(C.byref(d))),
-                                                         weight.shape[-1])).to(x.device)
+    wp = P.pack_conv_weight(weight, P.conv_weight_layout(prec, uses_split, rt.dwproj != 0, rt.tile, weight.shape[-1])).to(x.device)
     keep.append(wp)
     d.w = wp.data_ptr()
     L.check(lib.uavsal_conv_gemm(C.byref(d), _stream(x)), "uavsal_conv_gemm")
@@ -204,8 +207,8 @@ def conv3x3_winograd(x, weight, scale=None, bias=None, act=L.ACT_NONE, res=None,
     return out
 
 
-def twa_step(x_t, h_prev, pre_t, w_h, prec="f32", tile=0, stream_k=False):
-    """One ConvTWA step given pre_t = conv3x3(W[:, :C], x_t): returns h_t (NHWC)."""
+def twa_step(x_t, h_prev, pre_t, w_h, prec="f32", tile=0, stream_k=False, route=None):
+    """One ConvTWA step given pre_t = conv3x3(W[:, :C], x_t): returns h_t (NHWC).  `route`: as in conv_gemm."""
     lib = L.load()
     ap, lda, n, h, w, c = _nhwc_view(h_prev)
     xp, ldr, *_ = _nhwc_view(x_t)
@@ -223,8 +226,10 @@ def twa_step(x_t, h_prev, pre_t, w_h, prec="f32", tile=0, stream_k=False):
         ws = torch.zeros(int(lib.uavsal_streamk_workspace_bytes()), dtype=torch.uint8, device=x_t.device)
         d.sk_ws, d.sk_ws_bytes = ws.data_ptr(), ws.numel()
     # weights last: the fp32 kernels with 32-float K stages (tiles 8-10) take the 3x3 K order in 32-channel blocks
-    wp = P.pack_conv_weight(w_h, P.conv_weight_layout(prec, False, False, int(lib.uavsal_conv_tile(C.byref(d))),
-                                                      w_h.shape[-1])).to(x_t.device)
+    rt = L.conv_route(lib, d)
+    if route is not None:
+        route.update(rt._asdict())
+    wp = P.pack_conv_weight(w_h, P.conv_weight_layout(prec, False, False, rt.tile, w_h.shape[-1])).to(x_t.device)
     d.w = wp.data_ptr()
     L.check(lib.uavsal_conv_gemm(C.byref(d), _stream(x_t)), "uavsal_conv_gemm(TWA)")
     torch.cuda.current_stream(x_t.device).synchronize()

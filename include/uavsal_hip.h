@@ -121,10 +121,9 @@ typedef struct uavsal_conv_desc {
                                   * F32 with Cin % 32 == 0, K stages of 32 floats = one cache line per tile row
                                   * (conv_gemm_k32.hip; 3x3 weights then in the 'f32k32' K order, see `w`): 8: 128x128,
                                   * 9: 256x128 on 8 waves, 10: 128x128 as one continuous stage stream (vector affine
-                                  * epilogue only), 11: 64x64.  With `sk_ws`, 8 / 10 / 11 split K over workgroups when
-                                  * the tiles alone would leave most of the chip idle (8: shares + reduce launch;
-                                  * 10, 11: the last share to arrive adds them in share order inside the launch).
-                                  * Shapes an instance cannot take fall back: 10 -> 8 -> 1, 9 -> 7, 11 -> 4. */
+                                  * epilogue only), 11: 64x64.  Shapes an instance cannot take fall back: 10 -> 8 -> 1,
+                                  * 9 -> 7, 11 -> 4.  What a descriptor actually runs -- kernel family, tile, K shares per
+                                  * tile -- is decided in one place and uavsal_conv_route_of tells it (uavsal_conv_route). */
     float*       out2;   int32_t ld2;                 /* EPI_LSTM only: c_t (image stride = o_img_stride) */
     /* Fused depthwise producer (taps == 1, EPI_AFFINE): when dw_w9c != NULL, `a` is the EXPANDED tensor E
      * [n_img, dw_Hin, dw_Win, Cin] of an inverted-residual block and the GEMM's A operand is computed on the
@@ -185,19 +184,40 @@ typedef struct uavsal_conv_desc {
 } uavsal_conv_desc;
 
 int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t stream);
-/* block tile `uavsal_conv_gemm` will use for this descriptor (1..11, see `tile`); no launch.  Callers pack fp32
- * 3x3 weights by it: tiles 8-11 take the K order with 32-channel blocks (k = ((ci / 32) * 9 + tap) * 32 + ci % 32,
- * packing.py 'f32k32'), the others 16-channel blocks ('f32'); 1x1 weights are the same either way. */
-int uavsal_conv_tile(const uavsal_conv_desc* d);
-/* 1 when `uavsal_conv_gemm` will take the pre-split LDS-DMA path for this descriptor (a_split set, shape
- * eligible) and therefore expects `w` in the 'f16x3i' packing, else 0; no launch */
-int uavsal_conv_uses_split(const uavsal_conv_desc* d);
-/* 0, or the LDS-halo depthwise -> projection instance this descriptor launches (no launch): its output-channel
- * tile 256 / 128 / 64 / 32 = dwproj_kernel<PREC,2,4,2,2> / <PREC,2,4,2,1> / <PREC,4,2,1,1> / <PREC,4,1,1,1> */
-int uavsal_conv_dwproj(const uavsal_conv_desc* d);
 /* size of the optional stream-K workspace (see uavsal_conv_desc.sk_ws) */
 long long uavsal_streamk_workspace_bytes(void);
-/* workgroups of the stream-K launch `uavsal_conv_gemm` will use for this descriptor, 0 = whole tiles; no launch */
+
+/* What `uavsal_conv_gemm` runs for a descriptor: everything that is decided from the descriptor before a kernel starts.
+ * It is decided once per launch, by one function (conv_route in csrc/conv_gemm.hip; the K-split rules and the fp32
+ * 32-float-K eligibility it uses are in csrc/conv_route.h), in this order of families:
+ *   PRESPLIT   both operands by LDS-DMA from split shadows (a_split set, shape eligible): `w` packed 'f16x3i'
+ *   DWPROJ     LDS-halo depthwise -> projection, output-channel tile `dwproj` = dwproj_kernel<PREC,2,4,2,2> (256) /
+ *              <PREC,2,4,2,1> (128) / <PREC,4,2,1,1> (64) / <PREC,4,1,1,1> (32); F16X3 weights packed 'f16x3j'
+ *   STREAMK    fp32 LDS-DMA kernel, tiles 1 / 3 / 4, `streamk` workgroups share the K loops of some tiles
+ *   K32        fp32 kernels with 32-float K stages, tiles 8 .. 11: 3x3 weights in the K order with 32-channel blocks
+ *              (k = ((ci / 32) * 9 + tap) * 32 + ci % 32, packing.py 'f32k32'; every other family 16-channel blocks)
+ *   F32_DMA    fp32 LDS-DMA kernel, whole tiles
+ *   STAGED     register-staged kernel of the descriptor's precision (and fp32 with the fused depthwise producer)
+ * `ksplit` > 1: that many workgroups share the K loop of every tile (needs `sk_ws`; the count is a function of the shape and
+ * of fixed constants only), and `reduce` says where their sums meet: in splitk_reduce_kernel, a second launch that adds
+ * them in share order, or inside the launch, where the last share to arrive adds them in share order. */
+enum { UAVSAL_ROUTE_PRESPLIT = 1, UAVSAL_ROUTE_DWPROJ, UAVSAL_ROUTE_STREAMK, UAVSAL_ROUTE_K32, UAVSAL_ROUTE_F32_DMA,
+       UAVSAL_ROUTE_STAGED };
+enum { UAVSAL_REDUCE_NONE = 0, UAVSAL_REDUCE_LAUNCH, UAVSAL_REDUCE_IN_LAUNCH };
+typedef struct uavsal_conv_route {
+    int32_t family;   /* UAVSAL_ROUTE_* */
+    int32_t tile;     /* 1 .. 11, see uavsal_conv_desc.tile */
+    int32_t dwproj;   /* 0, or the output-channel tile of the DWPROJ instance: 32 / 64 / 128 / 256 */
+    int32_t streamk;  /* workgroups of the stream-K launch, 0 = whole tiles */
+    int32_t ksplit;   /* K shares per tile, 1 = none */
+    int32_t reduce;   /* UAVSAL_REDUCE_* */
+} uavsal_conv_route;
+/* fills `*r` for `d`; no launch and no pointer of `d` is read (their alignment is).  0, or UAVSAL_EINVAL (null / non-positive size) */
+int uavsal_conv_route_of(const uavsal_conv_desc* d, uavsal_conv_route* r);
+/* single fields of the route, 0 where the descriptor has none: tile; family == PRESPLIT; dwproj; streamk */
+int uavsal_conv_tile(const uavsal_conv_desc* d);
+int uavsal_conv_uses_split(const uavsal_conv_desc* d);
+int uavsal_conv_dwproj(const uavsal_conv_desc* d);
 int uavsal_conv_streamk_grid(const uavsal_conv_desc* d);
 
 /*
@@ -670,7 +690,7 @@ int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_time(uavsal_plan* p, int first, int last, int iters, uavsal_stream_t stream, float* ms);
 
 int uavsal_abi_version(void);
-int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score,15 letterbox,16 overlay,17 gaze,18 loss */
+int uavsal_sizeof_desc(int which); /* 0 conv,1 dw,2 stem,3 bilinear,4 tdiff,5 tsum,6 layout,7 post,8 guard,9 copy,10 fused_ir,11 wino,12 dw_dot,13 fill,14 score,15 letterbox,16 overlay,17 gaze,18 loss,19 conv_route */
 const char* uavsal_build_info(void);
 
 #ifdef __cplusplus

@@ -1,7 +1,7 @@
 """Census of dispatch signatures: which kernel instance and which edge path every launch of a plan takes, per model size.
 
-Which code a launch runs is decided from its shape: `effective_tile` / `pick_tile` / `streamk_plan` / `split_eligible` /
-`dwproj_eligible` (csrc/conv_gemm.hip), `dw_variant` / `map_lds_slab` / `rowclass_fits` (csrc/dw_conv.hip), the patch shape of the
+Which code a launch runs is decided from its shape: `conv_route` (`route_tile` / `pick_tile` / `streamk_plan` / `split_eligible` /
+`dwproj_eligible`, csrc/conv_gemm.hip; csrc/conv_route.h), `dw_variant` / `map_lds_slab` / `rowclass_fits` (csrc/dw_conv.hip), the patch shape of the
 fused blocks (csrc/fused_ir.hip), and in engine.py the Winograd `r`, the step tile and the fused-block choices.  A *dispatch
 signature* (`signature`) is the tuple of everything that selects code or an edge path in one recorded op: the instance, and how
 ragged the work lies against that instance's tile (`M % BM`, `Cout % BN`, odd maps under stride 2, maps smaller than a patch).

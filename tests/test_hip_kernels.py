@@ -311,9 +311,10 @@ def test_twa_step_stream_k(ops):
 
 @pytest.mark.parametrize("shape", [(1, 45, 80), (2, 12, 20), (1, 23, 40), (3, 9, 13)])
 def test_twa_step_f32_full_line_split_k(ops, shape):
-    """fp32 ConvTWA step on the kernel with 32-float K stages (tile 8) with K split over up to 8 workgroups per
-    128 x 128 tile (one clip at 45 x 80: 58 tiles x 72 stages -> 464 shares); the shares meet in the reduce launch, which
-    applies the ConvTWA update.  Against F.conv2d on the CPU, the whole-tile launch (tile 4) and its own second run."""
+    """fp32 ConvTWA step on the kernels with 32-float K stages with K split over up to 4 workgroups per tile (one clip at
+    45 x 80: 58 tiles of 128 x 128 x 72 stages -> 232 shares); on tile 8 the shares meet in the reduce launch, which applies
+    the ConvTWA update.  Against F.conv2d on the CPU, the whole-tile launch (tile 4) and its own second run."""
+    from iip_uavsal_saliency_amd import _lib as L
     n, h, w = shape
     c = 256
     x = rnd((n, c, h, w), 50, 2.0)
@@ -325,7 +326,10 @@ def test_twa_step_f32_full_line_split_k(ops, shape):
     whole = ops.twa_step(nhwc(x), nhwc(hp), pre, wt[:, c:].contiguous(), prec="f32", tile=4)
     for tile in (8, 10, 11, 0):     # 8: shares + reduce launch; 10: flat pipeline, the last share to arrive reduces;
                                     # 11: 64 x 64 tiles, shares over workgroups, reduced in the launch; 0: the default
-        split = ops.twa_step(nhwc(x), nhwc(hp), pre, wt[:, c:].contiguous(), prec="f32", tile=tile, stream_k=True)
+        rt = {}
+        split = ops.twa_step(nhwc(x), nhwc(hp), pre, wt[:, c:].contiguous(), prec="f32", tile=tile, stream_k=True, route=rt)
+        assert rt["family"] == L.ROUTE_K32 and rt["tile"] == (tile or 8) and rt["ksplit"] > 1, (tile, rt)
+        assert rt["reduce"] == (L.REDUCE_LAUNCH if rt["tile"] == 8 else L.REDUCE_IN_LAUNCH), (tile, rt)
         again = ops.twa_step(nhwc(x), nhwc(hp), pre, wt[:, c:].contiguous(), prec="f32", tile=tile, stream_k=True)
         assert torch.equal(split, again), tile                       # fixed summation order, whoever reduces
         assert (split - whole).abs().max().item() <= TOL["f32"] * 4.0, tile
@@ -335,7 +339,9 @@ def test_twa_step_f32_full_line_split_k(ops, shape):
 @pytest.mark.parametrize("case", [(2, 12, 20, 1920, 256, 1, 1, True), (1, 23, 40, 960, 160, 1, 0, False),
                                   (8, 12, 20, 1024, 256, 1, 1, False), (2, 12, 20, 256, 256, 9, 1, True)])
 def test_conv_f32_full_line_split_k(ops, case):
-    """Affine convs with few 128 x 128 tiles and a long K on tile 8 with the workspace: K split + reduce launch."""
+    """Affine convs with few tiles and a long K on tiles 8 / 10 / 11 with the workspace: K split + reduce launch (8), or the
+    shares reduced inside the launch (10, 11)."""
+    from iip_uavsal_saliency_amd import _lib as L
     n, h, w, cin, cout, taps, act, use_res = case
     kk = 3 if taps == 9 else 1
     x = rnd((n, cin, h, w), 53, 2.0)
@@ -347,8 +353,11 @@ def test_conv_f32_full_line_split_k(ops, case):
     if use_res:
         ref = ref + res
     for tile in (8, 10, 11):
+        rt = {}
         got = ops.conv_gemm(nhwc(x), wt, scale, bias, act=act, res=nhwc(res) if use_res else None, prec="f32", tile=tile,
-                            stream_k=True)
+                            stream_k=True, route=rt)
+        assert rt["family"] == L.ROUTE_K32 and rt["tile"] == tile and rt["ksplit"] > 1, (tile, case, rt)
+        assert rt["reduce"] == (L.REDUCE_LAUNCH if tile == 8 else L.REDUCE_IN_LAUNCH), (tile, case, rt)
         assert (nchw(got) - ref).abs().max().item() <= TOL["f32"] * 4.0, (tile, case)
 
 
@@ -405,7 +414,10 @@ def test_twa_step_split_k(ops, prec, shape):
     ref = gate * x + (1 - gate) * hp
     pre = ops.conv_gemm(nhwc(x), wt[:, :c].contiguous(), None, None, prec=prec)
     whole = ops.twa_step(nhwc(x), nhwc(hp), pre, wt[:, c:].contiguous(), prec=prec)
-    split = ops.twa_step(nhwc(x), nhwc(hp), pre, wt[:, c:].contiguous(), prec=prec, stream_k=True)
+    rt = {}
+    split = ops.twa_step(nhwc(x), nhwc(hp), pre, wt[:, c:].contiguous(), prec=prec, stream_k=True, route=rt)
+    from iip_uavsal_saliency_amd import _lib as L
+    assert rt["family"] == L.ROUTE_STAGED and rt["tile"] == 4 and rt["ksplit"] > 1 and rt["reduce"] == L.REDUCE_LAUNCH, rt
     assert (split - whole).abs().max().item() <= TOL[prec] * 4.0
     assert (nchw(split) - ref).abs().max().item() <= TOL[prec] * 4.0
 
@@ -418,7 +430,10 @@ def test_conv1x1_small_map_split_k(ops, prec):
     sc, bi = rnd((256,), 58) * 0.5 + 1.0, rnd((256,), 59)
     res = rnd((2, 256, 12, 20), 60)
     ref = F.conv2d(x, wt) * sc.view(1, -1, 1, 1) + bi.view(1, -1, 1, 1) + res
-    got = ops.conv_gemm(nhwc(x), wt, sc, bi, res=nhwc(res), prec=prec, tile=4, stream_k=True)
+    rt = {}
+    got = ops.conv_gemm(nhwc(x), wt, sc, bi, res=nhwc(res), prec=prec, tile=4, stream_k=True, route=rt)
+    from iip_uavsal_saliency_amd import _lib as L
+    assert rt["family"] == L.ROUTE_STAGED and rt["ksplit"] > 1 and rt["reduce"] == L.REDUCE_LAUNCH, rt
     whole = ops.conv_gemm(nhwc(x), wt, sc, bi, res=nhwc(res), prec=prec, tile=4)
     assert (got - whole).abs().max().item() <= TOL[prec] * 4.0
     assert (nchw(got) - ref).abs().max().item() <= TOL[prec] * 4.0
@@ -433,19 +448,26 @@ def test_conv1x1_split_k_ragged(ops, case):
     sc, bi = rnd((cout,), 63) * 0.5 + 1.0, rnd((cout,), 64)
     ref = torch.clamp(F.conv2d(x, wt) * sc.view(1, -1, 1, 1) + bi.view(1, -1, 1, 1), 0, 6)
     from iip_uavsal_saliency_amd import _lib as L
-    got = ops.conv_gemm(nhwc(x), wt, sc, bi, act=L.ACT_RELU6, prec="f16x3", tile=4, stream_k=True)
+    rt = {}
+    got = ops.conv_gemm(nhwc(x), wt, sc, bi, act=L.ACT_RELU6, prec="f16x3", tile=4, stream_k=True, route=rt)
+    assert rt["family"] == L.ROUTE_STAGED and rt["ksplit"] > 1 and rt["reduce"] == L.REDUCE_LAUNCH, (case, rt)
     assert (nchw(got) - ref).abs().max().item() <= TOL["f16x3"] * 4.0
 
 
 def test_conv3x3_small_map_split_k(ops):
-    """A plain 3x3 conv (BN + ReLU6 + residual) on a small map in f16x3 with the workspace: same split path, affine epilogue."""
+    """A plain 3x3 conv (BN + ReLU6 + residual) on a small map in f16x3 with the workspace: the register-staged 64 x 64 tile
+    the split-K launches use, affine epilogue.  K is NOT split at this shape, and never was: of its 18 K steps a share of whole
+    taps would get 9, fewer than the 18 the rule asks for (staged_shares, csrc/conv_route.h); test_twa_step_split_k covers the
+    3x3 split."""
     x = rnd((2, 64, 23, 40), 51, 2.0)
     wt = rnd((64, 64, 3, 3), 52, 1.0 / np.sqrt(9 * 64))
     sc, bi = rnd((64,), 53) * 0.5 + 1.0, rnd((64,), 54)
     res = rnd((2, 64, 23, 40), 55)
     ref = torch.clamp(F.conv2d(x, wt, padding=1) * sc.view(1, -1, 1, 1) + bi.view(1, -1, 1, 1), 0, 6) + res
     from iip_uavsal_saliency_amd import _lib as L
-    got = ops.conv_gemm(nhwc(x), wt, sc, bi, act=L.ACT_RELU6, res=nhwc(res), prec="f16x3", tile=4, stream_k=True)
+    rt = {}
+    got = ops.conv_gemm(nhwc(x), wt, sc, bi, act=L.ACT_RELU6, res=nhwc(res), prec="f16x3", tile=4, stream_k=True, route=rt)
+    assert rt["family"] == L.ROUTE_STAGED and rt["tile"] == 4 and rt["ksplit"] == 1, rt
     assert (nchw(got) - ref).abs().max().item() <= TOL["f16x3"] * 4.0
 
 
@@ -508,10 +530,12 @@ DWPROJ_CASES = [
     (2, 9, 17, 48, 128, 0, True, True), (1, 8, 16, 64, 64, 0, False, False), (2, 1, 37, 32, 40, 1, False, True),
     (1, 23, 1, 16, 24, 0, False, False), (17, 7, 5, 80, 32, 2, False, False), (1, 90, 160, 64, 256, 0, False, False),
     (40, 17, 33, 16, 300, 0, True, False),
-    # narrow outputs with few tiles and a long K walk: K is split over 2-4 workgroups per tile + the reduce launch
+    # few tiles and a long K walk.  The first (Cout <= 32: the narrowest instance) splits K over 4 workgroups per tile + the
+    # reduce launch; the other three take the 64-wide instance, which is never split (dwproj_shares, csrc/conv_route.h)
     (1, 16, 32, 768, 1, 2, False, False), (2, 9, 20, 384, 40, 1, True, True), (1, 8, 16, 1024, 64, 0, True, False),
     (3, 20, 20, 400, 33, 0, False, False),
 ]
+DWPROJ_SPLIT_K = DWPROJ_CASES[10:11]
 
 
 @pytest.mark.parametrize("prec", ["f32", "f16x3"])
@@ -545,8 +569,12 @@ def test_depthwise_projection_lds_halo(ops, case, prec):
     if use_res:
         rbuf = torch.zeros((n, h, w, cout + 2 * pad), device=dev)
         rbuf[..., pad:pad + cout] = nhwc(res)
+    rt = {}
     got = ops.conv_gemm(nhwc(e), wp, sp, bp, act=act, res=rbuf[..., pad:pad + cout] if use_res else None, out=out,
-                        prec=prec, dw=(wd, sd, bd, 1))
+                        prec=prec, dw=(wd, sd, bd, 1), route=rt)
+    assert rt["family"] == L.ROUTE_DWPROJ and rt["dwproj"] == inst, rt
+    if case in DWPROJ_SPLIT_K:
+        assert rt["ksplit"] > 1 and rt["reduce"] == L.REDUCE_LAUNCH, rt
     err = (nchw(got.contiguous()) - ref).abs().max().item()
     assert err <= (2e-5 if prec == "f32" else TOL[prec]) * max(1.0, ref.abs().max().item()), (case, prec, err)
     if sliced:                          # nothing outside the slice was written

@@ -43,7 +43,8 @@ def test_descriptor_sizes():
     assert _lib.DESC_TYPES[17] is _lib.GazeDesc and _lib.DESC_TYPES[18] is _lib.LossDesc
     assert lib.uavsal_sizeof_desc(17) == C.sizeof(_lib.GazeDesc)
     assert lib.uavsal_sizeof_desc(18) == C.sizeof(_lib.LossDesc)
-    assert lib.uavsal_sizeof_desc(19) < 0
+    assert _lib.DESC_TYPES[19] is _lib.ConvRoute and lib.uavsal_sizeof_desc(19) == C.sizeof(_lib.ConvRoute)
+    assert len(_lib.DESC_TYPES) == 20 and lib.uavsal_sizeof_desc(20) < 0
 
 
 def test_arguments_are_checked_before_any_launch():
