@@ -199,6 +199,24 @@ class LossDesc(C.Structure):
                 ("w_kl", C.c_double), ("w_cc", C.c_double), ("w_nss", C.c_double)]
 
 
+PRIOR_MIN_SLAB = 32           # UAVSAL_PRIOR_MIN_SLAB: no slab of uavsal_prior_accumulate is shorter (csrc/prior.hip)
+PRIOR_MAX_FRAMES = (2 ** 31 - 1) // 255
+
+
+class PriorAccDesc(C.Structure):
+    _fields_ = [("frames", _f), ("row_pitch", C.c_int64), ("col_pitch", C.c_int64), ("img_pitch", C.c_int64),
+                ("acc", _f), ("acc_row_pitch", C.c_int64), ("acc_col_pitch", C.c_int64),
+                ("n_img", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32)]
+
+
+class PriorFinishDesc(C.Structure):
+    _fields_ = [("acc", _f), ("acc_row_pitch", C.c_int64), ("acc_col_pitch", C.c_int64),
+                ("ws", _f), ("out", _f), ("image", _f),
+                ("n_frames", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+PRIOR_DESC_TYPES = [PriorAccDesc, PriorFinishDesc]        # sized by uavsal_prior_sizeof_desc
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -226,6 +244,10 @@ SYMBOLS = [
     ("uavsal_gaze_prepare", C.c_int, [C.POINTER(GazeDesc), C.c_void_p]),
     ("uavsal_loss_fu", C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
     ("uavsal_loss_fu_grad", C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
+    ("uavsal_prior_accumulate", C.c_int, [C.POINTER(PriorAccDesc), C.c_void_p]),
+    ("uavsal_prior_finish", C.c_int, [C.POINTER(PriorFinishDesc), C.c_void_p]),
+    ("uavsal_prior_slab_frames", C.c_int, [C.c_int64, C.c_int32]),
+    ("uavsal_prior_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -296,6 +318,10 @@ def load():
         if lib.uavsal_sizeof_desc(i) != C.sizeof(t):
             raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (
                 t.__name__, C.sizeof(t), lib.uavsal_sizeof_desc(i)))
+    for i, t in enumerate(PRIOR_DESC_TYPES):
+        if lib.uavsal_prior_sizeof_desc(i) != C.sizeof(t):
+            raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (
+                t.__name__, C.sizeof(t), lib.uavsal_prior_sizeof_desc(i)))
     _lib = lib
     return lib
 

@@ -531,6 +531,77 @@ def prepare_gaze(fix_map_u8, fix_loc_u8, h, w, layout=None):
     return y, flags.view(torch.bool)
 
 
+def prior_slab_frames(plane_pixels: int, n_frames: int) -> int:
+    """Frames per slab of `fixmap_accumulate` for a plane of `plane_pixels` and a chunk of `n_frames` (csrc/prior.hip; never
+    below `_lib.PRIOR_MIN_SLAB`): a chunk longer than this is summed by several workgroups per pixel."""
+    return int(L.load().uavsal_prior_slab_frames(int(plane_pixels), int(n_frames)))
+
+
+def fixmap_accumulate(fix_map_u8, acc=None, layout=None):
+    """`acc[r, c] += sum over the frames of fix_map[f, r, c]`: the streaming part of the reference's `get_meanmaps`
+    (utils_data.py:514-517) for one chunk of a video's uint8 `fixMap`, read in place in the layouts of `prepare_gaze`
+    (`[F,H0,W0]`, `[H0,W0,1,F]`, `[H0,W0,F]` with `layout="HWF"`, any strides).  `acc` is an int32 `[H0,W0]` tensor of exact
+    sums: none given, one is allocated and zeroed in the pixel order of the frames (a MATLAB-order `fixMap` gets a
+    transposed one, so that both stream); one given is added to and returned, after its size and device were checked.  It
+    carries the number of frames summed so far as `acc.n_frames`; 255 * that must stay below 2^31.  One launch on the current
+    stream, no synchronisation; integer atomics only, so two runs give the same bytes."""
+    lib = L.load()
+    m = _gaze_view(fix_map_u8, "fix_map", layout)
+    F, h0, w0 = m.shape
+    if h0 <= 0 or w0 <= 0:
+        raise RuntimeError("fixmap_accumulate: empty frames %r" % (tuple(m.shape),))
+    st = m.stride()
+    if acc is None:
+        matlab_order = (st[1] == 1 or h0 == 1) and (st[2] == h0 or w0 == 1) and not (st[2] == 1 and st[1] == w0)
+        acc = (torch.zeros((w0, h0), dtype=torch.int32, device=m.device).t() if matlab_order
+               else torch.zeros((h0, w0), dtype=torch.int32, device=m.device))
+        acc.n_frames = 0
+    elif not torch.is_tensor(acc) or acc.dtype != torch.int32 or acc.dim() != 2:
+        raise RuntimeError("fixmap_accumulate: acc must be an int32 [H0,W0] tensor")
+    elif tuple(acc.shape) != (h0, w0):
+        raise RuntimeError("fixmap_accumulate: acc is %r, the frames are %r" % (tuple(acc.shape), (h0, w0)))
+    elif acc.device != m.device:
+        raise RuntimeError("fixmap_accumulate: acc is on %s, the frames are on %s" % (acc.device, m.device))
+    total = int(getattr(acc, "n_frames", 0)) + F
+    if total > L.PRIOR_MAX_FRAMES:
+        raise RuntimeError("fixmap_accumulate: %d frames overflow the int32 sums (at most %d)" % (total, L.PRIOR_MAX_FRAMES))
+    if F > 0:
+        d = L.PriorAccDesc()
+        d.frames, d.acc = m.data_ptr(), acc.data_ptr()
+        d.img_pitch, d.row_pitch, d.col_pitch = st
+        d.acc_row_pitch, d.acc_col_pitch = acc.stride()
+        d.n_img, d.h0, d.w0 = F, h0, w0
+        L.check(lib.uavsal_prior_accumulate(C.byref(d), _stream(m)), "uavsal_prior_accumulate")
+    acc.n_frames = total
+    return acc
+
+
+def prior_map_from_sum(acc, n_frames, h, w, with_image=False):
+    """The rest of the reference's prior of one video from the sums of `fixmap_accumulate` (utils_data.py:517-520, 571-574):
+    `q = rint(255 * (m - min m) / (max m - min m + EPS))` of the mean `m = acc / n_frames` in double -- the uint8 picture
+    `cv2.imwrite` stores as `<video>.png` -- and the uint8 `[h,w]` map `padding(q, h, w, 1)`, letterboxed with the rule of
+    `letterbox_frames`.  Returns the map, or `(map, q [H0,W0])` with `with_image`.  Three launches on the current stream, no
+    synchronisation."""
+    lib = L.load()
+    if not torch.is_tensor(acc) or not acc.is_cuda or acc.dtype != torch.int32 or acc.dim() != 2:
+        raise RuntimeError("prior_map_from_sum: acc must be an int32 cuda [H0,W0] tensor")
+    n_frames, h, w = int(n_frames), int(h), int(w)
+    if n_frames <= 0 or n_frames > L.PRIOR_MAX_FRAMES:
+        raise RuntimeError("prior_map_from_sum: n_frames must be in 1..%d, got %d" % (L.PRIOR_MAX_FRAMES, n_frames))
+    h0, w0 = acc.shape
+    letterbox_geometry(h0, w0, h, w)
+    buf = torch.empty(8 + h * w + (h0 * w0 if with_image else 0), dtype=torch.uint8, device=acc.device)
+    out = buf[8:8 + h * w].view(h, w)
+    image = buf[8 + h * w:].view(h0, w0) if with_image else None
+    d = L.PriorFinishDesc()
+    d.acc, d.ws, d.out = acc.data_ptr(), buf.data_ptr(), out.data_ptr()
+    d.image = image.data_ptr() if with_image else None
+    d.acc_row_pitch, d.acc_col_pitch = acc.stride()
+    d.n_frames, d.h0, d.w0, d.h, d.w = n_frames, h0, w0, h, w
+    L.check(lib.uavsal_prior_finish(C.byref(d), _stream(acc)), "uavsal_prior_finish")
+    return (out, image) if with_image else out
+
+
 def lstm_step(x_t, h_prev, c_prev, weight, prec="f32"):
     """One ConvLSTM step (reference model_convlstm.py:111-126, bias=False) from NHWC tensors and the
     reference-layout weight [4*hid, in+hid, 3, 3]: returns (h_t, c_t).  The x half of the conv is

@@ -619,6 +619,51 @@ typedef struct uavsal_loss_desc {
 int uavsal_loss_fu(const uavsal_loss_desc* d, uavsal_stream_t stream);
 int uavsal_loss_fu_grad(const uavsal_loss_desc* d, uavsal_stream_t stream);
 
+/* ---- observed prior of a dataset: the mean fixation map of a video (utils_data.py:497-520, 569-574) ------------------
+ * (csrc/prior.hip states the rules and the sizing)
+ *
+ * uavsal_prior_accumulate: acc[r][c] += sum over the n_img frames of frames[img][r][c], int32 sums of uint8 values.
+ *   Element (img, r, c) of the frames at base + img * img_pitch + r * row_pitch + c * col_pitch BYTES, any non-negative
+ *   pitches and any byte offset, read in place (the contract of uavsal_gaze_prepare); element (r, c) of the sums at
+ *   acc + r * acc_row_pitch + c * acc_col_pitch ELEMENTS.  The caller zeroes `acc` once per video and may add any number
+ *   of chunks; it keeps the total below 2^31 / 255 frames.  A plane that is contiguous in memory in either pixel order
+ *   (rows of w0 bytes, or MATLAB's columns of h0 bytes), frames a multiple of 16 bytes apart and an `acc` in the same
+ *   pixel order stream at 16 bytes per lane; everything else is summed a byte at a time.  The frames are split into
+ *   slabs of uavsal_prior_slab_frames() across the grid and the slabs meet in INTEGER atomic adds: the result does not
+ *   depend on the order of arrival.  ONE launch, no allocation, no synchronisation.
+ *   UAVSAL_EALIGN: acc not 4-byte aligned.  UAVSAL_ESHAPE: 255 * n_img or h0 * w0 does not fit an int32.
+ * uavsal_prior_slab_frames: the slab length that call uses for a plane of `plane_pixels` and `n_img` frames (no launch;
+ *   0 for non-positive arguments).  Never below UAVSAL_PRIOR_MIN_SLAB.
+ * uavsal_prior_finish: out [h][w] uint8 = padding(q, h, w, 1) and, when `image` is not NULL, image [h0][w0] uint8 = q, the
+ *   picture the reference writes as <video>.png, with
+ *     m = acc / n_frames,   q = rint(255 * (m - min m) / (max m - min m + EPS))            EPS = 2.2204e-16
+ *   in double, every operation rounded on its own, the product in front of the quotient, rint to even (np.mean, :517-518;
+ *   cv2.imwrite's saturate_cast).  min / max are taken on the integer sums.  padding(): the geometry and the 8-bit
+ *   INTER_LINEAR rule of uavsal_letterbox_u8, zero bars; every byte of `out` is written.  `ws`: two device words the
+ *   call owns while it runs.  THREE launches (clear, min / max, map), no allocation, no synchronisation.
+ *   UAVSAL_EALIGN: acc / ws not 4-byte aligned.  UAVSAL_ESHAPE: a degenerate picture, 255 * n_frames or h0 * w0 beyond int32.
+ */
+#define UAVSAL_PRIOR_MIN_SLAB 32
+
+typedef struct uavsal_prior_acc_desc {
+    const uint8_t* frames;  int64_t row_pitch, col_pitch, img_pitch;   /* bytes */
+    int32_t* acc;  int64_t acc_row_pitch, acc_col_pitch;               /* elements */
+    int32_t n_img, h0, w0;
+} uavsal_prior_acc_desc;
+
+typedef struct uavsal_prior_finish_desc {
+    const int32_t* acc;  int64_t acc_row_pitch, acc_col_pitch;         /* elements */
+    int32_t* ws;                                                       /* [2] */
+    uint8_t* out;                                                      /* [h][w] */
+    uint8_t* image;                                                    /* [h0][w0] or NULL */
+    int32_t n_frames, h0, w0, h, w;
+} uavsal_prior_finish_desc;
+
+int uavsal_prior_accumulate(const uavsal_prior_acc_desc* d, uavsal_stream_t stream);
+int uavsal_prior_finish(const uavsal_prior_finish_desc* d, uavsal_stream_t stream);
+int uavsal_prior_slab_frames(int64_t plane_pixels, int32_t n_img);
+int uavsal_prior_sizeof_desc(int which);  /* 0 prior_acc, 1 prior_finish (uavsal_sizeof_desc's list is closed at 20) */
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 
