@@ -217,6 +217,29 @@ class PriorFinishDesc(C.Structure):
 
 PRIOR_DESC_TYPES = [PriorAccDesc, PriorFinishDesc]        # sized by uavsal_prior_sizeof_desc
 
+WGRAD_CHAIN = 1024            # UAVSAL_WGRAD_CHAIN: the longest MFMA accumulation chain of uavsal_twa_wgrad (csrc/train.hip)
+
+
+class TwaGateDesc(C.Structure):
+    _fields_ = [("g", _f), ("ldg", C.c_int32), ("carry", _f), ("z", _f), ("x", _f), ("ldx", C.c_int32),
+                ("hprev", _f), ("ldh", C.c_int32), ("dz", _f), ("carry_out", _f), ("dx", _f),
+                ("n_pix", C.c_int64), ("C", C.c_int32)]
+
+
+class TwaWgradDesc(C.Structure):
+    _fields_ = [("dz", _f), ("x", _f), ("ldx", C.c_int32), ("h", _f), ("ldh", C.c_int32), ("h0", _f), ("ldh0", C.c_int32),
+                ("ws", _f), ("ws_bytes", C.c_int64), ("out", _f),
+                ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("accumulate", C.c_int32)]
+
+
+class DecBwdDesc(C.Structure):
+    _fields_ = [("gy", _f), ("gy_img_pitch", C.c_int64), ("gy_row_pitch", C.c_int64), ("gy_col_pitch", C.c_int64),
+                ("y", _f), ("e", _f), ("d", _f), ("s1", _f), ("wd9", _f), ("s2", _f), ("w3", _f), ("s3", _f), ("ge", _f),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
+
+
+TRAIN_DESC_TYPES = [TwaGateDesc, TwaWgradDesc, DecBwdDesc]        # sized by uavsal_train_sizeof_desc
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -248,6 +271,12 @@ SYMBOLS = [
     ("uavsal_prior_finish", C.c_int, [C.POINTER(PriorFinishDesc), C.c_void_p]),
     ("uavsal_prior_slab_frames", C.c_int, [C.c_int64, C.c_int32]),
     ("uavsal_prior_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_twa_gate_bwd", C.c_int, [C.POINTER(TwaGateDesc), C.c_void_p]),
+    ("uavsal_twa_wgrad_workspace_bytes", C.c_int64, [C.POINTER(TwaWgradDesc)]),
+    ("uavsal_twa_wgrad_shares", C.c_int, [C.POINTER(TwaWgradDesc)]),
+    ("uavsal_twa_wgrad", C.c_int, [C.POINTER(TwaWgradDesc), C.c_void_p]),
+    ("uavsal_dec_bwd", C.c_int, [C.POINTER(DecBwdDesc), C.c_void_p]),
+    ("uavsal_train_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -318,10 +347,10 @@ def load():
         if lib.uavsal_sizeof_desc(i) != C.sizeof(t):
             raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (
                 t.__name__, C.sizeof(t), lib.uavsal_sizeof_desc(i)))
-    for i, t in enumerate(PRIOR_DESC_TYPES):
-        if lib.uavsal_prior_sizeof_desc(i) != C.sizeof(t):
-            raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (
-                t.__name__, C.sizeof(t), lib.uavsal_prior_sizeof_desc(i)))
+    for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES)):
+        for i, t in enumerate(types):
+            if sizeof(i) != C.sizeof(t):
+                raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))
     _lib = lib
     return lib
 

@@ -259,11 +259,12 @@ class UAVSal(nn.Module):
         import copy
         r = copy.copy(self)                      # parameters, modules and settings by reference; no runtime state (__getstate__)
         r._wshared, r._wversion = self._wshared, self._wversion
-        if "_wtensors" in self.__dict__:
-            r._wtensors = self._wtensors
+        for k in ("_wtensors", "_wvers"):
+            if k in self.__dict__:
+                setattr(r, k, self.__dict__[k])
         return r
 
-    _RUNTIME_STATE = ("_engines", "_wshared", "_wversion", "_wtensors", "_stream_replicas", "_stream_streams")
+    _RUNTIME_STATE = ("_engines", "_wshared", "_wversion", "_wtensors", "_wvers", "_stream_replicas", "_stream_streams")
 
     def __getstate__(self):
         """`torch.save(model)` (the form of the reference's checkpoints, model.py:339), `pickle` and `copy.deepcopy` carry the
@@ -283,6 +284,34 @@ class UAVSal(nn.Module):
         self._wversion = None
 
     invalidate_engines = _drop_engines
+
+    def refresh_weights(self, *modules):
+        """After an optimiser step on the parameters of `modules` (e.g. `model.rnn`): repack every packed copy of their conv
+        weights -- every layout in use, the Winograd transforms, the transposed forms of train.py -- INTO THE EXISTING DEVICE
+        TENSORS, and take the parameters' new version counters as the packed state, so that the next call neither drops nor
+        rebuilds a launch plan (plans hold the tensors' addresses).  Only the named modules are repacked.  If any OTHER
+        parameter or buffer was modified in place since the weights were packed, the plans and packed weights are dropped
+        instead (as `_check_weights` would at the next call) and everything is packed anew then.  Modules whose packed form
+        is not a plain conv weight (BatchNorm folds, depthwise, fused blocks) raise before anything is copied.
+        Returns the number of packed tensors refreshed (0 when nothing was packed yet, or when the plans were dropped)."""
+        from .weights import WeightCache
+        if self._wversion is None or "_wtensors" not in self.__dict__:
+            return 0
+        mods = {id(s): s for m in modules for s in m.modules()}
+        mine = {id(t) for m in modules for t in list(m.parameters()) + list(m.buffers())}
+        then = self.__dict__.get("_wvers")
+        if then is None or any(t._version != v for t, v in zip(self._wtensors, then) if id(t) not in mine):
+            self._drop_engines()
+            return 0
+        caches = [WeightCache(dev, store) for dev, store in self._wshared.items()]
+        for c in caches:
+            c.refresh(mods, dry=True)                    # every key can be remade, or nothing is touched
+        n = sum(c.refresh(mods) for c in caches)
+        for m in [self] + list(self.__dict__.get("_stream_replicas") or []):
+            if m._wversion is not None and "_wtensors" in m.__dict__:
+                m._wversion = m._weights_version()
+                m._wvers = [t._version for t in m._wtensors]
+        return n
 
     def invalidate_priors(self):
         """The next call of every plan of this model (and of the handles the streaming drivers keep on it) runs the prior nets
@@ -333,6 +362,7 @@ class UAVSal(nn.Module):
             self._wtensors = [t for k, t in self.state_dict(keep_vars=True).items()
                               if not k.endswith("num_batches_tracked")]
             self._wversion = self._weights_version()
+            self._wvers = [t._version for t in self._wtensors]      # per tensor: refresh_weights tells WHICH one moved
 
     def _engine(self, device, n_seq, seq_len, H, W, ctx_mode, taps=False, in_dtype=torch.float32, sync_default=True, static_priors=False):
         from .engine import Engine

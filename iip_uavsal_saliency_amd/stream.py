@@ -300,6 +300,56 @@ def validation_aggregates(losses):
     return {"video_mean": video_loss / len(losses), "run_loss": video_loss, "num_step": num_step}
 
 
+def _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout, bgr,
+                      gaze_layout, prepare, step):
+    """The loop over one video that `validate_video` and `finetune_video` share (Demo_Train_Test.py:105-153): argument
+    checks, the ground truth of the whole video by one `prepare` call, the groups and their skip rule, frames uploaded and
+    letterboxed per group, priors as zero-stride views, the carried state, the per-group table and the aggregates.
+    `step(x, cb, state, y_gaze_of_the_group) -> (loss 0-d tensor, next state)` is what a group that runs does."""
+    prepare = prepare or ops.prepare_gaze
+    dev = next(model.parameters()).device
+    T = model.time_dims
+    letterbox = None
+    if model_size is None:
+        if frame_layout != "CHW" or bgr:
+            raise RuntimeError("frame_layout / bgr describe source-size frames: pass model_size=(R, C) with them")
+    else:
+        if frame_layout not in ("CHW", "HWC") or frames_u8.dim() != 4 or frames_u8.dtype != torch.uint8:
+            raise RuntimeError("model_size needs uint8 frames [F,3,H0,W0] (frame_layout='CHW') or [F,H0,W0,3] ('HWC')")
+        R, C = int(model_size[0]), int(model_size[1])
+        h0, w0 = (frames_u8.shape[2:] if frame_layout == "CHW" else frames_u8.shape[1:3])
+        ops.letterbox_geometry(h0, w0, R, C)              # a degenerate picture raises here, before anything is launched
+        letterbox = (R, C, frame_layout, bool(bgr))
+    # the output size of the model is the size of its prior maps (shape_r_out x shape_c_out, Demo_Train_Test.py:64, 105-106)
+    with torch.no_grad():
+        y_gaze, has_gaze = prepare(fix_map.to(dev), fix_loc.to(dev), gauss_prior.shape[-2], gauss_prior.shape[-1], gaze_layout)
+    n_frames = min(frames_u8.shape[0], y_gaze.shape[0])                 # Demo_Train_Test.py:109
+    if (n_frames // T) * T < 2:
+        raise RuntimeError("need at least one full chunk of time_dims >= 2 frames")
+    groups = validation_groups(n_frames, T, batch_size, has_gaze.cpu().tolist())     # the one wait for the device
+    gauss_prior, ob_prior = gauss_prior.to(dev), ob_prior.to(dev)
+    state, ran = None, []
+    for a, b, run in groups:
+        if not run:
+            continue
+        x = frames_u8[a:b]
+        if x.device != torch.device(dev):
+            x = x.to(dev, non_blocking=True)
+        if letterbox is not None:
+            x = ops.letterbox_frames(x, letterbox[0], letterbox[1], layout=letterbox[2], bgr=letterbox[3])
+        n = b - a
+        cb = [gauss_prior.unsqueeze(0).expand(n, -1, -1, -1), ob_prior.unsqueeze(0).expand(n, -1, -1, -1)]
+        loss, state = step(x, cb, state, y_gaze[a:b])
+        ran.append(loss.reshape(()))
+    vals = torch.stack(ran).cpu().tolist() if ran else []                # the one copy back
+    per_group = torch.full((len(groups),), float("nan"), dtype=torch.float32)
+    for i, v in zip([i for i, g in enumerate(groups) if g[2]], vals):
+        per_group[i] = v
+    res = {"losses": per_group, "groups_run": len(ran)}
+    res.update(validation_aggregates(per_group.tolist()))
+    return res
+
+
 @torch.no_grad()
 def validate_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_prior: torch.Tensor,
                    fix_map: torch.Tensor, fix_loc: torch.Tensor, batch_size: int = 4, model_size: Optional[tuple] = None,
@@ -320,49 +370,39 @@ def validate_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `criterion` (default `losses.loss_fu`) and `prepare` (default `ops.prepare_gaze`) may be replaced."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
-    prepare = prepare or ops.prepare_gaze
-    dev = next(model.parameters()).device
-    T = model.time_dims
-    letterbox = None
-    if model_size is None:
-        if frame_layout != "CHW" or bgr:
-            raise RuntimeError("frame_layout / bgr describe source-size frames: pass model_size=(R, C) with them")
-    else:
-        if frame_layout not in ("CHW", "HWC") or frames_u8.dim() != 4 or frames_u8.dtype != torch.uint8:
-            raise RuntimeError("model_size needs uint8 frames [F,3,H0,W0] (frame_layout='CHW') or [F,H0,W0,3] ('HWC')")
-        R, C = int(model_size[0]), int(model_size[1])
-        h0, w0 = (frames_u8.shape[2:] if frame_layout == "CHW" else frames_u8.shape[1:3])
-        ops.letterbox_geometry(h0, w0, R, C)              # a degenerate picture raises here, before anything is launched
-        letterbox = (R, C, frame_layout, bool(bgr))
-    # the output size of the model is the size of its prior maps (shape_r_out x shape_c_out, Demo_Train_Test.py:64, 105-106)
-    y_gaze, has_gaze = prepare(fix_map.to(dev), fix_loc.to(dev), gauss_prior.shape[-2], gauss_prior.shape[-1], gaze_layout)
-    n_frames = min(frames_u8.shape[0], y_gaze.shape[0])                 # Demo_Train_Test.py:109
-    if (n_frames // T) * T < 2:
-        raise RuntimeError("need at least one full chunk of time_dims >= 2 frames")
-    groups = validation_groups(n_frames, T, batch_size, has_gaze.cpu().tolist())     # the one wait for the device
-    gauss_prior, ob_prior = gauss_prior.to(dev), ob_prior.to(dev)
     lstm = getattr(model, "rnn_type", "twa") == "lstm"
-    state, ran = None, []
-    for a, b, run in groups:
-        if not run:
-            continue
-        x = frames_u8[a:b]
-        if x.device != torch.device(dev):
-            x = x.to(dev, non_blocking=True)
-        if letterbox is not None:
-            x = ops.letterbox_frames(x, letterbox[0], letterbox[1], layout=letterbox[2], bgr=letterbox[3])
-        n = b - a
-        cb = [gauss_prior.unsqueeze(0).expand(n, -1, -1, -1), ob_prior.unsqueeze(0).expand(n, -1, -1, -1)]
+
+    def step(x, cb, state, y):
         out, st = model(x, cb, state)
-        state = [(st[0].detach(), st[1].detach())] if lstm else [st[0].detach()]
-        ran.append(criterion(out, y_gaze[a:b]).reshape(()))
-    vals = torch.stack(ran).cpu().tolist() if ran else []                # the one copy back
-    per_group = torch.full((len(groups),), float("nan"), dtype=torch.float32)
-    for i, v in zip([i for i, g in enumerate(groups) if g[2]], vals):
-        per_group[i] = v
-    res = {"losses": per_group, "groups_run": len(ran)}
-    res.update(validation_aggregates(per_group.tolist()))
-    return res
+        return criterion(out, y), ([(st[0].detach(), st[1].detach())] if lstm else [st[0].detach()])
+    return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,
+                             bgr, gaze_layout, prepare, step)
+
+
+def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_prior: torch.Tensor,
+                   fix_map: torch.Tensor, fix_loc: torch.Tensor, optimizer, batch_size: int = 4,
+                   model_size: Optional[tuple] = None, frame_layout: str = "CHW", bgr: bool = False,
+                   gaze_layout: Optional[str] = None, criterion=None, prepare=None):
+    """The inner loop of the reference's `train` phase for one video (Demo_Train_Test.py:105-153), for the stage this package
+    trains: the ConvTWA recurrence `model.rnn` (train.py).  Arguments, groups, skip rule, carried detached state and returned
+    aggregates are `validate_video`'s (one loop serves both); every group that runs does
+    `optimizer.zero_grad()`, `train.recurrence_step(...)`, `optimizer.step()`, `model.refresh_weights(model.rnn)`.
+    `optimizer` is the caller's `torch.optim` object over `model.rnn.parameters()`; the reference uses
+    `Adam(lr=1e-4, betas=(0.9, 0.999), weight_decay=5e-5)` (Demo_Train_Test.py:68-69) over ALL parameters.  Different from
+    the reference on purpose: the model stays in `eval()` -- every other stage is frozen and every BatchNorm uses its running
+    statistics.  A group's loss is the loss BEFORE its step, as `loss.data.item()` is there."""
+    from . import losses as _losses
+    from . import train as _train
+    criterion = criterion or _losses.loss_fu
+
+    def step(x, cb, state, y):
+        optimizer.zero_grad()
+        loss, _, state = _train.recurrence_step(model, x, cb, state, y, criterion)
+        optimizer.step()
+        model.refresh_weights(model.rnn)
+        return loss, state
+    return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,
+                             bgr, gaze_layout, prepare, step)
 
 
 class RequestPipeline:

@@ -1,0 +1,297 @@
+"""Fine-tuning the Temporal Weighted Average recurrence (`model.rnn`, reference model_convlstm.py:238-295) on the device.
+
+This is ONE stage of the reference's `train()` (Demo_Train_Test.py:35-174): the loss gradient is carried through the
+frozen decoder `conv_out_st` and back through time over the ConvTWA steps to the recurrence's only parameter, the
+`[256, 512, 3, 3]` weight `W = [W_x | W_h]` of `rnn_conv`, and to the recurrence's input.  Everything else stays frozen
+and in eval mode -- a deliberate difference from the reference, whose `train()` also trains `fust_layer`, the prior nets
+and the decoder and runs every BatchNorm on batch statistics.  The recurrence has no BatchNorm and no
+bias, so ITS gradient is the same in both modes.
+
+    z_t = conv3x3(W, cat[x_t, h_{t-1}]),   i_t = sigmoid(z_t),   h_t = i_t x_t + (1 - i_t) h_{t-1}
+
+New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
+`uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
+Tensors are float32 on the GPU with the logical shape `[T, C, h, w]`; a channels-last tensor (NHWC in memory, or a channel
+slice of one) is read in place, anything else is copied once.  Returned gradients are channels-last.  `f32` only; one
+sequence per call.  CPU tensors raise: this package has no CPU fallback."""
+from __future__ import annotations
+
+import ctypes as C
+import types
+
+import torch
+
+from . import _lib as L
+from . import packing as P
+from .ops import _nhwc_view, _stream
+from .weights import WeightCache
+
+HID = 256
+
+
+def _nhwc(t, name, c=None):
+    """`t` `[n,c,h,w]` as an NHWC view `[n,h,w,c]` the kernels can read (a copy only when its memory is not NHWC)."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
+        raise RuntimeError("%s must be a float32 cuda tensor [n,c,h,w] (no CPU fallback)" % name)
+    if c is not None and t.shape[1] != c:
+        raise RuntimeError("%s must have %d channels, got %r" % (name, c, tuple(t.shape)))
+    v = t.detach().permute(0, 2, 3, 1)
+    try:
+        p, ld, *_ = _nhwc_view(v)
+        if p % 16 == 0 and ld % 4 == 0:
+            return v
+    except RuntimeError:
+        pass
+    return v.contiguous()
+
+
+def _conv(lib, cache, x, conv, cout, taps, wslice=None, transposed=False, bn=None, act=L.ACT_NONE, res=None):
+    """One `uavsal_conv_gemm` launch on the current stream (no synchronisation): `x` NHWC, the weights of `conv` (or of its
+    transposed conv) from `cache` in the layout the route of this launch takes."""
+    ap, lda, n, h, w, cin = _nhwc_view(x)
+    out = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.device)
+    d = L.ConvDesc()
+    d.a, d.lda, d.a_img_stride = ap, lda, h * w
+    d.out, d.ldc, d.o_img_stride = out.data_ptr(), cout, h * w
+    if bn is not None:
+        s, b = cache.affine(bn, cout)
+        d.scale, d.bias = s.data_ptr(), b.data_ptr()
+    if res is not None:
+        rp, ldr, *_ = _nhwc_view(res)
+        d.res, d.ldr, d.r_img_stride = rp, ldr, h * w
+    d.n_img, d.H, d.W, d.Cin, d.Cout, d.taps = n, h, w, cin, cout, taps
+    d.prec, d.act, d.epi, d.tile = L.PREC["f32"], act, L.EPI_AFFINE, 0
+    d.w = 1 << 20
+    rt = L.conv_route(lib, d)
+    layout = P.conv_weight_layout("f32", False, False, rt.tile, 3 if taps == 9 else 1)
+    wp = cache.conv_t(conv, wslice, layout) if transposed else cache.conv(conv, wslice, 0, layout)
+    d.w = wp.data_ptr()
+    L.check(lib.uavsal_conv_gemm(C.byref(d), _stream(x)), "uavsal_conv_gemm")
+    return out
+
+
+def _decoder_parts(block):
+    seq = block.conv
+    if getattr(block, "expand_ratio", 0) == 1 or len(seq) != 4 or seq[2].weight.shape[0] != 1:
+        raise RuntimeError("decoder_input_grad takes model.conv_out_st (expand 1x1, depthwise 3x3, projection to one channel)")
+    if block.training:
+        raise RuntimeError("the decoder is frozen: its BatchNorms are folded in eval mode (call model.eval())")
+    return seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
+
+
+def decoder_input_grad(block, h_seq, grad_out, cache=None, y=None, parts=None):
+    """The gradient of the loss with respect to the recurrence output `h_seq` `[T,256,h,w]`, given `grad_out` `[T,1,h,w]` =
+    d loss / d prediction, through the frozen decoder `block` = `model.conv_out_st` + sigmoid (model.py:372-373) with its
+    eval BatchNorms folded.  `e` and `d` (the expanded and the depthwise tensor) are recomputed from `h_seq` by the forward's
+    own launches, `uavsal_dec_bwd` goes back to `e` and a 1536 -> 256 GEMM with W1^T to `h`.
+    `cache`: the `WeightCache` to take packed weights from (default: packed for this call); `y`: the prediction of the
+    forward `[T,1,h,w]` (default: recomputed); `parts`: a dict that receives the intermediate NHWC tensors (tests)."""
+    lib = L.load()
+    pw, pwbn, dwc, dwbn, pl, plbn = _decoder_parts(block)
+    h = _nhwc(h_seq, "h_seq", pw.weight.shape[1])
+    T, hh, ww, _ = h.shape
+    if (not torch.is_tensor(grad_out) or not grad_out.is_cuda or grad_out.dtype != torch.float32
+            or tuple(grad_out.shape) != (T, 1, hh, ww)):
+        raise RuntimeError("grad_out must be a float32 cuda tensor [%d,1,%d,%d]" % (T, hh, ww))
+    dev = h.device
+    hid = pw.weight.shape[0]
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        st = _stream(h)
+        e = _conv(lib, cache, h, pw, hid, 1, bn=pwbn, act=L.ACT_RELU6)
+        w9, s2, b2 = cache.depthwise(dwc, dwbn)
+        dd = torch.empty_like(e)
+        q = L.DwDesc()
+        q.inp, q.ldi, q.w9c, q.scale, q.bias = e.data_ptr(), hid, w9.data_ptr(), s2.data_ptr(), b2.data_ptr()
+        q.out, q.ldo = dd.data_ptr(), hid
+        q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, 1, 1, L.ACT_RELU6
+        L.check(lib.uavsal_dw3x3(C.byref(q), st), "uavsal_dw3x3")
+        _, _, _, w3, s3, b3 = cache.dw_dot(dwc, dwbn, pl, plbn)
+        if y is None:
+            y = torch.empty((T, hh, ww, 1), dtype=torch.float32, device=dev)
+            k = L.DwDotDesc()
+            k.inp, k.ldi = e.data_ptr(), hid
+            k.w9c, k.scale, k.bias, k.w2, k.scale2, k.bias2 = (t.data_ptr() for t in (w9, s2, b2, w3, s3, b3))
+            k.out, k.ldo = y.data_ptr(), 1
+            k.n_img, k.H, k.W, k.C, k.act = T, hh, ww, hid, L.ACT_SIGMOID
+            L.check(lib.uavsal_dw3x3_dot(C.byref(k), st), "uavsal_dw3x3_dot")
+        else:
+            if tuple(y.shape) != (T, 1, hh, ww) or y.dtype != torch.float32 or y.device != dev:
+                raise RuntimeError("y must be the prediction [%d,1,%d,%d] on the same device" % (T, hh, ww))
+            y = y.detach().contiguous()
+        ge = dec_bwd(grad_out, y, e, dd, cache.affine(pwbn, hid)[0], w9, s2, w3, s3)
+        g = _conv(lib, cache, ge, pw, pw.weight.shape[1], 1, transposed=True)
+        if parts is not None:
+            parts.update(e=e, d=dd, y=y, ge=ge)
+    return g.permute(0, 3, 1, 2)
+
+
+def dec_bwd(grad_out, y, e, d, s1, wd9, s2, w3, s3):
+    """`uavsal_dec_bwd` on the current stream: `grad_out` `[T,1,h,w]` (any strides), `y` dense `[T,h,w]` in any shape,
+    `e`, `d` dense NHWC `[T,h,w,C]`, the folded scales and the tap-major depthwise weights on the device -> `ge` NHWC."""
+    lib = L.load()
+    T, hh, ww, c = e.shape
+    if not (e.is_contiguous() and d.is_contiguous() and y.is_contiguous()) or e.shape != d.shape or y.numel() != T * hh * ww:
+        raise RuntimeError("dec_bwd: e, d must be dense NHWC tensors of one shape and y dense [T,h,w]")
+    ge = torch.empty_like(e)
+    k = L.DecBwdDesc()
+    k.gy = grad_out.data_ptr()
+    k.gy_img_pitch, _, k.gy_row_pitch, k.gy_col_pitch = grad_out.stride()
+    k.y, k.e, k.d, k.ge = y.data_ptr(), e.data_ptr(), d.data_ptr(), ge.data_ptr()
+    k.s1, k.wd9, k.s2, k.w3, k.s3 = s1.data_ptr(), wd9.data_ptr(), s2.data_ptr(), w3.data_ptr(), s3.data_ptr()
+    k.n_img, k.H, k.W, k.C = T, hh, ww, c
+    L.check(lib.uavsal_dec_bwd(C.byref(k), _stream(e)), "uavsal_dec_bwd")
+    return ge
+
+
+def twa_gate_bwd(g, carry, z, x, hprev, need_dx=False):
+    """`uavsal_twa_gate_bwd` on NHWC tensors `[1,h,w,256]` (`g`, `x`, `hprev` may be channel slices; `carry` dense or None):
+    returns `(dz, carry_out, dx | None)`, dense."""
+    lib = L.load()
+    gp, ldg, n, hh, ww, c = _nhwc_view(g)
+    xp, ldx, *xs = _nhwc_view(x)
+    hp, ldh, *hs = _nhwc_view(hprev)
+    if xs != [n, hh, ww, c] or hs != [n, hh, ww, c] or x.device != g.device or hprev.device != g.device:
+        raise RuntimeError("twa_gate_bwd: g, x and hprev must have one shape [n,h,w,256] on one device")
+    for name, t in (("z", z), ("carry", carry)):
+        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == g.device
+                                  and tuple(t.shape) == (n, hh, ww, c) and t.is_contiguous()):
+            raise RuntimeError("twa_gate_bwd: %s must be a dense float32 [n,h,w,256] tensor of g's shape and device" % name)
+    dz = torch.empty((n, hh, ww, c), dtype=torch.float32, device=g.device)
+    co = torch.empty_like(dz)
+    dx = torch.empty_like(dz) if need_dx else None
+    _gate(lib, gp, ldg, carry, z, xp, ldx, hp, ldh, dz, co, dx, n * hh * ww, c, _stream(g))
+    return dz, co, dx
+
+
+def _gate(lib, gp, ldg, carry, z, xp, ldx, hp, ldh, dz, co, dx, n_pix, c, st):
+    k = L.TwaGateDesc()
+    k.g, k.ldg, k.carry, k.z = gp, ldg, (carry.data_ptr() if carry is not None else None), z.data_ptr()
+    k.x, k.ldx, k.hprev, k.ldh = xp, ldx, hp, ldh
+    k.dz, k.carry_out, k.dx = dz.data_ptr(), co.data_ptr(), (dx.data_ptr() if dx is not None else None)
+    k.n_pix, k.C = n_pix, c
+    L.check(lib.uavsal_twa_gate_bwd(C.byref(k), st), "uavsal_twa_gate_bwd")
+
+
+def twa_wgrad(dz, x, h, h0, out=None, accumulate=False):
+    """`uavsal_twa_wgrad` on NHWC tensors: `dz` dense `[T,h,w,256]`, `x`, `h` `[T,h,w,256]`, `h0` `[1,h,w,256]` (channel slices
+    allowed) -> `dW` `[256,512,3,3]`, written to `out` or (`accumulate`) added to it.  Two launches, no synchronisation."""
+    lib = L.load()
+    if not torch.is_tensor(dz) or dz.dim() != 4 or not dz.is_contiguous():
+        raise RuntimeError("twa_wgrad: dz must be a dense [T,h,w,256] tensor")
+    T, hh, ww, c = dz.shape
+    if dz.dim() != 4 or dz.dtype != torch.float32 or not dz.is_cuda:
+        raise RuntimeError("twa_wgrad: dz must be a float32 cuda tensor [T,h,w,256]")
+    xp, ldx, *xs = _nhwc_view(x)
+    hp, ldh, *hs = _nhwc_view(h)
+    h0p, ldh0, *h0s = _nhwc_view(h0)
+    if xs != [T, hh, ww, c] or hs != [T, hh, ww, c] or h0s != [1, hh, ww, c] or any(t.device != dz.device for t in (x, h, h0)):
+        raise RuntimeError("twa_wgrad: x and h must be [T,h,w,256] like dz and h0 [1,h,w,256], all on one device")
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `out`")
+        out = torch.empty((c, 2 * c, 3, 3), dtype=torch.float32, device=dz.device)
+    if (tuple(out.shape) != (c, 2 * c, 3, 3) or out.dtype != torch.float32 or out.device != dz.device or not out.is_contiguous()):
+        raise RuntimeError("out must be a dense float32 [%d,%d,3,3] tensor on the device" % (c, 2 * c))
+    k = L.TwaWgradDesc()
+    k.dz, k.x, k.ldx, k.h, k.ldh, k.h0, k.ldh0 = dz.data_ptr(), xp, ldx, hp, ldh, h0p, ldh0
+    k.T, k.H, k.W, k.C, k.accumulate = T, hh, ww, c, int(bool(accumulate))
+    nbytes = int(lib.uavsal_twa_wgrad_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_twa_wgrad")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dz.device)
+    k.ws, k.ws_bytes, k.out = ws.data_ptr(), nbytes, out.data_ptr()
+    L.check(lib.uavsal_twa_wgrad(C.byref(k), _stream(dz)), "uavsal_twa_wgrad")
+    return out
+
+
+def twa_backward(x_seq, h_seq, h0, weight, grad_h, need_x_grad=False, out=None, accumulate=False, cache=None, module=None,
+                 parts=None):
+    """Back-propagation through time over one ConvTWA sequence.  `x_seq` `[T,256,h,w]` the recurrence input, `h_seq`
+    `[T,256,h,w]` its output history, `h0` `[1,256,h,w]` the state it started from (None = zeros), `weight` `[256,512,3,3]`,
+    `grad_h` `[T,256,h,w]` the gradient of the loss with respect to every `h_t` (the carried part excluded).
+    Returns `(grad_weight [256,512,3,3], grad_x [T,256,h,w] | None, grad_h0 [1,256,h,w])`; `out` / `accumulate`: the weight
+    gradient is written to `out` or added to it (`.grad +=`).
+    The gates are recomputed from the known history by two batched 3x3 convs over all frames, so the forward stays what it is
+    and only the carry runs step by step: per step one `uavsal_twa_gate_bwd` and one 3x3 conv with flip(W_h)^T.
+    `cache` + `module`: take the packed forms of the weight from a `WeightCache` under the id of `module` (the conv that
+    owns `weight`); default: packed on the host for this call.  `parts`: a dict that receives `z`, `dz` (NHWC; tests)."""
+    lib = L.load()
+    x = _nhwc(x_seq, "x_seq", HID)
+    h = _nhwc(h_seq, "h_seq", HID)
+    G = _nhwc(grad_h, "grad_h", HID)
+    T, hh, ww, _ = x.shape
+    if h.shape != x.shape or G.shape != x.shape:
+        raise RuntimeError("x_seq, h_seq and grad_h must have one shape [T,256,h,w]")
+    dev = x.device
+    if (not torch.is_tensor(weight) or tuple(weight.shape) != (HID, 2 * HID, 3, 3) or weight.dtype != torch.float32
+            or weight.device != dev):
+        raise RuntimeError("weight must be the float32 [256,512,3,3] ConvTWA weight on the device")
+    with torch.cuda.device(dev):
+        if h0 is None:
+            h0n = torch.zeros((1, hh, ww, HID), dtype=torch.float32, device=dev)
+        else:
+            h0n = _nhwc(h0, "h0", HID)
+            if tuple(h0n.shape) != (1, hh, ww, HID):
+                raise RuntimeError("h0 must be [1,256,%d,%d]" % (hh, ww))
+        if cache is None or module is None:
+            cache, module = WeightCache(dev, {}), types.SimpleNamespace(weight=weight)
+        st = _stream(x)
+        hprev = torch.cat([h0n, h[:T - 1]], 0)                       # h_{t-1} of every frame, dense
+        z = _conv(lib, cache, x, module, HID, 9, wslice=(0, HID))
+        z = _conv(lib, cache, hprev, module, HID, 9, wslice=(HID, 2 * HID), res=z)
+        dz = torch.empty((T, hh, ww, HID), dtype=torch.float32, device=dev)
+        dx = torch.empty_like(dz) if need_x_grad else None
+        cbuf = torch.empty((1, hh, ww, HID), dtype=torch.float32, device=dev)
+        carry = None
+        hw = hh * ww
+        gp, ldg, *_ = _nhwc_view(G)
+        xp, ldx, *_ = _nhwc_view(x)
+        for t in range(T - 1, -1, -1):
+            _gate(lib, gp + 4 * t * hw * ldg, ldg, carry, z[t], xp + 4 * t * hw * ldx, ldx, hprev[t].data_ptr(), HID,
+                  dz[t], cbuf, dx[t] if need_x_grad else None, hw, HID, st)
+            carry = _conv(lib, cache, dz[t:t + 1], module, HID, 9, wslice=(HID, 2 * HID), transposed=True, res=cbuf)
+        if need_x_grad:
+            dx = _conv(lib, cache, dz, module, HID, 9, wslice=(0, HID), transposed=True, res=dx)
+        gw = twa_wgrad(dz, x, h, h0n, out=out, accumulate=accumulate)
+        if parts is not None:
+            parts.update(z=z, dz=dz)
+    return gw, (dx.permute(0, 3, 1, 2) if need_x_grad else None), carry.permute(0, 3, 1, 2)
+
+
+def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None):
+    """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
+    criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
+    `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
+    and no other parameter touched.  Returns `(loss, out, [h_last.detach()])`, the forward's contract plus the loss.
+    The model is in eval mode (every other stage is frozen, its BatchNorms folded); a model in training mode, CPU tensors,
+    a precision other than 'f32' or `UAVSAL_LSTM` raise.  After `optimizer.step()` call `model.refresh_weights(model.rnn)`."""
+    from . import losses as _losses
+    criterion = criterion or _losses.loss_fu
+    if getattr(model, "rnn_type", "twa") != "twa":
+        raise RuntimeError("recurrence_step covers the ConvTWA recurrence, not UAVSAL_LSTM")
+    if model.training:
+        raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
+    if model.precision != "f32":
+        raise RuntimeError("recurrence_step supports precision 'f32' only, got %r" % (model.precision,))
+    if not torch.is_tensor(x) or not x.is_cuda or not torch.is_tensor(y_gaze) or not y_gaze.is_cuda:
+        raise RuntimeError("recurrence_step needs tensors on the MI355X (cuda) device; there is no CPU fallback")
+    rc = model.rnn.cell_list[0].rnn_conv
+    taps = {}
+    out, st = model(x, cb, in_state, taps=taps)
+    pred = out.detach().requires_grad_(True)
+    with torch.enable_grad():
+        loss = criterion(pred, y_gaze)
+        (g_y,) = torch.autograd.grad(loss, pred)
+    dev = x.device
+    cache = WeightCache(dev, model._wshared.setdefault(str(torch.device(dev)), {}))
+    cl = torch.channels_last
+    h_seq, x_seq = taps["rnn"].contiguous(memory_format=cl), taps["prefuse"].contiguous(memory_format=cl)
+    grad_h = decoder_input_grad(model.conv_out_st, h_seq, g_y, cache=cache, y=out)
+    h0 = None if in_state is None else in_state[0]
+    w = rc.weight
+    had = w.grad is not None
+    if not had:
+        w.grad = torch.empty_like(w, memory_format=torch.contiguous_format)
+    twa_backward(x_seq, h_seq, h0, w.detach(), grad_h, out=w.grad, accumulate=had, cache=cache, module=rc)
+    return loss.detach(), out, [st[0].detach()]

@@ -68,6 +68,48 @@ class WeightCache:
         """The Winograd F(r x r, 3x3) filter transform of a dense 3x3 conv (input channels `wslice`)."""
         return self._get(("wino", id(conv), wslice, r), lambda: self._up(P.pack_wino_weight(_weight([conv], wslice), r))[0])
 
+    def conv_t(self, conv, wslice, layout):
+        """The weights of the TRANSPOSED conv of `conv` (input channels `wslice`), packed for `layout`: input and output channels
+        swapped and the taps flipped, `Wt[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx]` -- the conv that carries a gradient with
+        respect to `conv`'s output back to its input (train.py)."""
+        def make():
+            w = _weight([conv], wslice).transpose(0, 1).flip(2, 3)
+            return self._up(P.pack_conv_weight(w, layout))[0]
+        return self._get(("wT", id(conv), wslice, layout), make)
+
+    def refresh(self, mods, dry=False):
+        """Repack, INTO THE EXISTING DEVICE TENSORS, every entry whose key holds the id of a module in `mods` (id -> module)
+        from the module's current parameters: launch plans that recorded the tensors' addresses stay valid.  Conv weights in
+        every layout, their Winograd transforms and transposed forms are refreshable; an entry of another kind (folded
+        BatchNorm, depthwise, fused block, stem) that names such a module raises -- `model.invalidate_engines()` is for those.
+        `dry`: only check that every such entry can be remade (raise otherwise), pack and copy nothing.
+        Returns the number of entries refreshed (that would be)."""
+        n = 0
+        for key in list(self.store):
+            if not isinstance(key, tuple) or not any(isinstance(i, int) and i in mods for i in key[1:]):
+                continue
+            kind = key[0]
+            if kind not in ("w", "wino", "wT"):
+                raise NotImplementedError("packed %r weights cannot be refreshed in place: call model.invalidate_engines()" % (kind,))
+            if kind == "w" and not all(i in mods for i in key[1:-3]):
+                raise RuntimeError("a packed weight joins several convs: refresh all of them together")
+            if dry:
+                n += 1
+                continue
+            if kind == "w":
+                ids, (wslice, layout, gi) = key[1:-3], key[-3:]
+                w = _weight([mods[i] for i in ids], wslice)
+                if gi:
+                    w = w.reshape(4, gi, *w.shape[1:]).permute(1, 0, 2, 3, 4).reshape(w.shape)
+                new = P.pack_conv_weight(w, layout)
+            elif kind == "wino":
+                new = P.pack_wino_weight(_weight([mods[key[1]]], key[2]), key[3])
+            else:
+                new = P.pack_conv_weight(_weight([mods[key[1]]], key[2]).transpose(0, 1).flip(2, 3), key[3])
+            self.store[key].copy_(new.to(self.device, non_blocking=False))
+            n += 1
+        return n
+
     def depthwise(self, conv, bn):
         """(tap-major weights, scale, bias) of a depthwise 3x3 + BatchNorm, or of a list of them as channel groups.  The
         standalone launch and the depthwise inside a projection GEMM's loader share the entry."""

@@ -664,6 +664,73 @@ int uavsal_prior_finish(const uavsal_prior_finish_desc* d, uavsal_stream_t strea
 int uavsal_prior_slab_frames(int64_t plane_pixels, int32_t n_img);
 int uavsal_prior_sizeof_desc(int which);  /* 0 prior_acc, 1 prior_finish (uavsal_sizeof_desc's list is closed at 20) */
 
+/* ---- fine-tuning the ConvTWA recurrence: backward of model.rnn and of the frozen decoder (csrc/train.hip) --------------
+ * All activations NHWC fp32, C = 256 hidden channels (anything else: UAVSAL_ESHAPE), one sequence per call.
+ * Notation: x_t the recurrence input, h_t the output history (h_{-1} = h0), W = [W_x | W_h] along the input channels,
+ *   z_t = conv3x3(W, cat[x_t, h_{t-1}]),  i_t = sigmoid(z_t),  h_t = i_t x_t + (1 - i_t) h_{t-1}   (model_convlstm.py:276-292)
+ *
+ * uavsal_twa_gate_bwd: one step of back-propagation through time, element-wise, ONE launch.  With g = G_t + carry (the
+ *   direct gradient of h_t plus what step t+1 hands back; carry NULL = none):
+ *     dz = g (x_t - h_{t-1}) i (1 - i),   carry_out = g (1 - i),   dx = g i  (dx NULL = not wanted)
+ *   i and 1 - i are both computed from exp(-|z|), so neither loses its relative accuracy in a saturated gate.
+ *   Rows of C floats `ld*` floats apart; dz, carry_out and dx may alias nothing they are computed from except that
+ *   carry_out may be `carry`.  UAVSAL_EALIGN: a pointer or ld not 16-byte aligned.
+ *
+ * uavsal_twa_wgrad: dW[co][ci][ky][kx] = sum over t and pixels p of dz_t[p][co] * cat_t[p + (ky-1, kx-1)][ci], zero outside
+ *   the picture, never across frames; cat_t is not materialised (ci < C reads x_t, ci >= C reads h_{t-1}; frame 0 reads h0).
+ *   A GEMM whose reduction runs over the T*H*W pixels (M = C, N = 9 * 2C) on the exact-fp32 MFMA, 128 x 128 tiles.  The
+ *   pixels are cut into chunks of UAVSAL_WGRAD_CHAIN = 1024: no MFMA accumulation chain is longer than that; a workgroup
+ *   owns one tile and a share of whole chunks, adds its chunks' tiles in fp32 and writes the partial tile to `ws`.  A
+ *   second launch sums the shares in a fixed order in double, rounds once and overwrites `out` [C][2C][3][3] or
+ *   (`accumulate`) adds it to what is there.  No atomics: two calls return the same bits.  TWO launches, no allocation.
+ *   `ws`: uavsal_twa_wgrad_workspace_bytes(d) bytes, 16-byte aligned (UAVSAL_EINVAL when ws_bytes is smaller).
+ *
+ * uavsal_dec_bwd: the input gradient of the middle of the frozen decoder conv_out_st (eval BatchNorm folded),
+ *     e = ReLU6(s1 (W1 h) + b1),  d = ReLU6(s2 dw3x3(e) + b2),  y = sigmoid(s3 (w3 . d) + b3):
+ *     ge[p][c] = s1[c] 1[0 < e[p][c] < 6] s2[c] sum over taps k of wd[k][c] t[p - (k - (1,1))][c],
+ *     t[q][c]  = gy[q] y[q] (1 - y[q]) s3 w3[c] 1[0 < d[q][c] < 6]
+ *   from the stored e and d (the masks are torch's: strict inequalities).  gy is read at
+ *   img * gy_img_pitch + row * gy_row_pitch + col * gy_col_pitch elements; y is dense [n_img][H][W]; e, d, ge dense
+ *   [n_img][H][W][C], C % 4 == 0; wd9 tap-major [9][C] as in uavsal_dw_desc.  ONE launch, memory bound.
+ */
+#define UAVSAL_WGRAD_CHAIN 1024
+
+typedef struct uavsal_twa_gate_desc {
+    const float* g;      int32_t ldg;       /* G_t */
+    const float* carry;                     /* dense [n_pix][C] or NULL */
+    const float* z;                         /* dense */
+    const float* x;      int32_t ldx;
+    const float* hprev;  int32_t ldh;
+    float* dz;  float* carry_out;  float* dx;           /* dense; dx may be NULL */
+    int64_t n_pix;  int32_t C;
+} uavsal_twa_gate_desc;
+
+typedef struct uavsal_twa_wgrad_desc {
+    const float* dz;                        /* dense [T][H][W][C] */
+    const float* x;      int32_t ldx;       /* [T][H][W] rows */
+    const float* h;      int32_t ldh;       /* [T][H][W] rows: the history h_0 .. h_{T-1} (frame t reads h_{t-1}) */
+    const float* h0;     int32_t ldh0;      /* [H][W] rows */
+    float* ws;  int64_t ws_bytes;
+    float* out;                             /* [C][2C][3][3] */
+    int32_t T, H, W, C, accumulate;
+} uavsal_twa_wgrad_desc;
+
+typedef struct uavsal_dec_bwd_desc {
+    const float* gy;  int64_t gy_img_pitch, gy_row_pitch, gy_col_pitch;
+    const float* y;
+    const float* e;  const float* d;
+    const float* s1;  const float* wd9;  const float* s2;  const float* w3;  const float* s3;   /* s3: one float */
+    float* ge;
+    int32_t n_img, H, W, C;
+} uavsal_dec_bwd_desc;
+
+int uavsal_twa_gate_bwd(const uavsal_twa_gate_desc* d, uavsal_stream_t stream);
+int64_t uavsal_twa_wgrad_workspace_bytes(const uavsal_twa_wgrad_desc* d);
+int uavsal_twa_wgrad_shares(const uavsal_twa_wgrad_desc* d);   /* K shares per tile of that call (no launch) */
+int uavsal_twa_wgrad(const uavsal_twa_wgrad_desc* d, uavsal_stream_t stream);
+int uavsal_dec_bwd(const uavsal_dec_bwd_desc* d, uavsal_stream_t stream);
+int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd (uavsal_sizeof_desc's list is closed at 20) */
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 

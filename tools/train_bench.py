@@ -1,0 +1,153 @@
+"""What one fine-tuning step of the ConvTWA recurrence costs on the device, phase by phase.  Prints one JSON line.
+
+At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_size 4 x time_dims 5) and of T = 5 frames:
+  forward      `model(x, cb, None, taps=...)`, the plan `train.recurrence_step` runs (it keeps prefuse and rnn);
+  dec_grad     `train.decoder_input_grad`: e and d recomputed, `uavsal_dec_bwd`, the 1536 -> 256 GEMM;
+  twa_backward the whole of `train.twa_backward` without the input gradient (what `recurrence_step` runs);
+  wgrad        `uavsal_twa_wgrad` alone (two launches), with its TFLOP/s (2 * 256 * 4608 * T*45*80 FLOP) against the
+               157.3 TFLOP/s fp32 MFMA peak; bptt = twa_backward - wgrad: the two gate convs, and per step the gate kernel and
+               the 3x3 conv with flip(W_h)^T;
+  step         `train.recurrence_step` as a whole (forward, criterion, its gradient, the two above);
+  refresh      `model.refresh_weights(model.rnn)` after an in-place edit of the weight (host repacking and uploads);
+  eager        torch autograd of the restated recurrence + decoder (float32, eval BatchNorm folded) on the same device,
+               forward + backward from the same inputs, if torch's conv kernels run there.
+Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
+
+Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from iip_uavsal_saliency_amd import UAVSal, losses, ops, synth, train      # noqa: E402
+from iip_uavsal_saliency_amd import _lib as L                              # noqa: E402
+from iip_uavsal_saliency_amd import packing as P                           # noqa: E402
+from iip_uavsal_saliency_amd.weights import WeightCache                    # noqa: E402
+
+PEAK_TFLOPS = 157.3
+
+
+def per_call(fn, iters):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters
+
+
+def best_of(fn, iters, repeats):
+    per_call(fn, 2)
+    return min(per_call(fn, iters) for _ in range(repeats))
+
+
+def eager_step(model, x_seq, h0, gy):
+    """the restated recurrence + decoder under torch autograd: returns a function that runs forward + backward"""
+    rc = model.rnn.cell_list[0].rnn_conv
+    seq = model.conv_out_st.conv
+    dev = x_seq.device
+    fold = [tuple(t.to(dev).view(1, -1, 1, 1) for t in P.fold_bn(bn)) for bn in (seq[0][1], seq[1][1], seq[3])]
+    w1, wd, w3 = seq[0][0].weight.detach(), seq[1][0].weight.detach(), seq[2].weight.detach()
+
+    def run():
+        w = rc.weight.detach().clone().requires_grad_(True)
+        h, hs = h0, []
+        for t in range(x_seq.shape[0]):
+            i = torch.sigmoid(F.conv2d(torch.cat([x_seq[t:t + 1], h], 1), w, padding=1))
+            h = i * x_seq[t:t + 1] + (1 - i) * h
+            hs.append(h)
+        hh = torch.cat(hs, 0)
+        e = (F.conv2d(hh, w1) * fold[0][0] + fold[0][1]).clamp(0, 6)
+        d = (F.conv2d(e, wd, padding=1, groups=wd.shape[0]) * fold[1][0] + fold[1][1]).clamp(0, 6)
+        y = torch.sigmoid(F.conv2d(d, w3) * fold[2][0] + fold[2][1])
+        return torch.autograd.grad(y, w, gy)[0]
+    return run
+
+
+def bench(T, iters, repeats, dev, skip_eager):
+    H, W, h, w = 360, 640, 45, 80
+    m = UAVSal(time_dims=5)
+    synth.load_synth_weights(m, 0)
+    m = m.to(dev).eval()
+    x = torch.from_numpy(synth.normalize_frames(synth.synth_frames_u8(T, H, W, 3))).to(dev)
+    gp = torch.from_numpy(synth.gauss_priors(1, h, w)[0]).to(dev)
+    op_ = torch.from_numpy(synth.ob_priors(1, h, w)[0]).to(dev)
+    cb = [gp.unsqueeze(0).expand(T, -1, -1, -1), op_.unsqueeze(0).expand(T, -1, -1, -1)]
+    loc = synth.synth_fix_points(T, 360, 640, 20, 4)
+    fmap = np.rint(synth.synth_fix_maps(loc, 8.0) * 255).astype(np.uint8)
+    y_gaze, _ = ops.prepare_gaze(torch.from_numpy(fmap).to(dev), torch.from_numpy(loc).to(dev), h, w)
+    rc = m.rnn.cell_list[0].rnn_conv
+    cache = WeightCache(torch.device(dev), m._wshared.setdefault(str(torch.device(dev)), {}))
+    taps = {}
+    out, _ = m(x, cb, None, taps=taps)
+    cl = torch.channels_last
+    x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
+    pred = out.detach().requires_grad_(True)
+    g_y = torch.autograd.grad(losses.loss_fu(pred, y_gaze), pred)[0]
+    grad_h = train.decoder_input_grad(m.conv_out_st, h_seq, g_y, cache=cache, y=out)
+    parts = {}
+    train.twa_backward(x_seq, h_seq, None, rc.weight.detach(), grad_h, cache=cache, module=rc, parts=parts)
+    dz = parts["dz"]
+    xn, hn = x_seq.permute(0, 2, 3, 1), h_seq.permute(0, 2, 3, 1)
+    h0n = torch.zeros((1, h, w, 256), device=dev)
+    gw = torch.empty_like(rc.weight)
+
+    def refresh():
+        with torch.no_grad():
+            rc.weight.mul_(1.0)
+        m.refresh_weights(m.rnn)
+
+    def step():
+        rc.weight.grad = None
+        train.recurrence_step(m, x, cb, None, y_gaze)
+    res = {"T": T}
+    cases = {"forward": lambda: m(x, cb, None, taps={}),
+             "dec_grad": lambda: train.decoder_input_grad(m.conv_out_st, h_seq, g_y, cache=cache, y=out),
+             "twa_backward": lambda: train.twa_backward(x_seq, h_seq, None, rc.weight.detach(), grad_h, out=gw, cache=cache, module=rc),
+             "wgrad": lambda: train.twa_wgrad(dz, xn, hn, h0n, out=gw),
+             "step": step, "refresh": refresh}
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    res["bptt_ms"] = res["twa_backward_ms"] - res["wgrad_ms"]
+    flop = 2.0 * 256 * 4608 * T * h * w
+    res["wgrad_gflop"] = flop / 1e9
+    d = L.TwaWgradDesc()
+    d.T, d.H, d.W, d.C = T, h, w, 256
+    res["wgrad_shares"] = int(L.load().uavsal_twa_wgrad_shares(C.byref(d)))
+    res["wgrad_tflops"] = flop / (res["wgrad_ms"] * 1e-3) / 1e12
+    res["wgrad_of_peak"] = res["wgrad_tflops"] / PEAK_TFLOPS
+    if not skip_eager:
+        try:
+            run = eager_step(m, taps["prefuse"], torch.zeros((1, 256, h, w), device=dev), g_y)
+            ge = run()
+            res["eager_fwdbwd_ms"] = 1e3 * best_of(run, max(1, iters // 2), repeats)
+            train.twa_wgrad(dz, xn, hn, h0n, out=gw)
+            res["eager_vs_hip_grad_rel_l2"] = float((ge - gw).norm() / ge.norm())
+        except RuntimeError as e:                     # torch's own conv kernels may not exist for this device
+            res["eager_error"] = str(e).splitlines()[0][:200]
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--skip-eager", action="store_true")
+    a = ap.parse_args()
+    dev = "cuda:0"
+    out = {"device": torch.cuda.get_device_name(0), "map": [45, 80], "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager) for T in (20, 5)]}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
