@@ -401,7 +401,7 @@ def test_arena_layout_of_the_real_plans():
         assert st["live_bound_mb"] <= st["arena_mb"] <= cap_mb and st["arena_mb"] < 0.3 * st["unshared_mb"], st
         # lanes: what the temporal branch of STBlock 0 touches on lane 6 is live from its fork to its join
         names = [o["name"] for o in e.ops_meta]
-        if C * T > 8:        # (the temporal branch has its side lane from nine frames up: Engine._build, the ST blocks)
+        if C * T > 8:        # (the temporal branch has its side lane from nine frames up: topology.record_forward, the ST blocks)
             fork = max(i for i, nm in enumerate(names) if nm == "fork6" and i < names.index("st0.sub.pw"))
             join = min(i for i, nm in enumerate(names) if nm == "join6" and i > names.index("st0.sub.pw"))
             te1 = [t for t in lay if t[0] == "st0_te1"][0]           # (written on lane 6, read on the main lane after the join)

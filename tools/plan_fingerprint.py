@@ -4,10 +4,12 @@
 Plans are recorded on the CPU (tests/mock_plan.py: real shape queries, stubbed recording, nothing launched).  Per configuration
 the document holds `ops_meta`, `op_args` (torch modules as their dotted name inside the model, `OpView`s as their `repr`),
 `stage_ranges`, `arena_layout()`, `arena_stats`, every field of every descriptor handed to the plan in recording order (with
-the arguments of the guard / fork / join / set_lane / patch_ptr calls between them) and the weight cache as {key: sha256 of
-the tensor bytes, dtype and shape}.  Addresses differ from run to run, so a pointer field -- the `c_void_p` fields and arrays
+the arguments of the guard / fork / join / set_lane calls between them) and the weight cache as {key: sha256 of
+the tensor bytes, dtype and shape}.  Every configuration that is not `persistent` is also bound once to zero-filled host
+tensors of the plan's shapes, without a state (`Engine._bind_in_place`): `bind` holds the resulting patch_ptr calls as
+(op, slot, pointer), sorted by (op, slot) -- their order within a call means nothing to the native plan.  Addresses differ from run to run, so a pointer field -- the `c_void_p` fields and arrays
 of `_lib`'s structures -- is written as (owner, byte offset): the arena, a weight-cache key, a shadow or resident buffer's name,
-a scratch key, a staging tensor's name, a lane's stream-K workspace or the mock's error word.  A non-null pointer that
+a scratch key, a staging tensor's name, a bound tensor's name, a lane's stream-K workspace or the mock's error word.  A non-null pointer that
 resolves to no owner is an error.
 
 Configurations: the variants of tests/test_host_cpu.py::test_recording_pass_addresses_every_activation_inside_its_live_range
@@ -33,6 +35,7 @@ from iip_uavsal_saliency_amd import UAVSal
 from iip_uavsal_saliency_amd.engine import OpView
 
 STAGING = ("x_in", "cb0_in", "cb1_in", "state_in", "zero_state", "state_out", "cstate_in", "cstate_out", "out", "logits")
+BOUND = ("x", "cb0", "cb1", "out", "state_in", "state_out", "cstate_in", "cstate_out")
 ERR_WORD = 4096                     # mock_plan.MockLib: uavsal_plan_error_word
 
 
@@ -147,19 +150,28 @@ def fingerprint(model, store, eng, mock):
         own.add("stage:" + name, getattr(eng, name, None))
     for lane, t in eng._sk_ws.items():
         own.add("streamk:%d" % lane, t)
+    if not eng.persistent:
+        x, cb0, cb1 = (torch.zeros(t.shape, dtype=t.dtype) for t in (eng.x_in, eng.cb0_in, eng.cb1_in))
+        eng._bind_in_place(x, cb0, cb1, None, None, eng.lstm)
+        for name in BOUND:
+            try:
+                own.add("bound:" + name, eng.bound(name))
+            except KeyError:
+                pass
     own.freeze()
-    calls = []
+    calls, bind = [], []
     for name, a in mock.calls:
         if isinstance(a, C.Structure):
             calls.append([name, desc_fields(a, own)])
         elif name == "uavsal_plan_add_guard":
             calls.append([name, [own(x) if i % 2 == 0 else x for i, x in enumerate(a)]])
         elif name == "uavsal_plan_patch_ptr":
-            calls.append([name, [a[0], a[1], own(a[2])]])
+            bind.append([a[0], a[1], own(a[2])])
         else:
             calls.append([name, list(a)])
     return dict(ops_meta=canon(eng.ops_meta, names), op_args=canon(eng.op_args, names), stage_ranges=canon(eng.stage_ranges, names),
                 arena_layout=canon(eng.arena_layout(), names), arena_stats=canon(eng.arena_stats, names), calls=calls,
+                bind=sorted(bind, key=lambda b: b[:2]),
                 weights=dict(sorted(weights.items())))
 
 
