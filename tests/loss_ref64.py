@@ -23,6 +23,11 @@ LOSS_FU, LOSS_KL = (10.0, -2.0, -1.0), (10.0, 0.0, 0.0)
 
 # (name, h, w, B, seed): the random cases of the goldens
 RANDOM_CASES = [("45x80_B20", 45, 80, 20, 11), ("90x160_B8", 90, 160, 8, 12)]
+# More than 64 frames, against this restatement only (no goldens): one wave of csrc/loss.hip averages the per-frame records,
+# lane i taking frames i, i + 64, ...  12x20_B65: the vector path (240 pixels), ONE frame in the second stride; 9x15_B130: the
+# scalar path (135 pixels), three strides, the last one two lanes wide.  The default validation / fine-tuning group is 80 frames.
+STRIDE_CASES = [("12x20_B65", 12, 20, 65, 21), ("9x15_B130", 9, 15, 130, 22)]
+MEAN_LANES = 64
 EDGE_SHAPE = (6, 45, 80)
 EDGE_CONSTANT = {3: 0.0, 4: 0.5, 5: 1.0}          # frame -> its constant prediction
 EDGE_ZERO_MAP, EDGE_SINGLE_FIX = 1, 2

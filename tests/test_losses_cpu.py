@@ -97,6 +97,29 @@ def test_restatement_reproduces_the_reference_float64(golden_dir, name, h, w, B,
     assert rel.max() <= 1e-12
 
 
+def test_mean_of_the_first_64_frames_is_not_the_mean():
+    """The condition of the GPU test's wrong reference at B = 65, from the restatement alone: every value averaged over the first
+    64 frames only lies at least 4 fp32 ulps from the value over all 65, so a device value within one ulp of the right one
+    cannot also be within one ulp of the wrong one.  The cases beyond 64 frames are what their names say."""
+    assert [c[:4] for c in R.STRIDE_CASES] == [("12x20_B65", 12, 20, 65), ("9x15_B130", 9, 15, 130)]
+    assert (12 * 20) % 4 == 0 and (9 * 15) % 4 != 0                          # the vector and the scalar path of csrc/loss.hip
+    assert not {c[0] for c in R.STRIDE_CASES} & {c[0] for c in R.RANDOM_CASES}
+    name, h, w, B, seed = R.STRIDE_CASES[0]
+    y_pred, y_true = R.random_inputs(h, w, B, seed)
+    n = R.MEAN_LANES
+    assert B == n + 1
+    for weights, names in ((R.LOSS_FU, VALUES[:4]), (R.LOSS_KL, ("loss_kl",))):
+        right, wrong = R.loss(y_pred, y_true, weights)[-len(names):], R.loss(y_pred[:n], y_true[:n], weights)[-len(names):]
+        for k, a, b in zip(names, right, wrong):
+            ulp = float(np.spacing(np.float32(abs(a))))
+            print("%s %s: all %d frames %.17g, the first %d %.17g: %.0f ulps apart" % (name, k, B, a, n, b, abs(a - b) / ulp))
+            assert abs(a - b) >= 4 * ulp, k
+    for name, h, w, B, seed in R.STRIDE_CASES:                                # no degenerate frame in either case
+        kl, cc, nss = R.frame_metrics(*R.random_inputs(h, w, B, seed))
+        assert np.isfinite(kl).all() and np.isfinite(cc).all() and np.isfinite(nss).all() and len(kl) == B
+        assert np.isfinite(R.loss_grad(*R.random_inputs(h, w, B, seed))).all()
+
+
 def test_restatement_reproduces_the_reference_on_the_edge_batch(golden_dir):
     g = _golden(golden_dir, "loss_edge_45x80.npz")
     y_pred, y_true = R.edge_inputs()

@@ -5,7 +5,12 @@ Tolerances.  The device accumulates in double and rounds once, so against the fl
 the final rounding: one fp32 ulp of the value; a gradient element by one fp32 ulp of the frame's largest gradient
 magnitude.  Against the reference's fp32 results the generator recorded, per case, the gap between the reference's fp32
 and float64 runs -- the reference's own summation error --: twice that gap (another torch build sums in another order)
-plus the ulp above.  Integer results (the ground truth) and repeated runs are compared for equality."""
+plus the ulp above.  Integer results (the ground truth) and repeated runs are compared for equality.
+
+Batches: loss_ref64.RANDOM_CASES (B = 20 and 8, with goldens) keep the mean over the frames -- one wave, lane i takes frames
+i, i + 64, ... -- inside its first stride.  loss_ref64.STRIDE_CASES go beyond it, against the restatement with the same
+tolerances: 12x20_B65 (vector path, one frame in the second stride) and 9x15_B130 (scalar path, three strides, the last two
+lanes wide); at B = 65 the mean over the first 64 frames only -- the loop without its second stride -- must be rejected."""
 import os
 
 import numpy as np
@@ -107,7 +112,7 @@ def test_prepare_gaze_full_size_sources():
 
 # ------------------------------------------------------------------------------------------------ criterion
 
-@pytest.mark.parametrize("name,h,w,B,seed", R.RANDOM_CASES)
+@pytest.mark.parametrize("name,h,w,B,seed", R.RANDOM_CASES + R.STRIDE_CASES)
 def test_forward_and_gradient_against_the_restatement(name, h, w, B, seed):
     y_pred, y_true = R.random_inputs(h, w, B, seed)
     got = _device_values(y_pred, y_true)
@@ -180,6 +185,30 @@ def test_two_runs_are_bit_identical_and_autograd_is_the_direct_call():
     gr = _device_grad(yp, yt, losses.loss_fu).astype(np.float64)
     ref = R.loss_grad(yp, yt)
     assert (np.abs(gr - ref) <= _ulp(_frame_max(ref))).all()
+
+
+def test_mean_beyond_one_stride_of_the_wave():
+    """B = 65: two runs give equal bits, and the mean the loop would give without its second stride (the first 64 frames
+    only) is more than the value's one ulp away from every device value -- tests/test_losses_cpu.py holds that wrong
+    reference at least 4 ulps from the right one."""
+    name, h, w, B, seed = R.STRIDE_CASES[0]
+    assert B == R.MEAN_LANES + 1
+    y_pred, y_true = R.random_inputs(h, w, B, seed)
+    p, t = torch.from_numpy(y_pred).to(DEV), torch.from_numpy(y_true).to(DEV)
+    out1, stats1 = losses.loss_components(p, t)
+    out2, stats2 = losses.loss_components(p, t)
+    assert torch.equal(out1.view(torch.int32), out2.view(torch.int32)) and torch.equal(stats1.view(torch.int64), stats2.view(torch.int64))
+    one = torch.ones((), device=DEV)
+    assert torch.equal(losses.loss_grad(p, t, stats1, one).view(torch.int32), losses.loss_grad(p, t, stats2, one).view(torch.int32))
+    got = _device_values(y_pred, y_true)
+    assert [got[k] for k in VALUES[:4]] == out1.cpu().tolist()
+    n = R.MEAN_LANES
+    wrong = dict(zip(VALUES[:4], R.loss(y_pred[:n], y_true[:n])))
+    wrong["loss_kl"] = R.loss(y_pred[:n], y_true[:n], R.LOSS_KL)[3]
+    for k in VALUES:
+        ratio = abs(got[k] - wrong[k]) / float(_ulp(wrong[k]))
+        print("%s %s: device %.9g, mean of the first %d frames %.17g: %.0f ulps apart" % (name, k, got[k], n, wrong[k], ratio))
+        assert ratio > 1.0, k
 
 
 def test_degenerate_frames(golden_dir):

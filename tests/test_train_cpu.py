@@ -1,6 +1,9 @@
 """The trainable slice without a GPU: the C ABI of csrc/train.hip, the float64 restatement (tests/train_ref64.py) against the
 reference's recorded autograd results (tests/golden/train_*.npz), the driver's group logic, argument errors, and the
-condition under which the decoder's end-to-end GPU test is meaningful (asserted on the float64 reference alone)."""
+conditions under which two GPU tests are meaningful, asserted on the float64 reference alone: the decoder's end-to-end test,
+and the weight gradient's wrong references at the shapes with a real K split (train_ref64.WGRAD_SPLIT_SHAPES).  The K split
+itself is held to train_ref64.wgrad_partition: the exact share count of every tested shape and of the two real calls,
+(20,45,80) and (80,45,80)."""
 import ctypes as C
 import math
 import os
@@ -45,6 +48,53 @@ def test_wgrad_split_keeps_every_chain_short(lib):
         assert lib.uavsal_twa_wgrad_workspace_bytes(C.byref(d)) == shares * 256 * 9 * 512 * 4
     d.T, d.H, d.W = 20, 45, 80
     assert lib.uavsal_twa_wgrad_shares(C.byref(d)) == 12                  # 71 chunks, 6 per share
+
+
+def test_wgrad_share_count_is_the_restated_partition(lib):
+    """`uavsal_twa_wgrad_shares` against train_ref64.wgrad_partition, and the restated shares tile [0, K)."""
+    table = {(20, 27, 27): (2, 8, 244), (9, 45, 80): (3, 11, 1680), (5, 45, 80): (2, 9, 1616),       # (cps, shares, last share)
+             (20, 45, 80): (6, 12, 4416), (80, 45, 80): (21, 14, 8448)}
+    for shape in R.SHAPES + R.WGRAD_SPLIT_SHAPES + [(5, 45, 80), (20, 45, 80), (80, 45, 80)]:
+        T, H, W = shape
+        K = T * H * W
+        cps, shares, spans = R.wgrad_partition(T, H, W)
+        d = _lib.TwaWgradDesc()
+        d.T, d.H, d.W, d.C = T, H, W, 256
+        assert lib.uavsal_twa_wgrad_shares(C.byref(d)) == shares == len(spans), shape
+        assert lib.uavsal_twa_wgrad_workspace_bytes(C.byref(d)) == shares * 256 * 9 * 512 * 4
+        assert spans[0][0] == 0 and spans[-1][1] == K
+        assert all(a[1] == b[0] for a, b in zip(spans, spans[1:]))             # no gap, no overlap
+        assert all(p1 - p0 == cps * _lib.WGRAD_CHAIN for p0, p1 in spans[:-1])
+        assert 0 < spans[-1][1] - spans[-1][0] <= cps * _lib.WGRAD_CHAIN
+        if shape in R.SHAPES:
+            assert cps == 1                                                    # why WGRAD_SPLIT_SHAPES exist
+        if shape in table:
+            assert (cps, shares, spans[-1][1] - spans[-1][0]) == table[shape], shape
+    assert R.WGRAD_CHAIN == _lib.WGRAD_CHAIN
+
+
+@pytest.mark.parametrize("shape", R.WGRAD_SPLIT_SHAPES, ids=R.name)
+def test_wgrad_wrong_references_lie_outside_the_bound(shape):
+    """The GPU test rejects the kernel's result against four wrong references by the bound it passes against the right one.
+    That says something only if each wrong reference lies well outside the bound: at least 4 bounds from the right one on
+    some element, so that the kernel's own error of at most 1 bound cannot bring it back inside.  From the float64 reference
+    alone, on the GPU test's inputs, over 16 of the 256 output channels (the GPU test takes the maximum over all)."""
+    T, H, W = shape
+    w = R.wgrad_wrong_weights(T, H, W)
+    cps, shares, spans = R.wgrad_partition(T, H, W)
+    gone = lambda k: int((w[k] == 0).sum())                                   # noqa: E731
+    assert gone("last_share") == spans[-1][1] - spans[-1][0] and 0 < gone("tail_step") < R.WGRAD_KSTEP
+    assert int((w["chain_twice"] == 2).sum()) == R.WGRAD_CHAIN * sum(b - a > R.WGRAD_CHAIN for a, b in spans) > 0
+    i64 = R.to64(R.wgrad_inputs(shape))
+    assert float(i64["h0"].abs().max()) > 0
+    dz = i64["dz"][:, ::16]
+    right, bound = R.wgrad_ref(dz, i64["x"], i64["hist"], i64["h0"])
+    wrong = R.wgrad_wrong_refs(dz, i64["x"], i64["hist"], i64["h0"])
+    assert sorted(wrong) == sorted(R.WGRAD_WRONG)
+    for k in R.WGRAD_WRONG:
+        ratio = float(((wrong[k] - right).abs() / bound).max())
+        print("%s %s: the wrong reference is up to %.1f bounds from the right one" % (R.name(shape), k, ratio))
+        assert ratio >= 4.0, k
 
 
 def test_argument_validation_without_gpu(lib):

@@ -2,6 +2,13 @@
 runs on the device in torch float64, and the reference's recorded autograd results (tests/golden/train_*.npz).
 Shapes (T, H, W): (3,5,7) 35 pixels, below one tile and odd; (1,9,16) one step, no carry; (5,12,20) a non-zero h0;
 (2,45,80) the real map: 3600 rows are no multiple of 128, K is split into several shares and over both frames.
+In all four a workgroup of the weight gradient owns ONE chunk of 1024 pixels (cps = 1).  The weight gradient alone also runs
+at train_ref64.WGRAD_SPLIT_SHAPES: (20,27,27), cps = 2, 8 shares -- a chain ends in the middle of a share, the second
+register tile matters, the last share is 244 pixels, frames straddle every K step and chunk border, h0 and 19 history
+frames --, and (9,45,80), cps = 3, 11 shares -- the last share owns fewer chunks than the others and ends in a partial chain
+with a half-filled K step.  There the kernel's result must also be REJECTED, by the bound it passes, against four wrong
+references (train_ref64.wgrad_wrong_refs; the CPU test holds each at least 4 bounds away).  The step from a carried state
+runs at 360x640 with five frames: the 45x80 map, cps = 2, 9 shares, the last one 1024 + 592 pixels.
 Bounds: train_ref64's docstring.  Teacher-forced tests hand every kernel the float64 reference's inputs rounded to fp32."""
 import math
 import os
@@ -43,7 +50,7 @@ def _nchw64(t_nhwc):
 def _check(got, want, bound, what):
     err = (got.double() - want).abs()
     worst = float((err / bound.clamp_min(1e-300)).max())
-    print("%s: worst error / bound %.3f (max |err| %.3e, max |ref| %.3e)" % (what, worst, float(err.max()), float(want.abs().max())))
+    print("%s: worst error / bound %.4f (max |err| %.3e, max |ref| %.3e)" % (what, worst, float(err.max()), float(want.abs().max())))
     assert torch.isfinite(got).all() and bool((err <= bound).all()), what
 
 
@@ -82,10 +89,28 @@ def test_gate_kernel(shape, with_carry):
         _check(_nchw64(got), y, R.EPS * E, "gate %s %s" % (name, R.name(shape)))
 
 
-@pytest.mark.parametrize("shape", R.SHAPES, ids=SHAPE_IDS)
+@pytest.mark.parametrize("shape", R.SHAPES + R.WGRAD_SPLIT_SHAPES, ids=R.name)
 def test_wgrad_kernel(shape):
     want, bound = _wgrad_ref(shape)
     _check(_wgrad(shape), want, bound, "wgrad " + R.name(shape))
+
+
+@pytest.mark.parametrize("shape", R.WGRAD_SPLIT_SHAPES, ids=R.name)
+def test_wgrad_kernel_is_rejected_against_wrong_partitions(shape):
+    """The bound that accepts the kernel against the right reference rejects it against each wrong one: a last share left
+    out, a chain counted twice, the final partial K step left out, frame 0 paired with zeros instead of h0."""
+    t = _teacher(shape)
+    inp = R.wgrad_inputs(shape)
+    assert all(torch.equal(t[k].cpu(), torch.as_tensor(inp[k])) for k in ("dz", "x", "hist", "h0"))      # the CPU test's inputs
+    want, bound = _wgrad_ref(shape)
+    got = _wgrad(shape).double()
+    assert bool(((got - want).abs() <= bound).all())
+    wrong = R.wgrad_wrong_refs(t["dz"].double(), t["x"].double(), t["hist"].double(), t["h0"].double())
+    assert sorted(wrong) == sorted(R.WGRAD_WRONG)
+    for k in R.WGRAD_WRONG:
+        ratio = float(((got - wrong[k]).abs() / bound.clamp_min(1e-300)).max())
+        print("wgrad %s against %s: worst error / bound %.1f" % (R.name(shape), k, ratio))
+        assert ratio > 1.0, k
 
 
 @pytest.mark.parametrize("shape", R.SHAPES, ids=SHAPE_IDS)
@@ -146,6 +171,37 @@ def test_wgrad_border_taps():
     want, bound = R.wgrad_ref(dz.double(), t["x"].double(), t["hist"].double(), t["h0"].double())
     assert float(want.abs().max()) > 0
     _check(got, want, bound, "wgrad corners")
+
+
+def test_wgrad_two_calls_equal_bits_with_two_chains_per_share():
+    first, again = _wgrad((20, 27, 27)), _wgrad((20, 27, 27))
+    assert torch.equal(first.view(torch.int32), again.view(torch.int32))
+
+
+def test_wgrad_reads_channel_slices_in_place():
+    """x, h and h0 as the channels 32..287 of 320-channel channels-last buffers (ldx = ldh = ldh0 = 320) whose other channels
+    hold a large constant: the same bits as from dense operands"""
+    shape = (3, 5, 7)
+    t = _teacher(shape)
+    dz = _nhwc(t["dz"]).contiguous()
+
+    def sliced(a):
+        big = torch.full((a.shape[0], 320) + tuple(a.shape[2:]), 1.0e6, device=DEV).contiguous(memory_format=torch.channels_last)
+        big[:, 32:288] = a
+        v = big[:, 32:288].permute(0, 2, 3, 1)
+        assert v.stride(2) == 320 and not v.is_contiguous() and torch.equal(v, _nhwc(a))
+        return v
+    dense = train.twa_wgrad(dz, _nhwc(t["x"]), _nhwc(t["hist"]), _nhwc(t["h0"]))
+    assert float(dense.abs().max()) > 0 and float(t["h0"].abs().max()) == 0
+    got = train.twa_wgrad(dz, sliced(t["x"]), sliced(t["hist"]), sliced(t["h0"]))
+    assert torch.equal(got.view(torch.int32), dense.view(torch.int32))
+    # h0 is zeros at this shape: once more with the carry as a non-zero h0
+    h0 = 100.0 * t["carry"]
+    dense = train.twa_wgrad(dz, _nhwc(t["x"]), _nhwc(t["hist"]), _nhwc(h0))
+    got = train.twa_wgrad(dz, sliced(t["x"]), sliced(t["hist"]), sliced(h0))
+    assert torch.equal(got.view(torch.int32), dense.view(torch.int32))
+    want, bound = R.wgrad_ref(t["dz"].double(), t["x"].double(), t["hist"].double(), h0.double())
+    _check(got, want, bound, "wgrad from channel slices, non-zero h0")
 
 
 @pytest.mark.parametrize("shape", [(3, 5, 7), (2, 45, 80)], ids=R.name)
@@ -318,6 +374,55 @@ def test_recurrence_step_sets_only_the_recurrence_gradient():
         m.refresh_weights(m.rnn)
     fd, an = (vals[0] - vals[1]) / (2 * s), float(g1.norm())
     print("directional derivative: finite difference %.6e, <grad, D> %.6e, step %.3e" % (fd, an, s))
+    assert abs(fd - an) <= 0.10 * abs(an)
+
+
+def test_recurrence_step_from_a_carried_state_at_the_real_map():
+    """360x640, time_dims 5, one group of five frames that starts from the state the forward left after five OTHER frames:
+    the 45x80 map, K = 18000, two chunks per share, 9 shares, the last one 1024 + 592 pixels.  in_state[0] is h0: the start of
+    the history, frame 0's partner in the weight gradient, and it arrives as the forward hands it over."""
+    from iip_uavsal_saliency_amd import UAVSal
+    HH, WW, T = 360, 640, 5
+    h, w = HH // 8, WW // 8
+    assert R.wgrad_partition(T, h, w)[:2] == (2, 9)
+    m = UAVSal(time_dims=T)
+    synth.load_synth_weights(m, 0)
+    m = m.to(DEV).eval()
+    frames = torch.from_numpy(synth.normalize_frames(synth.synth_frames_u8(2 * T, HH, WW, 3))).to(DEV)
+    cb = [torch.from_numpy(synth.gauss_priors(T, h, w)).to(DEV), torch.from_numpy(synth.ob_priors(T, h, w, seed=3)).to(DEV)]
+    loc = synth.synth_fix_points(T, 180, 320, 12, 4)
+    fmap = np.rint(synth.synth_fix_maps(loc, 6.0) * 255).astype(np.uint8)
+    y, has = ops.prepare_gaze(torch.from_numpy(fmap).to(DEV), torch.from_numpy(loc).to(DEV), h, w)
+    assert bool(has.all())
+    _, state = m(frames[:T], cb, None)
+    x = frames[T:]
+    state = [state[0].detach()]
+    assert tuple(state[0].shape) == (1, 256, h, w) and float(state[0].abs().max()) > 0
+    s0 = state[0].clone()
+    rc = m.rnn.cell_list[0].rnn_conv
+    loss, out, st = train.recurrence_step(m, x, cb, state, y)
+    assert torch.equal(state[0], s0)                                               # the step left the caller's state alone
+    ref_out, ref_st = m(x, cb, state)
+    assert torch.equal(out, ref_out) and torch.equal(st[0], ref_st[0]) and not st[0].requires_grad
+    assert loss.item() == losses.loss_fu(ref_out, y).item()
+    assert not torch.equal(ref_out, m(x, cb, None)[0])                             # the state matters to this group
+    assert [k for k, p in m.named_parameters() if p.grad is not None] == ["rnn.cell_list.0.rnn_conv.weight"]
+    g1 = rc.weight.grad.clone()
+    assert torch.isfinite(g1).all() and float(g1.abs().max()) > 0
+    # the directional derivative of test_recurrence_step_sets_only_the_recurrence_gradient, from the same in_state
+    with torch.no_grad():
+        D = g1 / g1.norm()
+        w0 = rc.weight.detach().clone()
+        s = 2e-2 / float(g1.norm())
+        vals = []
+        for sign in (1.0, -1.0):
+            rc.weight.copy_(w0 + sign * s * D)
+            m.refresh_weights(m.rnn)
+            vals.append(losses.loss_fu(m(x, cb, state)[0], y).item())
+        rc.weight.copy_(w0)
+        m.refresh_weights(m.rnn)
+    fd, an = (vals[0] - vals[1]) / (2 * s), float(g1.norm())
+    print("carried state, 45x80 map: finite difference %.6e, <grad, D> %.6e, step %.3e" % (fd, an, s))
     assert abs(fd - an) <= 0.10 * abs(an)
 
 

@@ -14,6 +14,17 @@ per-element bounds of the three kernels of csrc/train.hip in the convention of t
   |G| + |carry| and |x| + |h|; three products.  dz: [(|G| + |carry|) |x - h| + |g| (|x| + |h|)] i (1 - i) + 11 |dz|;
   carry' = g (1 - i): (|G| + |carry|) (1 - i) + 6 |carry'|; dx = g i the same with i.
 
+The weight gradient's K split (csrc/train.hip: chunks of 1024 pixels, `cps` whole chunks per workgroup = one share) is at
+its degenerate value cps = 1 in every shape of SHAPES.  WGRAD_SPLIT_SHAPES are the smallest shapes with a real partition,
+for the weight-gradient tests only (a 1536-channel float64 decoder at these sizes would gain nothing):
+* (20,27,27): K = 14580, 15 chunks, cps = 2, 8 shares, the last one 244 pixels (7.6 K steps).  The smallest K with cps = 2:
+  every share but the last ends one chain and starts another; frames of 729 pixels straddle every 32-pixel K step and every
+  chunk border; h0 and then 19 history frames.
+* (9,45,80): K = 32400, 32 chunks, cps = 3, 11 shares, the last one 1680 = 1024 + 656 pixels: fewer chunks than the others,
+  and it ends in a partial chain whose final K step is half filled.  The real map.
+`wgrad_partition` restates the split, `wgrad_wrong_refs` are the float64 results of four kernels that get it wrong (the
+idiom of plan_ref64's chan / row / bias); the CPU test holds each at least 4 bounds from the right one.
+
 Every function takes and returns float64 NCHW tensors on the device of its inputs."""
 import hashlib
 import math
@@ -28,8 +39,11 @@ C = 256
 HID = 1536
 SHAPES = [(3, 5, 7), (1, 9, 16), (5, 12, 20), (2, 45, 80)]      # (T, H, W)
 GOLDEN_SHAPES = [(3, 5, 7), (5, 12, 20)]
-H0_NONZERO = {(5, 12, 20), (2, 45, 80)}
-SEED = {(3, 5, 7): 101, (1, 9, 16): 102, (5, 12, 20): 103, (2, 45, 80): 104}
+WGRAD_SPLIT_SHAPES = [(20, 27, 27), (9, 45, 80)]                  # weight gradient only: cps = 2 and cps = 3 (docstring)
+H0_NONZERO = {(5, 12, 20), (2, 45, 80), (20, 27, 27), (9, 45, 80)}
+SEED = {(3, 5, 7): 101, (1, 9, 16): 102, (5, 12, 20): 103, (2, 45, 80): 104, (20, 27, 27): 105, (9, 45, 80): 106}
+WGRAD_CHAIN, WGRAD_KSTEP, WGRAD_TILES, WGRAD_TARGET_WGS = 1024, 32, 72, 1024      # csrc/train.hip, restated
+WGRAD_WRONG = ("last_share", "chain_twice", "tail_step", "frame0_h0")
 DW_SUBSET = (slice(None, None, 5), slice(None, None, 7))          # the strided part of dW the goldens keep: [52, 74, 3, 3]
 
 
@@ -174,15 +188,82 @@ def gate_ref(G, carry, z, x, hprev):
             "dx": (dx, (ga * i + 6 * dx.abs()) / 8)}
 
 
-def wgrad_ref(dz, x, hist, h0):
-    """uavsal_twa_wgrad: `(dW [256,512,3,3], bound)`; frame t pairs dz_t with cat[x_t, h_{t-1}], h_{-1} = h0."""
-    T, _, H, W = dz.shape
-    cat = torch.cat([x, torch.cat([h0, hist[:T - 1]], 0)], 1)
+def wgrad_inputs(shape):
+    """The weight-gradient tests' operands (float32 numpy): `dz`, `hist` of `teacher_inputs`, `x` of `twa_inputs`, and `h0` =
+    100 * `carry` (N(0, 1)) for the shapes in H0_NONZERO, zeros otherwise."""
+    t = teacher_inputs(shape)
+    h0 = np.float32(100.0) * t["carry"] if shape in H0_NONZERO else np.zeros_like(t["carry"])
+    return {"dz": t["dz"], "x": twa_inputs(shape)["x"], "hist": t["hist"], "h0": h0}
 
-    def run(a, b):
-        cols = F.unfold(b, 3, padding=1)                                   # [T, 512 * 9, HW], rows (ci, ky, kx)
-        return torch.einsum("tcp,tkp->ck", a.reshape(T, C, H * W), cols).reshape(C, 2 * C, 3, 3)
-    return run(dz, cat), LAMBDA * U * math.sqrt(T * H * W) * run(dz.abs(), cat.abs())
+
+def _wgrad_cat(x, hist, h0):
+    return torch.cat([x, torch.cat([h0, hist[:x.shape[0] - 1]], 0)], 1)
+
+
+def _wgrad_sum(a, b):
+    """sum over frames t and pixels p of a[t, co, p] * unfold3x3(b)[t, (ci, ky, kx), p] -> [co, ci, 3, 3]; a frame at a time, so
+    that only one frame's columns exist at once"""
+    T, co, H, W = a.shape
+    out = a.new_zeros((co, b.shape[1] * 9))
+    for t in range(T):
+        out += a[t].reshape(co, H * W) @ F.unfold(b[t:t + 1], 3, padding=1)[0].T       # rows (ci, ky, kx)
+    return out.reshape(co, b.shape[1], 3, 3)
+
+
+def wgrad_ref(dz, x, hist, h0):
+    """uavsal_twa_wgrad: `(dW [co,512,3,3], bound)`; frame t pairs dz_t with cat[x_t, h_{t-1}], h_{-1} = h0.  `dz` may hold
+    a slice of the 256 output channels."""
+    T, _, H, W = dz.shape
+    cat = _wgrad_cat(x, hist, h0)
+    return _wgrad_sum(dz, cat), LAMBDA * U * math.sqrt(T * H * W) * _wgrad_sum(dz.abs(), cat.abs())
+
+
+def wgrad_partition(T, H, W):
+    """The K split of uavsal_twa_wgrad, restated: `(cps, shares, [(p0, p1) per share])`.  The K = T H W pixels are cut into
+    chunks of 1024; with 72 tiles and a grid of about 1024 workgroups at most 14 workgroups share a tile; every share is the
+    same whole number `cps` of chunks, the smallest with which 14 shares cover all chunks, and the last share takes what is left."""
+    K = T * H * W
+    chunks = -(-K // WGRAD_CHAIN)
+    most = min(WGRAD_TARGET_WGS // WGRAD_TILES, chunks)
+    cps = next(c for c in range(1, chunks + 1) if c * most >= chunks)
+    span = cps * WGRAD_CHAIN
+    spans = [(p, min(p + span, K)) for p in range(0, K, span)]
+    return cps, len(spans), spans
+
+
+def wgrad_wrong_weights(T, H, W):
+    """How often three wrong kernels count each of the K pixels (`{name: float64 numpy [K]}`, 1 = right):
+    last_share   the last share's pixels are left out (a grid one share short, or a short last share dropped);
+    chain_twice  the first chunk of every share of more than one chunk counts twice: `acc` not cleared at the first chain end,
+                 so the second chain's tile still holds the first when it is added to `tot`;
+    tail_step    the pixels of the final, partial 32-pixel K step are left out (steps rounded down)."""
+    _, _, spans = wgrad_partition(T, H, W)
+    K = T * H * W
+    w = {k: np.ones(K) for k in WGRAD_WRONG[:3]}
+    p0, p1 = spans[-1]
+    w["last_share"][p0:p1] = 0
+    for a, b in spans:
+        if b - a > WGRAD_CHAIN:
+            w["chain_twice"][a:a + WGRAD_CHAIN] = 2
+    w["tail_step"][p0 + (p1 - p0 - 1) // WGRAD_KSTEP * WGRAD_KSTEP:p1] = 0
+    return w
+
+
+def wgrad_wrong_refs(dz, x, hist, h0):
+    """`{name: dW}` of the four wrong kernels of WGRAD_WRONG in float64: the three of `wgrad_wrong_weights` by weighting dz per
+    pixel (one pass over the unfolded columns for all three), and frame0_h0, frame 0 paired with zeros instead of h0: the
+    right sum less frame 0's terms in the history half of the input channels."""
+    T, co, H, W = dz.shape
+    cat = _wgrad_cat(x, hist, h0)
+    wg = wgrad_wrong_weights(T, H, W)
+    names = WGRAD_WRONG[:3]
+    scaled = [dz * torch.as_tensor(wg[k]).to(dz).view(T, 1, H, W) for k in names]
+    right, *wrong = _wgrad_sum(torch.cat([dz] + scaled, 1), cat).split(co, 0)
+    out = dict(zip(names, wrong))
+    f0 = right.clone()
+    f0[:, C:] -= _wgrad_sum(dz[:1], h0)
+    out["frame0_h0"] = f0
+    return out
 
 
 def input_grad_ref(dz, w_slice, res=None):
