@@ -240,6 +240,29 @@ class DecBwdDesc(C.Structure):
 
 TRAIN_DESC_TYPES = [TwaGateDesc, TwaWgradDesc, DecBwdDesc]        # sized by uavsal_train_sizeof_desc
 
+class PixGemmDesc(C.Structure):
+    _fields_ = [("a", _f), ("lda", C.c_int32), ("b", _f), ("ldb", C.c_int32), ("row_scale", _f),
+                ("w", _f), ("ldw", C.c_int32), ("rowdot", C.c_void_p), ("ws", _f), ("ws_bytes", C.c_int64),
+                ("out", _f), ("ldo", C.c_int32), ("K", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("accumulate", C.c_int32)]
+
+
+class DecSumsDesc(C.Structure):
+    _fields_ = [("gy", _f), ("gy_img_pitch", C.c_int64), ("gy_row_pitch", C.c_int64), ("gy_col_pitch", C.c_int64),
+                ("y", _f), ("e", _f), ("d", _f), ("ga", _f), ("w3", _f), ("s3", _f),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
+
+
+class DecFinishDesc(C.Structure):
+    _fields_ = [("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("rowdot", C.c_void_p)] + [(n, _f) for n in (
+        "wd", "w3", "s2", "s3", "r1", "mu1", "r2", "mu2", "r3", "mu3",
+        "g_gamma1", "g_beta1", "g_wd", "g_gamma2", "g_beta2", "g_w3", "g_gamma3", "g_beta3")] + [
+        ("C", C.c_int32), ("slabs", C.c_int32), ("accumulate", C.c_int32)]
+
+
+DEC_NSUM = 12                 # UAVSAL_DEC_NSUM: sums per channel in the workspace of uavsal_dec_sums (csrc/train_decoder.hip)
+TRAIN_DECODER_DESC_TYPES = [PixGemmDesc, DecSumsDesc, DecFinishDesc]        # sized by uavsal_train_decoder_sizeof_desc
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -277,6 +300,15 @@ SYMBOLS = [
     ("uavsal_twa_wgrad", C.c_int, [C.POINTER(TwaWgradDesc), C.c_void_p]),
     ("uavsal_dec_bwd", C.c_int, [C.POINTER(DecBwdDesc), C.c_void_p]),
     ("uavsal_train_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_pix_gemm_workspace_bytes", C.c_int64, [C.POINTER(PixGemmDesc)]),
+    ("uavsal_pix_gemm_shares", C.c_int, [C.POINTER(PixGemmDesc)]),
+    ("uavsal_pix_gemm", C.c_int, [C.POINTER(PixGemmDesc), C.c_void_p]),
+    ("uavsal_dec_sums_workspace_bytes", C.c_int64, [C.POINTER(DecSumsDesc)]),
+    ("uavsal_dec_sums_slabs", C.c_int, [C.POINTER(DecSumsDesc)]),
+    ("uavsal_dec_sums_slab_rows", C.c_int, [C.POINTER(DecSumsDesc)]),
+    ("uavsal_dec_sums", C.c_int, [C.POINTER(DecSumsDesc), C.c_void_p]),
+    ("uavsal_dec_finish", C.c_int, [C.POINTER(DecFinishDesc), C.c_void_p]),
+    ("uavsal_train_decoder_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -347,7 +379,8 @@ def load():
         if lib.uavsal_sizeof_desc(i) != C.sizeof(t):
             raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (
                 t.__name__, C.sizeof(t), lib.uavsal_sizeof_desc(i)))
-    for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES)):
+    for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES),
+                          (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

@@ -8,6 +8,8 @@
 // 2. uavsal_twa_wgrad: dW = dz^T . im2col(cat[x, h_prev]) with the reduction over pixels.  Both operands are pixel-major with
 //    the M (output channel) / N (input channel) index contiguous, which is what v_mfma_f32_32x32x2_f32 reads from LDS without
 //    a transpose: lane l takes A[m = l & 31][k = l >> 5] = dz[pixel k][co m] and B[k][n = l & 31] = cat[pixel k + tap][ci n].
+//    (The tile loop itself -- K steps, MFMA tiles, chains -- is csrc/pix_gemm_tile.h, shared with uavsal_pix_gemm of
+//    csrc/train_decoder.hip; this file supplies the operand loaders: the rows of dz, and b_row below.)
 //      tiles   128 (co) x 128 (ci of ONE tap; 256 % 128 == 0, so a tile reads x or the history, never both): 2 x 36 = 72.
 //      K step  32 pixels: 2 x 20 KB of LDS (32 rows of 128 floats padded to 160: the two half-waves of a ds_read_b32 hit disjoint banks),
 //              loaded as float4 by 256 threads, the next step's global loads in flight while the current one multiplies.
@@ -30,16 +32,14 @@
 //    patch, reads the 4 x 4 halo of d once, masks it, scales it by the per-pixel factor gy y (1 - y) s3 and correlates with the
 //    flipped depthwise taps.  Reads e and d, writes ge: 3 x 1536 channels x 4 bytes per pixel.
 #include "common.h"
+#include "pix_gemm_tile.h"
 
 namespace {
 
+using pixgemm::kTile; using pixgemm::kStep; using pixgemm::kRow; using pixgemm::kTargetWGs; using pixgemm::ld4;
 constexpr int kC = 256;                      // hidden channels: the only size the model builds
-constexpr int kTile = 128, kStep = 32, kRow = 160;
 constexpr int kNT = 9 * (2 * kC / kTile);    // 36 N tiles
 constexpr int kTiles = (kC / kTile) * kNT;   // 72
-constexpr int kTargetWGs = 1024;
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // ------------------------------------------------------------------------------------------------ gate
 struct GateK {
@@ -96,73 +96,26 @@ __device__ __forceinline__ const float* b_row(const WgK& k, long long g, int dy,
     return k.h + ((long long)(t - 1) * k.HW + q) * k.ldh + (ci0 - kC);
 }
 
-__global__ __launch_bounds__(256) void twa_wgrad_kernel(const WgK k) {
-    __shared__ float As[kStep * kRow];
-    __shared__ float Bs[kStep * kRow];
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void twa_wgrad_kernel(const WgK k) {
     const int tile = blockIdx.x, share = blockIdx.y;
     const int mt = tile % (kC / kTile), nt = tile / (kC / kTile);
     const int tap = nt / (2 * kC / kTile), ci0 = (nt % (2 * kC / kTile)) * kTile;
     const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-    const int lrow = tid >> 5, lc = (tid & 31) * 4;           // loader: row lrow + 8 i of the step, 4 floats at lc
+    const int lc = (threadIdx.x & 31) * 4;
 
     const long long p0 = (long long)share * k.cps * UAVSAL_WGRAD_CHAIN;
     long long p1 = p0 + (long long)k.cps * UAVSAL_WGRAD_CHAIN;
     if (p1 > k.K) p1 = k.K;
-    const int steps = (int)((p1 - p0 + kStep - 1) / kStep);
 
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x16 acc[2][2], tot[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; tot[i][j][r] = 0.f; }
-
-    f32x4 ra[4], rb[4];
-    auto fetch = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const long long g = p0 + (long long)s * kStep + lrow + 8 * i;
-            ra[i] = g < p1 ? ld4(k.dz + g * kC + mt * kTile + lc) : zero4;
-            const float* bp = g < p1 ? b_row(k, g, dy, dx, ci0) : nullptr;
-            rb[i] = bp ? ld4(bp + lc) : zero4;
-        }
-    };
-    if (steps > 0) fetch(0);
-    for (int s = 0; s < steps; ++s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<f32x4*>(&As[(lrow + 8 * i) * kRow + lc]) = ra[i];
-            *reinterpret_cast<f32x4*>(&Bs[(lrow + 8 * i) * kRow + lc]) = rb[i];
-        }
-        __syncthreads();
-        if (s + 1 < steps) fetch(s + 1);
-        const float* ap = As + (lane >> 5) * kRow + wm + (lane & 31);
-        const float* bp = Bs + (lane >> 5) * kRow + wn + (lane & 31);
-#pragma unroll
-        for (int kk = 0; kk < kStep / 2; ++kk) {
-            const float a0 = ap[kk * 2 * kRow], a1 = ap[kk * 2 * kRow + 32];
-            const float b0 = bp[kk * 2 * kRow], b1 = bp[kk * 2 * kRow + 32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if ((s + 1) % (UAVSAL_WGRAD_CHAIN / kStep) == 0 || s + 1 == steps) {      // the chain ends: at most 1024 products
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    tot[i][j] += acc[i][j];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-                }
-        }
-        __syncthreads();
-    }
+    f32x16 tot[2][2];
+    pixgemm::tile_loop(p0, p1,
+        [&](long long g) { return k.dz + g * kC + mt * kTile + lc; },
+        [&](long long g) {
+            const float* bp = b_row(k, g, dy, dx, ci0);
+            return bp ? bp + lc : nullptr;
+        }, tot);
     // D: column n = lane & 31, row m = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  ws [share][co][tap][ci]
     float* w = k.ws + (long long)share * (kC * 9 * 2 * kC);
 #pragma unroll
@@ -199,13 +152,7 @@ bool wgrad_plan(const uavsal_twa_wgrad_desc* d, WgK& k) {
     if (hw > 0x7fffffffll) return false;
     k.HW = (int)hw;
     k.K = hw * d->T;
-    const long long chunks = (k.K + UAVSAL_WGRAD_CHAIN - 1) / UAVSAL_WGRAD_CHAIN;
-    long long want = kTargetWGs / kTiles;                      // at most 14 shares
-    if (want > chunks) want = chunks;
-    const long long cps = (chunks + want - 1) / want;
-    const long long shares = (chunks + cps - 1) / cps;
-    if (cps > 0x7fffffffll / UAVSAL_WGRAD_CHAIN || shares > 65535) return false;
-    k.cps = (int)cps; k.shares = (int)shares;
+    if (!pixgemm::split(k.K, kTiles, k.cps, k.shares)) return false;      // at most 14 shares
     return true;
 }
 

@@ -1,0 +1,357 @@
+// Parameter gradients of the decoder conv_out_st (a dwBlock(256, 1) in eval mode + sigmoid): the three launches behind
+// train.decoder_param_grads (include/uavsal_hip.h states the formulas).
+//
+// 1. uavsal_pix_gemm: out[m][n] = row_scale[m] sum over pixels p of A[p][m] B[p][n].  The tile loop of uavsal_twa_wgrad
+//    (csrc/pix_gemm_tile.h: 128 x 128 tiles, 32-pixel K steps, chains of at most UAVSAL_WGRAD_CHAIN products, a second fp32
+//    register tile per share) with plain pitched rows as both operands.  K split by the same rule: (M / 128) (N / 128) tiles,
+//    about 1024 workgroups.  M = 1536, N = 256 is 24 tiles, at most 42 shares: T = 20 at 45 x 80 (71 chunks) runs 36 shares of
+//    2 chunks.  Partial tiles [share][M][N] -> a second launch, one workgroup per row m, sums the shares in share order in
+//    double, writes fl(row_scale G) (+ the old value) and, when asked, rowdot[m] = sum_n w[m][n] G[m][n] in double: each
+//    thread adds its columns n = tid, tid + 256, ... in that order and the 256 partial sums meet in a fixed tree in LDS.
+//
+// 2. uavsal_dec_sums: the channel sums S3, G3, S2, Gd, S1.  The access pattern of dec_bwd_kernel: a lane owns four channels
+//    (16-byte loads), a wave 256 channels.  A workgroup owns one channel group of 256 and a slab of whole picture rows (rows
+//    of all frames counted through: a slab may end one frame and begin the next; the halo of e is masked per pixel by the
+//    row inside ITS frame, so no frame sees its neighbour); its four waves take the slab's pixels in turn.  Per pixel a lane
+//    reads d and ga once and the 3 x 3 neighbourhood of e (neighbouring pixels re-read it from the cache), forms delta3 and
+//    delta2 in fp32 as dec_bwd_kernel does, and adds every product to a double accumulator: 4 channels x 12 sums per lane =
+//    96 VGPRs of accumulators.  At the end the four waves' sums meet in LDS in wave order and the workgroup writes ONE partial
+//    per sum to the workspace [slab][12][C] (+ S3 behind them, by channel group 0).  No atomics; the slab size depends on
+//    the shape alone, so two calls return the same bits.
+//
+// 3. uavsal_dec_finish: one launch, a thread per channel: sums the slabs in slab order in double and writes the eight small
+//    gradients, each rounded once.  Workgroup 0 also forms the two one-element gradients of the last BatchNorm, for which it
+//    sums G3 of ALL channels itself (sum_c w3[c] G3[c]: per thread its channels in order, then the fixed tree).
+#include "common.h"
+#include "pix_gemm_tile.h"
+
+namespace {
+
+using pixgemm::kTile; using pixgemm::kStep; using pixgemm::kRow; using pixgemm::ld4;
+constexpr int kGroup = 256;                  // channels of one workgroup of the sums: 64 lanes x 4
+constexpr int kNS = UAVSAL_DEC_NSUM;         // 12 sums per channel: G3, S2, Gd[9], S1
+constexpr int kSlabPixels = 512, kMaxSlabs = 256;
+
+// ------------------------------------------------------------------------------------------------ pixel GEMM
+struct PgK {
+    const float *a, *b, *row_scale, *w;
+    double* rowdot;
+    float *ws, *out;
+    long long K;
+    int lda, ldb, ldw, ldo, M, N, mt_n;
+    int cps, shares, accumulate;
+};
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void pix_gemm_kernel(const PgK k) {
+    const int tile = blockIdx.x, share = blockIdx.y;
+    const int mt = tile % k.mt_n, nt = tile / k.mt_n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
+    const int lc = (threadIdx.x & 31) * 4;
+
+    const long long p0 = (long long)share * k.cps * UAVSAL_WGRAD_CHAIN;
+    long long p1 = p0 + (long long)k.cps * UAVSAL_WGRAD_CHAIN;
+    if (p1 > k.K) p1 = k.K;
+
+    f32x16 tot[2][2];
+    const float* arow = k.a + mt * kTile + lc;
+    const float* brow = k.b + nt * kTile + lc;
+    pixgemm::tile_loop(p0, p1,
+        [&](long long g) { return arow + g * k.lda; },
+        [&](long long g) { return brow + g * k.ldb; }, tot);
+    float* w = k.ws + (long long)share * k.M * k.N;           // ws [share][m][n]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = mt * kTile + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int n = nt * kTile + wn + j * 32 + (lane & 31);
+                w[(long long)m * k.N + n] = tot[i][j][r];
+            }
+}
+
+// the 256 doubles of `red` summed in a fixed tree; the result in red[0]
+__device__ __forceinline__ void tree256(double* red) {
+    for (int s = 128; s > 0; s >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void pix_gemm_reduce_kernel(const PgK k) {
+    __shared__ double red[256];
+    const int m = blockIdx.x;
+    const double rs = k.row_scale ? (double)k.row_scale[m] : 1.0;
+    double dot = 0.0;
+    for (int n = threadIdx.x; n < k.N; n += 256) {
+        const float* p = k.ws + (long long)m * k.N + n;
+        double s = 0.0;
+        for (int sh = 0; sh < k.shares; ++sh) s += (double)p[(long long)sh * k.M * k.N];
+        if (k.rowdot) dot += (double)k.w[(long long)m * k.ldw + n] * s;
+        float* o = k.out + (long long)m * k.ldo + n;
+        double v = rs * s;
+        if (k.accumulate) v += (double)*o;
+        *o = (float)v;
+    }
+    if (!k.rowdot) return;                                     // uniform over the workgroup
+    red[threadIdx.x] = dot;
+    tree256(red);
+    if (threadIdx.x == 0) k.rowdot[m] = red[0];
+}
+
+bool pg_plan(const uavsal_pix_gemm_desc* d, PgK& k) {
+    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || (d->M % kTile) || (d->N % kTile)) return false;
+    if ((long long)d->M * d->N > 0x7fffffffll || (long long)(d->M / kTile) * (d->N / kTile) > 65535) return false;
+    k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = d->M / kTile;
+    return pixgemm::split(k.K, k.mt_n * (d->N / kTile), k.cps, k.shares);
+}
+
+// ------------------------------------------------------------------------------------------------ channel sums
+struct SumK {
+    const float *gy, *y, *e, *d, *ga, *w3, *s3;
+    double* ws;
+    long long gi, gr, gc;
+    long long rows;             // n_img * H
+    int H, W, C, slab_rows, slabs;
+};
+
+__global__ __launch_bounds__(256) void dec_sums_kernel(const SumK p) {
+    __shared__ double red[4 * kGroup];
+    const int slab = blockIdx.x, cg = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = cg * kGroup + lane * 4;
+    const long long r0 = (long long)slab * p.slab_rows;
+    long long r1 = r0 + p.slab_rows;
+    if (r1 > p.rows) r1 = p.rows;
+    const long long q0 = r0 * p.W, q1 = r1 * p.W;              // global pixels of the slab
+
+    const f32x4 w3 = ld4(p.w3 + c);
+    const float s3 = p.s3[0];
+    double acc[kNS][4];
+#pragma unroll
+    for (int j = 0; j < kNS; ++j)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[j][u] = 0.0;
+    double a3 = 0.0;
+
+    for (long long q = q0 + wave; q < q1; q += 4) {
+        const long long row = q / p.W;
+        const int x = (int)(q - row * p.W);
+        const int n = (int)(row / p.H);
+        const int yy = (int)(row - (long long)n * p.H);
+        const float yv = p.y[q];
+        const float d3 = p.gy[n * p.gi + yy * p.gr + x * p.gc] * yv * (1.f - yv);
+        const float a = d3 * s3;
+        const f32x4 dv = ld4(p.d + q * p.C + c);
+        const f32x4 gv = ld4(p.ga + q * p.C + c);
+        f32x4 d2;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) d2[u] = (dv[u] > 0.f && dv[u] < 6.f) ? a * w3[u] : 0.f;
+        a3 += (double)d3;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc[0][u] += (double)d3 * (double)dv[u];
+            acc[1][u] += (double)d2[u];
+            acc[11][u] += (double)gv[u];
+        }
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int iy = yy + ky - 1;
+            if (iy < 0 || iy >= p.H) continue;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ix = x + kx - 1;
+                if (ix < 0 || ix >= p.W) continue;
+                const f32x4 ev = ld4(p.e + (q + (long long)(ky - 1) * p.W + (kx - 1)) * p.C + c);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc[2 + ky * 3 + kx][u] += (double)d2[u] * (double)ev[u];
+            }
+        }
+    }
+    // the four waves meet in wave order; ws [slab][kNS][C] doubles, then S3 of the slab behind the kNS * C
+    double* o = p.ws + (long long)slab * ((long long)kNS * p.C + 1);
+#pragma unroll
+    for (int j = 0; j < kNS; ++j) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = acc[j][u];
+        __syncthreads();
+        const int t = threadIdx.x;
+        o[(long long)j * p.C + cg * kGroup + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
+        __syncthreads();
+    }
+    if (cg == 0) {
+        if (lane == 0) red[wave] = a3;
+        __syncthreads();
+        if (threadIdx.x == 0) o[(long long)kNS * p.C] = ((red[0] + red[1]) + red[2]) + red[3];
+    }
+}
+
+bool sums_plan(const uavsal_dec_sums_desc* d, SumK& k) {
+    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0 || (d->C % kGroup)) return false;
+    if ((long long)d->H * d->W > 0x7fffffffll || d->C / kGroup > 65535) return false;
+    k.H = d->H; k.W = d->W; k.C = d->C;
+    k.rows = (long long)d->n_img * d->H;
+    long long sr = (kSlabPixels + d->W - 1) / d->W;            // rows of about kSlabPixels pixels ...
+    const long long cap = (k.rows + kMaxSlabs - 1) / kMaxSlabs; // ... but at most kMaxSlabs slabs
+    if (sr < cap) sr = cap;
+    if (sr > 0x7fffffffll) return false;
+    k.slab_rows = (int)sr;
+    k.slabs = (int)((k.rows + sr - 1) / sr);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ finalise
+struct FinK {
+    const double *ws, *rowdot;
+    const float *wd, *w3, *s2, *s3, *r1, *mu1, *r2, *mu2, *r3, *mu3;
+    float *g_gamma1, *g_beta1, *g_wd, *g_gamma2, *g_beta2, *g_w3, *g_gamma3, *g_beta3;
+    int C, slabs, accumulate;
+};
+
+__device__ __forceinline__ void put(float* o, double v, int accumulate) {
+    if (accumulate) v += (double)*o;
+    *o = (float)v;
+}
+
+__global__ __launch_bounds__(256) void dec_finish_kernel(const FinK k) {
+    __shared__ double red[256];
+    const long long stride = (long long)kNS * k.C + 1;
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < k.C) {
+        double s[kNS];
+#pragma unroll
+        for (int j = 0; j < kNS; ++j) s[j] = 0.0;
+        for (int sl = 0; sl < k.slabs; ++sl) {
+            const double* q = k.ws + sl * stride + c;
+#pragma unroll
+            for (int j = 0; j < kNS; ++j) s[j] += q[(long long)j * k.C];
+        }
+        const double s2 = (double)k.s2[c];
+        double dotd = 0.0;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            put(k.g_wd + (long long)c * 9 + t, s2 * s[2 + t], k.accumulate);
+            dotd += (double)k.wd[(long long)c * 9 + t] * s[2 + t];
+        }
+        put(k.g_w3 + c, (double)k.s3[0] * s[0], k.accumulate);
+        put(k.g_beta2 + c, s[1], k.accumulate);
+        put(k.g_gamma2 + c, (double)k.r2[c] * (dotd - (double)k.mu2[c] * s[1]), k.accumulate);
+        put(k.g_beta1 + c, s[11], k.accumulate);
+        put(k.g_gamma1 + c, (double)k.r1[c] * (k.rowdot[c] - (double)k.mu1[c] * s[11]), k.accumulate);
+    }
+    if (blockIdx.x != 0) return;
+    double dot3 = 0.0;
+    for (int ch = threadIdx.x; ch < k.C; ch += 256) {
+        double g3 = 0.0;
+        for (int sl = 0; sl < k.slabs; ++sl) g3 += k.ws[sl * stride + ch];
+        dot3 += (double)k.w3[ch] * g3;
+    }
+    red[threadIdx.x] = dot3;
+    tree256(red);
+    if (threadIdx.x == 0) {
+        double S3 = 0.0;
+        for (int sl = 0; sl < k.slabs; ++sl) S3 += k.ws[sl * stride + (long long)kNS * k.C];
+        put(k.g_beta3, S3, k.accumulate);
+        put(k.g_gamma3, (double)k.r3[0] * (red[0] - (double)k.mu3[0] * S3), k.accumulate);
+    }
+}
+
+bool al16(const void* p) { return uavsal_aligned16(p); }
+bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+}  // namespace
+
+extern "C" int uavsal_train_decoder_sizeof_desc(int which) {
+    return which == 0 ? (int)sizeof(uavsal_pix_gemm_desc) : which == 1 ? (int)sizeof(uavsal_dec_sums_desc)
+         : which == 2 ? (int)sizeof(uavsal_dec_finish_desc) : -1;
+}
+
+extern "C" int uavsal_pix_gemm_shares(const uavsal_pix_gemm_desc* d) {
+    PgK k;
+    return pg_plan(d, k) ? k.shares : 0;
+}
+
+extern "C" int64_t uavsal_pix_gemm_workspace_bytes(const uavsal_pix_gemm_desc* d) {
+    PgK k;
+    if (!pg_plan(d, k)) return 0;
+    return (int64_t)k.shares * k.M * k.N * (int64_t)sizeof(float);
+}
+
+extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t stream) {
+    if (!d || !d->a || !d->b || !d->ws || !d->out) return UAVSAL_EINVAL;
+    if (d->K <= 0 || d->M <= 0 || d->N <= 0) return UAVSAL_EINVAL;
+    if (d->rowdot && !d->w) return UAVSAL_EINVAL;
+    if ((d->M % kTile) || (d->N % kTile)) return UAVSAL_ESHAPE;
+    PgK k;
+    if (!pg_plan(d, k)) return UAVSAL_ESHAPE;
+    if (d->ws_bytes < uavsal_pix_gemm_workspace_bytes(d)) return UAVSAL_EINVAL;
+    if (d->lda < d->M || d->ldb < d->N || d->ldo < d->N || (d->rowdot && d->ldw < d->N)) return UAVSAL_EINVAL;
+    if ((d->lda | d->ldb) & 3) return UAVSAL_EALIGN;
+    if (!al16(d->a) || !al16(d->b) || !al16(d->ws) || !al4(d->out) || (d->row_scale && !al4(d->row_scale)) ||
+        (d->rowdot && (!al8(d->rowdot) || !al4(d->w)))) return UAVSAL_EALIGN;
+    k.a = d->a; k.b = d->b; k.row_scale = d->row_scale; k.w = d->w; k.rowdot = d->rowdot; k.ws = d->ws; k.out = d->out;
+    k.lda = d->lda; k.ldb = d->ldb; k.ldw = d->ldw; k.ldo = d->ldo;
+    k.accumulate = d->accumulate != 0;
+    hipLaunchKernelGGL(pix_gemm_kernel, dim3((unsigned)(k.mt_n * (k.N / kTile)), (unsigned)k.shares), dim3(256), 0,
+                       (hipStream_t)stream, k);
+    hipLaunchKernelGGL(pix_gemm_reduce_kernel, dim3((unsigned)k.M), dim3(256), 0, (hipStream_t)stream, k);
+    return uavsal_launch_status();
+}
+
+extern "C" int uavsal_dec_sums_slabs(const uavsal_dec_sums_desc* d) {
+    SumK k;
+    return sums_plan(d, k) ? k.slabs : 0;
+}
+
+extern "C" int uavsal_dec_sums_slab_rows(const uavsal_dec_sums_desc* d) {
+    SumK k;
+    return sums_plan(d, k) ? k.slab_rows : 0;
+}
+
+extern "C" int64_t uavsal_dec_sums_workspace_bytes(const uavsal_dec_sums_desc* d) {
+    SumK k;
+    if (!sums_plan(d, k)) return 0;
+    return (int64_t)k.slabs * ((int64_t)kNS * k.C + 1) * (int64_t)sizeof(double);
+}
+
+extern "C" int uavsal_dec_sums(const uavsal_dec_sums_desc* d, uavsal_stream_t stream) {
+    if (!d || !d->gy || !d->y || !d->e || !d->d || !d->ga || !d->w3 || !d->s3 || !d->ws) return UAVSAL_EINVAL;
+    if (d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0) return UAVSAL_EINVAL;
+    if (d->gy_img_pitch < 0 || d->gy_row_pitch < 0 || d->gy_col_pitch < 0) return UAVSAL_EINVAL;
+    if (d->C % kGroup) return UAVSAL_ESHAPE;
+    SumK k;
+    if (!sums_plan(d, k)) return UAVSAL_ESHAPE;
+    if (d->ws_bytes < uavsal_dec_sums_workspace_bytes(d)) return UAVSAL_EINVAL;
+    if (!al16(d->e) || !al16(d->d) || !al16(d->ga) || !al16(d->w3) || !al8(d->ws) || !al4(d->gy) || !al4(d->y) || !al4(d->s3))
+        return UAVSAL_EALIGN;
+    k.gy = d->gy; k.y = d->y; k.e = d->e; k.d = d->d; k.ga = d->ga; k.w3 = d->w3; k.s3 = d->s3; k.ws = d->ws;
+    k.gi = d->gy_img_pitch; k.gr = d->gy_row_pitch; k.gc = d->gy_col_pitch;
+    hipLaunchKernelGGL(dec_sums_kernel, dim3((unsigned)k.slabs, (unsigned)(k.C / kGroup)), dim3(256), 0, (hipStream_t)stream, k);
+    return uavsal_launch_status();
+}
+
+extern "C" int uavsal_dec_finish(const uavsal_dec_finish_desc* d, uavsal_stream_t stream) {
+    if (!d || !d->ws || !d->rowdot || !d->wd || !d->w3 || !d->s2 || !d->s3 || !d->r1 || !d->mu1 || !d->r2 || !d->mu2 ||
+        !d->r3 || !d->mu3 || !d->g_gamma1 || !d->g_beta1 || !d->g_wd || !d->g_gamma2 || !d->g_beta2 || !d->g_w3 ||
+        !d->g_gamma3 || !d->g_beta3) return UAVSAL_EINVAL;
+    if (d->C <= 0 || d->slabs <= 0) return UAVSAL_EINVAL;
+    if (d->C % kGroup) return UAVSAL_ESHAPE;
+    if (d->ws_bytes < (int64_t)d->slabs * ((int64_t)kNS * d->C + 1) * (int64_t)sizeof(double)) return UAVSAL_EINVAL;
+    const void* f4[] = {d->wd, d->w3, d->s2, d->s3, d->r1, d->mu1, d->r2, d->mu2, d->r3, d->mu3, d->g_gamma1, d->g_beta1,
+                        d->g_wd, d->g_gamma2, d->g_beta2, d->g_w3, d->g_gamma3, d->g_beta3};
+    for (const void* p : f4)
+        if (!al4(p)) return UAVSAL_EALIGN;
+    if (!al8(d->ws) || !al8(d->rowdot)) return UAVSAL_EALIGN;
+    FinK k;
+    k.ws = d->ws; k.rowdot = d->rowdot; k.wd = d->wd; k.w3 = d->w3; k.s2 = d->s2; k.s3 = d->s3;
+    k.r1 = d->r1; k.mu1 = d->mu1; k.r2 = d->r2; k.mu2 = d->mu2; k.r3 = d->r3; k.mu3 = d->mu3;
+    k.g_gamma1 = d->g_gamma1; k.g_beta1 = d->g_beta1; k.g_wd = d->g_wd; k.g_gamma2 = d->g_gamma2; k.g_beta2 = d->g_beta2;
+    k.g_w3 = d->g_w3; k.g_gamma3 = d->g_gamma3; k.g_beta3 = d->g_beta3;
+    k.C = d->C; k.slabs = d->slabs; k.accumulate = d->accumulate != 0;
+    hipLaunchKernelGGL(dec_finish_kernel, dim3((unsigned)(d->C / 256)), dim3(256), 0, (hipStream_t)stream, k);
+    return uavsal_launch_status();
+}

@@ -286,13 +286,14 @@ class UAVSal(nn.Module):
     invalidate_engines = _drop_engines
 
     def refresh_weights(self, *modules):
-        """After an optimiser step on the parameters of `modules` (e.g. `model.rnn`): repack every packed copy of their conv
-        weights -- every layout in use, the Winograd transforms, the transposed forms of train.py -- INTO THE EXISTING DEVICE
+        """After an optimiser step on the parameters of `modules` (e.g. `model.rnn`, `model.conv_out_st`): repack every packed
+        copy of their weights -- conv weights in every layout in use, the Winograd transforms, the transposed forms of
+        train.py, and for the decoder its BatchNorm folds and statistics and its depthwise entries -- INTO THE EXISTING DEVICE
         TENSORS, and take the parameters' new version counters as the packed state, so that the next call neither drops nor
         rebuilds a launch plan (plans hold the tensors' addresses).  Only the named modules are repacked.  If any OTHER
         parameter or buffer was modified in place since the weights were packed, the plans and packed weights are dropped
-        instead (as `_check_weights` would at the next call) and everything is packed anew then.  Modules whose packed form
-        is not a plain conv weight (BatchNorm folds, depthwise, fused blocks) raise before anything is copied.
+        instead (as `_check_weights` would at the next call) and everything is packed anew then.  Modules with a packed form
+        that cannot be remade in place (fused blocks, the stem) raise before anything is copied.
         Returns the number of packed tensors refreshed (0 when nothing was packed yet, or when the plans were dropped)."""
         from .weights import WeightCache
         if self._wversion is None or "_wtensors" not in self.__dict__:

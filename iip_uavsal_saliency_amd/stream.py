@@ -382,7 +382,7 @@ def validate_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
 def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_prior: torch.Tensor,
                    fix_map: torch.Tensor, fix_loc: torch.Tensor, optimizer, batch_size: int = 4,
                    model_size: Optional[tuple] = None, frame_layout: str = "CHW", bgr: bool = False,
-                   gaze_layout: Optional[str] = None, criterion=None, prepare=None):
+                   gaze_layout: Optional[str] = None, criterion=None, prepare=None, stages=("rnn",)):
     """The inner loop of the reference's `train` phase for one video (Demo_Train_Test.py:105-153), for the stage this package
     trains: the ConvTWA recurrence `model.rnn` (train.py).  Arguments, groups, skip rule, carried detached state and returned
     aggregates are `validate_video`'s (one loop serves both); every group that runs does
@@ -390,13 +390,23 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `optimizer` is the caller's `torch.optim` object over `model.rnn.parameters()`; the reference uses
     `Adam(lr=1e-4, betas=(0.9, 0.999), weight_decay=5e-5)` (Demo_Train_Test.py:68-69) over ALL parameters.  Different from
     the reference on purpose: the model stays in `eval()` -- every other stage is frozen and every BatchNorm uses its running
-    statistics.  A group's loss is the loss BEFORE its step, as `loss.data.item()` is there."""
+    statistics.  A group's loss is the loss BEFORE its step, as `loss.data.item()` is there.
+    `stages`: `("rnn",)` or `("rnn", "decoder")`: with the decoder, `recurrence_step(..., decoder=True)` also sets the
+    gradients of `model.conv_out_st` (the optimiser then holds its parameters too) and both stages are refreshed."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
+    stages = tuple(stages)
+    if stages not in (("rnn",), ("rnn", "decoder")):
+        raise ValueError("stages must be ('rnn',) or ('rnn', 'decoder'), got %r" % (stages,))
 
     def step(x, cb, state, y):
         optimizer.zero_grad()
+        if "decoder" in stages:
+            loss, _, state = _train.recurrence_step(model, x, cb, state, y, criterion, decoder=True)
+            optimizer.step()
+            model.refresh_weights(model.rnn, model.conv_out_st)
+            return loss, state
         loss, _, state = _train.recurrence_step(model, x, cb, state, y, criterion)
         optimizer.step()
         model.refresh_weights(model.rnn)

@@ -9,6 +9,10 @@ bias, so ITS gradient is the same in both modes.
 
     z_t = conv3x3(W, cat[x_t, h_{t-1}]),   i_t = sigmoid(z_t),   h_t = i_t x_t + (1 - i_t) h_{t-1}
 
+A second stage can be trained with it: the decoder `model.conv_out_st` (`decoder_backward`, `decoder_param_grads`,
+`recurrence_step(decoder=True)`; csrc/train_decoder.hip: `uavsal_pix_gemm`, `uavsal_dec_sums`, `uavsal_dec_finish`), its
+BatchNorms on their running statistics.
+
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
 Tensors are float32 on the GPU with the logical shape `[T, C, h, w]`; a channels-last tensor (NHWC in memory, or a channel
@@ -45,9 +49,10 @@ def _nhwc(t, name, c=None):
     return v.contiguous()
 
 
-def _conv(lib, cache, x, conv, cout, taps, wslice=None, transposed=False, bn=None, act=L.ACT_NONE, res=None):
+def _conv(lib, cache, x, conv, cout, taps, wslice=None, transposed=False, bn=None, act=L.ACT_NONE, res=None, tscale=None):
     """One `uavsal_conv_gemm` launch on the current stream (no synchronisation): `x` NHWC, the weights of `conv` (or of its
-    transposed conv) from `cache` in the layout the route of this launch takes."""
+    transposed conv; `tscale`: with the folded scale of that BatchNorm in its rows) from `cache` in the layout the route of
+    this launch takes."""
     ap, lda, n, h, w, cin = _nhwc_view(x)
     out = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.device)
     d = L.ConvDesc()
@@ -64,19 +69,54 @@ def _conv(lib, cache, x, conv, cout, taps, wslice=None, transposed=False, bn=Non
     d.w = 1 << 20
     rt = L.conv_route(lib, d)
     layout = P.conv_weight_layout("f32", False, False, rt.tile, 3 if taps == 9 else 1)
-    wp = cache.conv_t(conv, wslice, layout) if transposed else cache.conv(conv, wslice, 0, layout)
+    if tscale is not None:
+        wp = cache.conv_t_scaled(conv, tscale, layout)
+    else:
+        wp = cache.conv_t(conv, wslice, layout) if transposed else cache.conv(conv, wslice, 0, layout)
     d.w = wp.data_ptr()
     L.check(lib.uavsal_conv_gemm(C.byref(d), _stream(x)), "uavsal_conv_gemm")
     return out
 
 
-def _decoder_parts(block):
+def _decoder_parts(block, trained=False):
     seq = block.conv
     if getattr(block, "expand_ratio", 0) == 1 or len(seq) != 4 or seq[2].weight.shape[0] != 1:
         raise RuntimeError("decoder_input_grad takes model.conv_out_st (expand 1x1, depthwise 3x3, projection to one channel)")
     if block.training:
-        raise RuntimeError("the decoder is frozen: its BatchNorms are folded in eval mode (call model.eval())")
+        raise RuntimeError("the decoder's BatchNorms use their running statistics: call model.eval()" if trained else
+                           "the decoder is frozen: its BatchNorms are folded in eval mode (call model.eval())")
     return seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
+
+
+def _decoder_recompute(lib, cache, block, h, y):
+    """`e`, `d` (dense NHWC) from the NHWC `h` by the forward's own launches, and `y` dense `[T,h,w,1]` when it is not given
+    (`[T,1,h,w]`); plus the packed `(wd9, s2, w3, s3)`."""
+    pw, pwbn, dwc, dwbn, pl, plbn = _decoder_parts(block)
+    T, hh, ww, _ = h.shape
+    dev, hid = h.device, pw.weight.shape[0]
+    st = _stream(h)
+    e = _conv(lib, cache, h, pw, hid, 1, bn=pwbn, act=L.ACT_RELU6)
+    w9, s2, b2 = cache.depthwise(dwc, dwbn)
+    dd = torch.empty_like(e)
+    q = L.DwDesc()
+    q.inp, q.ldi, q.w9c, q.scale, q.bias = e.data_ptr(), hid, w9.data_ptr(), s2.data_ptr(), b2.data_ptr()
+    q.out, q.ldo = dd.data_ptr(), hid
+    q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, 1, 1, L.ACT_RELU6
+    L.check(lib.uavsal_dw3x3(C.byref(q), st), "uavsal_dw3x3")
+    _, _, _, w3, s3, b3 = cache.dw_dot(dwc, dwbn, pl, plbn)
+    if y is None:
+        y = torch.empty((T, hh, ww, 1), dtype=torch.float32, device=dev)
+        k = L.DwDotDesc()
+        k.inp, k.ldi = e.data_ptr(), hid
+        k.w9c, k.scale, k.bias, k.w2, k.scale2, k.bias2 = (t.data_ptr() for t in (w9, s2, b2, w3, s3, b3))
+        k.out, k.ldo = y.data_ptr(), 1
+        k.n_img, k.H, k.W, k.C, k.act = T, hh, ww, hid, L.ACT_SIGMOID
+        L.check(lib.uavsal_dw3x3_dot(C.byref(k), st), "uavsal_dw3x3_dot")
+    else:
+        if tuple(y.shape) != (T, 1, hh, ww) or y.dtype != torch.float32 or y.device != dev:
+            raise RuntimeError("y must be the prediction [%d,1,%d,%d] on the same device" % (T, hh, ww))
+        y = y.detach().contiguous()
+    return e, dd, y, (w9, s2, w3, s3)
 
 
 def decoder_input_grad(block, h_seq, grad_out, cache=None, y=None, parts=None):
@@ -97,28 +137,7 @@ def decoder_input_grad(block, h_seq, grad_out, cache=None, y=None, parts=None):
     hid = pw.weight.shape[0]
     with torch.cuda.device(dev):
         cache = cache or WeightCache(dev, {})
-        st = _stream(h)
-        e = _conv(lib, cache, h, pw, hid, 1, bn=pwbn, act=L.ACT_RELU6)
-        w9, s2, b2 = cache.depthwise(dwc, dwbn)
-        dd = torch.empty_like(e)
-        q = L.DwDesc()
-        q.inp, q.ldi, q.w9c, q.scale, q.bias = e.data_ptr(), hid, w9.data_ptr(), s2.data_ptr(), b2.data_ptr()
-        q.out, q.ldo = dd.data_ptr(), hid
-        q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, 1, 1, L.ACT_RELU6
-        L.check(lib.uavsal_dw3x3(C.byref(q), st), "uavsal_dw3x3")
-        _, _, _, w3, s3, b3 = cache.dw_dot(dwc, dwbn, pl, plbn)
-        if y is None:
-            y = torch.empty((T, hh, ww, 1), dtype=torch.float32, device=dev)
-            k = L.DwDotDesc()
-            k.inp, k.ldi = e.data_ptr(), hid
-            k.w9c, k.scale, k.bias, k.w2, k.scale2, k.bias2 = (t.data_ptr() for t in (w9, s2, b2, w3, s3, b3))
-            k.out, k.ldo = y.data_ptr(), 1
-            k.n_img, k.H, k.W, k.C, k.act = T, hh, ww, hid, L.ACT_SIGMOID
-            L.check(lib.uavsal_dw3x3_dot(C.byref(k), st), "uavsal_dw3x3_dot")
-        else:
-            if tuple(y.shape) != (T, 1, hh, ww) or y.dtype != torch.float32 or y.device != dev:
-                raise RuntimeError("y must be the prediction [%d,1,%d,%d] on the same device" % (T, hh, ww))
-            y = y.detach().contiguous()
+        e, dd, y, (w9, s2, w3, s3) = _decoder_recompute(lib, cache, block, h, y)
         ge = dec_bwd(grad_out, y, e, dd, cache.affine(pwbn, hid)[0], w9, s2, w3, s3)
         g = _conv(lib, cache, ge, pw, pw.weight.shape[1], 1, transposed=True)
         if parts is not None:
@@ -142,6 +161,168 @@ def dec_bwd(grad_out, y, e, d, s1, wd9, s2, w3, s3):
     k.n_img, k.H, k.W, k.C = T, hh, ww, c
     L.check(lib.uavsal_dec_bwd(C.byref(k), _stream(e)), "uavsal_dec_bwd")
     return ge
+
+
+DECODER_PARAMS = ("conv.0.0.weight", "conv.0.1.weight", "conv.0.1.bias", "conv.1.0.weight", "conv.1.1.weight", "conv.1.1.bias",
+                  "conv.2.weight", "conv.3.weight", "conv.3.bias")      # W1, gamma1, beta1, Wd, gamma2, beta2, W3, gamma3, beta3
+
+
+def pix_gemm(a, b, out=None, row_scale=None, w=None, rowdot=None, accumulate=False):
+    """`uavsal_pix_gemm` on the current stream: `a` `[..., M]`, `b` `[..., N]` NHWC tensors of the same pixels (channel slices
+    are read in place) -> `out[m][n] = row_scale[m] sum_p a[p][m] b[p][n]` (dense `[M, N]`; `accumulate`: added to `out`), and
+    with `w` `[M, N]` and `rowdot` (float64 `[M]`) `rowdot[m] = sum_n w[m][n] G[m][n]`.  Two launches, no synchronisation."""
+    lib = L.load()
+    ap, lda, *sa = _nhwc_view(a)
+    bp, ldb, *sb = _nhwc_view(b)
+    M, N = sa[3], sb[3]
+    if sa[:3] != sb[:3] or a.device != b.device:
+        raise RuntimeError("pix_gemm: a and b must cover the same pixels on one device")
+    dev = a.device
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `out`")
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    if out.numel() != M * N or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError("out must be a dense float32 tensor of %d x %d elements on the device" % (M, N))
+    k = L.PixGemmDesc()
+    k.a, k.lda, k.b, k.ldb = ap, lda, bp, ldb
+    k.K, k.M, k.N, k.accumulate = sa[0] * sa[1] * sa[2], M, N, int(bool(accumulate))
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or row_scale.device != dev or row_scale.numel() < M or not row_scale.is_contiguous():
+            raise RuntimeError("row_scale must be a dense float32 vector of at least %d elements on the device" % M)
+        k.row_scale = row_scale.data_ptr()
+    if rowdot is not None:
+        if (w is None or w.numel() != M * N or not w.is_contiguous() or w.dtype != torch.float32 or w.device != dev
+                or rowdot.dtype != torch.float64 or rowdot.numel() != M or not rowdot.is_contiguous() or rowdot.device != dev):
+            raise RuntimeError("rowdot needs a dense float32 `w` of %d x %d elements and a dense float64 [%d] on the device" % (M, N, M))
+        k.w, k.ldw, k.rowdot = w.data_ptr(), N, rowdot.data_ptr()
+    k.out, k.ldo = out.data_ptr(), N
+    nbytes = int(lib.uavsal_pix_gemm_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_pix_gemm")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    L.check(lib.uavsal_pix_gemm(C.byref(k), _stream(a)), "uavsal_pix_gemm")
+    return out
+
+
+def dec_sums(grad_out, y, e, d, ga, w3, s3):
+    """`uavsal_dec_sums` on the current stream -> `(ws, slabs)`: the per-slab partial sums (float64, the layout of
+    include/uavsal_hip.h) that `uavsal_dec_finish` takes.  Arguments as `dec_bwd`'s; `ga` dense NHWC like `e`."""
+    lib = L.load()
+    T, hh, ww, c = e.shape
+    if (not (e.is_contiguous() and d.is_contiguous() and ga.is_contiguous() and y.is_contiguous()) or e.shape != d.shape
+            or e.shape != ga.shape or y.numel() != T * hh * ww):
+        raise RuntimeError("dec_sums: e, d, ga must be dense NHWC tensors of one shape and y dense [T,h,w]")
+    k = L.DecSumsDesc()
+    k.gy = grad_out.data_ptr()
+    k.gy_img_pitch, _, k.gy_row_pitch, k.gy_col_pitch = grad_out.stride()
+    k.y, k.e, k.d, k.ga, k.w3, k.s3 = y.data_ptr(), e.data_ptr(), d.data_ptr(), ga.data_ptr(), w3.data_ptr(), s3.data_ptr()
+    k.n_img, k.H, k.W, k.C = T, hh, ww, c
+    nbytes = int(lib.uavsal_dec_sums_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_dec_sums")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    L.check(lib.uavsal_dec_sums(C.byref(k), _stream(e)), "uavsal_dec_sums")
+    return ws, int(lib.uavsal_dec_sums_slabs(C.byref(k)))
+
+
+def _grad_tensors(block, out, accumulate):
+    params = dict(block.named_parameters())
+    if sorted(params) != sorted(DECODER_PARAMS):
+        raise RuntimeError("the decoder's parameters must be %r" % (DECODER_PARAMS,))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `out`")
+        out = {n: torch.empty_like(params[n], memory_format=torch.contiguous_format) for n in DECODER_PARAMS}
+    for n in DECODER_PARAMS:
+        t, q = out.get(n), params[n]
+        if (not torch.is_tensor(t) or t.shape != q.shape or t.dtype != torch.float32 or t.device != q.device
+                or not t.is_contiguous()):
+            raise RuntimeError("out[%r] must be a dense float32 tensor of the parameter's shape on its device" % n)
+    return params, out
+
+
+def decoder_param_grads(block, h, e, d, y, grad_out, ga=None, cache=None, out=None, accumulate=False):
+    """The gradients of the nine parameters of the decoder `block` = `model.conv_out_st` (eval mode: the BatchNorms on their
+    running statistics, which are not updated) from given tensors, teacher-forced: `h` `[T,256,h,w]` the block's input,
+    `e`, `d` dense NHWC `[T,h,w,1536]` its expanded and depthwise tensors, `y` `[T,1,h,w]` the prediction, `grad_out`
+    `[T,1,h,w]` = d loss / d y, `ga` dense NHWC = d loss / d a1 (default: one `uavsal_dec_bwd` with ones for s1).  Returns a
+    dict keyed by the block's parameter names (`DECODER_PARAMS`), the values `torch.autograd` gives for the reference's
+    `dwBlock` (include/uavsal_hip.h states the formulas); `out`: such a dict of dense tensors to write into, or
+    (`accumulate`) to add to.  Nothing of the forward is recomputed; four launches (GEMM, its reduction, channel sums,
+    finalise) on the current stream, no synchronisation."""
+    lib = L.load()
+    pw, pwbn, dwc, dwbn, pl, plbn = _decoder_parts(block, trained=True)
+    hn = _nhwc(h, "h", pw.weight.shape[1])
+    T, hh, ww, _ = hn.shape
+    hid = pw.weight.shape[0]
+    dev = hn.device
+    for name, t in (("e", e), ("d", d)) + ((("ga", ga),) if ga is not None else ()):
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (T, hh, ww, hid)
+                or not t.is_contiguous()):
+            raise RuntimeError("%s must be a dense float32 NHWC tensor [%d,%d,%d,%d] on the device" % (name, T, hh, ww, hid))
+    if (not torch.is_tensor(grad_out) or grad_out.device != dev or grad_out.dtype != torch.float32
+            or tuple(grad_out.shape) != (T, 1, hh, ww)):
+        raise RuntimeError("grad_out must be a float32 cuda tensor [%d,1,%d,%d]" % (T, hh, ww))
+    if not torch.is_tensor(y) or y.dtype != torch.float32 or y.device != dev or y.numel() != T * hh * ww:
+        raise RuntimeError("y must be the prediction [%d,1,%d,%d] on the same device" % (T, hh, ww))
+    params, out = _grad_tensors(block, out, accumulate)
+    if any(q.device != dev or not q.is_contiguous() for q in params.values()):
+        raise RuntimeError("the decoder's parameters must be dense tensors on the device of `h`")
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        y = y.detach().contiguous()
+        w9, s2, _ = cache.depthwise(dwc, dwbn)
+        _, _, _, w3, s3, _ = cache.dw_dot(dwc, dwbn, pl, plbn)
+        s1 = cache.affine(pwbn, hid)[0]
+        if ga is None:
+            ga = dec_bwd(grad_out, y, e, d, torch.ones(hid, dtype=torch.float32, device=dev), w9, s2, w3, s3)
+        (r1, mu1), (r2, mu2), (r3, mu3) = (cache.bn_stats(b) for b in (pwbn, dwbn, plbn))
+        rowdot = torch.empty(hid, dtype=torch.float64, device=dev)
+        pix_gemm(ga, hn, out=out[DECODER_PARAMS[0]], row_scale=s1, w=pw.weight.detach(), rowdot=rowdot, accumulate=accumulate)
+        ws, slabs = dec_sums(grad_out, y, e, d, ga, w3, s3)
+        k = L.DecFinishDesc()
+        k.ws, k.ws_bytes, k.rowdot = ws.data_ptr(), ws.numel() * 8, rowdot.data_ptr()
+        k.wd, k.w3, k.s2, k.s3 = dwc.weight.data_ptr(), pl.weight.data_ptr(), s2.data_ptr(), s3.data_ptr()
+        k.r1, k.mu1, k.r2, k.mu2, k.r3, k.mu3 = (t.data_ptr() for t in (r1, mu1, r2, mu2, r3, mu3))
+        (k.g_gamma1, k.g_beta1, k.g_wd, k.g_gamma2, k.g_beta2, k.g_w3, k.g_gamma3, k.g_beta3) = (
+            out[n].data_ptr() for n in DECODER_PARAMS[1:])
+        k.C, k.slabs, k.accumulate = hid, slabs, int(bool(accumulate))
+        L.check(lib.uavsal_dec_finish(C.byref(k), _stream(hn)), "uavsal_dec_finish")
+    return out
+
+
+def decoder_backward(block, h_seq, grad_out, cache=None, y=None, parts=None, grads=None, accumulate=False):
+    """`decoder_input_grad` for a decoder that is TRAINED: returns `(grad_h [T,256,h,w], grads)` with `grads` the dict of
+    `decoder_param_grads` (written into `grads`, or with `accumulate` added to it, when given).  `e` and `d` are recomputed
+    from `h_seq` by the forward's own launches, `ga` = d loss / d a1 comes from `uavsal_dec_bwd` handed ones for s1, and
+    `grad_h = ga . (diag(s1) W1)` from one 1536 -> 256 GEMM whose transposed weights carry s1 in their rows
+    (`WeightCache.conv_t_scaled`) -- the gamma gradients need the unscaled `ga`.  `decoder_input_grad` scales by s1 in the
+    kernel and multiplies by the plain W1^T instead: the two paths round in a different order and may differ in the last
+    bits of `grad_h`.  `parts` receives `e`, `d`, `y`, `ga` (dense NHWC).  A block in training mode raises: the BatchNorms use
+    their running statistics (which are not updated), as everywhere in this package."""
+    lib = L.load()
+    pw, pwbn, dwc, dwbn, pl, plbn = _decoder_parts(block, trained=True)
+    h = _nhwc(h_seq, "h_seq", pw.weight.shape[1])
+    T, hh, ww, _ = h.shape
+    if (not torch.is_tensor(grad_out) or not grad_out.is_cuda or grad_out.dtype != torch.float32
+            or tuple(grad_out.shape) != (T, 1, hh, ww)):
+        raise RuntimeError("grad_out must be a float32 cuda tensor [%d,1,%d,%d]" % (T, hh, ww))
+    dev = h.device
+    hid = pw.weight.shape[0]
+    _grad_tensors(block, grads, accumulate)                          # raise before anything is launched
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        e, dd, y, (w9, s2, w3, s3) = _decoder_recompute(lib, cache, block, h, y)
+        ga = dec_bwd(grad_out, y, e, dd, torch.ones(hid, dtype=torch.float32, device=dev), w9, s2, w3, s3)
+        g = _conv(lib, cache, ga, pw, pw.weight.shape[1], 1, tscale=pwbn)
+        grads = decoder_param_grads(block, h.permute(0, 3, 1, 2), e, dd, y, grad_out, ga=ga, cache=cache, out=grads,
+                                    accumulate=accumulate)
+        if parts is not None:
+            parts.update(e=e, d=dd, y=y, ga=ga)
+    return g.permute(0, 3, 1, 2), grads
 
 
 def twa_gate_bwd(g, carry, z, x, hprev, need_dx=False):
@@ -259,13 +440,16 @@ def twa_backward(x_seq, h_seq, h0, weight, grad_h, need_x_grad=False, out=None, 
     return gw, (dx.permute(0, 3, 1, 2) if need_x_grad else None), carry.permute(0, 3, 1, 2)
 
 
-def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None):
+def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
     and no other parameter touched.  Returns `(loss, out, [h_last.detach()])`, the forward's contract plus the loss.
     The model is in eval mode (every other stage is frozen, its BatchNorms folded); a model in training mode, CPU tensors,
-    a precision other than 'f32' or `UAVSAL_LSTM` raise.  After `optimizer.step()` call `model.refresh_weights(model.rnn)`."""
+    a precision other than 'f32' or `UAVSAL_LSTM` raise.  After `optimizer.step()` call `model.refresh_weights(model.rnn)`.
+    `decoder=True`: the decoder `model.conv_out_st` is trained too (`decoder_backward`): its nine parameters' `.grad` are set
+    as well, or added to, and the recurrence receives that path's `grad_h`; afterwards call
+    `model.refresh_weights(model.rnn, model.conv_out_st)`.  The BatchNorms still use their running statistics."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
@@ -287,7 +471,17 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None):
     cache = WeightCache(dev, model._wshared.setdefault(str(torch.device(dev)), {}))
     cl = torch.channels_last
     h_seq, x_seq = taps["rnn"].contiguous(memory_format=cl), taps["prefuse"].contiguous(memory_format=cl)
-    grad_h = decoder_input_grad(model.conv_out_st, h_seq, g_y, cache=cache, y=out)
+    if decoder:
+        blk = model.conv_out_st
+        params = dict(blk.named_parameters())
+        acc = any(q.grad is not None for q in params.values())
+        for q in params.values():
+            if q.grad is None:                                       # (some but not all exist: the missing ones start at zero)
+                q.grad = (torch.zeros_like if acc else torch.empty_like)(q, memory_format=torch.contiguous_format)
+        grad_h, _ = decoder_backward(blk, h_seq, g_y, cache=cache, y=out, grads={n: q.grad for n, q in params.items()},
+                                     accumulate=acc)
+    else:
+        grad_h = decoder_input_grad(model.conv_out_st, h_seq, g_y, cache=cache, y=out)
     h0 = None if in_state is None else in_state[0]
     w = rc.weight
     had = w.grad is not None

@@ -29,6 +29,31 @@ def _weight(convs, wslice):
     return w if wslice is None else w[:, wslice[0]:wslice[1]]
 
 
+def _scaled_t(conv, bn):
+    s = P.fold_bn(bn)[0]
+    return (conv.weight.detach().float().cpu() * s.view(-1, 1, 1, 1)).transpose(0, 1).flip(2, 3)
+
+
+def _bn_stats(bn):
+    r = 1.0 / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    return r.float(), bn.running_mean.detach().float().cpu()
+
+
+def _bn_after(mods, conv):
+    """The BatchNorm that follows `conv` in the container (among `mods`) that holds both."""
+    for m in mods.values():
+        ch = list(m.children())
+        for a, b in zip(ch, ch[1:]):
+            if a is conv and isinstance(b, torch.nn.BatchNorm2d):
+                return b
+    raise RuntimeError("the BatchNorm of a packed depthwise entry is not among the refreshed modules: pass the whole block")
+
+
+# kind -> the module ids of a key of that kind (everything `refresh` can remake)
+_REFRESH_IDS = {"w": lambda k: k[1:-3], "wino": lambda k: k[1:2], "wT": lambda k: k[1:2], "wTs": lambda k: k[1:3],
+                "bn": lambda k: k[1:-1], "bnstat": lambda k: k[1:2], "dw": lambda k: k[1:], "dwdot": lambda k: k[1:3]}
+
+
 class WeightCache:
     def __init__(self, device, store):
         self.device, self.store = torch.device(device), store
@@ -77,11 +102,27 @@ class WeightCache:
             return self._up(P.pack_conv_weight(w, layout))[0]
         return self._get(("wT", id(conv), wslice, layout), make)
 
+    def conv_t_scaled(self, conv, bn, layout):
+        """The weights of the transposed 1x1 conv of `conv` + BatchNorm `bn` with the BatchNorm's folded scale s in its rows,
+        `Wt[ci, co] = s[co] W[co, ci]` (the product rounded once), packed for `layout`: it carries the gradient with respect
+        to the BatchNorm's OUTPUT back to the conv's input (train.decoder_backward)."""
+        def make():
+            return self._up(P.pack_conv_weight(_scaled_t(conv, bn), layout))[0]
+        return self._get(("wTs", id(conv), id(bn), layout), make)
+
+    def bn_stats(self, bn):
+        """(r, mu) of one BatchNorm on the device: r = 1 / sqrt(running_var + eps) computed in double and rounded once, mu the
+        running mean -- what the gradient of the BatchNorm's weight needs beside the fold (train.decoder_param_grads)."""
+        return self._get(("bnstat", id(bn)), lambda: self._up(*_bn_stats(bn)))
+
     def refresh(self, mods, dry=False):
         """Repack, INTO THE EXISTING DEVICE TENSORS, every entry whose key holds the id of a module in `mods` (id -> module)
         from the module's current parameters: launch plans that recorded the tensors' addresses stay valid.  Conv weights in
-        every layout, their Winograd transforms and transposed forms are refreshable; an entry of another kind (folded
-        BatchNorm, depthwise, fused block, stem) that names such a module raises -- `model.invalidate_engines()` is for those.
+        every layout, their Winograd transforms and transposed forms, BatchNorm folds (with their identity padding) and
+        statistics, depthwise and depthwise-dot entries are refreshable; a fused block or a stem that names such a module
+        raises -- `model.invalidate_engines()` is for those.  A key that joins several modules needs all of them in `mods`;
+        a depthwise entry's key holds its conv alone: its BatchNorm is the module that follows the conv in the container
+        that holds both, which must be in `mods` too (pass the block, not the conv).
         `dry`: only check that every such entry can be remade (raise otherwise), pack and copy nothing.
         Returns the number of entries refreshed (that would be)."""
         n = 0
@@ -89,10 +130,18 @@ class WeightCache:
             if not isinstance(key, tuple) or not any(isinstance(i, int) and i in mods for i in key[1:]):
                 continue
             kind = key[0]
-            if kind not in ("w", "wino", "wT"):
+            if kind not in _REFRESH_IDS:
                 raise NotImplementedError("packed %r weights cannot be refreshed in place: call model.invalidate_engines()" % (kind,))
-            if kind == "w" and not all(i in mods for i in key[1:-3]):
-                raise RuntimeError("a packed weight joins several convs: refresh all of them together")
+            ids = _REFRESH_IDS[kind](key)
+            if not all(i in mods for i in ids):
+                raise RuntimeError("a packed %r entry joins several modules: refresh all of them together" % (kind,))
+            if kind in ("bn", "bnstat", "dw", "dwdot", "wTs"):
+                new = self._remake(kind, key, [mods[i] for i in ids], mods)      # small: made in the dry pass too, so that it can raise
+                if not dry:
+                    for dst, src in zip(self.store[key] if isinstance(self.store[key], tuple) else (self.store[key],), new):
+                        dst.copy_(src.to(self.device, non_blocking=False))
+                n += 1
+                continue
             if dry:
                 n += 1
                 continue
@@ -109,6 +158,22 @@ class WeightCache:
             self.store[key].copy_(new.to(self.device, non_blocking=False))
             n += 1
         return n
+
+    def _remake(self, kind, key, ms, mods):
+        """The host tensors of one refreshable non-conv entry, in the order of the stored tuple."""
+        if kind == "bn":
+            s, b = _folded(ms)
+            n = P.roundup(key[-1], 32)
+            return P.pad_vec(s, n, 1.0), P.pad_vec(b, n, 0.0)
+        if kind == "bnstat":
+            return _bn_stats(ms[0])
+        if kind == "wTs":
+            return (P.pack_conv_weight(_scaled_t(ms[0], ms[1]), key[3]),)
+        if kind == "dw":
+            return (torch.cat([P.pack_dw_weight(c.weight) for c in ms], 1), *_folded([_bn_after(mods, c) for c in ms]))
+        dwc, pl = ms
+        return (P.pack_dw_weight(dwc.weight), *P.fold_bn(_bn_after(mods, dwc)), pl.weight.detach().float().cpu().reshape(-1),
+                *(t.reshape(1) for t in P.fold_bn(_bn_after(mods, pl))))
 
     def depthwise(self, conv, bn):
         """(tap-major weights, scale, bias) of a depthwise 3x3 + BatchNorm, or of a list of them as channel groups.  The

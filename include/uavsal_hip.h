@@ -731,6 +731,84 @@ int uavsal_twa_wgrad(const uavsal_twa_wgrad_desc* d, uavsal_stream_t stream);
 int uavsal_dec_bwd(const uavsal_dec_bwd_desc* d, uavsal_stream_t stream);
 int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd (uavsal_sizeof_desc's list is closed at 20) */
 
+/* ---- fine-tuning the decoder conv_out_st: its nine parameter gradients (csrc/train_decoder.hip) -----------------------
+ * The decoder in eval mode, r = 1 / sqrt(var + eps), s = gamma r, b = beta - mu s per BatchNorm:
+ *     u1 = W1 h, a1 = s1 u1 + b1, e = ReLU6(a1);  u2 = dw3x3(Wd, e), a2 = s2 u2 + b2, d = ReLU6(a2);
+ *     a3 = s3 (w3 . d) + b3, y = sigmoid(a3).
+ * With gy = d loss / d y:
+ *     delta3[p]    = gy[p] y[p] (1 - y[p])
+ *     delta2[p][c] = delta3[p] s3 w3[c] 1[0 < d[p][c] < 6]
+ *     ga[p][c]     = 1[0 < e[p][c] < 6] s2[c] sum over taps k of wd[k][c] delta2[p - (k - (1,1))][c]      (= d loss / d a1:
+ *                    what uavsal_dec_bwd writes when it is handed ones for s1)
+ * and the sums over all n_img * H * W pixels p
+ *     S3 = sum delta3,  G3[c] = sum delta3[p] d[p][c],  S2[c] = sum delta2[p][c],  S1[c] = sum ga[p][c],
+ *     Gd[c][ky][kx] = sum delta2[p][c] e[p + (ky-1, kx-1)][c]   (zero outside the picture, never across frames),
+ *     G1[c][j] = sum ga[p][c] h[p][j]
+ * the gradients are
+ *     W1[c][j]: s1[c] G1[c][j]    beta1: S1    gamma1[c]: r1[c] (sum_j W1[c][j] G1[c][j] - mu1[c] S1[c])
+ *     Wd[c][k]: s2[c] Gd[c][k]    beta2: S2    gamma2[c]: r2[c] (sum_k Wd[c][k] Gd[c][k] - mu2[c] S2[c])
+ *     W3[c]:    s3 G3[c]          beta3: S3    gamma3:    r3 (sum_c W3[c] G3[c] - mu3 S3)
+ * The gamma gradients come from the UNSCALED sums: nothing divides by gamma or s (a channel with gamma = 0 has a zero
+ * weight-gradient row and a non-zero gamma gradient).
+ *
+ * uavsal_pix_gemm: out[m][n] = fl(row_scale[m] G[m][n]) (+ the old value with `accumulate`), G[m][n] = sum over the K
+ *   pixels p of a[p][m] b[p][n]; row p of a / b at p * lda / p * ldb floats (channel slices are read in place).  M and N
+ *   multiples of 128 (else UAVSAL_ESHAPE).  The tile loop and the K split of uavsal_twa_wgrad: chunks of
+ *   UAVSAL_WGRAD_CHAIN pixels, shares of whole chunks for about 1024 workgroups over the (M / 128)(N / 128) tiles, partial
+ *   tiles in `ws`; a second launch sums the shares in share order in double and rounds once.  row_scale NULL = 1.
+ *   rowdot (optional, [M] doubles) = sum_n w[m][n] G[m][n] in double in a fixed order, w rows ldw floats apart.
+ *   No atomics: two calls return the same bits.  TWO launches, no allocation.  UAVSAL_EALIGN: a, b, ws not 16-byte
+ *   aligned or lda / ldb not a multiple of 4.
+ * uavsal_dec_sums: per slab of picture rows the partial sums S3, G3, S2, Gd, S1 -> `ws` (doubles), from gy (pitched as in
+ *   uavsal_dec_bwd_desc), y dense [n_img][H][W], e, d, ga dense [n_img][H][W][C], C % 256 == 0 (else UAVSAL_ESHAPE).
+ *   delta3 and delta2 are formed in fp32 exactly as uavsal_dec_bwd forms them; every product is accumulated in double.
+ *   ws layout: per slab UAVSAL_DEC_NSUM * C + 1 doubles: [0] G3, [1] S2, [2 + ky * 3 + kx] Gd, [11] S1, each [C], then S3.
+ *   The slabs depend on the shape alone (uavsal_dec_sums_slabs / _slab_rows): bit-reproducible.  ONE launch.
+ * uavsal_dec_finish: sums the slabs in slab order in double and writes the eight small gradients in the parameters' own
+ *   layouts (g_wd [C][3][3], the others [C] or one element), each rounded once, overwritten or (`accumulate`) added to.
+ *   rowdot: uavsal_pix_gemm's, with w = W1.  wd is the parameter [C][3][3], not the tap-major packing.  ONE launch.
+ */
+#define UAVSAL_DEC_NSUM 12
+
+typedef struct uavsal_pix_gemm_desc {
+    const float* a;  int32_t lda;           /* [K] rows of M floats */
+    const float* b;  int32_t ldb;           /* [K] rows of N floats */
+    const float* row_scale;                 /* [M] or NULL */
+    const float* w;  int32_t ldw;           /* [M] rows of N floats (needed with rowdot) */
+    double* rowdot;                         /* [M] or NULL */
+    float* ws;  int64_t ws_bytes;
+    float* out;  int32_t ldo;               /* [M] rows of N floats */
+    int64_t K;  int32_t M, N, accumulate;
+} uavsal_pix_gemm_desc;
+
+typedef struct uavsal_dec_sums_desc {
+    const float* gy;  int64_t gy_img_pitch, gy_row_pitch, gy_col_pitch;
+    const float* y;
+    const float* e;  const float* d;  const float* ga;
+    const float* w3;  const float* s3;      /* s3: one float */
+    double* ws;  int64_t ws_bytes;
+    int32_t n_img, H, W, C;
+} uavsal_dec_sums_desc;
+
+typedef struct uavsal_dec_finish_desc {
+    const double* ws;  int64_t ws_bytes;  const double* rowdot;
+    const float* wd;  const float* w3;  const float* s2;  const float* s3;
+    const float* r1;  const float* mu1;  const float* r2;  const float* mu2;  const float* r3;  const float* mu3;
+    float* g_gamma1;  float* g_beta1;  float* g_wd;  float* g_gamma2;  float* g_beta2;
+    float* g_w3;  float* g_gamma3;  float* g_beta3;
+    int32_t C, slabs, accumulate;
+} uavsal_dec_finish_desc;
+
+int64_t uavsal_pix_gemm_workspace_bytes(const uavsal_pix_gemm_desc* d);
+int uavsal_pix_gemm_shares(const uavsal_pix_gemm_desc* d);      /* K shares per tile of that call (no launch) */
+int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t stream);
+int64_t uavsal_dec_sums_workspace_bytes(const uavsal_dec_sums_desc* d);
+int uavsal_dec_sums_slabs(const uavsal_dec_sums_desc* d);       /* slabs of that call (no launch) */
+int uavsal_dec_sums_slab_rows(const uavsal_dec_sums_desc* d);   /* picture rows per slab */
+int uavsal_dec_sums(const uavsal_dec_sums_desc* d, uavsal_stream_t stream);
+int uavsal_dec_finish(const uavsal_dec_finish_desc* d, uavsal_stream_t stream);
+int uavsal_train_decoder_sizeof_desc(int which);  /* 0 pix_gemm, 1 dec_sums, 2 dec_finish (uavsal_train_sizeof_desc is closed at 3) */
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 

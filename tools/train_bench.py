@@ -9,6 +9,12 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                the 3x3 conv with flip(W_h)^T;
   step         `train.recurrence_step` as a whole (forward, criterion, its gradient, the two above);
   refresh      `model.refresh_weights(model.rnn)` after an in-place edit of the weight (host repacking and uploads);
+  decoder      the decoder trained too: `train.decoder_backward` (dec_bwd_grad, beside dec_grad), its three new launches
+               one by one -- `uavsal_pix_gemm` (pix_gemm: two launches, TFLOP/s from 2 * 1536 * 256 * T*45*80 FLOP),
+               `uavsal_dec_sums` (dec_sums: GB/s from the e halo-free, d and ga bytes, 3 * 1536 * 4 per pixel, beside
+               `uavsal_dec_bwd` at the same shape and byte count) and `uavsal_dec_finish` (dec_finish) --,
+               `recurrence_step(decoder=True)` (step_dec, alternated with step in the same run) and
+               `refresh_weights(model.rnn, model.conv_out_st)` (refresh_dec);
   eager        torch autograd of the restated recurrence + decoder (float32, eval BatchNorm folded) on the same device,
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
@@ -110,14 +116,71 @@ def bench(T, iters, repeats, dev, skip_eager):
     def step():
         rc.weight.grad = None
         train.recurrence_step(m, x, cb, None, y_gaze)
+
+    blk = m.conv_out_st
+    dparts = {}
+    _, dgrads = train.decoder_backward(blk, h_seq, g_y, cache=cache, y=out, parts=dparts)
+    e_, d_, y_, ga_ = (dparts[k] for k in ("e", "d", "y", "ga"))
+    pw, pwbn, dwc, dwbn, pl, plbn = train._decoder_parts(blk)
+    w9, s2, _ = cache.depthwise(dwc, dwbn)
+    _, _, _, w3, s3, _ = cache.dw_dot(dwc, dwbn, pl, plbn)
+    s1 = cache.affine(pwbn, 1536)[0]
+    rowdot = torch.empty(1536, dtype=torch.float64, device=dev)
+    g1 = dgrads[train.DECODER_PARAMS[0]]
+    ws, slabs = train.dec_sums(g_y, y_, e_, d_, ga_, w3, s3)
+    fin = L.DecFinishDesc()
+    fin.ws, fin.ws_bytes, fin.rowdot = ws.data_ptr(), ws.numel() * 8, rowdot.data_ptr()
+    fin.wd, fin.w3, fin.s2, fin.s3 = dwc.weight.data_ptr(), pl.weight.data_ptr(), s2.data_ptr(), s3.data_ptr()
+    (fin.r1, fin.mu1), (fin.r2, fin.mu2), (fin.r3, fin.mu3) = ((t.data_ptr() for t in cache.bn_stats(b)) for b in (pwbn, dwbn, plbn))
+    (fin.g_gamma1, fin.g_beta1, fin.g_wd, fin.g_gamma2, fin.g_beta2, fin.g_w3, fin.g_gamma3, fin.g_beta3) = (
+        dgrads[n].data_ptr() for n in train.DECODER_PARAMS[1:])
+    fin.C, fin.slabs, fin.accumulate = 1536, slabs, 0
+    lib = L.load()
+    train.pix_gemm(ga_, hn, out=g1, row_scale=s1, w=pw.weight.detach(), rowdot=rowdot)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def step_dec():
+        for q in list(m.rnn.parameters()) + list(blk.parameters()):
+            q.grad = None
+        train.recurrence_step(m, x, cb, None, y_gaze, decoder=True)
+
+    def refresh_dec():
+        with torch.no_grad():
+            rc.weight.mul_(1.0)
+            for q in blk.parameters():
+                q.mul_(1.0)
+        m.refresh_weights(m.rnn, blk)
     res = {"T": T}
     cases = {"forward": lambda: m(x, cb, None, taps={}),
              "dec_grad": lambda: train.decoder_input_grad(m.conv_out_st, h_seq, g_y, cache=cache, y=out),
              "twa_backward": lambda: train.twa_backward(x_seq, h_seq, None, rc.weight.detach(), grad_h, out=gw, cache=cache, module=rc),
              "wgrad": lambda: train.twa_wgrad(dz, xn, hn, h0n, out=gw),
-             "step": step, "refresh": refresh}
+             "step": step, "refresh": refresh,
+             "dec_bwd_grad": lambda: train.decoder_backward(blk, h_seq, g_y, cache=cache, y=out, grads=dgrads),
+             "dec_bwd_kernel": lambda: train.dec_bwd(g_y, y_, e_, d_, s1, w9, s2, w3, s3),
+             "pix_gemm": lambda: train.pix_gemm(ga_, hn, out=g1, row_scale=s1, w=pw.weight.detach(), rowdot=rowdot),
+             "dec_sums": lambda: train.dec_sums(g_y, y_, e_, d_, ga_, w3, s3),
+             "dec_finish": lambda: L.check(lib.uavsal_dec_finish(C.byref(fin), stream), "uavsal_dec_finish"),
+             "refresh_dec": refresh_dec}
     for k, fn in cases.items():
         res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    alt = {"step": [], "step_dec": []}                       # the two steps alternated in the same run
+    for _ in range(repeats):
+        alt["step"].append(per_call(step, iters))
+        alt["step_dec"].append(per_call(step_dec, iters))
+    res["step_alt_ms"], res["step_dec_ms"] = 1e3 * min(alt["step"]), 1e3 * min(alt["step_dec"])
+    for q in blk.parameters():
+        q.grad = None
+    pflop = 2.0 * 1536 * 256 * T * h * w
+    gd = L.PixGemmDesc()
+    gd.K, gd.M, gd.N = T * h * w, 1536, 256
+    res["pix_gemm_shares"] = int(lib.uavsal_pix_gemm_shares(C.byref(gd)))
+    res["pix_gemm_tflops"] = pflop / (res["pix_gemm_ms"] * 1e-3) / 1e12
+    res["pix_gemm_of_peak"] = res["pix_gemm_tflops"] / PEAK_TFLOPS
+    nbytes = 3.0 * 1536 * 4 * T * h * w
+    res["dec_sums_slabs"] = slabs
+    res["dec_sums_gbs"] = nbytes / (res["dec_sums_ms"] * 1e-3) / 1e9
+    res["dec_bwd_kernel_gbs"] = nbytes / (res["dec_bwd_kernel_ms"] * 1e-3) / 1e9
     res["bptt_ms"] = res["twa_backward_ms"] - res["wgrad_ms"]
     flop = 2.0 * 256 * 4608 * T * h * w
     res["wgrad_gflop"] = flop / 1e9
