@@ -107,8 +107,8 @@ def _pick_bias_channel(pre, b, act):
     return int(torch.argmax(b.abs() * live.double()))
 
 
-def stage(v, B, w, s, b, act, stride=1, padding=0, dilation=1, groups=1, cbias=None, mut=None):
-    """One conv + affine + activation stage on (values, abs-bound) pairs."""
+def stage(v, B, w, s, b, act, stride=1, padding=0, dilation=1, groups=1, cbias=None, mut=None, pre=None):
+    """One conv + affine + activation stage on (values, abs-bound) pairs (`mut`, `pre`: see activate)."""
     y = F.conv2d(v, w, stride=stride, padding=padding, dilation=dilation, groups=groups)
     yb = F.conv2d(B, w.abs(), stride=stride, padding=padding, dilation=dilation, groups=groups)
     if cbias is not None:
@@ -118,12 +118,16 @@ def stage(v, B, w, s, b, act, stride=1, padding=0, dilation=1, groups=1, cbias=N
         if mut == "bias":
             c = _pick_bias_channel(y, b, act)
             y[:, c] -= b[c]
-    return activate(y, yb, act)
+    return activate(y, yb, act, mut, pre)
 
 
-def activate(y, yb, act):
+def activate(y, yb, act, mut=None, pre=None):
+    """`mut` = "no_hi": a ReLU6 loses its upper clamp (the wrong reference of a kernel that computes max(v, 0));
+    `pre`: a list that receives the pre-activation of every ReLU6."""
     if act == ACT_RELU6:
-        return y.clamp(0.0, 6.0), yb
+        if pre is not None:
+            pre.append(y)
+        return (y.clamp(min=0.0) if mut == "no_hi" else y.clamp(0.0, 6.0)), yb
     if act == ACT_SIGMOID:
         return torch.sigmoid(y), yb / 4
     return y, yb
@@ -149,7 +153,7 @@ def _split_atol(prec, s, w, xmax, k):
 
 
 # ----------------------------------------------------------------------------------------------------------- GEMM-type ops
-def ref_conv(rec, a, res=None, aux=None, mut=None):
+def ref_conv(rec, a, res=None, aux=None, mut=None, pre=None):
     """conv1 / conv3 launches: AFFINE (BN, act, residual), n_group, fused depthwise loader, TWA and LSTM epilogues.
     `a`: the A operand ([n, groups * Cin, H, W] for n_group; the expanded tensor for a fused depthwise), `res` / `aux` the
     epilogue operands (TWA: res = x_t, aux = the hoisted x half, h_{t-1} = a; LSTM: res = c_{t-1}, aux = the x half)."""
@@ -161,12 +165,13 @@ def ref_conv(rec, a, res=None, aux=None, mut=None):
     s, b = fold_bn(rec["bn"], dev)
     pad = 1 if taps == 9 else 0
     x = mutate_input(a, mut if mut in ("chan", "row") else None)
+    hi = mut if mut == "no_hi" else None
     B = a.abs()
     rt = 0.0
     if rec.get("dw") is not None:                         # depthwise 3x3 + BN + ReLU6 inside the loader
         dwc, dwbn, dstride = rec["dw"]
         ds, db = fold_bn(dwbn, dev)
-        x, B = stage(x, B, _w(dwc, dev), ds, db, ACT_RELU6, stride=dstride, padding=1, groups=a.shape[1])
+        x, B = stage(x, B, _w(dwc, dev), ds, db, ACT_RELU6, stride=dstride, padding=1, groups=a.shape[1], mut=hi, pre=pre)
         rt += rtol("f32", 9)
     k = (w.shape[1]) * taps
     rt += rtol(prec, k)
@@ -181,10 +186,10 @@ def ref_conv(rec, a, res=None, aux=None, mut=None):
             if mut == "bias":
                 c = _pick_bias_channel(y, b, act)
                 y[:, c] -= b[c]
-        y, yb = activate(y, yb, act)
+        y, yb = activate(y, yb, act, hi, pre)
     else:
         y, yb = stage(x, B, w, s, b, act if epi == EPI_AFFINE else ACT_NONE, padding=pad, cbias=cbias,
-                      mut=mut if mut == "bias" else None)
+                      mut=mut if mut in ("bias", "no_hi") else None, pre=pre)
     atol = _split_atol(prec, s, w, xmax, k)
     if epi == EPI_AFFINE:
         E = y.abs()
@@ -260,7 +265,7 @@ def wino_conv(x, w, r, absolute=False):
     return y[:, :, :hh, :ww].contiguous()
 
 
-def ref_wino(rec, a, twa=None, mut=None):
+def ref_wino(rec, a, twa=None, mut=None, pre=None):
     """Winograd triple (input transform, plane GEMM, output transform with BN / ReLU6 or the ConvTWA update), against the
     direct 3x3 convolution; `twa` = (x_t, pre) with h_{t-1} = a."""
     dev = a.device
@@ -280,12 +285,12 @@ def ref_wino(rec, a, twa=None, mut=None):
         if mut == "bias":
             c = _pick_bias_channel(y, b, rec["act"])
             y[:, c] -= b[c]
-    y, yb = activate(y, yb, rec["act"])
+    y, yb = activate(y, yb, rec["act"], mut, pre)
     return Ref(y, yb, y.abs(), None, rt, 0.0)
 
 
 # ------------------------------------------------------------------------------------------------------ depthwise family
-def ref_dw(rec, a, mut=None):
+def ref_dw(rec, a, mut=None, pre=None):
     """Depthwise 3x3 + BN + ReLU6, stride, dilation (pad = dilation), or channel groups with their own dilation."""
     dev = a.device
     x = mutate_input(a, mut if mut in ("chan", "row") else None)
@@ -293,45 +298,51 @@ def ref_dw(rec, a, mut=None):
     if isinstance(conv, (list, tuple)):
         cg = a.shape[1] // len(conv)
         outs = [stage(x[:, i * cg:(i + 1) * cg], a[:, i * cg:(i + 1) * cg].abs(), _w(c_, dev), *fold_bn(b_, dev), ACT_RELU6,
-                      padding=d_, dilation=d_, groups=cg, mut=mut if (mut == "bias" and i == 0) else None)
+                      padding=d_, dilation=d_, groups=cg, mut=mut if (mut == "bias" and i == 0) or mut == "no_hi" else None,
+                      pre=pre)
                 for i, (c_, b_, d_) in enumerate(zip(conv, bn, dil))]
         y, yb = torch.cat([o[0] for o in outs], 1), torch.cat([o[1] for o in outs], 1)
     else:
         y, yb = stage(x, a.abs(), _w(conv, dev), *fold_bn(bn, dev), ACT_RELU6, stride=stride, padding=dil, dilation=dil,
-                      groups=a.shape[1], mut=mut if mut == "bias" else None)
+                      groups=a.shape[1], mut=mut if mut in ("bias", "no_hi") else None, pre=pre)
+    if pre:                                               # (channel groups: one stage)
+        pre[:] = [torch.cat(pre, 1)]
     return Ref(y, yb, y.abs(), None, rtol("f32", 9), 0.0)
 
 
-def ref_dw_dot(rec, a, mut=None):
+def ref_dw_dot(rec, a, mut=None, pre=None):
     """Depthwise 3x3 + BN + ReLU6 -> projection to one channel + BN + act (conv_out_st)."""
     dev = a.device
     dwc, dwbn = rec["dw"]
     x = mutate_input(a, mut if mut in ("chan", "row") else None)
-    d, db = stage(x, a.abs(), _w(dwc, dev), *fold_bn(dwbn, dev), ACT_RELU6, padding=1, groups=a.shape[1])
+    hi = mut if mut == "no_hi" else None
+    d, db = stage(x, a.abs(), _w(dwc, dev), *fold_bn(dwbn, dev), ACT_RELU6, padding=1, groups=a.shape[1], mut=hi, pre=pre)
     s, b = fold_bn(rec["bn"], dev)
     y, yb = stage(d, db, _w(rec["conv"], dev), s, b, ACT_NONE)
     if mut == "bias":
         y = y - b[0]
-    y, yb = activate(y, yb, rec["act"])
+    y, yb = activate(y, yb, rec["act"], hi, pre)
     return Ref(y, yb, y.abs(), None, rtol("f32", 9) + rtol("f32", a.shape[1]), 0.0)
 
 
-def ref_fused_ir(rec, a, mut=None):
+def ref_fused_ir(rec, a, mut=None, pre=None):
     """A whole inverted-residual block: expand 1x1 + BN + ReLU6 -> depthwise 3x3 (stride) + BN + ReLU6 -> project 1x1 + BN
     (+ the block input)."""
     dev = a.device
     blk = rec["blk"]
     seq = blk.conv
     x = mutate_input(a, mut if mut in ("chan", "row") else None)
+    hi = mut if mut == "no_hi" else None
     B = a.abs()
     rt = 0.0
     if blk.expand_ratio != 1:
-        x, B = stage(x, B, _w(seq[0][0], dev), *fold_bn(seq[0][1], dev), ACT_RELU6)
+        x, B = stage(x, B, _w(seq[0][0], dev), *fold_bn(seq[0][1], dev), ACT_RELU6, mut=hi, pre=pre)
         rt += rtol("f32", a.shape[1])
         dwc, dwbn, pl, plbn = seq[1][0], seq[1][1], seq[2], seq[3]
     else:
         dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1], seq[2]
-    x, B = stage(x, B, _w(dwc, dev), *fold_bn(dwbn, dev), ACT_RELU6, stride=blk.stride, padding=1, groups=x.shape[1])
+    x, B = stage(x, B, _w(dwc, dev), *fold_bn(dwbn, dev), ACT_RELU6, stride=blk.stride, padding=1, groups=x.shape[1], mut=hi,
+                 pre=pre)
     y, yb = stage(x, B, _w(pl, dev), *fold_bn(plbn, dev), ACT_NONE, mut=mut if mut == "bias" else None)
     rt += rtol("f32", 9) + rtol("f32", x.shape[1])
     if blk.use_res_connect:
@@ -339,7 +350,7 @@ def ref_fused_ir(rec, a, mut=None):
     return Ref(y, yb, y.abs(), None, rt, 0.0)
 
 
-def ref_stem(rec, x, mut=None):
+def ref_stem(rec, x, mut=None, pre=None):
     """features.0: 3x3 stride-2 conv 3 -> 32 + BN + ReLU6 of the caller's NCHW frames (uint8: normalised on load)."""
     dev = x.device
     rt = rtol("f32", 27)
@@ -351,7 +362,7 @@ def ref_stem(rec, x, mut=None):
     xm = mutate_input(x, mut if mut in ("chan", "row") else None)
     s, b = fold_bn(rec["bn"], dev)
     w = _w(rec["conv"], dev)
-    y, yb = stage(xm, x.abs(), w, s, b, ACT_RELU6, stride=2, padding=1, mut=mut if mut == "bias" else None)
+    y, yb = stage(xm, x.abs(), w, s, b, ACT_RELU6, stride=2, padding=1, mut=mut if mut in ("bias", "no_hi") else None, pre=pre)
     return Ref(y, yb, y.abs(), None, rt, 0.0)
 
 

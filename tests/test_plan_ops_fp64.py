@@ -16,12 +16,17 @@ A Winograd triple (input transform, plane GEMM, output transform) is checked as 
 `test_dispatch_cover` walks the configurations of `plan_census.WALKS` the same way: together with the cases above they reach every
 dispatch signature (kernel instance x edge path, tests/plan_census.py) of the model sizes in `plan_census.DOMAIN`; the first op of
 every signature that no earlier walk visits carries the wrong references too.
+
+`test_saturated_relu6_walk` walks two small plans whose BatchNorms saturate the ReLU6 behind them (tests/saturate_bn.py): every op
+with a ReLU6 stage holds the share condition of tests/act_ref64.py in its reference and rejects the reference without the
+upper clamps (`mut="no_hi"`).
 """
 import time
 
 import pytest
 import torch
 
+import act_ref64 as A
 import plan_census as PC
 import plan_ref64 as R
 from iip_uavsal_saliency_amd import engine as E
@@ -71,9 +76,26 @@ def _rd(eng, d, images=None, shadow=False):
     return E.read_view(eng, d, shadow=shadow, images=images, device="cuda")
 
 
+def relu6_kind(rec):
+    """The kind under which the saturated walk counts an op with a ReLU6 stage ("" if it has none)."""
+    k = rec["kind"]
+    if "triple" in rec:                             # a part of a Winograd triple: counted with the triple's last op
+        return ""
+    if k in ("dw", "dw_dot", "fused_ir", "stem"):
+        return k
+    if k in ("conv1", "conv3"):
+        if rec.get("dw") is not None:
+            return k + "/fused-dw"
+        return k if rec["epi"] == R.EPI_AFFINE and rec["act"] == R.ACT_RELU6 else ""
+    if k == "wino":
+        return "wino" if rec["twa"] is None and rec["act"] == R.ACT_RELU6 else ""
+    return ""
+
+
 class Walk:
-    def __init__(self, eng, tag, mutations=None):
+    def __init__(self, eng, tag, mutations=None, saturated=False):
         self.eng, self.tag, self.mutations = eng, tag, mutations or {}
+        self.sat = {} if saturated else None        # kind -> [ops with a ReLU6 stage checked, smallest `no_hi` err / bound]
         self.worst = {}                 # kind -> worst err / bound
         self.step_cmp = {}              # recurrence step -> (max |err|, worst err / the direct-f32 bound of that step)
         self.checked = 0
@@ -113,6 +135,22 @@ class Walk:
             self.mut_results[(name, m)] = ratio
             assert ratio > 1.0, "%s %s: the wrong reference '%s' passes (%.3g x the bound): the bound is too loose" % (
                 self.tag, name, m, ratio)
+
+    def _clamps(self, name, kind, got, bnd, fn):
+        """Saturated walk, an op with a ReLU6 stage: the share condition (tests/act_ref64.py) holds on the float64
+        pre-activations of every such stage of its reference, and the reference without the upper clamps is rejected.
+        `fn(mut, pre)` -> Ref."""
+        if self.sat is None:
+            return
+        pre = []
+        fn(None, pre)
+        assert pre, "%s %s: no ReLU6 stage in the reference" % (self.tag, name)
+        for k, v in enumerate(pre):
+            assert A.share_ok(v), "%s %s (%s) ReLU6 stage %d: (n, <= 0, >= 6, inside) = %s" % (self.tag, name, kind, k, A.shares(v))
+        ratio = _ratio((got - fn("no_hi", None).y).abs(), bnd)
+        n, least = self.sat.get(kind, (0, float("inf")))
+        self.sat[kind] = (n + 1, min(least, ratio))
+        assert ratio > 1.0, "%s %s (%s): the reference without the upper clamp passes (%.3g x the bound)" % (self.tag, name, kind, ratio)
 
     def _check_out_shadow(self, name, od, got, images):
         if od.sp is None or od.buf is None:
@@ -186,6 +224,8 @@ class Walk:
             self._step_cmp(name, got, R.ref_conv(dict(rec, prec="f32"), inputs[-1], res=res, aux=aux))
         self._check_out_shadow(name, od, got if rec["epi"] != R.EPI_LSTM else None, imgs)
         self._mutants(name, got, bnd, lambda m: R.ref_conv(rec, inputs[0], res=res, aux=aux, mut=m))
+        if relu6_kind(rec):
+            self._clamps(name, relu6_kind(rec), got, bnd, lambda m, pre: R.ref_conv(rec, inputs[0], res=res, aux=aux, mut=m, pre=pre))
 
     op_conv3 = op_conv1
 
@@ -215,6 +255,8 @@ class Walk:
                              twa[1], twa[0], a, R.rtol("f32", 9 * w.shape[1]))
             self._step_cmp(name, got, d)
         self._mutants(name, got, bnd, lambda m: R.ref_wino(rec, a, twa, mut=m))
+        if relu6_kind(rec):
+            self._clamps(name, relu6_kind(rec), got, bnd, lambda m, pre: R.ref_wino(rec, a, twa, mut=m, pre=pre))
 
     def op_dw(self, i, last, rec):
         eng, name = self.eng, rec["name"]
@@ -232,6 +274,7 @@ class Walk:
             got = _rd(eng, od, imgs)
             bnd = self._judge(name, "dw", got, ref)
         self._mutants(name, got, bnd, lambda m: R.ref_dw(rec, a, mut=m))
+        self._clamps(name, "dw", got, bnd, lambda m, pre: R.ref_dw(rec, a, mut=m, pre=pre))
 
     def op_dw_dot(self, i, last, rec):
         eng, name = self.eng, rec["name"]
@@ -242,6 +285,7 @@ class Walk:
         got = _rd(eng, rec["out"], imgs)
         bnd = self._judge(name, "dw_dot", got, R.ref_dw_dot(rec, a))
         self._mutants(name, got, bnd, lambda m: R.ref_dw_dot(rec, a, mut=m))
+        self._clamps(name, "dw_dot", got, bnd, lambda m, pre: R.ref_dw_dot(rec, a, mut=m, pre=pre))
 
     def op_fused_ir(self, i, last, rec):
         eng, name = self.eng, rec["name"]
@@ -252,6 +296,7 @@ class Walk:
         got = _rd(eng, rec["out"], imgs)
         bnd = self._judge(name, "fused_ir", got, R.ref_fused_ir(rec, a))
         self._mutants(name, got, bnd, lambda m: R.ref_fused_ir(rec, a, mut=m))
+        self._clamps(name, "fused_ir", got, bnd, lambda m, pre: R.ref_fused_ir(rec, a, mut=m, pre=pre))
 
     def op_stem(self, i, last, rec):
         eng, name = self.eng, rec["name"]
@@ -262,6 +307,7 @@ class Walk:
         got = _rd(eng, rec["out"], imgs)
         bnd = self._judge(name, "stem/u8" if rec["u8"] else "stem", got, R.ref_stem(rec, x))
         self._mutants(name, got, bnd, lambda m: R.ref_stem(rec, x, mut=m))
+        self._clamps(name, "stem", got, bnd, lambda m, pre: R.ref_stem(rec, x, mut=m, pre=pre))
 
     def op_bilinear(self, i, last, rec):
         eng, name = self.eng, rec["name"]
@@ -342,7 +388,7 @@ def _engine(m, C, T, H, W, prec, static=False, u8=False):
                      static_priors=static)
 
 
-def _walk(m, C, T, H, W, prec, tag, static=False, u8=False, calls=1, mutations=None, rand_state=False):
+def _walk(m, C, T, H, W, prec, tag, static=False, u8=False, calls=1, mutations=None, rand_state=False, saturated=False):
     """`mutations`: {op name: wrong references}, or a function of the engine that returns it; `rand_state`: the call starts from
     a non-zero recurrent state (with the zero state the first step's h operand is all zeros, and so is any mutation of it)."""
     eng = _engine(m, C, T, H, W, prec, static, u8)
@@ -361,7 +407,7 @@ def _walk(m, C, T, H, W, prec, tag, static=False, u8=False, calls=1, mutations=N
         x, cb0, cb1 = _inputs(C * T, H, W, 0, u8, t0=(call + 1) * T)
     eng._bind_in_place(x, cb0, cb1, state, cstate, lstm)
     t0 = time.perf_counter()
-    w = Walk(eng, tag, mutations).run()
+    w = Walk(eng, tag, mutations, saturated).run()
     print(w.summary() + " (%.1f s)" % (time.perf_counter() - t0))
     return w
 
@@ -433,6 +479,23 @@ def test_ragged_small_maps(prec):
     """C: 72x104, 1 x 3 -- 9x13 feature maps (f32 with uint8 frames: the stem's normalising path)."""
     m = _model(3)
     _walk(m, 1, 3, 72, 104, prec, "C " + prec, u8=prec == "f32")
+
+
+@pytest.mark.parametrize("prec", ["f32", "f16x3"])
+def test_saturated_relu6_walk(prec):
+    """C and D's sizes (72x104 1 x 3, 96x160 1 x 4) with BatchNorms that saturate the ReLU6 behind them (tests/saturate_bn.py):
+    every op with a ReLU6 stage keeps its bound, has both clamps populated in its reference's pre-activations, and rejects the
+    reference whose ReLU6 stages lack the upper clamp."""
+    import saturate_bn
+    for T, H, W in ((3, 72, 104), (4, 96, 160)):
+        m = _model(T)
+        assert saturate_bn.saturate_relu6_bn(m) > 0
+        w = _walk(m, 1, T, H, W, prec, "saturated %dx%d %s" % (H, W, prec), saturated=True)
+        present = {relu6_kind(r) for r in w.eng.op_args if r["kind"] not in SKIP} - {""}
+        assert present >= {"conv1", "dw", "dw_dot", "fused_ir", "stem"} and present & {"wino", "conv3"}, present
+        assert set(w.sat) == present and all(n > 0 for n, _ in w.sat.values()), (w.sat, present)
+        print("[plan-ops-fp64] saturated %dx%d %s: ops with a ReLU6 stage and smallest no_hi err/bound: %s" % (
+            H, W, prec, ", ".join("%s %d %.3g" % (k, n, r) for k, (n, r) in sorted(w.sat.items()))))
 
 
 def test_persistent_state_second_call():
