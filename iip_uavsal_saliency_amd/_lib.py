@@ -263,6 +263,28 @@ class DecFinishDesc(C.Structure):
 DEC_NSUM = 12                 # UAVSAL_DEC_NSUM: sums per channel in the workspace of uavsal_dec_sums (csrc/train_decoder.hip)
 TRAIN_DECODER_DESC_TYPES = [PixGemmDesc, DecSumsDesc, DecFinishDesc]        # sized by uavsal_train_decoder_sizeof_desc
 
+
+class IrBwdDesc(C.Structure):
+    _fields_ = [("gd", _f), ("d", _f), ("e", _f), ("wd9", _f), ("s2", _f), ("ga", _f),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
+
+
+class IrSumsDesc(C.Structure):
+    _fields_ = [("gd", _f), ("d", _f), ("e", _f), ("ga", _f), ("go", _f), ("ldgo", C.c_int32),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ch", C.c_int32), ("Co", C.c_int32)]
+
+
+class IrFinishDesc(C.Structure):
+    _fields_ = [("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("rowdot1", C.c_void_p), ("rowdot3", C.c_void_p)] + [(n, _f) for n in (
+        "wd", "s2", "r1", "mu1", "r2", "mu2", "r3", "mu3",
+        "g_gamma1", "g_beta1", "g_wd", "g_gamma2", "g_beta2", "g_gamma3", "g_beta3")] + [
+        ("Ch", C.c_int32), ("Co", C.c_int32), ("slabs", C.c_int32), ("accumulate", C.c_int32)]
+
+
+IR_NSUM = 11                  # UAVSAL_IR_NSUM: sums per hidden channel in the workspace of uavsal_ir_sums (csrc/train_block.hip)
+BLOCK_DESC_TYPES = [IrBwdDesc, IrSumsDesc, IrFinishDesc]        # sized by uavsal_block_sizeof_desc
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -309,6 +331,13 @@ SYMBOLS = [
     ("uavsal_dec_sums", C.c_int, [C.POINTER(DecSumsDesc), C.c_void_p]),
     ("uavsal_dec_finish", C.c_int, [C.POINTER(DecFinishDesc), C.c_void_p]),
     ("uavsal_train_decoder_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_ir_bwd", C.c_int, [C.POINTER(IrBwdDesc), C.c_void_p]),
+    ("uavsal_ir_sums_workspace_bytes", C.c_int64, [C.POINTER(IrSumsDesc)]),
+    ("uavsal_ir_sums_slabs", C.c_int, [C.POINTER(IrSumsDesc)]),
+    ("uavsal_ir_sums_slab_rows", C.c_int, [C.POINTER(IrSumsDesc)]),
+    ("uavsal_ir_sums", C.c_int, [C.POINTER(IrSumsDesc), C.c_void_p]),
+    ("uavsal_ir_finish", C.c_int, [C.POINTER(IrFinishDesc), C.c_void_p]),
+    ("uavsal_block_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -380,7 +409,8 @@ def load():
             raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (
                 t.__name__, C.sizeof(t), lib.uavsal_sizeof_desc(i)))
     for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES),
-                          (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES)):
+                          (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES),
+                          (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

@@ -7,8 +7,8 @@
 //   chains  after UAVSAL_WGRAD_CHAIN / 32 K steps (and at the end) the chain's tile is added to a second fp32 register tile
 //           and a new chain starts: no accumulation chain is longer than UAVSAL_WGRAD_CHAIN products.
 // The operand loaders are the parameter: `fa(g)` / `fb(g)` return the address of the four floats this thread loads (column
-// (tid & 31) * 4 of the tile) of the A / B row of global pixel g (p0 <= g < p1), or nullptr for a row of zeros; rows behind
-// p1 are zeros and are never asked for.
+// (tid & 31) * 4 of the tile) of the A / B row of global pixel g (p0 <= g < p1), or nullptr for zeros (a whole row, or this
+// thread's four columns: uavsal_pix_gemm's last N tile may end at column 64); rows behind p1 are zeros and are never asked for.
 #pragma once
 #include "common.h"
 

@@ -38,7 +38,7 @@ struct PgK {
     double* rowdot;
     float *ws, *out;
     long long K;
-    int lda, ldb, ldw, ldo, M, N, mt_n;
+    int lda, ldb, ldw, ldo, M, N, mt_n, nt_n;
     int cps, shares, accumulate;
 };
 
@@ -56,9 +56,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     f32x16 tot[2][2];
     const float* arow = k.a + mt * kTile + lc;
     const float* brow = k.b + nt * kTile + lc;
+    const bool bok = nt * kTile + lc < k.N;                   // N % 64 == 0: the last N tile may be half empty
     pixgemm::tile_loop(p0, p1,
         [&](long long g) { return arow + g * k.lda; },
-        [&](long long g) { return brow + g * k.ldb; }, tot);
+        [&](long long g) { return bok ? brow + g * k.ldb : nullptr; }, tot);
     float* w = k.ws + (long long)share * k.M * k.N;           // ws [share][m][n]
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
             for (int r = 0; r < 16; ++r) {
                 const int m = mt * kTile + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 const int n = nt * kTile + wn + j * 32 + (lane & 31);
-                w[(long long)m * k.N + n] = tot[i][j][r];
+                if (n < k.N) w[(long long)m * k.N + n] = tot[i][j][r];
             }
 }
 
@@ -103,10 +104,11 @@ __global__ __launch_bounds__(256) void pix_gemm_reduce_kernel(const PgK k) {
 }
 
 bool pg_plan(const uavsal_pix_gemm_desc* d, PgK& k) {
-    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || (d->M % kTile) || (d->N % kTile)) return false;
-    if ((long long)d->M * d->N > 0x7fffffffll || (long long)(d->M / kTile) * (d->N / kTile) > 65535) return false;
-    k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = d->M / kTile;
-    return pixgemm::split(k.K, k.mt_n * (d->N / kTile), k.cps, k.shares);
+    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || (d->M % kTile) || (d->N % (kTile / 2))) return false;
+    const int nt_n = (d->N + kTile - 1) / kTile;
+    if ((long long)d->M * d->N > 0x7fffffffll || (long long)(d->M / kTile) * nt_n > 65535) return false;
+    k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = d->M / kTile; k.nt_n = nt_n;
+    return pixgemm::split(k.K, k.mt_n * nt_n, k.cps, k.shares);
 }
 
 // ------------------------------------------------------------------------------------------------ channel sums
@@ -285,7 +287,7 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     if (!d || !d->a || !d->b || !d->ws || !d->out) return UAVSAL_EINVAL;
     if (d->K <= 0 || d->M <= 0 || d->N <= 0) return UAVSAL_EINVAL;
     if (d->rowdot && !d->w) return UAVSAL_EINVAL;
-    if ((d->M % kTile) || (d->N % kTile)) return UAVSAL_ESHAPE;
+    if ((d->M % kTile) || (d->N % (kTile / 2))) return UAVSAL_ESHAPE;
     PgK k;
     if (!pg_plan(d, k)) return UAVSAL_ESHAPE;
     if (d->ws_bytes < uavsal_pix_gemm_workspace_bytes(d)) return UAVSAL_EINVAL;
@@ -296,7 +298,7 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     k.a = d->a; k.b = d->b; k.row_scale = d->row_scale; k.w = d->w; k.rowdot = d->rowdot; k.ws = d->ws; k.out = d->out;
     k.lda = d->lda; k.ldb = d->ldb; k.ldw = d->ldw; k.ldo = d->ldo;
     k.accumulate = d->accumulate != 0;
-    hipLaunchKernelGGL(pix_gemm_kernel, dim3((unsigned)(k.mt_n * (k.N / kTile)), (unsigned)k.shares), dim3(256), 0,
+    hipLaunchKernelGGL(pix_gemm_kernel, dim3((unsigned)(k.mt_n * k.nt_n), (unsigned)k.shares), dim3(256), 0,
                        (hipStream_t)stream, k);
     hipLaunchKernelGGL(pix_gemm_reduce_kernel, dim3((unsigned)k.M), dim3(256), 0, (hipStream_t)stream, k);
     return uavsal_launch_status();

@@ -231,12 +231,15 @@ class Engine:
     _arena = property(lambda self: self.arena.buf)              # the pool (one float32 tensor)
     arena_stats = property(lambda self: self.arena.stats)
     TAP_NAMES = ("c3", "c4", "c5", "sfnet", "st0", "st1", "fust_in_cb", "prefuse", "rnn")
+    # kept like the taps, but read back only when the caller asks for them by handing a `taps` dict that already holds the
+    # name (any value): fucbst_layer's whole input, as ONE channels-last copy (train.recurrence_step(fuse=True) reads it NHWC)
+    TAPS_ON_REQUEST = ("fu320",)
 
     def _size(self):
         """Pass 1: sizes the shared scratch and lays the arena out (nothing allocated, nothing recorded)."""
         self.rec.begin(dry=True)
         record_forward(self.rec, self)
-        self.rec.place(self.TAP_NAMES if self.keep_taps else ())      # (what `tap` reads back after the run stays live to the end)
+        self.rec.place(self.TAP_NAMES + self.TAPS_ON_REQUEST if self.keep_taps else ())      # (what `tap` reads back after the run stays live to the end)
 
     def arena_layout(self):
         """[(buffer id, offset, floats, first op, last op, lane key, first / last op in recording order)], by offset."""
@@ -453,6 +456,11 @@ class Engine:
             if taps is not None:
                 if not self.keep_taps:
                     raise RuntimeError("engine was built without taps")
+                for k in self.TAPS_ON_REQUEST:
+                    if k in taps:
+                        if k not in self.named:
+                            raise RuntimeError("this plan has no buffer %r to tap (a model without priors)" % k)
+                        taps[k] = self.tap(k, channels_last=True)
                 for k in self.TAP_NAMES:
                     if k in self.named:          # (no "fust_in_cb" in a model without priors)
                         taps[k] = self.tap(k)
@@ -520,14 +528,16 @@ class Engine:
         torch.cuda.synchronize(self.device)
         return all(int(ws[:65536].view(torch.int32).abs().sum().item()) == 0 for ws in self._sk_ws.values())
 
-    def tap(self, name) -> torch.Tensor:
-        """NCHW copy of a named NHWC buffer (debug / parity tests)."""
+    def tap(self, name, channels_last=False) -> torch.Tensor:
+        """NCHW copy of a named NHWC buffer (debug / parity tests); `channels_last`: the copy keeps the buffer's NHWC memory
+        (shape NCHW, `torch.channels_last` strides), which costs no transposition."""
         v = self.named[name]
         base = v.t.tensor() if isinstance(v.t, _ArenaRef) else v.t
         t = base.view(v.n, v.h, v.w, v.ld) if base.numel() == v.n * v.h * v.w * v.ld else None
         if t is None:
             raise RuntimeError("tap %s is not a dense buffer" % name)
-        return t[..., v.coff:v.coff + v.c].permute(0, 3, 1, 2).contiguous()
+        t = t[..., v.coff:v.coff + v.c]
+        return t.contiguous().permute(0, 3, 1, 2) if channels_last else t.permute(0, 3, 1, 2).contiguous()
 
     def run_ops(self, first, last):
         """Launch ops [first, last) once, flat on the current stream (no lanes, no staging): puts the activations an op reads

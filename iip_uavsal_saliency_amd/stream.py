@@ -392,24 +392,26 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     the reference on purpose: the model stays in `eval()` -- every other stage is frozen and every BatchNorm uses its running
     statistics.  A group's loss is the loss BEFORE its step, as `loss.data.item()` is there.
     `stages`: `("rnn",)` or `("rnn", "decoder")`: with the decoder, `recurrence_step(..., decoder=True)` also sets the
-    gradients of `model.conv_out_st` (the optimiser then holds its parameters too) and both stages are refreshed."""
+    gradients of `model.conv_out_st` (the optimiser then holds its parameters too) and both stages are refreshed.
+    `"fuse"` (after `"rnn"` and, when present, `"decoder"`): `recurrence_step(..., fuse=True)` also sets the gradients of
+    the fusion block in front of the recurrence (`train.fuse_block`: `model.fucbst_layer[0]` with any prior enabled, else
+    `model.fust_layer[0]`), and that block's container is refreshed with the other trained stages."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
     stages = tuple(stages)
-    if stages not in (("rnn",), ("rnn", "decoder")):
-        raise ValueError("stages must be ('rnn',) or ('rnn', 'decoder'), got %r" % (stages,))
+    if stages not in (("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse")):
+        raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, got %r" % (stages,))
+    kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
         optimizer.zero_grad()
-        if "decoder" in stages:
-            loss, _, state = _train.recurrence_step(model, x, cb, state, y, criterion, decoder=True)
-            optimizer.step()
-            model.refresh_weights(model.rnn, model.conv_out_st)
-            return loss, state
-        loss, _, state = _train.recurrence_step(model, x, cb, state, y, criterion)
+        loss, _, state = _train.recurrence_step(model, x, cb, state, y, criterion, **kw)
         optimizer.step()
-        model.refresh_weights(model.rnn)
+        mods = [model.rnn] + ([model.conv_out_st] if "decoder" in kw else [])
+        if "fuse" in kw:
+            mods.append(model.fucbst_layer if model.num_cb else model.fust_layer)
+        model.refresh_weights(*mods)
         return loss, state
     return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,
                              bgr, gaze_layout, prepare, step)

@@ -11,7 +11,10 @@ bias, so ITS gradient is the same in both modes.
 
 A second stage can be trained with it: the decoder `model.conv_out_st` (`decoder_backward`, `decoder_param_grads`,
 `recurrence_step(decoder=True)`; csrc/train_decoder.hip: `uavsal_pix_gemm`, `uavsal_dec_sums`, `uavsal_dec_finish`), its
-BatchNorms on their running statistics.
+BatchNorms on their running statistics.  A third one as well: the fusion block that produces the recurrence's input
+(`fuse_block`: `model.fucbst_layer[0]`, or `model.fust_layer[0]` without priors), through the backward of a general
+inverted-residual block (`block_backward`, `block_param_grads`, `recurrence_step(fuse=True)`; csrc/train_block.hip:
+`uavsal_ir_bwd`, `uavsal_ir_sums`, `uavsal_ir_finish`, and `uavsal_pix_gemm` for both 1x1 weight gradients).
 
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
@@ -325,6 +328,192 @@ def decoder_backward(block, h_seq, grad_out, cache=None, y=None, parts=None, gra
     return g.permute(0, 3, 1, 2), grads
 
 
+BLOCK_PARAMS = DECODER_PARAMS                                        # a dwBlock with an expand conv: the same nine names
+
+
+def _block_parts(block):
+    """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual block the block backward covers, or a RuntimeError."""
+    seq = getattr(block, "conv", None)
+    if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4 or getattr(block, "stride", None) != 1
+            or getattr(block, "dilation", None) != 1 or seq[1][0].stride != (1, 1) or seq[1][0].dilation != (1, 1)):
+        raise RuntimeError("block_backward takes a dwBlock with an expand conv, stride 1 and dilation 1 "
+                           "(expand 1x1, depthwise 3x3, projection 1x1)")
+    pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
+    hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    if cout % 128 or hid % 64 or cin % 64:
+        raise RuntimeError("block_backward needs Cout %% 128 == 0, hidden %% 64 == 0 and Cin %% 64 == 0, got %d -> %d -> %d"
+                           % (cin, hid, cout))
+    if block.training:
+        raise RuntimeError("the block's BatchNorms use their running statistics: call model.eval()")
+    return pw, pwbn, dwc, dwbn, pl, plbn
+
+
+def _block_grad_out(grad_out, x, cout):
+    T, hh, ww, _ = x.shape
+    if (not torch.is_tensor(grad_out) or not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.device != x.device
+            or tuple(grad_out.shape) != (T, cout, hh, ww)):
+        raise RuntimeError("grad_out must be a float32 cuda tensor [%d,%d,%d,%d]" % (T, cout, hh, ww))
+    return _nhwc(grad_out, "grad_out", cout)
+
+
+def _block_grad_tensors(block, out, accumulate):
+    params = dict(block.named_parameters())
+    if sorted(params) != sorted(BLOCK_PARAMS):
+        raise RuntimeError("the block's parameters must be %r" % (BLOCK_PARAMS,))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `out`")
+        out = {n: torch.empty_like(params[n], memory_format=torch.contiguous_format) for n in BLOCK_PARAMS}
+    for n in BLOCK_PARAMS:
+        t, q = out.get(n), params[n]
+        if (not torch.is_tensor(t) or t.shape != q.shape or t.dtype != torch.float32 or t.device != q.device
+                or not t.is_contiguous()):
+            raise RuntimeError("out[%r] must be a dense float32 tensor of the parameter's shape on its device" % n)
+    return params, out
+
+
+def ir_bwd(gd, d, e, wd9, s2):
+    """`uavsal_ir_bwd` on the current stream: `gd`, `d`, `e` dense NHWC `[T,h,w,C]`, the tap-major depthwise weights and the
+    folded scale of the depthwise BatchNorm on the device -> `ga` = d loss / d a1, dense NHWC."""
+    lib = L.load()
+    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
+                for t in (gd, d, e)) or gd.shape != d.shape or e.shape != d.shape):
+        raise RuntimeError("ir_bwd: gd, d, e must be dense float32 NHWC cuda tensors of one shape")
+    T, hh, ww, c = e.shape
+    for name, t, n in (("wd9", wd9, 9 * c), ("s2", s2, c)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == e.device and t.is_contiguous() and t.numel() >= n):
+            raise RuntimeError("ir_bwd: %s must be a dense float32 tensor of at least %d elements on the device of e" % (name, n))
+    ga = torch.empty_like(e)
+    k = L.IrBwdDesc()
+    k.gd, k.d, k.e, k.wd9, k.s2, k.ga = gd.data_ptr(), d.data_ptr(), e.data_ptr(), wd9.data_ptr(), s2.data_ptr(), ga.data_ptr()
+    k.n_img, k.H, k.W, k.C = T, hh, ww, c
+    L.check(lib.uavsal_ir_bwd(C.byref(k), _stream(e)), "uavsal_ir_bwd")
+    return ga
+
+
+def ir_sums(gd, d, e, ga, go):
+    """`uavsal_ir_sums` on the current stream -> `(ws, slabs)`: the per-slab partial sums (float64, the layout of
+    include/uavsal_hip.h) that `uavsal_ir_finish` takes.  `gd`, `d`, `e`, `ga` dense NHWC `[T,h,w,Ch]`; `go` an NHWC view
+    `[T,h,w,Co]` of the same pixels (a channel slice is read in place)."""
+    lib = L.load()
+    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
+                for t in (gd, d, e, ga)) or not all(t.shape == e.shape and t.device == e.device for t in (gd, d, ga))):
+        raise RuntimeError("ir_sums: gd, d, e, ga must be dense float32 NHWC cuda tensors of one shape on one device")
+    T, hh, ww, c = e.shape
+    if not torch.is_tensor(go) or go.dtype != torch.float32 or go.device != e.device:
+        raise RuntimeError("ir_sums: go must be a float32 tensor on the device of e")
+    gp, ldgo, *gs = _nhwc_view(go)
+    if gs[:3] != [T, hh, ww]:
+        raise RuntimeError("ir_sums: go must cover the pixels of e")
+    k = L.IrSumsDesc()
+    k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
+    k.n_img, k.H, k.W, k.Ch, k.Co = T, hh, ww, c, gs[3]
+    nbytes = int(lib.uavsal_ir_sums_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_ir_sums")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    L.check(lib.uavsal_ir_sums(C.byref(k), _stream(e)), "uavsal_ir_sums")
+    return ws, int(lib.uavsal_ir_sums_slabs(C.byref(k)))
+
+
+def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, out=None, accumulate=False):
+    """The gradients of the nine parameters of an inverted-residual `block` (a `dwBlock` with an expand conv, stride 1,
+    dilation 1, with or without the residual; eval mode: the BatchNorms on their running statistics, which are not updated)
+    from given tensors, teacher-forced: `x` `[T,Cin,h,w]` the block's input, `e`, `d` dense NHWC `[T,h,w,Ch]` its expanded
+    and depthwise tensors, `grad_out` `[T,Co,h,w]` = d loss / d output, `gd` dense NHWC = d loss / d d (default: one 1x1 conv
+    with the projection's transposed weights carrying s3 in their rows), `ga` dense NHWC = d loss / d a1 (default: one
+    `uavsal_ir_bwd`).  Returns a dict keyed by the block's parameter names (`BLOCK_PARAMS`), the values `torch.autograd`
+    gives for the reference's `dwBlock` (include/uavsal_hip.h states the formulas); `out`: such a dict of dense tensors to
+    write into, or (`accumulate`) to add to.  Nothing of the forward is recomputed; six launches (two pixel GEMMs with their
+    reductions -- `ga` x `x` for W1, `grad_out` x `d` for W3 --, channel sums, finalise) on the current stream, no
+    synchronisation.  Accepted: Co % 128 == 0, Ch % 64 == 0, Cin % 64 == 0."""
+    lib = L.load()
+    pw, pwbn, dwc, dwbn, pl, plbn = _block_parts(block)
+    hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    xn = _nhwc(x, "x", cin)
+    T, hh, ww, _ = xn.shape
+    dev = xn.device
+    for name, t in (("e", e), ("d", d)) + tuple((n, t) for n, t in (("gd", gd), ("ga", ga)) if t is not None):
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (T, hh, ww, hid)
+                or not t.is_contiguous()):
+            raise RuntimeError("%s must be a dense float32 NHWC tensor [%d,%d,%d,%d] on the device" % (name, T, hh, ww, hid))
+    go = _block_grad_out(grad_out, xn, cout)
+    params, out = _block_grad_tensors(block, out, accumulate)
+    if any(q.device != dev or not q.is_contiguous() for q in params.values()):
+        raise RuntimeError("the block's parameters must be dense tensors on the device of `x`")
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        w9, s2, _ = cache.depthwise(dwc, dwbn)
+        s1, s3 = cache.affine(pwbn, hid)[0], cache.affine(plbn, cout)[0]
+        if gd is None:
+            gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
+        if ga is None:
+            ga = ir_bwd(gd, d, e, w9, s2)
+        (r1, mu1), (r2, mu2), (r3, mu3) = (cache.bn_stats(b) for b in (pwbn, dwbn, plbn))
+        rd1 = torch.empty(hid, dtype=torch.float64, device=dev)
+        rd3 = torch.empty(cout, dtype=torch.float64, device=dev)
+        pix_gemm(ga, xn, out=out[BLOCK_PARAMS[0]], row_scale=s1, w=pw.weight.detach(), rowdot=rd1, accumulate=accumulate)
+        pix_gemm(go, d, out=out[BLOCK_PARAMS[6]], row_scale=s3, w=pl.weight.detach(), rowdot=rd3, accumulate=accumulate)
+        ws, slabs = ir_sums(gd, d, e, ga, go)
+        k = L.IrFinishDesc()
+        k.ws, k.ws_bytes, k.rowdot1, k.rowdot3 = ws.data_ptr(), ws.numel() * 8, rd1.data_ptr(), rd3.data_ptr()
+        k.wd, k.s2 = dwc.weight.data_ptr(), s2.data_ptr()
+        k.r1, k.mu1, k.r2, k.mu2, k.r3, k.mu3 = (t.data_ptr() for t in (r1, mu1, r2, mu2, r3, mu3))
+        (k.g_gamma1, k.g_beta1, k.g_wd, k.g_gamma2, k.g_beta2) = (out[n].data_ptr() for n in BLOCK_PARAMS[1:6])
+        k.g_gamma3, k.g_beta3 = out[BLOCK_PARAMS[7]].data_ptr(), out[BLOCK_PARAMS[8]].data_ptr()
+        k.Ch, k.Co, k.slabs, k.accumulate = hid, cout, slabs, int(bool(accumulate))
+        L.check(lib.uavsal_ir_finish(C.byref(k), _stream(xn)), "uavsal_ir_finish")
+    return out
+
+
+def _block_recompute(lib, cache, block, x):
+    """`e`, `d` (dense NHWC) from the NHWC `x` by the forward's own launches (expand conv, `uavsal_dw3x3`)."""
+    pw, pwbn, dwc, dwbn, _, _ = _block_parts(block)
+    T, hh, ww, _ = x.shape
+    hid = pw.weight.shape[0]
+    e = _conv(lib, cache, x, pw, hid, 1, bn=pwbn, act=L.ACT_RELU6)
+    w9, s2, b2 = cache.depthwise(dwc, dwbn)
+    dd = torch.empty_like(e)
+    q = L.DwDesc()
+    q.inp, q.ldi, q.w9c, q.scale, q.bias = e.data_ptr(), hid, w9.data_ptr(), s2.data_ptr(), b2.data_ptr()
+    q.out, q.ldo = dd.data_ptr(), hid
+    q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, 1, 1, L.ACT_RELU6
+    L.check(lib.uavsal_dw3x3(C.byref(q), _stream(x)), "uavsal_dw3x3")
+    return e, dd
+
+
+def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None, grads=None, accumulate=False):
+    """Backward of an inverted-residual `block` that is TRAINED (the blocks `block_param_grads` covers): `x` `[T,Cin,h,w]` its
+    input, `grad_out` `[T,Co,h,w]` = d loss / d output.  Returns `(grad_x [T,Cin,h,w] | None, grads)` with `grads` the dict
+    of `block_param_grads` (written into `grads`, or with `accumulate` added to it, when given).  `e` and `d` are recomputed
+    from `x` by the forward's own launches; `gd = grad_out . (diag(s3) W3)` is one 256 -> Ch GEMM whose transposed weights
+    carry s3 in their rows (`WeightCache.conv_t_scaled`), `ga` comes from `uavsal_ir_bwd`, and `grad_x = ga . (diag(s1) W1)`
+    (+ `grad_out` when the block has the residual) from one Ch -> Cin GEMM of the same kind.  `parts` receives `e`, `d`,
+    `gd`, `ga` (dense NHWC).  A block in training mode raises: the BatchNorms use their running statistics (which are not
+    updated), as everywhere in this package."""
+    lib = L.load()
+    pw, pwbn, dwc, dwbn, pl, plbn = _block_parts(block)
+    hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    xn = _nhwc(x, "x", cin)
+    go = _block_grad_out(grad_out, xn, cout)
+    dev = xn.device
+    _block_grad_tensors(block, grads, accumulate)                    # raise before anything is launched
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        e, dd = _block_recompute(lib, cache, block, xn)
+        gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
+        ga = ir_bwd(gd, dd, e, *cache.depthwise(dwc, dwbn)[:2])
+        g = None
+        if need_x_grad:
+            g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else None)
+        grads = block_param_grads(block, xn.permute(0, 3, 1, 2), e, dd, go.permute(0, 3, 1, 2), gd=gd, ga=ga, cache=cache,
+                                  out=grads, accumulate=accumulate)
+        if parts is not None:
+            parts.update(e=e, d=dd, gd=gd, ga=ga)
+    return (g.permute(0, 3, 1, 2) if need_x_grad else None), grads
+
+
 def twa_gate_bwd(g, carry, z, x, hprev, need_dx=False):
     """`uavsal_twa_gate_bwd` on NHWC tensors `[1,h,w,256]` (`g`, `x`, `hprev` may be channel slices; `carry` dense or None):
     returns `(dz, carry_out, dx | None)`, dense."""
@@ -440,7 +629,27 @@ def twa_backward(x_seq, h_seq, h0, weight, grad_h, need_x_grad=False, out=None, 
     return gw, (dx.permute(0, 3, 1, 2) if need_x_grad else None), carry.permute(0, 3, 1, 2)
 
 
-def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False):
+def fuse_block(model):
+    """The block that produces the recurrence's input (the `prefuse` tap), and the name of the tap that holds ITS input:
+    `model.fucbst_layer[0]` reading `fu320` with any prior enabled, else `model.fust_layer[0]` reading the last ST block's
+    output."""
+    if model.num_cb:
+        return model.fucbst_layer[0], "fu320"
+    return model.fust_layer[0], "st%d" % (len(model.st_layer) - 1)
+
+
+def _param_grad_tensors(blk):
+    """`({name: .grad}, accumulate)` of a block whose nine gradients a backward writes: missing `.grad`s are created, zeroed
+    when some but not all exist (the existing ones are added to, as `loss.backward()` would)."""
+    params = dict(blk.named_parameters())
+    acc = any(q.grad is not None for q in params.values())
+    for q in params.values():
+        if q.grad is None:
+            q.grad = (torch.zeros_like if acc else torch.empty_like)(q, memory_format=torch.contiguous_format)
+    return {n: q.grad for n, q in params.items()}, acc
+
+
+def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -449,7 +658,12 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     a precision other than 'f32' or `UAVSAL_LSTM` raise.  After `optimizer.step()` call `model.refresh_weights(model.rnn)`.
     `decoder=True`: the decoder `model.conv_out_st` is trained too (`decoder_backward`): its nine parameters' `.grad` are set
     as well, or added to, and the recurrence receives that path's `grad_h`; afterwards call
-    `model.refresh_weights(model.rnn, model.conv_out_st)`.  The BatchNorms still use their running statistics."""
+    `model.refresh_weights(model.rnn, model.conv_out_st)`.  The BatchNorms still use their running statistics.
+    `fuse=True`: the fusion block in front of the recurrence (`fuse_block`) is trained too: `twa_backward` also returns the
+    gradient of the recurrence's input, which `block_backward` carries to that block's nine parameters (`.grad` set, or added
+    to); everything in front of the block stays frozen, and nothing of `prefuse` bypasses the recurrence, so the gradient is
+    exact.  Refresh `model.fucbst_layer` (or `model.fust_layer` in a model without priors) afterwards as well.  Combines
+    freely with `decoder=True`; the default call runs the launches -- and the copies of taps -- it always ran."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
@@ -461,7 +675,8 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if not torch.is_tensor(x) or not x.is_cuda or not torch.is_tensor(y_gaze) or not y_gaze.is_cuda:
         raise RuntimeError("recurrence_step needs tensors on the MI355X (cuda) device; there is no CPU fallback")
     rc = model.rnn.cell_list[0].rnn_conv
-    taps = {}
+    blk, src = fuse_block(model) if fuse else (None, None)
+    taps = {src: None} if fuse else {}                               # (fu320 is read back on request only: engine.TAPS_ON_REQUEST)
     out, st = model(x, cb, in_state, taps=taps)
     pred = out.detach().requires_grad_(True)
     with torch.enable_grad():
@@ -472,14 +687,8 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     cl = torch.channels_last
     h_seq, x_seq = taps["rnn"].contiguous(memory_format=cl), taps["prefuse"].contiguous(memory_format=cl)
     if decoder:
-        blk = model.conv_out_st
-        params = dict(blk.named_parameters())
-        acc = any(q.grad is not None for q in params.values())
-        for q in params.values():
-            if q.grad is None:                                       # (some but not all exist: the missing ones start at zero)
-                q.grad = (torch.zeros_like if acc else torch.empty_like)(q, memory_format=torch.contiguous_format)
-        grad_h, _ = decoder_backward(blk, h_seq, g_y, cache=cache, y=out, grads={n: q.grad for n, q in params.items()},
-                                     accumulate=acc)
+        grads, acc = _param_grad_tensors(model.conv_out_st)
+        grad_h, _ = decoder_backward(model.conv_out_st, h_seq, g_y, cache=cache, y=out, grads=grads, accumulate=acc)
     else:
         grad_h = decoder_input_grad(model.conv_out_st, h_seq, g_y, cache=cache, y=out)
     h0 = None if in_state is None else in_state[0]
@@ -487,5 +696,10 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     had = w.grad is not None
     if not had:
         w.grad = torch.empty_like(w, memory_format=torch.contiguous_format)
-    twa_backward(x_seq, h_seq, h0, w.detach(), grad_h, out=w.grad, accumulate=had, cache=cache, module=rc)
+    _, grad_x, _ = twa_backward(x_seq, h_seq, h0, w.detach(), grad_h, need_x_grad=bool(fuse), out=w.grad, accumulate=had,
+                                cache=cache, module=rc)
+    if fuse:
+        grads, acc = _param_grad_tensors(blk)
+        block_backward(blk, taps[src].contiguous(memory_format=cl), grad_x, need_x_grad=False, cache=cache, grads=grads,
+                       accumulate=acc)
     return loss.detach(), out, [st[0].detach()]

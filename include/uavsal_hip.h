@@ -752,9 +752,10 @@ int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd 
  * weight-gradient row and a non-zero gamma gradient).
  *
  * uavsal_pix_gemm: out[m][n] = fl(row_scale[m] G[m][n]) (+ the old value with `accumulate`), G[m][n] = sum over the K
- *   pixels p of a[p][m] b[p][n]; row p of a / b at p * lda / p * ldb floats (channel slices are read in place).  M and N
- *   multiples of 128 (else UAVSAL_ESHAPE).  The tile loop and the K split of uavsal_twa_wgrad: chunks of
- *   UAVSAL_WGRAD_CHAIN pixels, shares of whole chunks for about 1024 workgroups over the (M / 128)(N / 128) tiles, partial
+ *   pixels p of a[p][m] b[p][n]; row p of a / b at p * lda / p * ldb floats (channel slices are read in place).  M a
+ *   multiple of 128 and N a multiple of 64 (else UAVSAL_ESHAPE; the last N tile may be half empty: nothing at or behind
+ *   column N is read or written).  The tile loop and the K split of uavsal_twa_wgrad: chunks of
+ *   UAVSAL_WGRAD_CHAIN pixels, shares of whole chunks for about 1024 workgroups over the (M / 128) ceil(N / 128) tiles, partial
  *   tiles in `ws`; a second launch sums the shares in share order in double and rounds once.  row_scale NULL = 1.
  *   rowdot (optional, [M] doubles) = sum_n w[m][n] G[m][n] in double in a fixed order, w rows ldw floats apart.
  *   No atomics: two calls return the same bits.  TWO launches, no allocation.  UAVSAL_EALIGN: a, b, ws not 16-byte
@@ -808,6 +809,74 @@ int uavsal_dec_sums_slab_rows(const uavsal_dec_sums_desc* d);   /* picture rows 
 int uavsal_dec_sums(const uavsal_dec_sums_desc* d, uavsal_stream_t stream);
 int uavsal_dec_finish(const uavsal_dec_finish_desc* d, uavsal_stream_t stream);
 int uavsal_train_decoder_sizeof_desc(int which);  /* 0 pix_gemm, 1 dec_sums, 2 dec_finish (uavsal_train_sizeof_desc is closed at 3) */
+
+/* ---- fine-tuning a general inverted-residual block: its backward (csrc/train_block.hip) --------------------------------
+ * A dwBlock with an expand conv, stride 1, dilation 1, in eval mode (r, s, b per BatchNorm as above); x is [P][Cin] with
+ * P = n_img * H * W pixels, Ch hidden and Co output channels:
+ *     u1 = W1 x, a1 = s1 u1 + b1, e = ReLU6(a1);  u2 = dw3x3(Wd, e), a2 = s2 u2 + b2, d = ReLU6(a2);
+ *     o = s3 (W3 d) + b3  (+ x when the block has the residual).
+ * With go = d loss / d o:
+ *     gd[p][c]     = sum_m go[p][m] s3[m] W3[m][c]
+ *     delta2[p][c] = gd[p][c] 1[0 < d[p][c] < 6]
+ *     ga[p][c]     = 1[0 < e[p][c] < 6] s2[c] sum over taps k of wd[k][c] delta2[p - (k - (1,1))][c]
+ *                    (zero outside the picture, never across frames)
+ *     gx[p][j]     = sum_c ga[p][c] s1[c] W1[c][j]  (+ go[p][j] with the residual)
+ * and the sums over all pixels
+ *     S3[m] = sum go[p][m],  G3[m][c] = sum go[p][m] d[p][c],  S2[c] = sum delta2[p][c],  S1[c] = sum ga[p][c],
+ *     Gd[c][ky][kx] = sum delta2[p][c] e[p + (ky-1, kx-1)][c],  G1[c][j] = sum ga[p][c] x[p][j]
+ * the gradients are
+ *     W1[c][j]: s1[c] G1[c][j]    beta1: S1    gamma1[c]: r1[c] (sum_j W1[c][j] G1[c][j] - mu1[c] S1[c])
+ *     Wd[c][k]: s2[c] Gd[c][k]    beta2: S2    gamma2[c]: r2[c] (sum_k Wd[c][k] Gd[c][k] - mu2[c] S2[c])
+ *     W3[m][c]: s3[m] G3[m][c]    beta3: S3    gamma3[m]: r3[m] (sum_c W3[m][c] G3[m][c] - mu3[m] S3[m])
+ * from the UNSCALED sums, as for the decoder.  gd and gx are 1x1 convs (uavsal_conv_gemm with the transposed weights that
+ * carry s3 / s1 in their rows); G1 and G3 with their row dots are two uavsal_pix_gemm calls (a = ga, b = x, w = W1 and
+ * a = go, b = d, w = W3); the rest is here.  The masks are torch's: strict inequalities on the stored e and d.
+ *
+ * uavsal_ir_bwd: ga from gd, d, e dense [n_img][H][W][C], wd9 tap-major [9][C] as in uavsal_dw_desc and s2 [C]; delta2 is
+ *   not materialised.  C % 4 == 0 and 16-byte aligned pointers (else UAVSAL_EALIGN).  ONE launch, memory bound.
+ * uavsal_ir_sums: per slab of picture rows the partial sums S2, Gd, S1 and S3 -> `ws` (doubles), from gd, d, e, ga dense
+ *   [n_img][H][W][Ch] and go, rows of Co floats ldgo floats apart.  Ch % 64 == 0 (else UAVSAL_ESHAPE), Co and ldgo
+ *   multiples of 4.  delta2 is formed in fp32 exactly as uavsal_ir_bwd forms it; every product is accumulated in double.
+ *   ws layout: per slab UAVSAL_IR_NSUM * Ch + Co doubles: [0] S2, [1 + ky * 3 + kx] Gd, [10] S1, each [Ch], then S3 [Co].
+ *   The slabs follow the rule of uavsal_dec_sums and depend on the shape alone (uavsal_ir_sums_slabs / _slab_rows): no
+ *   atomics, bit-reproducible.  ONE launch.
+ * uavsal_ir_finish: sums the slabs in slab order in double and writes gamma1, beta1 [Ch], Wd [Ch][3][3], gamma2, beta2
+ *   [Ch], gamma3, beta3 [Co] in the parameters' own layouts, each rounded once, overwritten or (`accumulate`) added to.
+ *   rowdot1 [Ch]: uavsal_pix_gemm's with w = W1; rowdot3 [Co]: with w = W3.  wd is the parameter [Ch][3][3].  ONE launch.
+ * block_param_grads is SIX launches (two GEMMs with their reductions, sums, finish); block_backward adds the recomputation
+ * of e and d (two), gd, uavsal_ir_bwd and, when wanted, gx.
+ */
+#define UAVSAL_IR_NSUM 11
+
+typedef struct uavsal_ir_bwd_desc {
+    const float* gd;  const float* d;  const float* e;
+    const float* wd9;  const float* s2;
+    float* ga;
+    int32_t n_img, H, W, C;
+} uavsal_ir_bwd_desc;
+
+typedef struct uavsal_ir_sums_desc {
+    const float* gd;  const float* d;  const float* e;  const float* ga;
+    const float* go;  int32_t ldgo;         /* [n_img * H * W] rows of Co floats */
+    double* ws;  int64_t ws_bytes;
+    int32_t n_img, H, W, Ch, Co;
+} uavsal_ir_sums_desc;
+
+typedef struct uavsal_ir_finish_desc {
+    const double* ws;  int64_t ws_bytes;  const double* rowdot1;  const double* rowdot3;
+    const float* wd;  const float* s2;
+    const float* r1;  const float* mu1;  const float* r2;  const float* mu2;  const float* r3;  const float* mu3;
+    float* g_gamma1;  float* g_beta1;  float* g_wd;  float* g_gamma2;  float* g_beta2;  float* g_gamma3;  float* g_beta3;
+    int32_t Ch, Co, slabs, accumulate;
+} uavsal_ir_finish_desc;
+
+int uavsal_ir_bwd(const uavsal_ir_bwd_desc* d, uavsal_stream_t stream);
+int64_t uavsal_ir_sums_workspace_bytes(const uavsal_ir_sums_desc* d);
+int uavsal_ir_sums_slabs(const uavsal_ir_sums_desc* d);         /* slabs of that call (no launch) */
+int uavsal_ir_sums_slab_rows(const uavsal_ir_sums_desc* d);     /* picture rows per slab */
+int uavsal_ir_sums(const uavsal_ir_sums_desc* d, uavsal_stream_t stream);
+int uavsal_ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t stream);
+int uavsal_block_sizeof_desc(int which);  /* 0 ir_bwd, 1 ir_sums, 2 ir_finish (uavsal_train_decoder_sizeof_desc is closed at 3) */
 
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;

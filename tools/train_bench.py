@@ -15,6 +15,14 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                `uavsal_dec_bwd` at the same shape and byte count) and `uavsal_dec_finish` (dec_finish) --,
                `recurrence_step(decoder=True)` (step_dec, alternated with step in the same run) and
                `refresh_weights(model.rnn, model.conv_out_st)` (refresh_dec);
+  fuse         the fusion block in front of the recurrence trained too (`train.fuse_block`: fucbst_layer[0], 320 -> 1920 ->
+               256): `train.block_backward` as the step runs it (block_bwd, no input gradient) and with it (block_bwd_x),
+               `uavsal_ir_bwd` and `uavsal_ir_sums` alone (GB/s from the bytes each must move: gd, d, e, ga = 4 * 1920 * 4
+               per pixel, the sums' go on top; beside dec_bwd_kernel and dec_sums of the same run), both pixel GEMMs
+               (pix_gemm_w1: ga x x, 1920 x 320 with its N tail; pix_gemm_w3: go x d, 256 x 1920; TFLOP/s),
+               `recurrence_step(fuse=True)` (step_fuse, alternated with step in the same run),
+               `refresh_weights(model.rnn, model.fucbst_layer)` (refresh_fuse), and an eager torch-autograd step of the
+               same block (eager_block: forward + the nine parameter gradients from the same input and output gradient);
   eager        torch autograd of the restated recurrence + decoder (float32, eval BatchNorm folded) on the same device,
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
@@ -80,6 +88,101 @@ def eager_step(model, x_seq, h0, gy):
     return run
 
 
+def eager_block(blk, x, go):
+    """the block (eval BatchNorm, as the package runs it) under torch autograd: forward + the nine parameter gradients"""
+    seq = blk.conv
+    bns = (seq[0][1], seq[1][1], seq[3])
+    hid = seq[1][0].weight.shape[0]
+
+    def bn(t, b, gamma, beta):
+        return F.batch_norm(t, b.running_mean, b.running_var, gamma, beta, False, 0.0, b.eps)
+
+    def run():
+        ps = [q.detach().clone().requires_grad_(True) for q in blk.parameters()]
+        w1, g1, b1, wd, g2, b2, w3, g3, b3 = ps
+        e = bn(F.conv2d(x, w1), bns[0], g1, b1).clamp(0, 6)
+        d = bn(F.conv2d(e, wd, padding=1, groups=hid), bns[1], g2, b2).clamp(0, 6)
+        o = bn(F.conv2d(d, w3), bns[2], g3, b3)
+        return torch.autograd.grad(o, ps, go)
+    return run
+
+
+def fuse_phases(res, m, x, cb, y_gaze, taps, grad_h, cache, iters, repeats, skip_eager):
+    """the phases of the trained fusion block, added to `res`"""
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    rc = m.rnn.cell_list[0].rnn_conv
+    blk, src = train.fuse_block(m)
+    box = m.fucbst_layer if m.num_cb else m.fust_layer
+    x_in = taps[src].contiguous(memory_format=cl)
+    x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
+    _, grad_x, _ = train.twa_backward(x_seq, h_seq, None, rc.weight.detach(), grad_h, need_x_grad=True, cache=cache, module=rc)
+    grad_x = grad_x.contiguous(memory_format=cl)
+    parts = {}
+    _, grads = train.block_backward(blk, x_in, grad_x, need_x_grad=False, cache=cache, parts=parts)
+    e_, d_, gd_, ga_ = (parts[k] for k in ("e", "d", "gd", "ga"))
+    pw, pwbn, dwc, dwbn, pl, plbn = train._block_parts(blk)
+    hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    w9, s2, _ = cache.depthwise(dwc, dwbn)
+    s1, s3 = cache.affine(pwbn, hid)[0], cache.affine(plbn, cout)[0]
+    xn, gon = x_in.permute(0, 2, 3, 1), grad_x.permute(0, 2, 3, 1)
+    rd1 = torch.empty(hid, dtype=torch.float64, device=dev)
+    rd3 = torch.empty(cout, dtype=torch.float64, device=dev)
+    g1, g3 = grads[train.BLOCK_PARAMS[0]], grads[train.BLOCK_PARAMS[6]]
+    n_pix = x_in.shape[0] * x_in.shape[2] * x_in.shape[3]
+
+    def step():
+        rc.weight.grad = None
+        train.recurrence_step(m, x, cb, None, y_gaze)
+
+    def step_fuse():
+        for q in list(m.rnn.parameters()) + list(blk.parameters()):
+            q.grad = None
+        train.recurrence_step(m, x, cb, None, y_gaze, fuse=True)
+
+    def refresh_fuse():
+        with torch.no_grad():
+            rc.weight.mul_(1.0)
+            for q in blk.parameters():
+                q.mul_(1.0)
+        m.refresh_weights(m.rnn, box)
+    cases = {"block_bwd": lambda: train.block_backward(blk, x_in, grad_x, need_x_grad=False, cache=cache, grads=grads),
+             "block_bwd_x": lambda: train.block_backward(blk, x_in, grad_x, cache=cache, grads=grads),
+             "ir_bwd": lambda: train.ir_bwd(gd_, d_, e_, w9, s2),
+             "ir_sums": lambda: train.ir_sums(gd_, d_, e_, ga_, gon),
+             "pix_gemm_w1": lambda: train.pix_gemm(ga_, xn, out=g1, row_scale=s1, w=pw.weight.detach(), rowdot=rd1),
+             "pix_gemm_w3": lambda: train.pix_gemm(gon, d_, out=g3, row_scale=s3, w=pl.weight.detach(), rowdot=rd3),
+             "refresh_fuse": refresh_fuse}
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    alt = {"step": [], "step_fuse": []}                      # the two steps alternated in the same run
+    for _ in range(repeats):
+        alt["step"].append(per_call(step, iters))
+        alt["step_fuse"].append(per_call(step_fuse, iters))
+    res["step_alt2_ms"], res["step_fuse_ms"] = 1e3 * min(alt["step"]), 1e3 * min(alt["step_fuse"])
+    for q in blk.parameters():
+        q.grad = None
+    res["fuse_block"] = [cin, hid, cout]
+    res["ir_bwd_gbs"] = 4.0 * hid * 4 * n_pix / (res["ir_bwd_ms"] * 1e-3) / 1e9
+    res["ir_sums_gbs"] = (4.0 * hid + cout) * 4 * n_pix / (res["ir_sums_ms"] * 1e-3) / 1e9
+    for key, (M, N) in (("pix_gemm_w1", (hid, cin)), ("pix_gemm_w3", (cout, hid))):
+        gd = L.PixGemmDesc()
+        gd.K, gd.M, gd.N = n_pix, M, N
+        res[key + "_shares"] = int(lib.uavsal_pix_gemm_shares(C.byref(gd)))
+        res[key + "_tflops"] = 2.0 * M * N * n_pix / (res[key + "_ms"] * 1e-3) / 1e12
+        res[key + "_of_peak"] = res[key + "_tflops"] / PEAK_TFLOPS
+    if not skip_eager:
+        try:
+            run = eager_block(blk, x_in, grad_x)
+            ge = run()
+            res["eager_block_ms"] = 1e3 * best_of(run, max(1, iters // 2), repeats)
+            train.block_backward(blk, x_in, grad_x, need_x_grad=False, cache=cache, grads=grads)
+            res["eager_block_vs_hip_rel_l2"] = max(float((a - grads[n]).norm() / a.norm()) for a, n in zip(ge, train.BLOCK_PARAMS))
+        except RuntimeError as e:                     # torch's own conv kernels may not exist for this device
+            res["eager_block_error"] = str(e).splitlines()[0][:200]
+
+
 def bench(T, iters, repeats, dev, skip_eager):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5)
@@ -94,7 +197,7 @@ def bench(T, iters, repeats, dev, skip_eager):
     y_gaze, _ = ops.prepare_gaze(torch.from_numpy(fmap).to(dev), torch.from_numpy(loc).to(dev), h, w)
     rc = m.rnn.cell_list[0].rnn_conv
     cache = WeightCache(torch.device(dev), m._wshared.setdefault(str(torch.device(dev)), {}))
-    taps = {}
+    taps = {train.fuse_block(m)[1]: None}                    # the fusion block's input is read back on request
     out, _ = m(x, cb, None, taps=taps)
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -189,6 +292,7 @@ def bench(T, iters, repeats, dev, skip_eager):
     res["wgrad_shares"] = int(L.load().uavsal_twa_wgrad_shares(C.byref(d)))
     res["wgrad_tflops"] = flop / (res["wgrad_ms"] * 1e-3) / 1e12
     res["wgrad_of_peak"] = res["wgrad_tflops"] / PEAK_TFLOPS
+    fuse_phases(res, m, x, cb, y_gaze, taps, grad_h, cache, iters, repeats, skip_eager)
     if not skip_eager:
         try:
             run = eager_step(m, taps["prefuse"], torch.zeros((1, 256, h, w), device=dev), g_y)
