@@ -374,6 +374,8 @@ SYMBOLS = [
     ("uavsal_plan_group_enable", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("uavsal_plan_group_launches", C.c_int, [C.c_void_p, C.c_int]),
     ("uavsal_plan_last_launches", C.c_int, [C.c_void_p]),
+    ("uavsal_plan_frame_repeat", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("uavsal_plan_frame_repeat_workgroups", C.c_int, [C.c_void_p, C.c_int]),
     ("uavsal_plan_graph_build", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_graph_launch", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_time", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),

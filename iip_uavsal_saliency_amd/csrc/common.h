@@ -21,6 +21,16 @@ static inline int uavsal_launch_status() {
 
 static inline bool uavsal_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// The frame-repeat forms of the conv launch (conv_gemm.hip), for the plan engine (plan.hip) only: not part of the C ABI.
+// uavsal_conv_repeat_pair: 1 when `pw` (a 1x1 expand) and `dw` (the depthwise -> projection launch that reads pw's output)
+// both take routes whose summation order per output element does not depend on where its tile lies in the launch, and
+// the image map "image f holds what image (f / div * div) % mod holds" leaves images out; else 0.
+__attribute__((visibility("hidden"))) int uavsal_conv_repeat_pair(const uavsal_conv_desc* pw, const uavsal_conv_desc* dw, int mod, int div);
+// the conv launch under that image map (div == 0: every image); *workgroups = the grid of the first kernel it started
+// (0 for a route that does not report one)
+__attribute__((visibility("hidden"))) int uavsal_conv_gemm_mapped(const uavsal_conv_desc* d, uavsal_stream_t stream, int mod, int div,
+                                                                    int* workgroups);
+
 // Blocks are dealt round-robin over the 8 XCDs (each with a private L2).  Map the
 // hardware block id to a virtual id so that each XCD owns one contiguous range of
 // virtual ids: neighbouring tiles (which share activation rows / halos / weights)

@@ -1390,7 +1390,8 @@ extern "C" int uavsal_conv_uses_split(const uavsal_conv_desc* d) { return route_
 extern "C" int uavsal_conv_dwproj(const uavsal_conv_desc* d) { return route_or_none(d, true).dwproj; }
 extern "C" int uavsal_conv_streamk_grid(const uavsal_conv_desc* d) { return route_or_none(d, true).streamk; }
 
-extern "C" int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t stream) {
+// fr_div != 0: the launch under the image map of uavsal_conv_gemm_mapped (ConvK.fr; the caller has asked uavsal_conv_repeat_pair)
+static int conv_gemm_run(const uavsal_conv_desc* d, uavsal_stream_t stream, int fr_mod, int fr_div) {
     if (!d || !d->w || !d->out) return UAVSAL_EINVAL;
     if (!d->a && !(d->a_split && d->epi == UAVSAL_EPI_AFFINE)) return UAVSAL_EINVAL;
     if (d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return UAVSAL_EINVAL;
@@ -1464,6 +1465,7 @@ extern "C" int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t strea
     k.ngrp = d->n_group; k.a_goff = d->a_group_off;
     k.a_sp = (const _Float16*)d->a_split; k.ldas = d->ldas;
     k.out_sp = (_Float16*)d->out_split; k.ldos = d->ldos;
+    if (fr_div) k.fr = fr_div | fr_mod << 16;      // (uavsal_conv_repeat_pair: both below 32768)
     if (route_status) return route_status;
     hipStream_t s = (hipStream_t)stream;
     const bool t1 = d->taps == 1;
@@ -1494,4 +1496,42 @@ extern "C" int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t strea
         case UAVSAL_PREC_F16X3: return launch_prec<UAVSAL_PREC_F16X3>(k, d->taps, r.tile, s);
         default: return launch_prec<UAVSAL_PREC_BF16>(k, d->taps, r.tile, s);
     }
+}
+
+extern "C" int uavsal_conv_gemm(const uavsal_conv_desc* d, uavsal_stream_t stream) { return conv_gemm_run(d, stream, 0, 0); }
+
+// ---- frame repeat (uavsal_plan_frame_repeat, plan.hip; the kernels' side: ConvK.fr) ---------------------------------
+__thread int uavsal_last_grid = 0;
+
+int uavsal_conv_gemm_mapped(const uavsal_conv_desc* d, uavsal_stream_t stream, int mod, int div, int* workgroups) {
+    uavsal_last_grid = 0;
+    const int e = conv_gemm_run(d, stream, mod, div);
+    if (workgroups) *workgroups = uavsal_last_grid;
+    return e;
+}
+
+// The routes that may leave images out: what an output element sums, and in which order, must not depend on which work unit
+// of the launch computes its tile.  True of the 32-float-K GEMMs (whole tiles, or K shares that meet in share order: in a
+// reduce launch or at the tile's own ticket) and of dwproj_kernel; not of stream-K, whose cuts through the K loops follow
+// the number of tiles.  The staged and pre-split 16-bit kernels do not carry the tile map.
+int uavsal_conv_repeat_pair(const uavsal_conv_desc* pw, const uavsal_conv_desc* dw, int mod, int div) {
+    if (!pw || !dw || mod <= 0 || div <= 0 || mod % div) return 0;
+    const int N = pw->n_img, ns = mod / div;
+    if (N != dw->n_img || mod > N || N % div || ns >= N || ns > 64) return 0;          // (nothing to leave out: ns == N)
+    const long long HW = (long long)pw->H * pw->W;
+    if (HW * N > 0x7fffffffLL || N >= 32768) return 0;
+    // dense images on both sides, the projection reads exactly what the expand writes, nothing but the affine epilogue
+    if (pw->H != dw->H || pw->W != dw->W || (const float*)pw->out != dw->a || pw->ldc != dw->lda || pw->Cout != dw->Cin) return 0;
+    if (pw->a_img_stride != HW || pw->o_img_stride != HW || dw->a_img_stride != HW || dw->o_img_stride != HW) return 0;
+    if (pw->taps != 1 || pw->epi != UAVSAL_EPI_AFFINE || pw->res || pw->out_split || pw->a_split || pw->dw_w9c || pw->w_group_stride ||
+        pw->n_group)
+        return 0;
+    if (dw->taps != 1 || dw->epi != UAVSAL_EPI_AFFINE || dw->res || dw->out_split || !dw->dw_w9c || dw->dw_stride != 1 ||
+        dw->prec != UAVSAL_PREC_F32)
+        return 0;
+    uavsal_conv_route rp, rd;
+    if (conv_route(pw, &rp) || conv_route(dw, &rd)) return 0;
+    if (rp.family != UAVSAL_ROUTE_K32 || !(rp.tile == 8 || rp.tile == 10 || rp.tile == 11)) return 0;
+    if (rd.family != UAVSAL_ROUTE_DWPROJ || rd.ksplit != 1 || !uavsal_dwproj_repeats()) return 0;
+    return 1;
 }

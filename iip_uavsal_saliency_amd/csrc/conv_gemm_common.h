@@ -35,9 +35,24 @@ struct ConvK {
     int ldas, ldos;            // their row strides in halves
     long long w_gs;            // per-image weights (uavsal_conv_desc.w_group_stride, floats; 0 = none): HW % 128 == 0
     int ngrp, a_goff;          // output-channel groups with their own A columns (uavsal_conv_desc.n_group / a_group_off; 0 = none)
+    // Frame repeat (plan.hip: uavsal_plan_frame_repeat; fr_div == 0: off, the launch covers every image).  Image f of the
+    // launch holds what image (f / fr_div * fr_div) % fr_mod holds, so only the fr_ns = fr_mod / fr_div "source" images
+    // j * fr_div are computed: a GEMM of the 32-float-K family walks the M tiles that hold a row of a source image (the
+    // work unit's compact tile index goes through fr_tile_m; tickets, partial sums and rows keep their real indices) and
+    // leaves the other rows unwritten; dwproj_kernel walks the patches of the source images and stores every finished
+    // patch to all the images that repeat it.  Kept to ONE word for the kernels, fr = fr_div | fr_mod << 16 (0: off) -- every
+    // argument a kernel reads is a scalar register it holds across its K loop; fr_bm: the M tile of the launch
+    // (splitk_reduce_kernel alone reads it).
+    int fr = 0, fr_bm = 0;
+    __host__ __device__ int fr_div() const { return fr & 0xffff; }
+    __host__ __device__ int fr_mod() const { return fr >> 16; }
+    __host__ __device__ int fr_ns() const { return fr_mod() / fr_div(); }
 };
 
 }  // namespace uavsal_gemm
+
+// grid of the last persistent-tile launch of this thread (launch_resident; conv_gemm.hip defines it)
+__attribute__((visibility("hidden"))) extern __thread int uavsal_last_grid;      // (__thread: no dynamic initialiser, so no TLS wrapper call)
 
 // The launchers of the other translation units.  Which of them runs, with which tile and how many K shares per tile
 // (k.ksplit), is decided before they are called (conv_route.h): a launcher derives nothing from the shape.
@@ -46,6 +61,7 @@ int uavsal_launch_f32_k32(const uavsal_gemm::ConvK& k, int taps, int tile, hipSt
 // dwproj.hip: depthwise 3x3 + BN + ReLU6 -> 1x1 projection in one launch (LDS halo tile), fp32 / split-fp16;
 // `bn` = its output-channel tile (uavsal_conv_route.dwproj)
 int uavsal_launch_dwproj(const uavsal_gemm::ConvK& k, int prec, int bn, hipStream_t stream);
+__attribute__((visibility("hidden"))) bool uavsal_dwproj_repeats();
 
 namespace {
 using uavsal_gemm::ConvK;
@@ -55,6 +71,26 @@ __device__ __forceinline__ long long row_off(int m, int HW, long long img_stride
     const int img = m / HW;
     return (long long)img * img_stride + (m - img * HW);
 }
+
+// Frame repeat (ConvK.fr): the c-th M tile, in ascending order, that holds a row of a source image -- source j is image
+// j * div, rows [j * div * HW, (j * div + 1) * HW); a tile that straddles into a neighbouring image counts whole, and one
+// that two sources share counts once.  Past the last such tile: -1 - (their number), which is how the host counts them
+// (fr_tiles_m).  A loop over the sources: they are the clips (or chunks) of a call, a handful.
+__host__ __device__ inline int fr_tile_m(int c, int ns, int div, int HW, int bm) {
+    int prev = -1, left = c;
+    for (int j = 0; j < ns; ++j) {
+        const int r0 = j * div * HW;
+        int lo = r0 / bm;
+        const int hi = (r0 + HW - 1) / bm;
+        if (lo <= prev) lo = prev + 1;
+        if (hi < lo) continue;
+        if (left <= hi - lo) return lo + left;
+        left -= hi - lo + 1;
+        prev = hi;
+    }
+    return -1 - (c - left);
+}
+inline int fr_tiles_m(const ConvK& k, int bm) { return -1 - fr_tile_m(0x7fffffff, k.fr_ns(), k.fr_div(), k.HW, bm); }
 
 // F16X3 pre-scales: activations by 2^4 while staging (saturating at the fp16 range: hi and lo
 // each stop at 65504, i.e. |x| beyond ~8188 clips), weights by 2^6 on the host; the accumulator
@@ -259,8 +295,13 @@ __device__ __attribute__((aligned(16))) float g_zero_row[UAVSAL_DWPROJ_MAX_C + 1
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvK p, float acc_scale) {
     const int groups = (p.Cout + 3) >> 2;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)p.M * groups) return;
-    const int m = (int)(idx / groups), gn = (int)(idx - (long long)m * groups) * 4;
+    int m = (int)(idx / groups);
+    const int gn = (int)(idx - (long long)m * groups) * 4;
+    if (p.fr) {          // frame repeat: the launch covers the rows of the M tiles the GEMM walked, in its compact order
+        const int tc = m / p.fr_bm, tm = fr_tile_m(tc, p.fr_ns(), p.fr_div(), p.HW, p.fr_bm);
+        m = tm < 0 ? p.M : tm * p.fr_bm + (m - tc * p.fr_bm);
+    }
+    if (m >= p.M) return;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < p.ksplit; ++k) v += *reinterpret_cast<const f32x4*>(p.kpart + ((size_t)k * p.M + m) * p.Npad + gn);
     const int img = m / p.HW, pix = m - img * p.HW;
@@ -295,7 +336,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvK p, float
 }
 
 int launch_splitk_reduce(const ConvK& k, float acc_scale, hipStream_t stream) {
-    const long long items = (long long)k.M * ((k.Cout + 3) / 4);
+    const long long items = (k.fr ? (long long)fr_tiles_m(k, k.fr_bm) * k.fr_bm : (long long)k.M) * ((k.Cout + 3) / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, k, acc_scale);
     return uavsal_launch_status();
 }
@@ -333,7 +374,8 @@ template <auto Kernel, int SMEM, int NT, bool OPTIN = false>
 int launch_resident(const ConvK& k, hipStream_t stream) {
     if constexpr (OPTIN) UAVSAL_LDS_OPTIN(Kernel, SMEM);
     const int cap = UAVSAL_PER_DEVICE(resident_grid(Kernel, SMEM, NT));
-    hipLaunchKernelGGL(Kernel, dim3(k.nblk < cap ? k.nblk : cap), dim3(NT), SMEM, stream, k);
+    uavsal_last_grid = k.nblk < cap ? k.nblk : cap;
+    hipLaunchKernelGGL(Kernel, dim3(uavsal_last_grid), dim3(NT), SMEM, stream, k);
     return uavsal_launch_status();
 }
 // ... of the 1x1 or the 3x3 instance of a kernel

@@ -49,8 +49,10 @@
 
 namespace {
 
-template <int WAVES_M, int WAVES_N, int TAPS, int MINW>
-__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k32_kernel(const ConvK p) {
+// (the body, shared by the kernel and its frame-repeat instance -- FR: the work units are the M tiles of the source images,
+// ConvK.fr; a kernel of its own so that the instance every other launch runs is compiled without a trace of it)
+template <int WAVES_M, int WAVES_N, int TAPS, int MINW, bool FR>
+__device__ __forceinline__ void conv_gemm_f32_k32_body(const ConvK p) {
     constexpr int WM = 2, WN = 2;
     constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
     constexpr int KT = 32;
@@ -118,8 +120,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k3
             s0 = ks * nst_all / p.ksplit;
             nst = (ks + 1) * nst_all / p.ksplit - s0;
         }
-        const int tile_m = t / p.tiles_n;
+        int tile_m = t / p.tiles_n;
         const int tile_n = t - tile_m * p.tiles_n;
+        if (FR) tile_m = fr_tile_m(tile_m, p.fr_ns(), p.fr_div(), p.HW, BM);       // frame repeat: compact -> real M tile
         m0 = tile_m * BM;
         n0 = tile_n * BN;
 #pragma unroll
@@ -303,6 +306,14 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k3
 #endif
 }
 
+template <int WAVES_M, int WAVES_N, int TAPS, int MINW>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k32_kernel(const ConvK p) {
+    conv_gemm_f32_k32_body<WAVES_M, WAVES_N, TAPS, MINW, false>(p);
+}
+template <int WAVES_M, int WAVES_N, int TAPS, int MINW>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k32_repeat_kernel(const ConvK p) {
+    conv_gemm_f32_k32_body<WAVES_M, WAVES_N, TAPS, MINW, true>(p);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // The same GEMM as ONE continuous stream of K stages over all the tiles of a workgroup ("flat pipeline").
@@ -320,8 +331,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k3
 // long K: the ConvTWA step).  A share publishes its raw sums (write-through stores), takes a ticket on the tile's
 // counter, and the share that arrives LAST adds all of them in share order -- the order is fixed, whoever reduces --
 // and applies the epilogue (BN / activation / residual or the ConvTWA update, model_convlstm.py:276-292).  Nobody waits.
-template <int WAVES_M, int WAVES_N, int TAPS, int MINW, bool SPLIT = false>
-__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k32p_kernel(const ConvK p) {
+template <int WAVES_M, int WAVES_N, int TAPS, int MINW, bool SPLIT, bool FR>
+__device__ __forceinline__ void conv_gemm_f32_k32p_body(const ConvK p) {
     constexpr int WM = 2, WN = 2;
     constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
     constexpr int KT = 32;
@@ -377,8 +388,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k3
             s0 = sh * nst_all / ksplit;
             rq_nst = (sh + 1) * nst_all / ksplit - s0;
         }
-        const int tile_m = t / p.tiles_n;
-        const int rm0 = tile_m * BM, rn0 = (t - tile_m * p.tiles_n) * BN;
+        int tile_m = t / p.tiles_n;
+        const int rn0 = (t - tile_m * p.tiles_n) * BN;
+        if (FR) tile_m = fr_tile_m(tile_m, p.fr_ns(), p.fr_div(), p.HW, BM);       // frame repeat: compact -> real M tile
+        const int rm0 = tile_m * BM;
 #pragma unroll
         for (int it = 0; it < A_IT; ++it) {
             const int m = rm0 + r8 + it * RPI;
@@ -494,10 +507,17 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k3
     int g = 0;                                           // stages done so far: stage g lives in slot g & 1
     bool req = false;                                    // requests 2 .. LPT-1 of the stage announced at the last barrier are due
     for (int unit = walk.tile; unit < walk.end; unit += walk.stride) {
-        const int tile = SPLIT ? unit / ksplit : unit, share = SPLIT ? unit - tile * ksplit : 0;
+        int tile = SPLIT ? unit / ksplit : unit;
+        const int share = SPLIT ? unit - tile * ksplit : 0;
         const int nst = SPLIT ? (share + 1) * nst_all / ksplit - share * nst_all / ksplit : nst_all;
-        const int tile_m = tile / p.tiles_n;
-        const int m0c = tile_m * BM, n0c = (tile - tile_m * p.tiles_n) * BN;
+        int tile_m = tile / p.tiles_n;
+        const int n0c = (tile - tile_m * p.tiles_n) * BN;
+        if (FR) {                                    // frame repeat: the ticket counter is the real tile's too
+            const int tn = tile - tile_m * p.tiles_n;
+            tile_m = fr_tile_m(tile_m, p.fr_ns(), p.fr_div(), p.HW, BM);
+            tile = tile_m * p.tiles_n + tn;
+        }
+        const int m0c = tile_m * BM;
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -691,6 +711,15 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k3
 #endif
 }
 
+template <int WAVES_M, int WAVES_N, int TAPS, int MINW, bool SPLIT = false>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k32p_kernel(const ConvK p) {
+    conv_gemm_f32_k32p_body<WAVES_M, WAVES_N, TAPS, MINW, SPLIT, false>(p);
+}
+template <int WAVES_M, int WAVES_N, int TAPS, int MINW, bool SPLIT = false>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k32p_repeat_kernel(const ConvK p) {
+    conv_gemm_f32_k32p_body<WAVES_M, WAVES_N, TAPS, MINW, SPLIT, true>(p);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Few tiles, long K (the ConvTWA step: 3600 rows x 256 columns x K 2304; the projections of the 12x20 / 23x40 backbone
 // maps).  What bounds such a launch is the matrix work of ONE tile on ONE CU (a 64 x 64 x 960 tile is 30 700 cycles
@@ -701,8 +730,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_gemm_f32_k3
 // counter; the share that draws the last ticket adds all of them in share order -- one round of loads, 64 KB -- and
 // applies the epilogue (BN / activation / residual, or the ConvTWA update).  Nobody waits, the order is fixed.
 // SPLIT = false is the plain 64 x 64 instance (the usual epilogue, any epilogue kind).
-template <int TAPS, bool SPLIT>
-__global__ __launch_bounds__(256, 3) void conv_gemm_f32_k32s_kernel(const ConvK p) {
+template <int TAPS, bool SPLIT, bool FR>
+__device__ __forceinline__ void conv_gemm_f32_k32s_body(const ConvK p) {
     constexpr int WM = 1, WN = 1, WAVES_N = 2;
     constexpr int BM = 64, BN = 64, KT = 32, NT = 256;
     constexpr int APAN = BM * 128, BPAN = BN * 128, STAGE = APAN + BPAN;
@@ -742,9 +771,14 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_f32_k32s_kernel(const ConvK 
             s0 = share * nst_all / ksplit;
             nst = (share + 1) * nst_all / ksplit - s0;
         }
-        const int tile_m = tile_id / p.tiles_n;
+        int tile_m = tile_id / p.tiles_n;
+        const int tile_n = tile_id - tile_m * p.tiles_n;
+        if (FR) {                                    // frame repeat: compact -> real M tile (tickets and partial sums: the real tile's)
+            tile_m = fr_tile_m(tile_m, p.fr_ns(), p.fr_div(), p.HW, BM);
+            tile_id = tile_m * p.tiles_n + tile_n;
+        }
         m0 = tile_m * BM;
-        n0 = (tile_id - tile_m * p.tiles_n) * BN;
+        n0 = tile_n * BN;
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int m = m0 + r8 + it * 32;
@@ -900,6 +934,11 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_f32_k32s_kernel(const ConvK 
     }
 }
 
+template <int TAPS, bool SPLIT>
+__global__ __launch_bounds__(256, 3) void conv_gemm_f32_k32s_kernel(const ConvK p) { conv_gemm_f32_k32s_body<TAPS, SPLIT, false>(p); }
+template <int TAPS, bool SPLIT>
+__global__ __launch_bounds__(256, 3) void conv_gemm_f32_k32s_repeat_kernel(const ConvK p) { conv_gemm_f32_k32s_body<TAPS, SPLIT, true>(p); }
+
 // k.ksplit (conv_route.h: k32_shares / k32s_shares) workgroups share the K loop of a tile.  FLAT (tile 10): the last share to
 // arrive adds them inside the launch; else (tiles 8 / 9) they meet in splitk_reduce_kernel.
 template <int WAVES_M, int WAVES_N, int MINW, bool FLAT = false>
@@ -908,7 +947,19 @@ int launch_k32(const ConvK& k0, int taps, hipStream_t stream) {
     constexpr int SMEM = 2 * (BM + BN) * 128 + (FLAT ? 32 * BN * 4 : 0);
     ConvK k = k0;
     k.tiles_n = (k.Cout + BN - 1) / BN;
-    k.nblk = ((k.M + BM - 1) / BM) * k.tiles_n * k.ksplit;
+    k.fr_bm = BM;
+    if (taps != 1 || WAVES_M != 2) k.fr = 0;      // frame repeat: instances exist for the 1x1 kernels on 128-row tiles; else the whole launch
+    k.nblk = (k.fr ? fr_tiles_m(k, BM) : (k.M + BM - 1) / BM) * k.tiles_n * k.ksplit;
+    if constexpr (WAVES_M == 2) {
+        if (k.fr) {
+            if constexpr (!FLAT)
+                return then_reduce(launch_resident<conv_gemm_f32_k32_repeat_kernel<WAVES_M, WAVES_N, 1, MINW>, SMEM, NT, true>(k, stream), k, 1.0f, stream);
+            else if (k.ksplit > 1)
+                return launch_resident<conv_gemm_f32_k32p_repeat_kernel<WAVES_M, WAVES_N, 1, MINW, true>, SMEM, NT, true>(k, stream);
+            else
+                return launch_resident<conv_gemm_f32_k32p_repeat_kernel<WAVES_M, WAVES_N, 1, MINW>, SMEM, NT, true>(k, stream);
+        }
+    }
     if constexpr (FLAT) {
         if (k.ksplit > 1)          // (tile, K share) work units
             return launch_taps<conv_gemm_f32_k32p_kernel<WAVES_M, WAVES_N, 1, MINW, true>,
@@ -926,7 +977,12 @@ int launch_k32s(const ConvK& k0, int taps, hipStream_t stream) {
     constexpr int SMEM = 2 * (64 + 64) * 128;
     ConvK k = k0;
     k.tiles_n = (k.Cout + 63) / 64;
-    k.nblk = ((k.M + 63) / 64) * k.tiles_n * k.ksplit;
+    k.fr_bm = 64;
+    if (taps != 1) k.fr = 0;                      // (frame repeat: 1x1 instances only; else the whole launch)
+    k.nblk = (k.fr ? fr_tiles_m(k, 64) : (k.M + 63) / 64) * k.tiles_n * k.ksplit;
+    if (k.fr)
+        return k.ksplit > 1 ? launch_resident<conv_gemm_f32_k32s_repeat_kernel<1, true>, SMEM, 256>(k, stream)
+                            : launch_resident<conv_gemm_f32_k32s_repeat_kernel<1, false>, SMEM, 256>(k, stream);
     if (k.ksplit > 1) return launch_taps<conv_gemm_f32_k32s_kernel<1, true>, conv_gemm_f32_k32s_kernel<9, true>, SMEM, 256>(k, taps, stream);
     return launch_taps<conv_gemm_f32_k32s_kernel<1, false>, conv_gemm_f32_k32s_kernel<9, false>, SMEM, 256>(k, taps, stream);
 }

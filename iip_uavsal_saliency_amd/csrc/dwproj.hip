@@ -44,8 +44,10 @@ namespace {
 // bound by the requests (29 KB per step and workgroup), not by the matrix pipe.  All fragments of the next step are
 // read after the last MFMA and stay in flight across the barrier.
 // Shapes: stride 1, dilation 1, hidden channels % 16 == 0 (host: dwproj_eligible).
-template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN>
-__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 1) void dwproj_kernel(const ConvK p) {
+// (the body, shared by the kernel and its frame-repeat instance -- FR: patches of the source images only, each stored to every
+// image that repeats it, ConvK.fr; a kernel of its own so that the instance every other launch runs is compiled without it)
+template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN, bool FR>
+__device__ __forceinline__ void dwproj_body(const ConvK p) {
     static_assert(PREC == UAVSAL_PREC_F32 || PREC == UAVSAL_PREC_F16X3, "fp32 or split-fp16");
     constexpr bool H16 = PREC == UAVSAL_PREC_F16X3;
     constexpr int PH = 8, PW = 16, HPITCH = PW + 3, NHSLOT = (PH + 2) * HPITCH;
@@ -118,6 +120,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 1) void dwproj_kernel(const
         n0 = (t - tm * p.tiles_n) * BN;
         img = tm / (phn * pwn);
         const int rem = tm - img * (phn * pwn);
+        if (FR) img *= p.fr_div();                     // frame repeat: the patches of the source images only (ConvK.fr)
         const int pyi = rem / pwn;
         y0 = pyi * PH;
         x0 = (rem - pyi * pwn) * PW;
@@ -457,6 +460,22 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 1) void dwproj_kernel(const
                                 for (int c = 0; c < 4; ++c)
                                     if (gn + c < p.Cout) o[c] = v[c] + (rs ? rs[c] : 0.f);
                             }
+                            if (FR) {
+                                // frame repeat: the same values to every other image that repeats this source image, f with
+                                // (f / fr_div * fr_div) % fr_mod == cimg (the host arms no launch with a residual or a shadow)
+                                const int n_img = p.M / p.HW;
+                                for (int q = cimg; q < n_img; q += p.fr_mod())
+                                    for (int f = q + (q == cimg ? 1 : 0); f < q + p.fr_div() && f < n_img; ++f) {
+                                        float* o2 = p.out + ((long long)f * p.o_is + pix) * p.ldc + gn;
+                                        if (vec) {
+                                            *reinterpret_cast<f32x4*>(o2) = v;
+                                        } else {
+#pragma unroll
+                                            for (int c = 0; c < 4; ++c)
+                                                if (gn + c < p.Cout) o2[c] = v[c];
+                                        }
+                                    }
+                            }
                         }
                     }
                     __syncthreads();
@@ -470,6 +489,14 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 1) void dwproj_kernel(const
     else run(std::false_type{}, std::true_type{});
 }
 
+template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 1) void dwproj_kernel(const ConvK p) {
+    dwproj_body<PREC, WAVES_M, WAVES_N, WM, WN, false>(p);
+}
+template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 1) void dwproj_repeat_kernel(const ConvK p) {
+    dwproj_body<PREC, WAVES_M, WAVES_N, WM, WN, true>(p);
+}
 
 template <int PREC, int WAVES_M, int WAVES_N, int WM, int WN>
 int launch_dwproj_variant(const ConvK& k0, hipStream_t stream) {
@@ -477,8 +504,13 @@ int launch_dwproj_variant(const ConvK& k0, hipStream_t stream) {
     constexpr int SMEM = 3 * (13 * 1024) + 5 * BN * 64 + 3 * 128 * 64 + 1024;   // E slots, weight panels, A tiles, scratch
     ConvK k = k0;
     k.tiles_n = (k.Cout + BN - 1) / BN;
-    k.nblk = (k.M / k.HW) * ((k.H + 7) / 8) * ((k.W + 15) / 16) * k.tiles_n;
+    // frame repeat lives in the staged epilogue of a whole-K fp32 tile; anything else runs the whole launch
+    if (UAVSAL_DWPROJ_TEPI || k.ksplit > 1 || PREC != UAVSAL_PREC_F32) k.fr = 0;
+    k.nblk = (k.fr ? k.fr_ns() : k.M / k.HW) * ((k.H + 7) / 8) * ((k.W + 15) / 16) * k.tiles_n;
     k.nblk *= k.ksplit;      // (conv_route.h: dwproj_shares; the narrowest instance only)
+    if constexpr (PREC == UAVSAL_PREC_F32) {
+        if (k.fr) return launch_resident<dwproj_repeat_kernel<PREC, WAVES_M, WAVES_N, WM, WN>, SMEM, NT, true>(k, stream);
+    }
     return then_reduce(launch_resident<dwproj_kernel<PREC, WAVES_M, WAVES_N, WM, WN>, SMEM, NT, true>(k, stream), k,
                        PREC == UAVSAL_PREC_F16X3 ? F16X3_ACC_SCALE : 1.0f, stream);
 }
@@ -493,6 +525,9 @@ int launch_dwproj(const ConvK& k, int bn, hipStream_t stream) {
 
 
 }  // namespace
+
+// does this build's dwproj_kernel carry the frame-repeat stores (ConvK.fr)?
+__attribute__((visibility("hidden"))) bool uavsal_dwproj_repeats() { return !UAVSAL_DWPROJ_TEPI; }      // (its fp32 instances)
 
 int uavsal_launch_dwproj(const uavsal_gemm::ConvK& k, int prec, int bn, hipStream_t stream) {
     return prec == UAVSAL_PREC_F32 ? launch_dwproj<UAVSAL_PREC_F32>(k, bn, stream) : launch_dwproj<UAVSAL_PREC_F16X3>(k, bn, stream);

@@ -79,6 +79,11 @@ struct uavsal_plan {
     uint32_t groups_off = 0;
     int last_launches = 0;                // ops that launched in the most recent run (its ranges added up; an op may be >1 kernel)
     int graph_launches = 0;               // ... that the captured graph holds
+    // frame repeat (uavsal_plan_frame_repeat): the expand / depthwise-projection pair of ops it names, the image map, whether
+    // the next runs apply it, and the workgroups the pair's kernels started in the most recent run that launched them
+    int fr_pw = -1, fr_dw = -1, fr_mod = 0, fr_div = 0;
+    bool fr_on = false;
+    int fr_wg[2] = {0, 0};
 };
 
 extern "C" uavsal_plan* uavsal_plan_create(void) { return new (std::nothrow) uavsal_plan(); }
@@ -256,10 +261,23 @@ extern "C" int uavsal_plan_last_launches(const uavsal_plan* p) { return p ? p->l
 
 // ops [first, last); `masked`: leave out the ops of switched-off groups -- kernels, fork / join event operations and all.
 // *launched += ops that launched
-static int run_range(uavsal_plan* p, int first, int last, uavsal_stream_t stream, bool masked, int* launched) {
+// `repeat`: a run of the plan proper (uavsal_plan_run), which applies the frame-repeat mode when it is on and the range holds
+// the pair from the plan's first op on -- the whole plan, or the head of a streamed run; a single op or a range that starts
+// anywhere else (the float64 walkers, per-op timing) always runs in full
+static int run_range(uavsal_plan* p, int first, int last, uavsal_stream_t stream, bool masked, int* launched, bool repeat = false) {
     const int n = (int)p->ops.size();
     if (last < 0 || last > n) last = n;
     if (first < 0 || first > last) return UAVSAL_EINVAL;
+    bool fr = repeat && p->fr_on && p->fr_pw >= 0 && first == 0 && last > p->fr_dw;
+    if (fr) {
+        const Op& a = p->ops[p->fr_pw];
+        const Op& b = p->ops[p->fr_dw];
+        const uint32_t goff = masked ? p->groups_off : 0u;
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+        fr = cs == hipStreamCaptureStatusNone && !(a.group >= 0 && ((goff >> a.group) & 1u)) && !(b.group >= 0 && ((goff >> b.group) & 1u)) &&
+             uavsal_conv_repeat_pair(&a.u.conv, &b.u.conv, p->fr_mod, p->fr_div) == 1;
+    }
     // lanes are honoured only when the whole plan runs; a sub-range (per-op timing) is launched flat
     const bool lanes = p->lanes_on && first == 0 && last == n;
     const uint32_t off = masked ? p->groups_off : 0u;
@@ -284,7 +302,11 @@ static int run_range(uavsal_plan* p, int first, int last, uavsal_stream_t stream
         }
         uavsal_stream_t s = (lanes && op.lane > 0) ? (uavsal_stream_t)p->side[op.lane] : stream;
         if (lanes && op.lane > 0 && !p->side[op.lane]) return UAVSAL_ESTATE;    // op on a lane that was never forked
-        const int e = run_op(op, s);
+        int e;
+        if (repeat && (i == p->fr_pw || i == p->fr_dw))
+            e = uavsal_conv_gemm_mapped(&op.u.conv, s, fr ? p->fr_mod : 0, fr ? p->fr_div : 0, &p->fr_wg[i == p->fr_dw]);
+        else
+            e = run_op(op, s);
         if (e) return e;
         ++*launched;
     }
@@ -303,12 +325,34 @@ static int run_range(uavsal_plan* p, int first, int last, uavsal_stream_t stream
 extern "C" int uavsal_plan_run(uavsal_plan* p, int first, int last, uavsal_stream_t stream) {
     if (!p) return UAVSAL_EINVAL;
     if (first == 0) p->last_launches = 0;       // (a run issued in two ranges: the second adds to the first)
-    return run_range(p, first, last, stream, true, &p->last_launches);
+    return run_range(p, first, last, stream, true, &p->last_launches, true);
+}
+
+// Frame repeat.  Names the plan's expand / depthwise-projection pair (`op_pw` writes the hidden tensor that `op_dwpl` alone
+// reads) whose input is the same for every image f and image (f / src_div * src_div) % src_mod -- the map of the bilinear op
+// that broadcasts the context prior -- and switches the mode on or off for the runs that follow.  Returns 1 when those runs
+// will apply it, 0 when they run in full (`on` == 0, or the pair's routes / shapes are refused: uavsal_conv_repeat_pair in
+// csrc/conv_gemm.hip; a captured graph always replays the full launches), negative for bad arguments.
+extern "C" int uavsal_plan_frame_repeat(uavsal_plan* p, int op_pw, int op_dwpl, int src_mod, int src_div, int on) {
+    const int n = p ? (int)p->ops.size() : 0;
+    if (!p || op_pw < 0 || op_dwpl <= op_pw || op_dwpl >= n || src_mod <= 0 || src_div <= 0) return UAVSAL_EINVAL;
+    if (p->ops[op_pw].kind != OP_CONV || p->ops[op_dwpl].kind != OP_CONV) return UAVSAL_EINVAL;
+    p->fr_pw = op_pw; p->fr_dw = op_dwpl; p->fr_mod = src_mod; p->fr_div = src_div;
+    p->fr_on = on != 0 && !p->exec &&
+               uavsal_conv_repeat_pair(&p->ops[op_pw].u.conv, &p->ops[op_dwpl].u.conv, src_mod, src_div) == 1;
+    return p->fr_on ? 1 : 0;
+}
+
+// workgroups that the pair's kernel (which = 0: the expand, 1: the depthwise-projection) started in the most recent
+// uavsal_plan_run that launched it, armed or not; 0 before any
+extern "C" int uavsal_plan_frame_repeat_workgroups(const uavsal_plan* p, int which) {
+    return p && (which == 0 || which == 1) ? p->fr_wg[which] : UAVSAL_EINVAL;
 }
 
 extern "C" int uavsal_plan_graph_build(uavsal_plan* p, uavsal_stream_t stream) {
     if (!p) return UAVSAL_EINVAL;
     if (p->exec) return 0;
+    p->fr_on = false;          // (a captured graph holds the full launches)
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) return (int)e;

@@ -8,7 +8,8 @@ Built once per (device, clip count, sequence length, frame size, precision):
      `uavsal_plan` (C ABI, include/uavsal_hip.h) that is then replayed natively --
      as a launch loop or as one captured hipGraph.
 `run()` only stages the caller's tensors and launches the plan on torch's current
-stream.  PyTorch is used for device memory and streams, not for arithmetic.
+stream.  PyTorch is used for device memory and streams, not for arithmetic (one exception, off the hot path: the call that runs
+the prior nets compares the prior frames with their source frames, `PriorCache.compare_frames`).
 """
 from __future__ import annotations
 
@@ -84,6 +85,39 @@ class PriorCache:
         stay alive while they may be bound."""
         if self.new is not None:
             self.new["bound"].update(bound)
+
+    def compare_frames(self, src_idx):
+        """Frame repeat (Engine._arm_repeat): the call in progress runs the prior nets, so it also finds out whether every
+        frame f of each prior tensor it bound equals, element for element, its source frame `src_idx[f]` (a device index
+        tensor).  Started on the current stream in FRONT of the run's launches -- a later call that may leave the group out
+        has waited for this run (`gate`) and so for the answer -- into a pinned host word behind an event: nobody waits for
+        it.  NaN compares unequal.  One frame (the static-priors plan: a zero frame stride) is every frame without looking."""
+        if self.new is None:
+            return
+        ts = [t for t in self.new["bound"].values() if t.shape[0] > 1]
+        if not ts:
+            self.new["same"] = True
+            return
+        ok = None
+        for t in ts:
+            e = (t == t.index_select(0, src_idx)).all()
+            ok = e if ok is None else ok & e
+        word = torch.zeros(1, dtype=torch.bool).pin_memory()
+        word.copy_(ok.reshape(1), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.new["same"] = (ev, word)
+
+    def frames_repeat(self) -> bool:
+        """Did the run the record comes from find every prior frame identical to its source frame?  False while that is not
+        known yet (no wait)."""
+        s = self.rec.get("same") if self.rec is not None else None
+        if isinstance(s, tuple):
+            ev, word = s
+            if not ev.query():
+                return False
+            s = self.rec["same"] = bool(word[0])
+        return s is True
 
     def bound(self):
         """{caller name: tensor} the group last ran on (a call that leaves the group out keeps them bound)."""
@@ -271,6 +305,16 @@ class Engine:
             self.h_view, self.c_view = (rec.named[k].t.view(self.n_seq, h, w, 256).permute(0, 3, 1, 2) if k in rec.named else None
                                         for k in ("h0", "c0"))
         self.priors = PriorCache(self.lib, rec.plan, rec.prior_ops)
+        # frame repeat: the fusion block behind the priors (`fucb`, topology.py) reads cat[gauss, ob, ctx].  The context map
+        # of frame f is that of frame (f // div * div) % mod (the map of `ctx.up`), so when the caller's priors repeat over
+        # the frames in the same way the block's output does too, and its two launches compute the source frames only
+        # (uavsal_plan_frame_repeat; `_arm_repeat`).  (pw op, dwpl op, mod, div), or None for a plan without that pair
+        pw, dwpl = rec.op_idx.get("fucb.pw"), rec.op_idx.get("fucb.dwpl")
+        self._fr = None
+        if pw is not None and dwpl is not None and rec.ops_meta[pw]["kind"] == "conv1" and rec.ops_meta[dwpl]["kind"] == "conv1":
+            self._fr = (pw, dwpl) + ((N // self.ctx_T, 1) if self.ctx_mode == "tile" else (N, self.ctx_T))
+        self._fr_idx = None                  # source frame of every frame, on the device (built by the first miss)
+        self.repeat_armed = False            # did the most recent run apply the mode?
         self.use_lanes = bool(use_lanes)
         L.check(self.lib.uavsal_plan_enable_lanes(self.plan, 1 if self.use_lanes else 0), "plan_enable_lanes")
         self._graph_ready = False
@@ -315,6 +359,36 @@ class Engine:
         """May this call leave the prior group out (PriorCache.gate)?  The call's launches then go inside `priors.launches()`."""
         sig = self._prior_sig(srcs) if (self.inplace and bool(getattr(self.model, "cache_priors", True))) else None
         return self.priors.gate(sig, lambda: self.check(wait=True))
+
+    def _arm_repeat(self, skip):
+        """In front of a call's launches (after the binding).  A miss -- the call runs the prior nets -- starts the comparison
+        of the prior frames it bound and runs in full.  A hit arms the frame-repeat mode of the plan when that comparison is
+        over and said "identical", `dedupe_priors` and `cache_priors` are on and the plan is a launch loop; the native side
+        still refuses routes it cannot take (f16x3 plans, a three-launch block).  `_disarm_repeat` follows the launches."""
+        self.repeat_armed = False
+        if self._fr is None or not self.inplace:
+            return
+        pw, dwpl, mod, div = self._fr
+        if not skip:
+            if self._fr_idx is None:
+                self._fr_idx = torch.tensor([(f // div * div) % mod for f in range(self.N)], dtype=torch.int64, device=self.device)
+            self.priors.compare_frames(self._fr_idx)
+        on = (skip and bool(getattr(self.model, "dedupe_priors", True)) and bool(getattr(self.model, "cache_priors", True))
+              and self.priors.frames_repeat())
+        r = self.lib.uavsal_plan_frame_repeat(self.plan, pw, dwpl, mod, div, 1 if on else 0)
+        if r < 0:
+            L.check(r, "plan_frame_repeat")
+        self.repeat_armed = r == 1
+
+    def _disarm_repeat(self):
+        """Behind a call's launches: whatever runs next -- single ops, partial ranges, the per-op timer -- runs in full."""
+        if self.repeat_armed:
+            pw, dwpl, mod, div = self._fr
+            self.lib.uavsal_plan_frame_repeat(self.plan, pw, dwpl, mod, div, 0)
+
+    def repeat_workgroups(self):
+        """(workgroups of `fucb.pw`, of `fucb.dwpl`) in the most recent run of the plan: fewer when the mode was applied."""
+        return tuple(int(self.lib.uavsal_plan_frame_repeat_workgroups(self.plan, i)) for i in (0, 1))
 
     def last_launches(self) -> int:
         """Plan ops that launched in the most recent run of the plan (an op with a split-K reduction is two kernels, one op)."""
@@ -429,8 +503,12 @@ class Engine:
                 out, st = self._bind_in_place(x, cb0, cb1, state, cstate, lstm, skip)
             else:
                 self.stage_inputs(x, cb0, cb1, state, cstate)
+            self._arm_repeat(skip)
             with self.priors.launches():
-                self.launch()
+                try:
+                    self.launch()
+                finally:
+                    self._disarm_repeat()
             if self.sync_errors:
                 self.check(wait=True)
             if not self._first_run_verified and self.split_mode:
@@ -490,8 +568,12 @@ class Engine:
             skip = self._prior_gate((cb0, cb1))
             out, _ = self._bind_in_place(x, cb0, cb1, self.h_view, self.c_view, lstm, skip)      # (resident views: nothing is staged)
             split = self.state_split()
+            self._arm_repeat(skip)
             with self.priors.launches():
-                L.check(self.lib.uavsal_plan_run(self.plan, 0, split, self._stream()), "plan_run(head)")
+                try:
+                    L.check(self.lib.uavsal_plan_run(self.plan, 0, split, self._stream()), "plan_run(head)")
+                finally:
+                    self._disarm_repeat()
                 cur = torch.cuda.current_stream(self.device)
                 if prev_done is not None:
                     cur.wait_event(prev_done)

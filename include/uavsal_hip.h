@@ -939,6 +939,25 @@ int uavsal_plan_group_mark(uavsal_plan* p, int group, int first, int last);
 int uavsal_plan_group_enable(uavsal_plan* p, int group, int on);
 int uavsal_plan_group_launches(const uavsal_plan* p, int group);
 int uavsal_plan_last_launches(const uavsal_plan* p);
+/* Frame repeat: a run-time mode of ONE pair of conv ops of a recorded plan -- the 1x1 expand `op_pw` of an inverted-residual
+ * block and the depthwise -> projection launch `op_dwpl` that alone reads the expand's output -- for calls in which the
+ * block's input is the same for image f and image (f / src_div * src_div) % src_mod (the image map of uavsal_bilinear_desc:
+ * the fusion block behind the priors, model.py:363-364, when the caller's priors are one map set repeated over the frames).
+ * While it is on, a run that starts at the plan's first op and reaches past the pair (the whole plan, or the head range of
+ * a streamed run) computes only the src_mod / src_div "source" images: the expand walks the M tiles that hold a row of a
+ * source image (a tile that straddles into a neighbour is computed whole) with the kernel, tile, K shares, workspace and
+ * ticket layout of the full launch and leaves the other rows of the hidden tensor unwritten; the projection walks the
+ * patches of the source images and stores each to every image that repeats it.  The outputs are bit-identical to the
+ * full launches'.  Any other range, the per-op timer and a captured graph run the pair in full, and so does a pair whose
+ * routes could change an element's summation order with its tile's position or do not carry the map: armed are the
+ * expand routes UAVSAL_ROUTE_K32 with tile 8 / 10 / 11 (any K shares) and the projection route UAVSAL_ROUTE_DWPROJ with
+ * whole-K tiles, both UAVSAL_EPI_AFFINE on dense images, without residual or split shadow.
+ * Called at run time (not while recording); returns 1 when the following runs apply the mode, 0 when they run in full
+ * (`on` == 0, a refused pair, nothing to leave out, a built graph), negative on bad arguments.
+ * frame_repeat_workgroups: the grid that the kernel of op_pw (`which` = 0) / op_dwpl (1) was started with in the most
+ * recent uavsal_plan_run that launched it, in full or not. */
+int uavsal_plan_frame_repeat(uavsal_plan* p, int op_pw, int op_dwpl, int src_mod, int src_div, int on);
+int uavsal_plan_frame_repeat_workgroups(const uavsal_plan* p, int which);
 /* capture the whole plan into a hipGraph once, then replay it */
 int uavsal_plan_graph_build(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
