@@ -285,6 +285,25 @@ class IrFinishDesc(C.Structure):
 IR_NSUM = 11                  # UAVSAL_IR_NSUM: sums per hidden channel in the workspace of uavsal_ir_sums (csrc/train_block.hip)
 BLOCK_DESC_TYPES = [IrBwdDesc, IrSumsDesc, IrFinishDesc]        # sized by uavsal_block_sizeof_desc
 
+
+class IrBwdS2Desc(C.Structure):
+    _fields_ = [("gd", _f), ("d", _f), ("e", _f), ("wd9", _f), ("s2", _f), ("ga", _f),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
+
+
+class BilinearBwdDesc(C.Structure):
+    _fields_ = [("gout", _f), ("ldo", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32),
+                ("gin", _f), ("Hi", C.c_int32), ("Wi", C.c_int32),
+                ("n_out", C.c_int32), ("n_src", C.c_int32), ("C", C.c_int32), ("src_mod", C.c_int32), ("src_div", C.c_int32)]
+
+
+class TsumBwdDesc(C.Structure):
+    _fields_ = [("a", _f), ("lda", C.c_int32), ("g", _f), ("ldg", C.c_int32), ("out", _f), ("ldo", C.c_int32),
+                ("n_groups", C.c_int32), ("T", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32)]
+
+
+CTX_DESC_TYPES = [IrBwdS2Desc, BilinearBwdDesc, TsumBwdDesc]    # sized by uavsal_ctx_sizeof_desc (csrc/train_ctx.hip)
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -338,6 +357,10 @@ SYMBOLS = [
     ("uavsal_ir_sums", C.c_int, [C.POINTER(IrSumsDesc), C.c_void_p]),
     ("uavsal_ir_finish", C.c_int, [C.POINTER(IrFinishDesc), C.c_void_p]),
     ("uavsal_block_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_ir_bwd_s2", C.c_int, [C.POINTER(IrBwdS2Desc), C.c_void_p]),
+    ("uavsal_bilinear_ac_bwd", C.c_int, [C.POINTER(BilinearBwdDesc), C.c_void_p]),
+    ("uavsal_tsum_bwd", C.c_int, [C.POINTER(TsumBwdDesc), C.c_void_p]),
+    ("uavsal_ctx_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -412,7 +435,7 @@ def load():
                 t.__name__, C.sizeof(t), lib.uavsal_sizeof_desc(i)))
     for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES),
                           (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES),
-                          (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES)):
+                          (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

@@ -266,8 +266,9 @@ class Engine:
     arena_stats = property(lambda self: self.arena.stats)
     TAP_NAMES = ("c3", "c4", "c5", "sfnet", "st0", "st1", "fust_in_cb", "prefuse", "rnn")
     # kept like the taps, but read back only when the caller asks for them by handing a `taps` dict that already holds the
-    # name (any value): fucbst_layer's whole input, as ONE channels-last copy (train.recurrence_step(fuse=True) reads it NHWC)
-    TAPS_ON_REQUEST = ("fu320",)
+    # name (any value): fucbst_layer's whole input, as ONE channels-last copy (train.recurrence_step(fuse=True) reads it NHWC),
+    # and fucb_layer's whole input, the concatenated prior maps (train.recurrence_step(fust=True))
+    TAPS_ON_REQUEST = ("fu320", "cb192")
 
     def _size(self):
         """Pass 1: sizes the shared scratch and lays the arena out (nothing allocated, nothing recorded)."""

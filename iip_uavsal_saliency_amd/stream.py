@@ -395,13 +395,17 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     gradients of `model.conv_out_st` (the optimiser then holds its parameters too) and both stages are refreshed.
     `"fuse"` (after `"rnn"` and, when present, `"decoder"`): `recurrence_step(..., fuse=True)` also sets the gradients of
     the fusion block in front of the recurrence (`train.fuse_block`: `model.fucbst_layer[0]` with any prior enabled, else
-    `model.fust_layer[0]`), and that block's container is refreshed with the other trained stages."""
+    `model.fust_layer[0]`), and that block's container is refreshed with the other trained stages.
+    `"fust"` (last, and only behind `"fuse"`; a model with at least one prior): `recurrence_step(..., fust=True)` also sets
+    the gradients of `model.fust_layer[0]` behind the priors, and `model.fust_layer` is refreshed as well."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
     stages = tuple(stages)
-    if stages not in (("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse")):
-        raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, got %r" % (stages,))
+    if stages not in (("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse"), ("rnn", "fuse", "fust"),
+                      ("rnn", "decoder", "fuse", "fust")):
+        raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
+                         "'fuse', got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
@@ -411,6 +415,8 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
         mods = [model.rnn] + ([model.conv_out_st] if "decoder" in kw else [])
         if "fuse" in kw:
             mods.append(model.fucbst_layer if model.num_cb else model.fust_layer)
+        if "fust" in kw:
+            mods.append(model.fust_layer)
         model.refresh_weights(*mods)
         return loss, state
     return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,

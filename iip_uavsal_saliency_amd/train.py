@@ -14,7 +14,10 @@ A second stage can be trained with it: the decoder `model.conv_out_st` (`decoder
 BatchNorms on their running statistics.  A third one as well: the fusion block that produces the recurrence's input
 (`fuse_block`: `model.fucbst_layer[0]`, or `model.fust_layer[0]` without priors), through the backward of a general
 inverted-residual block (`block_backward`, `block_param_grads`, `recurrence_step(fuse=True)`; csrc/train_block.hip:
-`uavsal_ir_bwd`, `uavsal_ir_sums`, `uavsal_ir_finish`, and `uavsal_pix_gemm` for both 1x1 weight gradients).
+`uavsal_ir_bwd`, `uavsal_ir_sums`, `uavsal_ir_finish`, and `uavsal_pix_gemm` for both 1x1 weight gradients).  A fourth one
+in a model with priors: `model.fust_layer[0]` behind them (`recurrence_step(fust=True)`), whose output gradient comes
+through the fusion block's input directly and through the frozen context-prior path (`fust_output_grad`,
+`block_input_grad`; csrc/train_ctx.hip: `uavsal_ir_bwd_s2`, `uavsal_bilinear_ac_bwd`, `uavsal_tsum_bwd`).
 
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
@@ -31,6 +34,7 @@ import torch
 from . import _lib as L
 from . import packing as P
 from .ops import _nhwc_view, _stream
+from .ops import tsum as _tsum
 from .weights import WeightCache
 
 HID = 256
@@ -467,18 +471,19 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
     return out
 
 
-def _block_recompute(lib, cache, block, x):
-    """`e`, `d` (dense NHWC) from the NHWC `x` by the forward's own launches (expand conv, `uavsal_dw3x3`)."""
-    pw, pwbn, dwc, dwbn, _, _ = _block_parts(block)
+def _block_recompute(lib, cache, block, x, stride=1, prt=None):
+    """`e`, `d` (dense NHWC) from the NHWC `x` by the forward's own launches (expand conv, `uavsal_dw3x3`); `stride` 2: `d` is
+    `[T, (h-1)/2+1, (w-1)/2+1, Ch]`.  `prt`: the block's parts when the caller has checked them (`_input_grad_parts`)."""
+    pw, pwbn, dwc, dwbn, _, _ = prt or _block_parts(block)
     T, hh, ww, _ = x.shape
     hid = pw.weight.shape[0]
     e = _conv(lib, cache, x, pw, hid, 1, bn=pwbn, act=L.ACT_RELU6)
     w9, s2, b2 = cache.depthwise(dwc, dwbn)
-    dd = torch.empty_like(e)
+    dd = torch.empty((T, (hh - 1) // stride + 1, (ww - 1) // stride + 1, hid), dtype=torch.float32, device=x.device)
     q = L.DwDesc()
     q.inp, q.ldi, q.w9c, q.scale, q.bias = e.data_ptr(), hid, w9.data_ptr(), s2.data_ptr(), b2.data_ptr()
     q.out, q.ldo = dd.data_ptr(), hid
-    q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, 1, 1, L.ACT_RELU6
+    q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, stride, 1, L.ACT_RELU6
     L.check(lib.uavsal_dw3x3(C.byref(q), _stream(x)), "uavsal_dw3x3")
     return e, dd
 
@@ -512,6 +517,170 @@ def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None,
         if parts is not None:
             parts.update(e=e, d=dd, gd=gd, ga=ga)
     return (g.permute(0, 3, 1, 2) if need_x_grad else None), grads
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Input gradients of FROZEN blocks and of the context-prior path behind fust_layer (csrc/train_ctx.hip)
+def _dense_nhwc(name, what, *ts):
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous() for t in ts):
+        raise RuntimeError("%s: %s must be dense float32 NHWC cuda tensors" % (name, what))
+
+
+def ir_bwd_s2(gd, d, e, wd9, s2):
+    """`uavsal_ir_bwd_s2` on the current stream: `ir_bwd` for a depthwise 3x3 with stride 2.  `gd`, `d` dense NHWC
+    `[n,Ho,Wo,C]` with `Ho = (H-1)//2+1`, `Wo = (W-1)//2+1`, `e` dense NHWC `[n,H,W,C]`, the tap-major depthwise weights and
+    the folded scale of the depthwise BatchNorm on the device -> `ga` = d loss / d a1, dense NHWC like `e`."""
+    lib = L.load()
+    _dense_nhwc("ir_bwd_s2", "gd, d, e", gd, d, e)
+    n, hh, ww, c = e.shape
+    if gd.shape != d.shape or tuple(d.shape) != (n, (hh - 1) // 2 + 1, (ww - 1) // 2 + 1, c) or d.device != e.device or gd.device != e.device:
+        raise RuntimeError("ir_bwd_s2: gd and d must be [n,(H-1)//2+1,(W-1)//2+1,C] for e [n,H,W,C], on one device")
+    for name, t, m in (("wd9", wd9, 9 * c), ("s2", s2, c)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == e.device and t.is_contiguous() and t.numel() >= m):
+            raise RuntimeError("ir_bwd_s2: %s must be a dense float32 tensor of at least %d elements on the device of e" % (name, m))
+    ga = torch.empty_like(e)
+    k = L.IrBwdS2Desc()
+    k.gd, k.d, k.e, k.wd9, k.s2, k.ga = gd.data_ptr(), d.data_ptr(), e.data_ptr(), wd9.data_ptr(), s2.data_ptr(), ga.data_ptr()
+    k.n_img, k.H, k.W, k.C = n, hh, ww, c
+    L.check(lib.uavsal_ir_bwd_s2(C.byref(k), _stream(e)), "uavsal_ir_bwd_s2")
+    return ga
+
+
+def bilinear_bwd(gout, n_src, hi, wi, src_mod=None, src_div=1):
+    """`uavsal_bilinear_ac_bwd` on the current stream: the adjoint of the `align_corners=True` resize `[n_src,hi,wi,C]` ->
+    `[n_out,Ho,Wo,C]` in which output image `n` reads source image `(n % src_mod) // src_div` (default `src_mod = n_out`).
+    `gout`: an NHWC view `[n_out,Ho,Wo,C]` (a channel slice is read in place) -> the gradient of the source, dense NHWC."""
+    lib = L.load()
+    gp, ldo, n_out, ho, wo, c = _nhwc_view(gout)
+    src_mod = n_out if src_mod is None else int(src_mod)
+    gin = torch.empty((n_src, hi, wi, c), dtype=torch.float32, device=gout.device)
+    k = L.BilinearBwdDesc()
+    k.gout, k.ldo, k.Ho, k.Wo, k.gin, k.Hi, k.Wi = gp, ldo, ho, wo, gin.data_ptr(), hi, wi
+    k.n_out, k.n_src, k.C, k.src_mod, k.src_div = n_out, n_src, c, src_mod, int(src_div)
+    L.check(lib.uavsal_bilinear_ac_bwd(C.byref(k), _stream(gout)), "uavsal_bilinear_ac_bwd")
+    return gin
+
+
+def tsum_bwd(a, g, T):
+    """`uavsal_tsum_bwd` on the current stream: `out[b*T+t] = a[b*T+t] + g[b]`, the adjoint of the sum over chunks of `T` frames
+    added to a gradient that is already there.  `a` `[N,h,w,C]`, `g` `[N//T,h,w,C]` NHWC views (channel slices are read in
+    place) -> dense NHWC `[N,h,w,C]`."""
+    lib = L.load()
+    ap, lda, n, hh, ww, c = _nhwc_view(a)
+    gp, ldg, *gs = _nhwc_view(g)
+    if T <= 0 or n % T or gs != [n // T, hh, ww, c] or g.device != a.device:
+        raise RuntimeError("tsum_bwd: g must be [%d // T,%d,%d,%d] on the device of a, T a divisor of %d" % (n, hh, ww, c, n))
+    out = torch.empty((n, hh, ww, c), dtype=torch.float32, device=a.device)
+    k = L.TsumBwdDesc()
+    k.a, k.lda, k.g, k.ldg, k.out, k.ldo = ap, lda, gp, ldg, out.data_ptr(), c
+    k.n_groups, k.T, k.HW, k.C = n // T, T, hh * ww, c
+    L.check(lib.uavsal_tsum_bwd(C.byref(k), _stream(a)), "uavsal_tsum_bwd")
+    return out
+
+
+def _input_grad_parts(block):
+    """`(pw, pwbn, dwc, dwbn, pl, plbn)` of a FROZEN inverted-residual block `block_input_grad` covers, or a RuntimeError."""
+    seq = getattr(block, "conv", None)
+    stride = getattr(block, "stride", None)
+    if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4 or stride not in (1, 2)
+            or getattr(block, "dilation", None) != 1 or seq[1][0].stride != (stride, stride) or seq[1][0].dilation != (1, 1)):
+        raise RuntimeError("block_input_grad takes a dwBlock with an expand conv, stride 1 or 2 and dilation 1 "
+                           "(expand 1x1, depthwise 3x3, projection 1x1)")
+    pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
+    hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    if cout % 32 or hid % 64 or cin % 32:
+        raise RuntimeError("block_input_grad needs Cout %% 32 == 0, hidden %% 64 == 0 and Cin %% 32 == 0, got %d -> %d -> %d"
+                           % (cin, hid, cout))
+    if block.training:
+        raise RuntimeError("the block is frozen: its BatchNorms are folded in eval mode (call model.eval())")
+    return pw, pwbn, dwc, dwbn, pl, plbn
+
+
+def _input_grad(lib, cache, block, prt, xn, go, ed=None, parts=None):
+    """`block_input_grad` on checked NHWC views; `ed`: the block's `(e, d)` when the caller has them."""
+    pw, pwbn, dwc, dwbn, pl, plbn = prt
+    hid, cin = pw.weight.shape[:2]
+    stride = dwc.stride[0]
+    e, dd = ed or _block_recompute(lib, cache, block, xn, stride, prt)
+    gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
+    ga = (ir_bwd if stride == 1 else ir_bwd_s2)(gd, dd, e, *cache.depthwise(dwc, dwbn)[:2])
+    g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else None)
+    if parts is not None:
+        parts.update(e=e, d=dd, gd=gd, ga=ga)
+    return g
+
+
+def block_input_grad(block, x, grad_out, cache=None, parts=None):
+    """The gradient with respect to the input `x` `[n,Cin,h,w]` of a FROZEN inverted-residual `block` (a `dwBlock` with an
+    expand conv, stride 1 or 2, dilation 1, with or without the residual; eval mode, its BatchNorms folded), given `grad_out`
+    `[n,Co,ho,wo]` = d loss / d output (`ho = (h-1)//stride+1`).  The frozen path beside `block_backward`, as
+    `decoder_input_grad` is beside `decoder_backward`: `e` and `d` are recomputed by the forward's own launches, `gd` is one
+    Co -> Ch GEMM with the transposed projection weights that carry s3, `ga` comes from `uavsal_ir_bwd` (stride 1) or
+    `uavsal_ir_bwd_s2` (stride 2), and `grad_x` from one Ch -> Cin GEMM with the transposed expand weights that carry s1
+    (+ `grad_out` with the residual).  No parameter gradient is computed and no `.grad` touched.  Accepted: Cin % 32 == 0,
+    Ch % 64 == 0, Co % 32 == 0.  `parts` receives `e`, `d`, `gd`, `ga` (dense NHWC)."""
+    lib = L.load()
+    prt = _input_grad_parts(block)
+    pw, pl, stride = prt[0], prt[4], prt[2].stride[0]
+    cin, cout = pw.weight.shape[1], pl.weight.shape[0]
+    xn = _nhwc(x, "x", cin)
+    n, hh, ww, _ = xn.shape
+    ho, wo = (hh - 1) // stride + 1, (ww - 1) // stride + 1
+    if (not torch.is_tensor(grad_out) or not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.device != xn.device
+            or tuple(grad_out.shape) != (n, cout, ho, wo)):
+        raise RuntimeError("grad_out must be a float32 cuda tensor [%d,%d,%d,%d]" % (n, cout, ho, wo))
+    go = _nhwc(grad_out, "grad_out", cout)
+    with torch.cuda.device(xn.device):
+        cache = cache or WeightCache(xn.device, {})
+        g = _input_grad(lib, cache, block, prt, xn, go, parts=parts)
+    return g.permute(0, 3, 1, 2)
+
+
+def fust_output_grad(model, fu320, cb192, grad_fu, cache=None, parts=None):
+    """The gradient with respect to the OUTPUT of `model.fust_layer[0]` `[N,256,h,w]` in a model with priors, given `grad_fu`
+    `[N,320,h,w]` = d loss / d `fu320` (the input of `model.fucbst_layer[0]`; `block_backward(..., need_x_grad=True)` returns
+    it).  That output is channels 0..255 of `fu320`, and with the context prior it also feeds channels 256..319 (reference
+    model.py:357-365): chunk sum, `cxt_cb_prior[0]`, `cxt_cb_prior[1]` (both stride 2), bilinear upsample with the tiling
+    frame map of `forward()` (frame k reads chunk k % B, B = N // time_dims), concat with the other priors, `fucb_layer[0]`.
+    All of these stay frozen; the gradient walks back through them (`block_input_grad`, `bilinear_bwd`, `tsum_bwd`) and is
+    added to `grad_fu[:, :256]`.  Without the context prior the result IS `grad_fu[:, :256]`.
+    `fu320` `[N,320,h,w]`, `cb192` `[N,64*num_cb,h,w]`: the taps of those names.  The chunk sum and `cxt_cb_prior[0]`'s output
+    are recomputed (B images).  `parts` receives `g_cb`, `g_ctx2`, `g_ctx1`, `g_sum` (NHWC) and `ctx_sum`, `ctx1`."""
+    lib = L.load()
+    if not getattr(model, "num_cb", 0):
+        raise RuntimeError("fust_output_grad takes a model with at least one prior (without priors nothing lies behind fust_layer "
+                           "but the recurrence)")
+    if model.training:
+        raise RuntimeError("the prior path is frozen: its BatchNorms are folded in eval mode (call model.eval())")
+    fu = _nhwc(fu320, "fu320", 320)
+    N, hh, ww, _ = fu.shape
+    gf = _block_grad_out(grad_fu, fu, 320)
+    if not model.use_context_prior:
+        return gf[..., :HID].permute(0, 3, 1, 2)
+    T = model.time_dims
+    if N % T:
+        raise RuntimeError("fu320 holds %d frames, not a multiple of time_dims = %d" % (N, T))
+    B = N // T
+    fucb, ctx0, ctx1b = model.fucb_layer[0], model.cxt_cb_prior[0], model.cxt_cb_prior[1]
+    p_cb, p_0, p_1 = _input_grad_parts(fucb), _input_grad_parts(ctx0), _input_grad_parts(ctx1b)
+    cb = _nhwc(cb192, "cb192", 64 * model.num_cb)
+    if tuple(cb.shape[:3]) != (N, hh, ww) or cb.device != fu.device:
+        raise RuntimeError("cb192 must be [%d,%d,%d,%d] on the device of fu320" % (N, 64 * model.num_cb, hh, ww))
+    off = 64 * (int(bool(model.use_gauss_prior)) + int(bool(model.use_ob_prior)))
+    down = lambda v: (v - 1) // 2 + 1                                     # noqa: E731
+    with torch.cuda.device(fu.device):
+        cache = cache or WeightCache(fu.device, {})
+        g_cb = _input_grad(lib, cache, fucb, p_cb, cb, gf[..., HID:])
+        g_c2 = bilinear_bwd(g_cb[..., off:off + 64], B, down(down(hh)), down(down(ww)), src_mod=B, src_div=1)
+        ctx_sum = _tsum(fu[..., :HID], T)
+        ed0 = _block_recompute(lib, cache, ctx0, ctx_sum, 2, p_0)
+        c1 = _conv(lib, cache, ed0[1], p_0[4], p_0[4].weight.shape[0], 1, bn=p_0[5])
+        g_c1 = _input_grad(lib, cache, ctx1b, p_1, c1, g_c2)
+        g_sum = _input_grad(lib, cache, ctx0, p_0, ctx_sum, g_c1, ed=ed0)
+        g = tsum_bwd(gf[..., :HID], g_sum, T)
+        if parts is not None:
+            parts.update(g_cb=g_cb, g_ctx2=g_c2, g_ctx1=g_c1, g_sum=g_sum, ctx_sum=ctx_sum, ctx1=c1)
+    return g.permute(0, 3, 1, 2)
 
 
 def twa_gate_bwd(g, carry, z, x, hprev, need_dx=False):
@@ -649,7 +818,7 @@ def _param_grad_tensors(blk):
     return {n: q.grad for n, q in params.items()}, acc
 
 
-def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False):
+def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -663,11 +832,20 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     gradient of the recurrence's input, which `block_backward` carries to that block's nine parameters (`.grad` set, or added
     to); everything in front of the block stays frozen, and nothing of `prefuse` bypasses the recurrence, so the gradient is
     exact.  Refresh `model.fucbst_layer` (or `model.fust_layer` in a model without priors) afterwards as well.  Combines
-    freely with `decoder=True`; the default call runs the launches -- and the copies of taps -- it always ran."""
+    freely with `decoder=True`; the default call runs the launches -- and the copies of taps -- it always ran.
+    `fust=True` (needs `fuse=True` and a model with at least one prior; without priors the `fuse` stage already IS
+    `model.fust_layer[0]`): the block behind the priors, `model.fust_layer[0]`, is trained as well.  `block_backward` of the
+    fusion block also returns the gradient of its input `fu320`, `fust_output_grad` carries it to fust_layer's output --
+    directly and, with the context prior, through the frozen `fucb_layer`, upsample, `cxt_cb_prior` and chunk sum -- and a
+    second `block_backward` to fust_layer's nine parameters (`.grad` set, or added to).  The ST blocks in front of it, the
+    prior nets, `fucb_layer` and `cxt_cb_prior` stay frozen.  Refresh `model.fust_layer` afterwards as well."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
         raise RuntimeError("recurrence_step covers the ConvTWA recurrence, not UAVSAL_LSTM")
+    if fust and not (fuse and getattr(model, "num_cb", 0)):
+        raise RuntimeError("fust=True needs fuse=True and a model with at least one prior (without priors the fuse stage "
+                           "already is model.fust_layer[0])")
     if model.training:
         raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
     if model.precision != "f32":
@@ -677,6 +855,8 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     rc = model.rnn.cell_list[0].rnn_conv
     blk, src = fuse_block(model) if fuse else (None, None)
     taps = {src: None} if fuse else {}                               # (fu320 is read back on request only: engine.TAPS_ON_REQUEST)
+    if fust:
+        taps["cb192"] = None                                         # (likewise)
     out, st = model(x, cb, in_state, taps=taps)
     pred = out.detach().requires_grad_(True)
     with torch.enable_grad():
@@ -700,6 +880,12 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
                                 cache=cache, module=rc)
     if fuse:
         grads, acc = _param_grad_tensors(blk)
-        block_backward(blk, taps[src].contiguous(memory_format=cl), grad_x, need_x_grad=False, cache=cache, grads=grads,
-                       accumulate=acc)
+        fu = taps[src].contiguous(memory_format=cl)
+        grad_fu, _ = block_backward(blk, fu, grad_x, need_x_grad=bool(fust), cache=cache, grads=grads, accumulate=acc)
+        if fust:
+            g = fust_output_grad(model, fu, taps["cb192"], grad_fu, cache=cache)
+            fb = model.fust_layer[0]
+            grads, acc = _param_grad_tensors(fb)
+            block_backward(fb, taps["st%d" % (len(model.st_layer) - 1)].contiguous(memory_format=cl), g, need_x_grad=False,
+                           cache=cache, grads=grads, accumulate=acc)
     return loss.detach(), out, [st[0].detach()]

@@ -878,6 +878,57 @@ int uavsal_ir_sums(const uavsal_ir_sums_desc* d, uavsal_stream_t stream);
 int uavsal_ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t stream);
 int uavsal_block_sizeof_desc(int which);  /* 0 ir_bwd, 1 ir_sums, 2 ir_finish (uavsal_train_decoder_sizeof_desc is closed at 3) */
 
+/* ---- input gradients of the frozen context-prior path (csrc/train_ctx.hip) ----------------------------------------------
+ * With any prior enabled the output f of fust_layer[0] reaches the fusion block's input fu320 twice (model.py:344-365):
+ * directly (channels 0..255) and through the context prior
+ *     c[b] = sum_t f[b T + t];  c1 = cxt_cb_prior[0](c) (stride 2);  c2 = cxt_cb_prior[1](c1) (stride 2);
+ *     u[n] = bilinear_ac(c2[(n % src_mod) / src_div]);  fu320[:, 256:] = fucb_layer[0](cat[priors..., u]).
+ * The three blocks are frozen; only their INPUT gradients are needed (train.block_input_grad: gd and gx as in the block
+ * backward above, ga from uavsal_ir_bwd or, for stride 2, from uavsal_ir_bwd_s2).
+ *
+ * uavsal_ir_bwd_s2: uavsal_ir_bwd for a depthwise 3x3 with stride 2, padding 1, dilation 1.  gd, d dense [n_img][Ho][Wo][C]
+ *   with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1; e, ga dense [n_img][H][W][C]; wd9 tap-major [9][C], s2 [C].  With
+ *   m6(v) = 1[0 < v < 6]:
+ *     ga[y][x] = m6(e[y][x]) s2 sum over (ky, kx) with y + 1 - ky and x + 1 - kx even, oy = (y + 1 - ky) / 2 in [0, Ho),
+ *                ox = (x + 1 - kx) / 2 in [0, Wo), of wd[ky][kx] m6(d[oy][ox]) gd[oy][ox]
+ *   (the sum, then * s2, then the mask by e: the order of uavsal_ir_bwd).  C % 4 == 0 (else UAVSAL_ESHAPE), 16-byte
+ *   aligned pointers.  ONE launch.
+ * uavsal_bilinear_ac_bwd: the adjoint of uavsal_bilinear_ac with its frame map.  gout: [n_out][Ho][Wo] rows of C floats ldo
+ *   floats apart (a channel slice is read in place); gin dense [n_src][Hi][Wi][C], every element written:
+ *     gin[ns][sy][sx] = sum over n with (n % src_mod) / src_div == ns, over (oy, ox), of wy(oy, sy) wx(ox, sx) gout[n][oy][ox]
+ *     wy(oy, sy) = hy 1[y0 == sy] + ly 1[y1 == sy]   with the forward's fp32 fy = sy_scale oy, y0 = (int)fy,
+ *                  y1 = y0 + (y0 < Hi - 1), ly = fy - y0, hy = 1 - ly (both terms where the border makes y0 == y1)
+ *   and wx likewise.  A gather: n, then oy, then ox in increasing order, accumulated in double and rounded once; no
+ *   atomics, bit-reproducible, a function of the shape alone.  n_src must cover the largest source image of the map.
+ * uavsal_tsum_bwd: out[b T + t] = a[b T + t] + g[b], the adjoint of uavsal_tsum added to a given gradient `a` (rows lda
+ *   floats apart: a channel slice is read in place); g rows ldg, out rows ldo floats apart.  ONE launch.
+ */
+typedef struct uavsal_ir_bwd_s2_desc {
+    const float* gd;  const float* d;       /* [n_img][Ho][Wo][C] */
+    const float* e;                         /* [n_img][H][W][C] */
+    const float* wd9;  const float* s2;
+    float* ga;                              /* [n_img][H][W][C] */
+    int32_t n_img, H, W, C;
+} uavsal_ir_bwd_s2_desc;
+
+typedef struct uavsal_bilinear_bwd_desc {
+    const float* gout;  int32_t ldo;  int32_t Ho, Wo;
+    float* gin;         int32_t Hi, Wi;
+    int32_t n_out, n_src, C, src_mod, src_div;
+} uavsal_bilinear_bwd_desc;
+
+typedef struct uavsal_tsum_bwd_desc {
+    const float* a;  int32_t lda;
+    const float* g;  int32_t ldg;
+    float* out;      int32_t ldo;
+    int32_t n_groups, T, HW, C;
+} uavsal_tsum_bwd_desc;
+
+int uavsal_ir_bwd_s2(const uavsal_ir_bwd_s2_desc* d, uavsal_stream_t stream);
+int uavsal_bilinear_ac_bwd(const uavsal_bilinear_bwd_desc* d, uavsal_stream_t stream);
+int uavsal_tsum_bwd(const uavsal_tsum_bwd_desc* d, uavsal_stream_t stream);
+int uavsal_ctx_sizeof_desc(int which);    /* 0 ir_bwd_s2, 1 bilinear_bwd, 2 tsum_bwd (uavsal_block_sizeof_desc is closed at 3) */
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 

@@ -23,6 +23,12 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                `recurrence_step(fuse=True)` (step_fuse, alternated with step in the same run),
                `refresh_weights(model.rnn, model.fucbst_layer)` (refresh_fuse), and an eager torch-autograd step of the
                same block (eager_block: forward + the nine parameter gradients from the same input and output gradient);
+  fust         fust_layer[0] behind the priors trained too, the fourth stage: `recurrence_step(decoder=True, fuse=True)`
+               (step3) and the same with `fust=True` (step4), alternated in the same run, every run listed (step3_all,
+               step4_all: the spread); `train.fust_output_grad` as a whole (the frozen context-prior path: B = T / 5 images),
+               the second `block_backward` (fust_block_bwd), the three launches of csrc/train_ctx.hip alone at the path's
+               shapes (ir_bwd_s2: cxt_cb_prior[0], B x 45 x 80 x 1536; bilinear_bwd: T x 45 x 80 x 64 out of cb192 ->
+               B x 12 x 20 x 64; tsum_bwd: T x 45 x 80 x 256), and `refresh_weights` over the four stages (refresh4);
   eager        torch autograd of the restated recurrence + decoder (float32, eval BatchNorm folded) on the same device,
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
@@ -183,6 +189,67 @@ def fuse_phases(res, m, x, cb, y_gaze, taps, grad_h, cache, iters, repeats, skip
             res["eager_block_error"] = str(e).splitlines()[0][:200]
 
 
+def fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats):
+    """the phases of the trained fust_layer behind the priors, added to `res`"""
+    cl = torch.channels_last
+    rc = m.rnn.cell_list[0].rnn_conv
+    taps = {"fu320": None, "cb192": None}
+    m(x, cb, None, taps=taps)
+    fu, cb192 = taps["fu320"], taps["cb192"]
+    st = taps["st%d" % (len(m.st_layer) - 1)].contiguous(memory_format=cl)
+    x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
+    _, grad_x, _ = train.twa_backward(x_seq, h_seq, None, rc.weight.detach(), grad_h, need_x_grad=True, cache=cache, module=rc)
+    grad_fu, _ = train.block_backward(m.fucbst_layer[0], fu, grad_x.contiguous(memory_format=cl), cache=cache)
+    parts = {}
+    g = train.fust_output_grad(m, fu, cb192, grad_fu, cache=cache, parts=parts)
+    fb = m.fust_layer[0]
+    _, grads = train.block_backward(fb, st, g, need_x_grad=False, cache=cache)
+    # the three new launches at the shapes of the path: cxt_cb_prior[0]'s depthwise backward, the resize's adjoint, the chunk sum's
+    ip = {}
+    train.block_input_grad(m.cxt_cb_prior[0], parts["ctx_sum"].permute(0, 3, 1, 2), parts["g_ctx1"].permute(0, 3, 1, 2), cache=cache,
+                           parts=ip)
+    _, _, dwc, dwbn, _, _ = train._input_grad_parts(m.cxt_cb_prior[0])
+    w9, s2, _ = cache.depthwise(dwc, dwbn)
+    T, _, h, w = fu.shape
+    B = T // m.time_dims
+    off = 64 * (int(bool(m.use_gauss_prior)) + int(bool(m.use_ob_prior)))
+    g_up = parts["g_cb"][..., off:off + 64]
+    trained = [q for mod in (m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer) for q in mod.parameters()]
+
+    def step3():
+        for q in trained:
+            q.grad = None
+        train.recurrence_step(m, x, cb, None, y_gaze, decoder=True, fuse=True)
+
+    def step4():
+        for q in trained:
+            q.grad = None
+        train.recurrence_step(m, x, cb, None, y_gaze, decoder=True, fuse=True, fust=True)
+
+    def refresh4():
+        with torch.no_grad():
+            for q in trained:
+                q.mul_(1.0)
+        m.refresh_weights(m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer)
+    cases = {"fust_output_grad": lambda: train.fust_output_grad(m, fu, cb192, grad_fu, cache=cache),
+             "fust_block_bwd": lambda: train.block_backward(fb, st, g, need_x_grad=False, cache=cache, grads=grads),
+             "ir_bwd_s2": lambda: train.ir_bwd_s2(ip["gd"], ip["d"], ip["e"], w9, s2),
+             "bilinear_bwd": lambda: train.bilinear_bwd(g_up, B, parts["g_ctx2"].shape[1], parts["g_ctx2"].shape[2], src_mod=B),
+             "tsum_bwd": lambda: train.tsum_bwd(grad_fu.permute(0, 2, 3, 1)[..., :256], parts["g_sum"], m.time_dims),
+             "refresh4": refresh4}
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    alt = {"step3": [], "step4": []}                         # the two steps alternated in the same run
+    for _ in range(repeats):
+        alt["step3"].append(per_call(step3, iters))
+        alt["step4"].append(per_call(step4, iters))
+    res["step3_ms"], res["step4_ms"] = 1e3 * min(alt["step3"]), 1e3 * min(alt["step4"])
+    res["step3_all_ms"], res["step4_all_ms"] = [1e3 * v for v in alt["step3"]], [1e3 * v for v in alt["step4"]]
+    for q in trained:
+        q.grad = None
+    res["ir_bwd_s2_shape"], res["bilinear_bwd_shape"] = list(ip["e"].shape), [list(g_up.shape), list(parts["g_ctx2"].shape)]
+
+
 def bench(T, iters, repeats, dev, skip_eager):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5)
@@ -293,6 +360,7 @@ def bench(T, iters, repeats, dev, skip_eager):
     res["wgrad_tflops"] = flop / (res["wgrad_ms"] * 1e-3) / 1e12
     res["wgrad_of_peak"] = res["wgrad_tflops"] / PEAK_TFLOPS
     fuse_phases(res, m, x, cb, y_gaze, taps, grad_h, cache, iters, repeats, skip_eager)
+    fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     if not skip_eager:
         try:
             run = eager_step(m, taps["prefuse"], torch.zeros((1, 256, h, w), device=dev), g_y)
