@@ -304,6 +304,13 @@ class TsumBwdDesc(C.Structure):
 
 CTX_DESC_TYPES = [IrBwdS2Desc, BilinearBwdDesc, TsumBwdDesc]    # sized by uavsal_ctx_sizeof_desc (csrc/train_ctx.hip)
 
+
+class IrSumsS2Desc(C.Structure):
+    _fields_ = IrSumsDesc._fields_          # the same fields; H, W are the INPUT's, gd / d / go live on the stride-2 grid
+
+
+MP_DESC_TYPES = [IrSumsS2Desc]              # sized by uavsal_mp_sizeof_desc (csrc/train_ctx.hip)
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -361,6 +368,11 @@ SYMBOLS = [
     ("uavsal_bilinear_ac_bwd", C.c_int, [C.POINTER(BilinearBwdDesc), C.c_void_p]),
     ("uavsal_tsum_bwd", C.c_int, [C.POINTER(TsumBwdDesc), C.c_void_p]),
     ("uavsal_ctx_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_ir_sums_s2_workspace_bytes", C.c_int64, [C.POINTER(IrSumsS2Desc)]),
+    ("uavsal_ir_sums_s2_slabs", C.c_int, [C.POINTER(IrSumsS2Desc)]),
+    ("uavsal_ir_sums_s2_slab_rows", C.c_int, [C.POINTER(IrSumsS2Desc)]),
+    ("uavsal_ir_sums_s2", C.c_int, [C.POINTER(IrSumsS2Desc), C.c_void_p]),
+    ("uavsal_mp_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -435,7 +447,8 @@ def load():
                 t.__name__, C.sizeof(t), lib.uavsal_sizeof_desc(i)))
     for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES),
                           (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES),
-                          (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES)):
+                          (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES),
+                          (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

@@ -8,7 +8,8 @@
 //           and a new chain starts: no accumulation chain is longer than UAVSAL_WGRAD_CHAIN products.
 // The operand loaders are the parameter: `fa(g)` / `fb(g)` return the address of the four floats this thread loads (column
 // (tid & 31) * 4 of the tile) of the A / B row of global pixel g (p0 <= g < p1), or nullptr for zeros (a whole row, or this
-// thread's four columns: uavsal_pix_gemm's last N tile may end at column 64); rows behind p1 are zeros and are never asked for.
+// thread's four columns: uavsal_pix_gemm's last M tile and last N tile may end at column 64); rows behind p1 are zeros and are
+// never asked for.
 #pragma once
 #include "common.h"
 

@@ -3,10 +3,11 @@
 //
 // 1. uavsal_pix_gemm: out[m][n] = row_scale[m] sum over pixels p of A[p][m] B[p][n].  The tile loop of uavsal_twa_wgrad
 //    (csrc/pix_gemm_tile.h: 128 x 128 tiles, 32-pixel K steps, chains of at most UAVSAL_WGRAD_CHAIN products, a second fp32
-//    register tile per share) with plain pitched rows as both operands.  K split by the same rule: (M / 128) (N / 128) tiles,
-//    about 1024 workgroups.  M = 1536, N = 256 is 24 tiles, at most 42 shares: T = 20 at 45 x 80 (71 chunks) runs 36 shares of
-//    2 chunks.  Partial tiles [share][M][N] -> a second launch, one workgroup per row m, sums the shares in share order in
-//    double, writes fl(row_scale G) (+ the old value) and, when asked, rowdot[m] = sum_n w[m][n] G[m][n] in double: each
+//    register tile per share) with plain pitched rows as both operands.  M and N are multiples of 64: the last tile of either
+//    may be half empty (its loader hands the tile loop zeros, nothing at or behind row M / column N is read or written).  K
+//    split by the same rule: ceil(M / 128) ceil(N / 128) tiles, about 1024 workgroups.  M = 1536, N = 256 is 24 tiles, at
+//    most 42 shares: T = 20 at 45 x 80 (71 chunks) runs 36 shares of 2 chunks.  Partial tiles [share][M][N] -> a second
+//    launch, one workgroup per row m, sums the shares in share order in double, writes fl(row_scale G) (+ the old value) and, when asked, rowdot[m] = sum_n w[m][n] G[m][n] in double: each
 //    thread adds its columns n = tid, tid + 256, ... in that order and the 256 partial sums meet in a fixed tree in LDS.
 //
 // 2. uavsal_dec_sums: the channel sums S3, G3, S2, Gd, S1.  The access pattern of dec_bwd_kernel: a lane owns four channels
@@ -42,6 +43,9 @@ struct PgK {
     int cps, shares, accumulate;
 };
 
+// kMTail: M % 128 == 64, the last M tile is half empty.  Without it the kernel is the instruction stream it was before M
+// tails existed (the A loader's test and the row guard fold away): the calls with whole M tiles keep their bits and their time.
+template <bool kMTail>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void pix_gemm_kernel(const PgK k) {
     const int tile = blockIdx.x, share = blockIdx.y;
     const int mt = tile % k.mt_n, nt = tile / k.mt_n;
@@ -57,8 +61,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     const float* arow = k.a + mt * kTile + lc;
     const float* brow = k.b + nt * kTile + lc;
     const bool bok = nt * kTile + lc < k.N;                   // N % 64 == 0: the last N tile may be half empty
+    const bool aok = !kMTail || mt * kTile + lc < k.M;        // M % 64 == 0: and so may the last M tile
     pixgemm::tile_loop(p0, p1,
-        [&](long long g) { return arow + g * k.lda; },
+        [&](long long g) { return aok ? arow + g * k.lda : nullptr; },
         [&](long long g) { return bok ? brow + g * k.ldb : nullptr; }, tot);
     float* w = k.ws + (long long)share * k.M * k.N;           // ws [share][m][n]
 #pragma unroll
@@ -69,7 +74,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
             for (int r = 0; r < 16; ++r) {
                 const int m = mt * kTile + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 const int n = nt * kTile + wn + j * 32 + (lane & 31);
-                if (n < k.N) w[(long long)m * k.N + n] = tot[i][j][r];
+                if ((!kMTail || m < k.M) && n < k.N) w[(long long)m * k.N + n] = tot[i][j][r];
             }
 }
 
@@ -104,10 +109,10 @@ __global__ __launch_bounds__(256) void pix_gemm_reduce_kernel(const PgK k) {
 }
 
 bool pg_plan(const uavsal_pix_gemm_desc* d, PgK& k) {
-    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || (d->M % kTile) || (d->N % (kTile / 2))) return false;
-    const int nt_n = (d->N + kTile - 1) / kTile;
-    if ((long long)d->M * d->N > 0x7fffffffll || (long long)(d->M / kTile) * nt_n > 65535) return false;
-    k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = d->M / kTile; k.nt_n = nt_n;
+    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || (d->M % (kTile / 2)) || (d->N % (kTile / 2))) return false;
+    const int mt_n = (d->M + kTile - 1) / kTile, nt_n = (d->N + kTile - 1) / kTile;
+    if ((long long)d->M * d->N > 0x7fffffffll || (long long)mt_n * nt_n > 65535) return false;
+    k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = mt_n; k.nt_n = nt_n;
     return pixgemm::split(k.K, k.mt_n * nt_n, k.cps, k.shares);
 }
 
@@ -287,7 +292,7 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     if (!d || !d->a || !d->b || !d->ws || !d->out) return UAVSAL_EINVAL;
     if (d->K <= 0 || d->M <= 0 || d->N <= 0) return UAVSAL_EINVAL;
     if (d->rowdot && !d->w) return UAVSAL_EINVAL;
-    if ((d->M % kTile) || (d->N % (kTile / 2))) return UAVSAL_ESHAPE;
+    if ((d->M % (kTile / 2)) || (d->N % (kTile / 2))) return UAVSAL_ESHAPE;
     PgK k;
     if (!pg_plan(d, k)) return UAVSAL_ESHAPE;
     if (d->ws_bytes < uavsal_pix_gemm_workspace_bytes(d)) return UAVSAL_EINVAL;
@@ -298,8 +303,9 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     k.a = d->a; k.b = d->b; k.row_scale = d->row_scale; k.w = d->w; k.rowdot = d->rowdot; k.ws = d->ws; k.out = d->out;
     k.lda = d->lda; k.ldb = d->ldb; k.ldw = d->ldw; k.ldo = d->ldo;
     k.accumulate = d->accumulate != 0;
-    hipLaunchKernelGGL(pix_gemm_kernel, dim3((unsigned)(k.mt_n * k.nt_n), (unsigned)k.shares), dim3(256), 0,
-                       (hipStream_t)stream, k);
+    const dim3 grid((unsigned)(k.mt_n * k.nt_n), (unsigned)k.shares);
+    if (k.M % kTile) hipLaunchKernelGGL(pix_gemm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL(pix_gemm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, k);
     hipLaunchKernelGGL(pix_gemm_reduce_kernel, dim3((unsigned)k.M), dim3(256), 0, (hipStream_t)stream, k);
     return uavsal_launch_status();
 }

@@ -397,15 +397,20 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     the fusion block in front of the recurrence (`train.fuse_block`: `model.fucbst_layer[0]` with any prior enabled, else
     `model.fust_layer[0]`), and that block's container is refreshed with the other trained stages.
     `"fust"` (last, and only behind `"fuse"`; a model with at least one prior): `recurrence_step(..., fust=True)` also sets
-    the gradients of `model.fust_layer[0]` behind the priors, and `model.fust_layer` is refreshed as well."""
+    the gradients of `model.fust_layer[0]` behind the priors, and `model.fust_layer` is refreshed as well.
+    `"ctx"` (last of all, only behind `"fuse"`, with or without `"fust"`; a model with at least one prior):
+    `recurrence_step(..., ctx=True)` also sets the gradients of the multi-prior path -- `model.fucb_layer[0]` and, with the
+    context prior, both blocks of `model.cxt_cb_prior` -- and those containers are refreshed as well."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
     stages = tuple(stages)
-    if stages not in (("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse"), ("rnn", "fuse", "fust"),
-                      ("rnn", "decoder", "fuse", "fust")):
+    allowed = [("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse"), ("rnn", "fuse", "fust"),
+               ("rnn", "decoder", "fuse", "fust")]
+    allowed += [s + ("ctx",) for s in allowed if "fuse" in s]
+    if stages not in allowed:
         raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
-                         "'fuse', got %r" % (stages,))
+                         "'fuse' (then 'ctx', behind 'fuse' too), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
@@ -417,6 +422,10 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
             mods.append(model.fucbst_layer if model.num_cb else model.fust_layer)
         if "fust" in kw:
             mods.append(model.fust_layer)
+        if "ctx" in kw:
+            mods.append(model.fucb_layer)
+            if getattr(model, "use_context_prior", False):
+                mods.append(model.cxt_cb_prior)
         model.refresh_weights(*mods)
         return loss, state
     return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,

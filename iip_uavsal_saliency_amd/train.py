@@ -17,7 +17,10 @@ inverted-residual block (`block_backward`, `block_param_grads`, `recurrence_step
 `uavsal_ir_bwd`, `uavsal_ir_sums`, `uavsal_ir_finish`, and `uavsal_pix_gemm` for both 1x1 weight gradients).  A fourth one
 in a model with priors: `model.fust_layer[0]` behind them (`recurrence_step(fust=True)`), whose output gradient comes
 through the fusion block's input directly and through the frozen context-prior path (`fust_output_grad`,
-`block_input_grad`; csrc/train_ctx.hip: `uavsal_ir_bwd_s2`, `uavsal_bilinear_ac_bwd`, `uavsal_tsum_bwd`).
+`block_input_grad`; csrc/train_ctx.hip: `uavsal_ir_bwd_s2`, `uavsal_bilinear_ac_bwd`, `uavsal_tsum_bwd`).  And a fifth: that
+path itself, `model.fucb_layer[0]` and the two stride-2 blocks of `model.cxt_cb_prior` (`recurrence_step(ctx=True)`): the one
+walk `prior_path_backward` hands each block's tensors to `block_param_grads`, which takes 64 output channels (`uavsal_pix_gemm`
+with M a multiple of 64) and stride 2 (`uavsal_ir_sums_s2`).  The gauss / ob prior nets stay frozen.
 
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
@@ -352,8 +355,30 @@ def _block_parts(block):
     return pw, pwbn, dwc, dwbn, pl, plbn
 
 
-def _block_grad_out(grad_out, x, cout):
+def _param_grad_parts(block):
+    """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual block whose nine gradients `block_param_grads` forms: what
+    `_block_parts` takes, and stride 2 and Cout % 64 == 0 besides (the blocks of the multi-prior path), or a RuntimeError."""
+    seq = getattr(block, "conv", None)
+    stride = getattr(block, "stride", None)
+    if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4 or stride not in (1, 2)
+            or getattr(block, "dilation", None) != 1 or seq[1][0].stride != (stride, stride) or seq[1][0].dilation != (1, 1)):
+        raise RuntimeError("block_param_grads takes a dwBlock with an expand conv, stride 1 or 2 and dilation 1 "
+                           "(expand 1x1, depthwise 3x3, projection 1x1)")
+    pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
+    hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    if cout % 64 or hid % 64 or cin % 64:
+        raise RuntimeError("block_param_grads needs Cout %% 64 == 0, hidden %% 64 == 0 and Cin %% 64 == 0, got %d -> %d -> %d"
+                           % (cin, hid, cout))
+    if stride == 2 and block.use_res_connect:
+        raise RuntimeError("block_param_grads: a block with stride 2 has no residual")
+    if block.training:
+        raise RuntimeError("the block's BatchNorms use their running statistics: call model.eval()")
+    return pw, pwbn, dwc, dwbn, pl, plbn
+
+
+def _block_grad_out(grad_out, x, cout, stride=1):
     T, hh, ww, _ = x.shape
+    hh, ww = (hh - 1) // stride + 1, (ww - 1) // stride + 1
     if (not torch.is_tensor(grad_out) or not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.device != x.device
             or tuple(grad_out.shape) != (T, cout, hh, ww)):
         raise RuntimeError("grad_out must be a float32 cuda tensor [%d,%d,%d,%d]" % (T, cout, hh, ww))
@@ -421,28 +446,62 @@ def ir_sums(gd, d, e, ga, go):
     return ws, int(lib.uavsal_ir_sums_slabs(C.byref(k)))
 
 
+def ir_sums_s2(gd, d, e, ga, go):
+    """`uavsal_ir_sums_s2` on the current stream -> `(ws, slabs)`: `ir_sums` for a depthwise 3x3 with stride 2, in the same
+    workspace layout.  `e`, `ga` dense NHWC `[n,H,W,Ch]`; `gd`, `d` dense NHWC `[n,Ho,Wo,Ch]` with `Ho = (H-1)//2+1`,
+    `Wo = (W-1)//2+1`; `go` an NHWC view `[n,Ho,Wo,Co]` (a channel slice is read in place)."""
+    lib = L.load()
+    _dense_nhwc("ir_sums_s2", "gd, d, e, ga", gd, d, e, ga)
+    n, hh, ww, c = e.shape
+    ho, wo = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
+    if (ga.shape != e.shape or gd.shape != d.shape or tuple(d.shape) != (n, ho, wo, c)
+            or any(t.device != e.device for t in (gd, d, ga))):
+        raise RuntimeError("ir_sums_s2: gd and d must be [n,(H-1)//2+1,(W-1)//2+1,Ch] for e and ga [n,H,W,Ch], on one device")
+    if not torch.is_tensor(go) or go.dtype != torch.float32 or go.device != e.device:
+        raise RuntimeError("ir_sums_s2: go must be a float32 tensor on the device of e")
+    gp, ldgo, *gs = _nhwc_view(go)
+    if gs[:3] != [n, ho, wo]:
+        raise RuntimeError("ir_sums_s2: go must cover the pixels of d")
+    k = L.IrSumsS2Desc()
+    k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
+    k.n_img, k.H, k.W, k.Ch, k.Co = n, hh, ww, c, gs[3]
+    nbytes = int(lib.uavsal_ir_sums_s2_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_ir_sums_s2")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    L.check(lib.uavsal_ir_sums_s2(C.byref(k), _stream(e)), "uavsal_ir_sums_s2")
+    return ws, int(lib.uavsal_ir_sums_s2_slabs(C.byref(k)))
+
+
 def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, out=None, accumulate=False):
-    """The gradients of the nine parameters of an inverted-residual `block` (a `dwBlock` with an expand conv, stride 1,
+    """The gradients of the nine parameters of an inverted-residual `block` (a `dwBlock` with an expand conv, stride 1 or 2,
     dilation 1, with or without the residual; eval mode: the BatchNorms on their running statistics, which are not updated)
-    from given tensors, teacher-forced: `x` `[T,Cin,h,w]` the block's input, `e`, `d` dense NHWC `[T,h,w,Ch]` its expanded
-    and depthwise tensors, `grad_out` `[T,Co,h,w]` = d loss / d output, `gd` dense NHWC = d loss / d d (default: one 1x1 conv
-    with the projection's transposed weights carrying s3 in their rows), `ga` dense NHWC = d loss / d a1 (default: one
-    `uavsal_ir_bwd`).  Returns a dict keyed by the block's parameter names (`BLOCK_PARAMS`), the values `torch.autograd`
+    from given tensors, teacher-forced: `x` `[T,Cin,h,w]` the block's input, `e` dense NHWC `[T,h,w,Ch]` its expanded and `d`
+    dense NHWC `[T,ho,wo,Ch]` its depthwise tensor (`ho = (h-1)//stride+1`), `grad_out` `[T,Co,ho,wo]` = d loss / d output,
+    `gd` dense NHWC like `d` = d loss / d d (default: one 1x1 conv with the projection's transposed weights carrying s3 in
+    their rows), `ga` dense NHWC like `e` = d loss / d a1 (default: one `uavsal_ir_bwd`, or `uavsal_ir_bwd_s2`).  With stride 2
+    `ga` x `x` and S1 run over the input pixels, `grad_out` x `d`, S2, Gd and S3 over the output pixels
+    (`uavsal_ir_sums_s2`).  Returns a dict keyed by the block's parameter names (`BLOCK_PARAMS`), the values `torch.autograd`
     gives for the reference's `dwBlock` (include/uavsal_hip.h states the formulas); `out`: such a dict of dense tensors to
     write into, or (`accumulate`) to add to.  Nothing of the forward is recomputed; six launches (two pixel GEMMs with their
     reductions -- `ga` x `x` for W1, `grad_out` x `d` for W3 --, channel sums, finalise) on the current stream, no
-    synchronisation.  Accepted: Co % 128 == 0, Ch % 64 == 0, Cin % 64 == 0."""
+    synchronisation.  Accepted: Co % 64 == 0, Ch % 64 == 0, Cin % 64 == 0 (`block_backward`, which recomputes `e` and `d`
+    itself, keeps to stride 1 and Co % 128 == 0)."""
     lib = L.load()
-    pw, pwbn, dwc, dwbn, pl, plbn = _block_parts(block)
+    pw, pwbn, dwc, dwbn, pl, plbn = _param_grad_parts(block)
     hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    stride = dwc.stride[0]
     xn = _nhwc(x, "x", cin)
     T, hh, ww, _ = xn.shape
+    ho, wo = (hh - 1) // stride + 1, (ww - 1) // stride + 1
     dev = xn.device
-    for name, t in (("e", e), ("d", d)) + tuple((n, t) for n, t in (("gd", gd), ("ga", ga)) if t is not None):
-        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (T, hh, ww, hid)
+    for name, t, (a, b) in ((("e", e, (hh, ww)), ("d", d, (ho, wo)))
+                            + tuple((n, t, s) for n, t, s in (("gd", gd, (ho, wo)), ("ga", ga, (hh, ww))) if t is not None)):
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (T, a, b, hid)
                 or not t.is_contiguous()):
-            raise RuntimeError("%s must be a dense float32 NHWC tensor [%d,%d,%d,%d] on the device" % (name, T, hh, ww, hid))
-    go = _block_grad_out(grad_out, xn, cout)
+            raise RuntimeError("%s must be a dense float32 NHWC tensor [%d,%d,%d,%d] on the device" % (name, T, a, b, hid))
+    go = _block_grad_out(grad_out, xn, cout, stride)
     params, out = _block_grad_tensors(block, out, accumulate)
     if any(q.device != dev or not q.is_contiguous() for q in params.values()):
         raise RuntimeError("the block's parameters must be dense tensors on the device of `x`")
@@ -453,13 +512,13 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
         if gd is None:
             gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
         if ga is None:
-            ga = ir_bwd(gd, d, e, w9, s2)
+            ga = (ir_bwd if stride == 1 else ir_bwd_s2)(gd, d, e, w9, s2)
         (r1, mu1), (r2, mu2), (r3, mu3) = (cache.bn_stats(b) for b in (pwbn, dwbn, plbn))
         rd1 = torch.empty(hid, dtype=torch.float64, device=dev)
         rd3 = torch.empty(cout, dtype=torch.float64, device=dev)
         pix_gemm(ga, xn, out=out[BLOCK_PARAMS[0]], row_scale=s1, w=pw.weight.detach(), rowdot=rd1, accumulate=accumulate)
         pix_gemm(go, d, out=out[BLOCK_PARAMS[6]], row_scale=s3, w=pl.weight.detach(), rowdot=rd3, accumulate=accumulate)
-        ws, slabs = ir_sums(gd, d, e, ga, go)
+        ws, slabs = (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go)
         k = L.IrFinishDesc()
         k.ws, k.ws_bytes, k.rowdot1, k.rowdot3 = ws.data_ptr(), ws.numel() * 8, rd1.data_ptr(), rd3.data_ptr()
         k.wd, k.s2 = dwc.weight.data_ptr(), s2.data_ptr()
@@ -596,15 +655,18 @@ def _input_grad_parts(block):
     return pw, pwbn, dwc, dwbn, pl, plbn
 
 
-def _input_grad(lib, cache, block, prt, xn, go, ed=None, parts=None):
-    """`block_input_grad` on checked NHWC views; `ed`: the block's `(e, d)` when the caller has them."""
+def _input_grad(lib, cache, block, prt, xn, go, ed=None, parts=None, need_x_grad=True):
+    """`block_input_grad` on checked NHWC views; `ed`: the block's `(e, d)` when the caller has them.  `need_x_grad=False`:
+    only `parts` is wanted (the operands of the block's parameter gradients), the last GEMM is left out and None returned."""
     pw, pwbn, dwc, dwbn, pl, plbn = prt
     hid, cin = pw.weight.shape[:2]
     stride = dwc.stride[0]
     e, dd = ed or _block_recompute(lib, cache, block, xn, stride, prt)
     gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
     ga = (ir_bwd if stride == 1 else ir_bwd_s2)(gd, dd, e, *cache.depthwise(dwc, dwbn)[:2])
-    g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else None)
+    g = None
+    if need_x_grad:
+        g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else None)
     if parts is not None:
         parts.update(e=e, d=dd, gd=gd, ga=ga)
     return g
@@ -636,51 +698,118 @@ def block_input_grad(block, x, grad_out, cache=None, parts=None):
     return g.permute(0, 3, 1, 2)
 
 
-def fust_output_grad(model, fu320, cb192, grad_fu, cache=None, parts=None):
-    """The gradient with respect to the OUTPUT of `model.fust_layer[0]` `[N,256,h,w]` in a model with priors, given `grad_fu`
+PRIOR_PATH_BLOCKS = ("fucb_layer.0", "cxt_cb_prior.1", "cxt_cb_prior.0")      # in the order the backward walk meets them
+
+
+def prior_path_blocks(model):
+    """`{name: block}` of the blocks of the multi-prior path that `prior_path_backward` trains in `model`, in the order of
+    `PRIOR_PATH_BLOCKS`: `fucb_layer[0]` with any prior, the two `cxt_cb_prior` blocks with the context prior."""
+    if not getattr(model, "num_cb", 0):
+        return {}
+    blocks = {PRIOR_PATH_BLOCKS[0]: model.fucb_layer[0]}
+    if model.use_context_prior:
+        blocks[PRIOR_PATH_BLOCKS[1]], blocks[PRIOR_PATH_BLOCKS[2]] = model.cxt_cb_prior[1], model.cxt_cb_prior[0]
+    return blocks
+
+
+def prior_path_backward(model, fu320, cb192, grad_fu, cache=None, parts=None, grads=None, accumulate=False, need_fust_grad=True):
+    """ONE backward walk of the multi-prior path of a model with priors (reference model.py:344-365), given `grad_fu`
     `[N,320,h,w]` = d loss / d `fu320` (the input of `model.fucbst_layer[0]`; `block_backward(..., need_x_grad=True)` returns
-    it).  That output is channels 0..255 of `fu320`, and with the context prior it also feeds channels 256..319 (reference
-    model.py:357-365): chunk sum, `cxt_cb_prior[0]`, `cxt_cb_prior[1]` (both stride 2), bilinear upsample with the tiling
-    frame map of `forward()` (frame k reads chunk k % B, B = N // time_dims), concat with the other priors, `fucb_layer[0]`.
-    All of these stay frozen; the gradient walks back through them (`block_input_grad`, `bilinear_bwd`, `tsum_bwd`) and is
-    added to `grad_fu[:, :256]`.  Without the context prior the result IS `grad_fu[:, :256]`.
-    `fu320` `[N,320,h,w]`, `cb192` `[N,64*num_cb,h,w]`: the taps of those names.  The chunk sum and `cxt_cb_prior[0]`'s output
-    are recomputed (B images).  `parts` receives `g_cb`, `g_ctx2`, `g_ctx1`, `g_sum` (NHWC) and `ctx_sum`, `ctx1`."""
+    it).  The output of `model.fust_layer[0]` is channels 0..255 of `fu320`, and with the context prior it also feeds channels
+    256..319: chunk sum, `cxt_cb_prior[0]`, `cxt_cb_prior[1]` (both stride 2), bilinear upsample with the tiling frame map of
+    `forward()` (frame k reads chunk k % B, B = N // time_dims), concat with the other priors, `fucb_layer[0]`.  The walk goes
+    back through them (`_input_grad`, `bilinear_bwd`, `tsum_bwd`) and serves two ends:
+    `need_fust_grad`: the gradient with respect to fust_layer's output `[N,256,h,w]`, the path's part added to
+    `grad_fu[:, :256]` (without the context prior it IS `grad_fu[:, :256]`); else None is returned in its place and what only
+    it needs is not launched.
+    `grads`: None -- the path is frozen, nothing but the walk is launched -- or a dict `{name: dict | None}` over
+    `prior_path_blocks(model)`: each named block's nine parameter gradients (`block_param_grads`, fed the `x`, `e`, `d`, `gd`,
+    `ga` and `grad_out` the walk already holds: nothing of the forward is recomputed twice) are written into the given dict of
+    dense tensors, or with `accumulate` (a bool, or a dict of bools by name) added to it; None: allocated.  The gauss / ob
+    prior nets stay frozen.  The chunk sum feeds `cxt_cb_prior` B images, not N: its gradients are sums over B images.
+    `fu320` `[N,320,h,w]`, `cb192` `[N,64*num_cb,h,w]`: the taps of those names, read in place as channel slices.  Returns
+    `(grad_fust | None, grads | None)`.  `parts` receives `g_cb`, `g_ctx2`, `g_ctx1`, `g_sum` (NHWC), `ctx_sum`, `ctx1` and,
+    per trained block, `name: dict(x=, go=, e=, d=, gd=, ga=)`."""
     lib = L.load()
     if not getattr(model, "num_cb", 0):
         raise RuntimeError("fust_output_grad takes a model with at least one prior (without priors nothing lies behind fust_layer "
                            "but the recurrence)")
     if model.training:
-        raise RuntimeError("the prior path is frozen: its BatchNorms are folded in eval mode (call model.eval())")
+        raise RuntimeError("the prior path is frozen: its BatchNorms are folded in eval mode (call model.eval())"
+                           if grads is None else "the prior path's BatchNorms use their running statistics: call model.eval()")
+    blocks = prior_path_blocks(model)
+    if grads is not None:
+        if not grads or any(n not in blocks for n in grads):
+            raise RuntimeError("grads must name blocks of this model's prior path: %r" % (tuple(blocks),))
+        for n in grads:
+            _param_grad_parts(blocks[n])
+            acc = accumulate[n] if isinstance(accumulate, dict) else accumulate
+            _block_grad_tensors(blocks[n], grads[n], acc)              # raise before anything is launched
+    train = grads or {}
     fu = _nhwc(fu320, "fu320", 320)
     N, hh, ww, _ = fu.shape
     gf = _block_grad_out(grad_fu, fu, 320)
-    if not model.use_context_prior:
-        return gf[..., :HID].permute(0, 3, 1, 2)
+    ctx = bool(model.use_context_prior)
+    if not ctx and not train:
+        return (gf[..., :HID].permute(0, 3, 1, 2) if need_fust_grad else None), grads
     T = model.time_dims
-    if N % T:
+    if ctx and N % T:
         raise RuntimeError("fu320 holds %d frames, not a multiple of time_dims = %d" % (N, T))
     B = N // T
-    fucb, ctx0, ctx1b = model.fucb_layer[0], model.cxt_cb_prior[0], model.cxt_cb_prior[1]
-    p_cb, p_0, p_1 = _input_grad_parts(fucb), _input_grad_parts(ctx0), _input_grad_parts(ctx1b)
+    fucb = model.fucb_layer[0]
+    p_cb = _input_grad_parts(fucb)
     cb = _nhwc(cb192, "cb192", 64 * model.num_cb)
     if tuple(cb.shape[:3]) != (N, hh, ww) or cb.device != fu.device:
         raise RuntimeError("cb192 must be [%d,%d,%d,%d] on the device of fu320" % (N, 64 * model.num_cb, hh, ww))
     off = 64 * (int(bool(model.use_gauss_prior)) + int(bool(model.use_ob_prior)))
     down = lambda v: (v - 1) // 2 + 1                                     # noqa: E731
+    nchw = lambda t: t.permute(0, 3, 1, 2)                                # noqa: E731
+
+    def param_grads(name, block, x, go, pt):
+        if name not in train:
+            return
+        acc = accumulate[name] if isinstance(accumulate, dict) else accumulate
+        grads[name] = block_param_grads(block, nchw(x), pt["e"], pt["d"], nchw(go), gd=pt["gd"], ga=pt["ga"], cache=cache,
+                                        out=grads[name], accumulate=acc)
+        if parts is not None:
+            parts[name] = dict(pt, x=x, go=go)
+
     with torch.cuda.device(fu.device):
         cache = cache or WeightCache(fu.device, {})
-        g_cb = _input_grad(lib, cache, fucb, p_cb, cb, gf[..., HID:])
+        walk = ctx and (need_fust_grad or any(n in train for n in PRIOR_PATH_BLOCKS[1:]))
+        pt = {}
+        g_cb = _input_grad(lib, cache, fucb, p_cb, cb, gf[..., HID:], parts=pt, need_x_grad=walk)
+        param_grads(PRIOR_PATH_BLOCKS[0], fucb, cb, gf[..., HID:], pt)
+        if not walk:
+            return (gf[..., :HID].permute(0, 3, 1, 2) if need_fust_grad else None), grads
+        ctx0, ctx1b = model.cxt_cb_prior[0], model.cxt_cb_prior[1]
+        p_0, p_1 = _input_grad_parts(ctx0), _input_grad_parts(ctx1b)
         g_c2 = bilinear_bwd(g_cb[..., off:off + 64], B, down(down(hh)), down(down(ww)), src_mod=B, src_div=1)
         ctx_sum = _tsum(fu[..., :HID], T)
         ed0 = _block_recompute(lib, cache, ctx0, ctx_sum, 2, p_0)
         c1 = _conv(lib, cache, ed0[1], p_0[4], p_0[4].weight.shape[0], 1, bn=p_0[5])
-        g_c1 = _input_grad(lib, cache, ctx1b, p_1, c1, g_c2)
-        g_sum = _input_grad(lib, cache, ctx0, p_0, ctx_sum, g_c1, ed=ed0)
-        g = tsum_bwd(gf[..., :HID], g_sum, T)
+        pt = {}
+        need1 = need_fust_grad or PRIOR_PATH_BLOCKS[2] in train
+        g_c1 = _input_grad(lib, cache, ctx1b, p_1, c1, g_c2, parts=pt, need_x_grad=need1)
+        param_grads(PRIOR_PATH_BLOCKS[1], ctx1b, c1, g_c2, pt)
+        g_sum = g = None
+        if need1:
+            pt = {}
+            g_sum = _input_grad(lib, cache, ctx0, p_0, ctx_sum, g_c1, ed=ed0, parts=pt, need_x_grad=need_fust_grad)
+            param_grads(PRIOR_PATH_BLOCKS[2], ctx0, ctx_sum, g_c1, pt)
+        if need_fust_grad:
+            g = tsum_bwd(gf[..., :HID], g_sum, T)
         if parts is not None:
             parts.update(g_cb=g_cb, g_ctx2=g_c2, g_ctx1=g_c1, g_sum=g_sum, ctx_sum=ctx_sum, ctx1=c1)
-    return g.permute(0, 3, 1, 2)
+    return (g.permute(0, 3, 1, 2) if need_fust_grad else None), grads
+
+
+def fust_output_grad(model, fu320, cb192, grad_fu, cache=None, parts=None):
+    """The gradient with respect to the OUTPUT of `model.fust_layer[0]` `[N,256,h,w]` in a model with priors, given `grad_fu`
+    `[N,320,h,w]` = d loss / d `fu320`: `prior_path_backward` with the whole path frozen (no parameter gradient is computed and
+    no `.grad` touched).  Without the context prior the result IS `grad_fu[:, :256]`.  The chunk sum and `cxt_cb_prior[0]`'s
+    output are recomputed (B images).  `parts` receives `g_cb`, `g_ctx2`, `g_ctx1`, `g_sum` (NHWC) and `ctx_sum`, `ctx1`."""
+    return prior_path_backward(model, fu320, cb192, grad_fu, cache=cache, parts=parts)[0]
 
 
 def twa_gate_bwd(g, carry, z, x, hprev, need_dx=False):
@@ -818,7 +947,7 @@ def _param_grad_tensors(blk):
     return {n: q.grad for n, q in params.items()}, acc
 
 
-def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False):
+def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -838,7 +967,12 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     fusion block also returns the gradient of its input `fu320`, `fust_output_grad` carries it to fust_layer's output --
     directly and, with the context prior, through the frozen `fucb_layer`, upsample, `cxt_cb_prior` and chunk sum -- and a
     second `block_backward` to fust_layer's nine parameters (`.grad` set, or added to).  The ST blocks in front of it, the
-    prior nets, `fucb_layer` and `cxt_cb_prior` stay frozen.  Refresh `model.fust_layer` afterwards as well."""
+    prior nets, `fucb_layer` and `cxt_cb_prior` stay frozen.  Refresh `model.fust_layer` afterwards as well.
+    `ctx=True` (needs `fuse=True` and a model with at least one prior; independent of `fust`): the multi-prior path is trained
+    as well -- `model.fucb_layer[0]` and, with the context prior, `model.cxt_cb_prior[1]` and `[0]` (`prior_path_blocks`): the
+    same ONE walk of `prior_path_backward` that yields fust_layer's output gradient also forms their 9, or 27, parameter
+    gradients (`.grad` set, or added to).  The gauss / ob prior nets stay frozen.  Refresh `model.fucb_layer` and
+    `model.cxt_cb_prior` afterwards as well."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
@@ -846,6 +980,9 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if fust and not (fuse and getattr(model, "num_cb", 0)):
         raise RuntimeError("fust=True needs fuse=True and a model with at least one prior (without priors the fuse stage "
                            "already is model.fust_layer[0])")
+    if ctx and not (fuse and getattr(model, "num_cb", 0)):
+        raise RuntimeError("ctx=True needs fuse=True and a model with at least one prior (without priors there is no "
+                           "multi-prior path)")
     if model.training:
         raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
     if model.precision != "f32":
@@ -855,7 +992,7 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     rc = model.rnn.cell_list[0].rnn_conv
     blk, src = fuse_block(model) if fuse else (None, None)
     taps = {src: None} if fuse else {}                               # (fu320 is read back on request only: engine.TAPS_ON_REQUEST)
-    if fust:
+    if fust or ctx:
         taps["cb192"] = None                                         # (likewise)
     out, st = model(x, cb, in_state, taps=taps)
     pred = out.detach().requires_grad_(True)
@@ -881,9 +1018,14 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if fuse:
         grads, acc = _param_grad_tensors(blk)
         fu = taps[src].contiguous(memory_format=cl)
-        grad_fu, _ = block_backward(blk, fu, grad_x, need_x_grad=bool(fust), cache=cache, grads=grads, accumulate=acc)
-        if fust:
+        grad_fu, _ = block_backward(blk, fu, grad_x, need_x_grad=bool(fust or ctx), cache=cache, grads=grads, accumulate=acc)
+        if ctx:
+            pg = {n: _param_grad_tensors(b) for n, b in prior_path_blocks(model).items()}
+            g, _ = prior_path_backward(model, fu, taps["cb192"], grad_fu, cache=cache, grads={n: v[0] for n, v in pg.items()},
+                                       accumulate={n: v[1] for n, v in pg.items()}, need_fust_grad=bool(fust))
+        elif fust:
             g = fust_output_grad(model, fu, taps["cb192"], grad_fu, cache=cache)
+        if fust:
             fb = model.fust_layer[0]
             grads, acc = _param_grad_tensors(fb)
             block_backward(fb, taps["st%d" % (len(model.st_layer) - 1)].contiguous(memory_format=cl), g, need_x_grad=False,

@@ -49,8 +49,35 @@ def _bn_after(mods, conv):
     raise RuntimeError("the BatchNorm of a packed depthwise entry is not among the refreshed modules: pass the whole block")
 
 
-# kind -> the module ids of a key of that kind (everything `refresh` can remake)
-_REFRESH_IDS = {"w": lambda k: k[1:-3], "wino": lambda k: k[1:2], "wT": lambda k: k[1:2], "wTs": lambda k: k[1:3],
+def _block_of(mods, dwc):
+    """The inverted-residual block (among `mods`) whose depthwise conv is `dwc`."""
+    for m in mods.values():
+        seq = list(getattr(m, "conv", None) or []) if hasattr(m, "expand_ratio") else []
+        i = 0 if getattr(m, "expand_ratio", None) == 1 else 1
+        if len(seq) > i and isinstance(seq[i], torch.nn.Sequential) and len(seq[i]) and seq[i][0] is dwc:
+            return m
+    raise RuntimeError("the block of a packed fused entry is not among the refreshed modules: pass the whole block")
+
+
+def _fused_host(blk, natural):
+    """The host tensors of a fused-block entry, by name (`WeightCache.fused_block`)."""
+    seq = list(blk.conv)
+    pw, pwbn = (None, None) if blk.expand_ratio == 1 else (seq[0][0], seq.pop(0)[1])
+    dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1], seq[2]
+
+    def mat(conv):
+        w = conv.weight.detach().float().cpu().reshape(conv.weight.shape[:2])
+        return w.clone() if natural else w.t()           # (a copy: on a CPU store the entry must not alias the parameter)
+    ws = {}
+    if pw is not None:
+        ws["w1"], ws["s1"], ws["b1"] = (mat(pw), *P.fold_bn(pwbn))
+    ws["wd"], ws["sd"], ws["bd"] = (P.pack_dw_weight(dwc.weight), *P.fold_bn(dwbn))
+    ws["w2"], ws["s2"], ws["b2"] = (mat(pl), *P.fold_bn(plbn))
+    return ws
+
+
+# kind -> the module ids of a key of that kind (everything `refresh` can remake); "fused": the natural-layout entries only
+_REFRESH_IDS = {"fused": lambda k: k[1:2], "w": lambda k: k[1:-3], "wino": lambda k: k[1:2], "wT": lambda k: k[1:2], "wTs": lambda k: k[1:3],
                 "bn": lambda k: k[1:-1], "bnstat": lambda k: k[1:2], "dw": lambda k: k[1:], "dwdot": lambda k: k[1:3]}
 
 
@@ -119,7 +146,9 @@ class WeightCache:
         """Repack, INTO THE EXISTING DEVICE TENSORS, every entry whose key holds the id of a module in `mods` (id -> module)
         from the module's current parameters: launch plans that recorded the tensors' addresses stay valid.  Conv weights in
         every layout, their Winograd transforms and transposed forms, BatchNorm folds (with their identity padding) and
-        statistics, depthwise and depthwise-dot entries are refreshable; a fused block or a stem that names such a module
+        statistics, depthwise and depthwise-dot entries and the natural-layout fused blocks (csrc/fused_mid.hip: the 1x1
+        weights as the module holds them; the key holds the depthwise conv alone, its neighbours are found in the block that
+        holds it, which must be in `mods`) are refreshable; a transposed-layout fused block or a stem that names such a module
         raises -- `model.invalidate_engines()` is for those.  A key that joins several modules needs all of them in `mods`;
         a depthwise entry's key holds its conv alone: its BatchNorm is the module that follows the conv in the container
         that holds both, which must be in `mods` too (pass the block, not the conv).
@@ -130,11 +159,20 @@ class WeightCache:
             if not isinstance(key, tuple) or not any(isinstance(i, int) and i in mods for i in key[1:]):
                 continue
             kind = key[0]
-            if kind not in _REFRESH_IDS:
+            if kind not in _REFRESH_IDS or (kind == "fused" and not key[2]):
                 raise NotImplementedError("packed %r weights cannot be refreshed in place: call model.invalidate_engines()" % (kind,))
             ids = _REFRESH_IDS[kind](key)
             if not all(i in mods for i in ids):
                 raise RuntimeError("a packed %r entry joins several modules: refresh all of them together" % (kind,))
+            if kind == "fused":
+                new = _fused_host(_block_of(mods, mods[key[1]]), True)           # raises in the dry pass when the block is missing
+                if sorted(new) != sorted(self.store[key]):
+                    raise RuntimeError("a packed fused entry does not match its block any more: call model.invalidate_engines()")
+                if not dry:
+                    for name, src in new.items():
+                        self.store[key][name].copy_(src.contiguous().to(self.device, non_blocking=False))
+                n += 1
+                continue
             if kind in ("bn", "bnstat", "dw", "dwdot", "wTs"):
                 new = self._remake(kind, key, [mods[i] for i in ids], mods)      # small: made in the dry pass too, so that it can raise
                 if not dry:
@@ -191,22 +229,8 @@ class WeightCache:
     def fused_block(self, blk, natural):
         """An inverted-residual block for the one-launch kernels: {w1, s1, b1 (with an expand conv), wd, sd, bd, w2, s2, b2}.
         The 1x1 weights are [Cin][Cout], or -- `natural` (csrc/fused_mid.hip) -- as the module holds them, [Cout][Cin]."""
-        seq = list(blk.conv)
-        pw, pwbn = (None, None) if blk.expand_ratio == 1 else (seq[0][0], seq.pop(0)[1])
-        dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1], seq[2]
-
-        def mat(conv):
-            w = conv.weight.detach().float().cpu().reshape(conv.weight.shape[:2])
-            return w if natural else w.t()
-
-        def make():
-            ws = {}
-            if pw is not None:
-                ws["w1"], ws["s1"], ws["b1"] = self._up(mat(pw), *P.fold_bn(pwbn))
-            ws["wd"], ws["sd"], ws["bd"] = self._up(P.pack_dw_weight(dwc.weight), *P.fold_bn(dwbn))
-            ws["w2"], ws["s2"], ws["b2"] = self._up(mat(pl), *P.fold_bn(plbn))
-            return ws
-        return self._get(("fused", id(dwc), natural), make)
+        dwc = list(blk.conv)[0 if blk.expand_ratio == 1 else 1][0]
+        return self._get(("fused", id(dwc), natural), lambda: {k: self._up(v)[0] for k, v in _fused_host(blk, natural).items()})
 
     def stem(self, conv, bn):
         """(weights [27, 32], scale, bias) of the stem conv + BatchNorm."""

@@ -752,10 +752,10 @@ int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd 
  * weight-gradient row and a non-zero gamma gradient).
  *
  * uavsal_pix_gemm: out[m][n] = fl(row_scale[m] G[m][n]) (+ the old value with `accumulate`), G[m][n] = sum over the K
- *   pixels p of a[p][m] b[p][n]; row p of a / b at p * lda / p * ldb floats (channel slices are read in place).  M a
- *   multiple of 128 and N a multiple of 64 (else UAVSAL_ESHAPE; the last N tile may be half empty: nothing at or behind
- *   column N is read or written).  The tile loop and the K split of uavsal_twa_wgrad: chunks of
- *   UAVSAL_WGRAD_CHAIN pixels, shares of whole chunks for about 1024 workgroups over the (M / 128) ceil(N / 128) tiles, partial
+ *   pixels p of a[p][m] b[p][n]; row p of a / b at p * lda / p * ldb floats (channel slices are read in place).  M and N
+ *   multiples of 64 (else UAVSAL_ESHAPE; the last M tile and the last N tile may be half empty: nothing at or behind row
+ *   M or column N is read, written or enters rowdot).  The tile loop and the K split of uavsal_twa_wgrad: chunks of
+ *   UAVSAL_WGRAD_CHAIN pixels, shares of whole chunks for about 1024 workgroups over the ceil(M / 128) ceil(N / 128) tiles, partial
  *   tiles in `ws`; a second launch sums the shares in share order in double and rounds once.  row_scale NULL = 1.
  *   rowdot (optional, [M] doubles) = sum_n w[m][n] G[m][n] in double in a fixed order, w rows ldw floats apart.
  *   No atomics: two calls return the same bits.  TWO launches, no allocation.  UAVSAL_EALIGN: a, b, ws not 16-byte
@@ -928,6 +928,38 @@ int uavsal_ir_bwd_s2(const uavsal_ir_bwd_s2_desc* d, uavsal_stream_t stream);
 int uavsal_bilinear_ac_bwd(const uavsal_bilinear_bwd_desc* d, uavsal_stream_t stream);
 int uavsal_tsum_bwd(const uavsal_tsum_bwd_desc* d, uavsal_stream_t stream);
 int uavsal_ctx_sizeof_desc(int which);    /* 0 ir_bwd_s2, 1 bilinear_bwd, 2 tsum_bwd (uavsal_block_sizeof_desc is closed at 3) */
+
+/* ---- fine-tuning the multi-prior path: the sums of a stride-2 block (csrc/train_ctx.hip) --------------------------------
+ * The three blocks of the path above, TRAINED (train.prior_path_backward): their parameter gradients are those of the block
+ * backward (uavsal_pix_gemm for G1 over the INPUT pixels and G3 over the OUTPUT pixels, uavsal_ir_finish); for the two
+ * stride-2 blocks the channel sums come from
+ *
+ * uavsal_ir_sums_s2: uavsal_ir_sums for a depthwise 3x3 with stride 2, padding 1, dilation 1.  d, gd dense
+ *   [n_img][Ho][Wo][Ch] with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1; e, ga dense [n_img][H][W][Ch]; go rows of Co floats
+ *   ldgo floats apart over the n_img Ho Wo output pixels.  With delta2 = gd m6(d) formed in fp32 as uavsal_ir_bwd_s2 forms it:
+ *     S2[c]         = sum over OUTPUT pixels of delta2[n][oy][ox][c]
+ *     Gd[c][ky][kx] = sum over OUTPUT pixels of delta2[n][oy][ox][c] e[n][2 oy - 1 + ky][2 ox - 1 + kx][c]  (zero outside)
+ *     S3[m]         = sum over OUTPUT pixels of go[n][oy][ox][m]
+ *     S1[c]         = sum over INPUT pixels of ga[n][y][x][c]
+ *   every product accumulated in double.  The workspace layout is uavsal_ir_sums' ([slab][UAVSAL_IR_NSUM * Ch + Co] doubles),
+ *   so uavsal_ir_finish is used unchanged.  A slab is a run of whole output rows counted through all images (about 256
+ *   input pixels, at most 256 slabs) with the input rows 2 oy and 2 oy + 1 of each; it depends on the shape alone
+ *   (uavsal_ir_sums_s2_slabs / _slab_rows): no atomics, bit-reproducible.  Ch % 64 == 0 (else UAVSAL_ESHAPE), Co and ldgo
+ *   multiples of 4, 16-byte aligned pointers (else UAVSAL_EALIGN).  ONE launch.
+ */
+typedef struct uavsal_ir_sums_s2_desc {
+    const float* gd;  const float* d;       /* [n_img][Ho][Wo][Ch] */
+    const float* e;  const float* ga;       /* [n_img][H][W][Ch] */
+    const float* go;  int32_t ldgo;         /* [n_img * Ho * Wo] rows of Co floats */
+    double* ws;  int64_t ws_bytes;
+    int32_t n_img, H, W, Ch, Co;
+} uavsal_ir_sums_s2_desc;
+
+int64_t uavsal_ir_sums_s2_workspace_bytes(const uavsal_ir_sums_s2_desc* d);
+int uavsal_ir_sums_s2_slabs(const uavsal_ir_sums_s2_desc* d);       /* slabs of that call (no launch) */
+int uavsal_ir_sums_s2_slab_rows(const uavsal_ir_sums_s2_desc* d);   /* OUTPUT rows per slab */
+int uavsal_ir_sums_s2(const uavsal_ir_sums_s2_desc* d, uavsal_stream_t stream);
+int uavsal_mp_sizeof_desc(int which);     /* 0 ir_sums_s2 (uavsal_ctx_sizeof_desc is closed at 3) */
 
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;

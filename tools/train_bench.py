@@ -29,6 +29,14 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                the second `block_backward` (fust_block_bwd), the three launches of csrc/train_ctx.hip alone at the path's
                shapes (ir_bwd_s2: cxt_cb_prior[0], B x 45 x 80 x 1536; bilinear_bwd: T x 45 x 80 x 64 out of cb192 ->
                B x 12 x 20 x 64; tsum_bwd: T x 45 x 80 x 256), and `refresh_weights` over the four stages (refresh4);
+  ctx          the multi-prior path trained too, the fifth stage (fucb_layer[0], cxt_cb_prior[1], cxt_cb_prior[0]): the
+               four-stage step (step4b) and the same with `ctx=True` (step5), and `recurrence_step(decoder=True, fuse=True,
+               ctx=True)` without fust (step4c), alternated in the same run, every run listed (the spread);
+               `train.prior_path_backward` frozen (prior_path_frozen: what `fust_output_grad` runs) and with the 27 gradients
+               (prior_path_trained); per trained block (fucb / ctx1 / ctx0) its channel sums alone (`uavsal_ir_sums` for the
+               stride-1 fucb_layer[0], `uavsal_ir_sums_s2` for the two stride-2 blocks; GB/s from the bytes they must move:
+               e and ga on the input grid, gd, d and go on the output grid) and its two pixel GEMMs with their reductions
+               (w1: ga x x; w3: go x d with M = 64, half a tile); and `refresh_weights` over the five stages (refresh5);
   eager        torch autograd of the restated recurrence + decoder (float32, eval BatchNorm folded) on the same device,
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
@@ -250,6 +258,81 @@ def fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats):
     res["ir_bwd_s2_shape"], res["bilinear_bwd_shape"] = list(ip["e"].shape), [list(g_up.shape), list(parts["g_ctx2"].shape)]
 
 
+def ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats):
+    """the phases of the trained multi-prior path (fucb_layer[0], cxt_cb_prior), the fifth stage, added to `res`"""
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    rc = m.rnn.cell_list[0].rnn_conv
+    taps = {"fu320": None, "cb192": None}
+    m(x, cb, None, taps=taps)
+    fu, cb192 = taps["fu320"], taps["cb192"]
+    x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
+    _, grad_x, _ = train.twa_backward(x_seq, h_seq, None, rc.weight.detach(), grad_h, need_x_grad=True, cache=cache, module=rc)
+    grad_fu, _ = train.block_backward(m.fucbst_layer[0], fu, grad_x.contiguous(memory_format=cl), cache=cache)
+    blocks = train.prior_path_blocks(m)
+    parts = {}
+    _, grads = train.prior_path_backward(m, fu, cb192, grad_fu, cache=cache, parts=parts, grads={n: None for n in blocks})
+    boxes = (m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer, m.fucb_layer, m.cxt_cb_prior)
+    trained = [q for mod in boxes for q in mod.parameters()]
+
+    def stepper(**kw):
+        def run():
+            for q in trained:
+                q.grad = None
+            train.recurrence_step(m, x, cb, None, y_gaze, decoder=True, fuse=True, **kw)
+        return run
+
+    def refresh5():
+        with torch.no_grad():
+            for q in trained:
+                q.mul_(1.0)
+        m.refresh_weights(*boxes)
+    cases = {"prior_path_frozen": lambda: train.fust_output_grad(m, fu, cb192, grad_fu, cache=cache),
+             "prior_path_trained": lambda: train.prior_path_backward(m, fu, cb192, grad_fu, cache=cache, grads=grads),
+             "refresh5": refresh5}
+    shapes = {}
+    for name, blk in blocks.items():
+        key = {"fucb_layer.0": "fucb", "cxt_cb_prior.1": "ctx1", "cxt_cb_prior.0": "ctx0"}[name]
+        pt = parts[name]
+        pw, pwbn, _, _, pl, plbn = train._param_grad_parts(blk)
+        hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+        s1, s3 = cache.affine(pwbn, hid)[0], cache.affine(plbn, cout)[0]
+        rd1 = torch.empty(hid, dtype=torch.float64, device=dev)
+        rd3 = torch.empty(cout, dtype=torch.float64, device=dev)
+        g1, g3 = grads[name][train.BLOCK_PARAMS[0]], grads[name][train.BLOCK_PARAMS[6]]
+        sums = train.ir_sums if blk.stride == 1 else train.ir_sums_s2
+        cases["%s_sums" % key] = lambda pt=pt, sums=sums: sums(pt["gd"], pt["d"], pt["e"], pt["ga"], pt["go"])
+        cases["%s_pix_gemm_w1" % key] = lambda pt=pt, g1=g1, s1=s1, pw=pw, rd1=rd1: train.pix_gemm(
+            pt["ga"], pt["x"], out=g1, row_scale=s1, w=pw.weight.detach(), rowdot=rd1)
+        cases["%s_pix_gemm_w3" % key] = lambda pt=pt, g3=g3, s3=s3, pl=pl, rd3=rd3: train.pix_gemm(
+            pt["go"], pt["d"], out=g3, row_scale=s3, w=pl.weight.detach(), rowdot=rd3)
+        n_in = pt["e"].shape[0] * pt["e"].shape[1] * pt["e"].shape[2]
+        n_out = pt["d"].shape[0] * pt["d"].shape[1] * pt["d"].shape[2]
+        shapes[key] = dict(block=[cin, hid, cout], stride=blk.stride, e=list(pt["e"].shape), d=list(pt["d"].shape), n_in=n_in, n_out=n_out)
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    for key, sh in shapes.items():
+        cin, hid, cout = sh["block"]
+        nbytes = 4.0 * (2 * hid * sh["n_in"] + (2 * hid + cout) * sh["n_out"])
+        res["%s_sums_gbs" % key] = nbytes / (res["%s_sums_ms" % key] * 1e-3) / 1e9
+        for tag, (M, N, K) in (("w1", (hid, cin, sh["n_in"])), ("w3", (cout, hid, sh["n_out"]))):
+            gd = L.PixGemmDesc()
+            gd.K, gd.M, gd.N = K, M, N
+            res["%s_pix_gemm_%s_shares" % (key, tag)] = int(lib.uavsal_pix_gemm_shares(C.byref(gd)))
+            res["%s_pix_gemm_%s_tflops" % (key, tag)] = 2.0 * M * N * K / (res["%s_pix_gemm_%s_ms" % (key, tag)] * 1e-3) / 1e12
+    res["ctx_shapes"] = shapes
+    runs = {"step4b": stepper(fust=True), "step5": stepper(fust=True, ctx=True), "step4c": stepper(ctx=True)}
+    alt = {k: [] for k in runs}                               # the three steps alternated in the same run
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    for q in trained:
+        q.grad = None
+
+
 def bench(T, iters, repeats, dev, skip_eager):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5)
@@ -361,6 +444,7 @@ def bench(T, iters, repeats, dev, skip_eager):
     res["wgrad_of_peak"] = res["wgrad_tflops"] / PEAK_TFLOPS
     fuse_phases(res, m, x, cb, y_gaze, taps, grad_h, cache, iters, repeats, skip_eager)
     fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
+    ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     if not skip_eager:
         try:
             run = eager_step(m, taps["prefuse"], torch.zeros((1, 256, h, w), device=dev), g_y)
