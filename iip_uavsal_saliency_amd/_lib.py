@@ -311,6 +311,28 @@ class IrSumsS2Desc(C.Structure):
 
 MP_DESC_TYPES = [IrSumsS2Desc]              # sized by uavsal_mp_sizeof_desc (csrc/train_ctx.hip)
 
+
+class IrNarrowDesc(C.Structure):
+    _fields_ = [("x", _f), ("e", _f), ("d", _f), ("gd", _f), ("ga", _f), ("go", _f), ("ldgo", C.c_int32),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Ch", C.c_int32), ("Co", C.c_int32)]
+
+
+class IrNarrowFinishDesc(C.Structure):
+    _fields_ = [("ws", C.c_void_p), ("ws_bytes", C.c_int64)] + [(n, _f) for n in (
+        "w1", "wd", "w3", "s1", "s2", "s3", "r1", "mu1", "r2", "mu2", "r3", "mu3",
+        "g_w1", "g_gamma1", "g_beta1", "g_wd", "g_gamma2", "g_beta2", "g_w3", "g_gamma3", "g_beta3")] + [
+        ("Cin", C.c_int32), ("Ch", C.c_int32), ("Co", C.c_int32), ("slabs", C.c_int32), ("accumulate", C.c_int32)]
+
+
+class FrameSumDesc(C.Structure):
+    _fields_ = [("a", _f), ("lda", C.c_int32), ("out", _f), ("ldo", C.c_int32),
+                ("N", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32)]
+
+
+NARROW_CHUNK = 32             # UAVSAL_NARROW_CHUNK: pixels whose G1 / G3 products uavsal_ir_narrow_grads adds in fp32 (csrc/train_nets.hip)
+NETS_DESC_TYPES = [IrNarrowDesc, IrNarrowFinishDesc, FrameSumDesc]      # sized by uavsal_nets_sizeof_desc
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -373,6 +395,13 @@ SYMBOLS = [
     ("uavsal_ir_sums_s2_slab_rows", C.c_int, [C.POINTER(IrSumsS2Desc)]),
     ("uavsal_ir_sums_s2", C.c_int, [C.POINTER(IrSumsS2Desc), C.c_void_p]),
     ("uavsal_mp_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_ir_narrow_workspace_bytes", C.c_int64, [C.POINTER(IrNarrowDesc)]),
+    ("uavsal_ir_narrow_slabs", C.c_int, [C.POINTER(IrNarrowDesc)]),
+    ("uavsal_ir_narrow_slab_rows", C.c_int, [C.POINTER(IrNarrowDesc)]),
+    ("uavsal_ir_narrow_grads", C.c_int, [C.POINTER(IrNarrowDesc), C.c_void_p]),
+    ("uavsal_ir_narrow_finish", C.c_int, [C.POINTER(IrNarrowFinishDesc), C.c_void_p]),
+    ("uavsal_frame_sum", C.c_int, [C.POINTER(FrameSumDesc), C.c_void_p]),
+    ("uavsal_nets_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -448,7 +477,7 @@ def load():
     for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES),
                           (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES),
                           (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES),
-                          (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES)):
+                          (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

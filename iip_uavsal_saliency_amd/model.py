@@ -295,6 +295,9 @@ class UAVSal(nn.Module):
         parameter or buffer was modified in place since the weights were packed, the plans and packed weights are dropped
         instead (as `_check_weights` would at the next call) and everything is packed anew then.  Modules with a packed form
         that cannot be remade in place (fused blocks, the stem) raise before anything is copied.
+        When one of `modules` is, or lies inside, `gauss_cb_layer` / `ob_cb_layer`, the prior record of every plan is dropped
+        as well (`invalidate_priors`): the maps those nets left in the plans' arenas belong to the old weights, and a call with
+        the same prior tensors must run them again (`cache_priors`).  Other modules leave the record alone.
         Returns the number of packed tensors refreshed (0 when nothing was packed yet, or when the plans were dropped)."""
         from .weights import WeightCache
         if self._wversion is None or "_wtensors" not in self.__dict__:
@@ -313,6 +316,11 @@ class UAVSal(nn.Module):
             if m._wversion is not None and "_wtensors" in m.__dict__:
                 m._wversion = m._weights_version()
                 m._wvers = [t._version for t in m._wtensors]
+        # what the prior nets left in the plans' arenas (`cache_priors`) came from the OLD weights: a call with the same prior
+        # tensors must run them again.  Any other module leaves the record alone, and those calls keep skipping the group
+        nets = [getattr(self, a, None) for a in ("gauss_cb_layer", "ob_cb_layer")]
+        if any(id(s) in mods for net in nets if net is not None for s in net.modules()):
+            self.invalidate_priors()
         return n
 
     def invalidate_priors(self):

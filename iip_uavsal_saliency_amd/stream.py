@@ -400,7 +400,11 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     the gradients of `model.fust_layer[0]` behind the priors, and `model.fust_layer` is refreshed as well.
     `"ctx"` (last of all, only behind `"fuse"`, with or without `"fust"`; a model with at least one prior):
     `recurrence_step(..., ctx=True)` also sets the gradients of the multi-prior path -- `model.fucb_layer[0]` and, with the
-    context prior, both blocks of `model.cxt_cb_prior` -- and those containers are refreshed as well."""
+    context prior, both blocks of `model.cxt_cb_prior` -- and those containers are refreshed as well.
+    `"nets"` (last of all, only behind `"fuse"`, with or without `"fust"` / `"ctx"`; a model with the gauss or the ob prior):
+    `recurrence_step(..., nets=True)` also sets the gradients of the prior nets `model.gauss_cb_layer` / `model.ob_cb_layer`,
+    and the enabled nets' containers are refreshed as well (which makes the next call run them again on the priors it is
+    handed).  With every stage named, the optimiser may hold exactly the parameters the reference's does."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
@@ -408,9 +412,10 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     allowed = [("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse"), ("rnn", "fuse", "fust"),
                ("rnn", "decoder", "fuse", "fust")]
     allowed += [s + ("ctx",) for s in allowed if "fuse" in s]
+    allowed += [s + ("nets",) for s in allowed if "fuse" in s]
     if stages not in allowed:
         raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
-                         "'fuse' (then 'ctx', behind 'fuse' too), got %r" % (stages,))
+                         "'fuse' (then 'ctx', then 'nets', behind 'fuse' too), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
@@ -426,6 +431,8 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
             mods.append(model.fucb_layer)
             if getattr(model, "use_context_prior", False):
                 mods.append(model.cxt_cb_prior)
+        if "nets" in kw:
+            mods.extend(_train.prior_nets(model).values())
         model.refresh_weights(*mods)
         return loss, state
     return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,

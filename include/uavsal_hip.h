@@ -961,6 +961,62 @@ int uavsal_ir_sums_s2_slab_rows(const uavsal_ir_sums_s2_desc* d);   /* OUTPUT ro
 int uavsal_ir_sums_s2(const uavsal_ir_sums_s2_desc* d, uavsal_stream_t stream);
 int uavsal_mp_sizeof_desc(int which);     /* 0 ir_sums_s2 (uavsal_ctx_sizeof_desc is closed at 3) */
 
+/* ---- fine-tuning the gauss / ob prior nets: a narrow block's gradients, the sum over frames (csrc/train_nets.hip) --------
+ * Block 0 of either prior net is 8 -> 48 -> 64 or 20 -> 120 -> 64 (stride 1, dilation 1, no residual): widths that
+ * uavsal_pix_gemm, uavsal_ir_sums and uavsal_ir_finish refuse.  The formulas are those of the block backward above.
+ *
+ * uavsal_ir_narrow_grads: from x dense [n_img][H][W][Cin], e, d, gd, ga dense [n_img][H][W][Ch] and go, rows of Co floats ldgo
+ *   floats apart (a channel slice is read in place), per slab of picture rows the partials of G1 = ga x x, G3 = go x d, S2,
+ *   Gd[9], S1 and S3 -> `ws` (doubles).  ws layout per slab: UAVSAL_IR_NSUM * Ch sums as in uavsal_ir_sums, S3 [Co],
+ *   G1 [Ch][Cin], G3 [Co][Ch].  delta2 = gd m6(d) is formed in fp32 as uavsal_ir_bwd forms it; the sums add every product in
+ *   double; G1 and G3 add the products of UAVSAL_NARROW_CHUNK consecutive pixels of the slab in fp32 (fused multiply-add, in
+ *   pixel order) and the chunks in double.  A slab is a run of whole picture rows counted through all images, about 256 pixels
+ *   and at most 256 slabs (the rule of uavsal_ir_sums at half its slab size; uavsal_ir_narrow_slabs / _slab_rows): a function of
+ *   the shape alone, no atomics, bit-reproducible.  Accepted: Cin % 4 == 0, Cin <= 32, Ch % 4 == 0,
+ *   Ch <= 128, Co == 64 (else UAVSAL_ESHAPE); ldgo % 4 == 0 and 16-byte aligned pointers (else UAVSAL_EALIGN).  Nothing at
+ *   or behind Cin, Ch or Co is read.  ONE launch.
+ * uavsal_ir_narrow_finish: sums the slabs in slab order in double and writes the nine gradients in the parameters' own
+ *   layouts (w1 [Ch][Cin], wd [Ch][3][3], w3 [Co][Ch]): W = s G, beta = S, gamma = r (sum W G - mu S) with the row dots taken
+ *   in index order in double from the unscaled sums, each result rounded once, overwritten or (`accumulate`) added to.
+ *   s1, s2, s3 the folded scales, r, mu as above.  ONE launch.
+ * uavsal_frame_sum: out[p][c] = sum over n of a[n][p][c] for HW pixels and C channels; a: N images of HW rows lda floats
+ *   apart (a channel slice is read in place), out rows ldo floats apart.  Frames are added in frame order in double and the
+ *   sum is rounded once; N == 1 returns the input's bits.  C, lda, ldo multiples of 4, 16-byte aligned pointers.  ONE launch.
+ */
+#define UAVSAL_NARROW_CHUNK 32
+
+typedef struct uavsal_ir_narrow_desc {
+    const float* x;                         /* [n_img][H][W][Cin] */
+    const float* e;  const float* d;  const float* gd;  const float* ga;      /* [n_img][H][W][Ch] */
+    const float* go;  int32_t ldgo;         /* [n_img * H * W] rows of Co floats */
+    double* ws;  int64_t ws_bytes;
+    int32_t n_img, H, W, Cin, Ch, Co;
+} uavsal_ir_narrow_desc;
+
+typedef struct uavsal_ir_narrow_finish_desc {
+    const double* ws;  int64_t ws_bytes;
+    const float* w1;  const float* wd;  const float* w3;
+    const float* s1;  const float* s2;  const float* s3;
+    const float* r1;  const float* mu1;  const float* r2;  const float* mu2;  const float* r3;  const float* mu3;
+    float* g_w1;  float* g_gamma1;  float* g_beta1;  float* g_wd;  float* g_gamma2;  float* g_beta2;
+    float* g_w3;  float* g_gamma3;  float* g_beta3;
+    int32_t Cin, Ch, Co, slabs, accumulate;
+} uavsal_ir_narrow_finish_desc;
+
+typedef struct uavsal_frame_sum_desc {
+    const float* a;  int32_t lda;
+    float* out;      int32_t ldo;
+    int32_t N, HW, C;
+} uavsal_frame_sum_desc;
+
+int64_t uavsal_ir_narrow_workspace_bytes(const uavsal_ir_narrow_desc* d);
+int uavsal_ir_narrow_slabs(const uavsal_ir_narrow_desc* d);         /* slabs of that call (no launch) */
+int uavsal_ir_narrow_slab_rows(const uavsal_ir_narrow_desc* d);     /* picture rows per slab */
+int uavsal_ir_narrow_grads(const uavsal_ir_narrow_desc* d, uavsal_stream_t stream);
+int uavsal_ir_narrow_finish(const uavsal_ir_narrow_finish_desc* d, uavsal_stream_t stream);
+int uavsal_frame_sum(const uavsal_frame_sum_desc* d, uavsal_stream_t stream);
+int uavsal_nets_sizeof_desc(int which);   /* 0 ir_narrow, 1 ir_narrow_finish, 2 frame_sum (uavsal_mp_sizeof_desc is closed at 1) */
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 

@@ -37,6 +37,14 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                stride-1 fucb_layer[0], `uavsal_ir_sums_s2` for the two stride-2 blocks; GB/s from the bytes they must move:
                e and ga on the input grid, gd, d and go on the output grid) and its two pixel GEMMs with their reductions
                (w1: ga x x; w3: go x d with M = 64, half a tile); and `refresh_weights` over the five stages (refresh5);
+  nets         the gauss / ob prior nets trained too, the sixth stage (both blocks of `gauss_cb_layer` and `ob_cb_layer`): the
+               five-stage step (step5b) and the same with `nets=True` (step6), alternated in the same run, every run listed
+               (the spread); the nets' backward alone as the step runs it on this benchmark's one prior map broadcast over
+               the frames (nets_backward: per net `train.frame_sum` + `train.prior_net_backward` on ONE frame) and on
+               materialised per-frame priors (nets_backward_frames: N frames); per net's narrow block 0 (gauss0: 8 -> 48 ->
+               64, ob0: 20 -> 120 -> 64) `train.narrow_block_param_grads` from given parts (two launches) and its first
+               launch `uavsal_ir_narrow_grads` alone, with the slab count; `uavsal_frame_sum` of one 64-channel slice of
+               g_cb; and `refresh_weights` over the six stages (refresh6);
   eager        torch autograd of the restated recurrence + decoder (float32, eval BatchNorm folded) on the same device,
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
@@ -333,6 +341,70 @@ def ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats):
         q.grad = None
 
 
+def nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
+    """the phases of the trained prior nets (gauss_cb_layer, ob_cb_layer), the sixth stage, added to `res`"""
+    lib = L.load()
+    taps = {"cb192": None}
+    m(x, cb, None, taps=taps)
+    g_cb = torch.randn_like(taps["cb192"]).permute(0, 2, 3, 1).contiguous()      # (timing only: any gradient of the right shape)
+    nets = train.prior_nets(m)
+    boxes = (m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer, m.fucb_layer, m.cxt_cb_prior) + tuple(nets.values())
+    trained = [q for mod in boxes for q in mod.parameters()]
+    frames = [c.contiguous() for c in cb]                      # the same priors materialised per frame
+    nchw = lambda t: t.permute(0, 3, 1, 2)                     # noqa: E731
+
+    def stepper(**kw):
+        def run():
+            for q in trained:
+                q.grad = None
+            train.recurrence_step(m, x, cb, None, y_gaze, decoder=True, fuse=True, fust=True, ctx=True, **kw)
+        return run
+
+    def backward(static):
+        def run():
+            for i, net in enumerate(nets.values()):
+                go, c = g_cb[..., 64 * i:64 * i + 64], (cb if static else frames)[i]
+                if static:
+                    go, c = train.frame_sum(go), c[:1]
+                train.prior_net_backward(net, c, go, cache=cache)
+        return run
+
+    def refresh6():
+        with torch.no_grad():
+            for q in trained:
+                q.mul_(1.0)
+        m.refresh_weights(*boxes)
+    cases = {"nets_backward": backward(True), "nets_backward_frames": backward(False), "refresh6": refresh6,
+             "frame_sum": lambda: train.frame_sum(g_cb[..., :64])}
+    for i, (name, net) in enumerate(nets.items()):
+        key = name.split("_")[0] + "0"
+        for static in (True, False):
+            go, c = g_cb[..., 64 * i:64 * i + 64], (cb if static else frames)[i]
+            if static:
+                go, c = train.frame_sum(go), c[:1]
+            parts = {}
+            train.prior_net_backward(net, c, go, cache=cache, parts=parts)
+            p0 = parts["0"]
+            tag = "%s_%s" % (key, "one_frame" if static else "frames")
+            cases[tag + "_narrow"] = lambda p0=p0, net=net: train.narrow_block_param_grads(
+                net[0], nchw(p0["x"]), p0["e"], p0["d"], nchw(p0["go"]), gd=p0["gd"], ga=p0["ga"], cache=cache)
+            cases[tag + "_narrow_first"] = lambda p0=p0: train.ir_narrow_grads(p0["x"], p0["e"], p0["d"], p0["gd"], p0["ga"], p0["go"])
+            d = L.IrNarrowDesc()
+            d.n_img, d.H, d.W, d.Cin, d.Ch, d.Co = p0["e"].shape[0], p0["e"].shape[1], p0["e"].shape[2], p0["x"].shape[3], p0["e"].shape[3], 64
+            res[tag + "_slabs"] = int(lib.uavsal_ir_narrow_slabs(C.byref(d)))
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    runs = {"step5b": stepper(), "step6": stepper(nets=True)}
+    alt = {k: [] for k in runs}                               # the two steps alternated in the same run
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    for q in trained:
+        q.grad = None
+
+
 def bench(T, iters, repeats, dev, skip_eager):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5)
@@ -445,6 +517,7 @@ def bench(T, iters, repeats, dev, skip_eager):
     fuse_phases(res, m, x, cb, y_gaze, taps, grad_h, cache, iters, repeats, skip_eager)
     fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
+    nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
     if not skip_eager:
         try:
             run = eager_step(m, taps["prefuse"], torch.zeros((1, 256, h, w), device=dev), g_y)
