@@ -333,6 +333,23 @@ class FrameSumDesc(C.Structure):
 NARROW_CHUNK = 32             # UAVSAL_NARROW_CHUNK: pixels whose G1 / G3 products uavsal_ir_narrow_grads adds in fp32 (csrc/train_nets.hip)
 NETS_DESC_TYPES = [IrNarrowDesc, IrNarrowFinishDesc, FrameSumDesc]      # sized by uavsal_nets_sizeof_desc
 
+REPACK_MAX_SRC = 4            # UAVSAL_REPACK_MAX_SRC: weights / BatchNorms side by side in one entry (csrc/repack.hip)
+REPACK_CONV, REPACK_WINO, REPACK_FOLD, REPACK_DW, REPACK_COPY = range(5)
+REPACK_LAYOUT = {"f32": 0, "f32k32": 0, "f16x3": 1, "f16x3i": 2, "f16x3j": 3, "bf16": 4, "bf16x3": 5}
+REPACK_SCALE, REPACK_BIAS, REPACK_RSTD, REPACK_MEAN = range(4)
+
+
+class RepackEntry(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("layout", C.c_int32), ("dst", _f), ("units", C.c_int64),
+                ("src", _f * REPACK_MAX_SRC), ("beta", _f * REPACK_MAX_SRC), ("mean", _f * REPACK_MAX_SRC),
+                ("var", _f * REPACK_MAX_SRC), ("eps", C.c_double * REPACK_MAX_SRC), ("rows", C.c_int32 * REPACK_MAX_SRC),
+                ("n_src", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("taps", C.c_int32), ("Npad", C.c_int32),
+                ("Kpad", C.c_int32), ("kt", C.c_int32), ("flip", C.c_int32), ("gi", C.c_int32), ("P", C.c_int32),
+                ("sN", C.c_int64), ("sC", C.c_int64), ("off", C.c_int64),
+                ("sg", _f), ("sv", _f), ("seps", C.c_double), ("pad", C.c_float), ("reserved", C.c_int32),
+                ("G", C.c_double * 18)]
+
+
 DESC_TYPES = [ConvDesc, DwDesc, StemDesc, BilinearDesc, TdiffDesc, TsumDesc, LayoutDesc, PostDesc, GuardDesc, CopyDesc,
               FusedIrDesc, WinoDesc, DwDotDesc, FillDesc, ScoreDesc, LetterboxDesc, OverlayDesc, GazeDesc, LossDesc, ConvRoute]
 
@@ -402,6 +419,8 @@ SYMBOLS = [
     ("uavsal_ir_narrow_finish", C.c_int, [C.POINTER(IrNarrowFinishDesc), C.c_void_p]),
     ("uavsal_frame_sum", C.c_int, [C.POINTER(FrameSumDesc), C.c_void_p]),
     ("uavsal_nets_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_repack", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("uavsal_repack_sizeof_desc", C.c_int, []),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
     ("uavsal_copy_rows", C.c_int, [C.POINTER(CopyDesc), C.c_void_p]),
     ("uavsal_fill", C.c_int, [C.POINTER(FillDesc), C.c_void_p]),
@@ -481,6 +500,8 @@ def load():
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))
+    if lib.uavsal_repack_sizeof_desc() != C.sizeof(RepackEntry):
+        raise RuntimeError("descriptor RepackEntry: ctypes size %d != C size %d" % (C.sizeof(RepackEntry), lib.uavsal_repack_sizeof_desc()))
     _lib = lib
     return lib
 

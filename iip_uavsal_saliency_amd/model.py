@@ -285,7 +285,7 @@ class UAVSal(nn.Module):
 
     invalidate_engines = _drop_engines
 
-    def refresh_weights(self, *modules):
+    def refresh_weights(self, *modules, device=False):
         """After an optimiser step on the parameters of `modules` (e.g. `model.rnn`, `model.conv_out_st`, `model.fucbst_layer`):
         repack every packed copy of their weights -- conv weights in every layout in use, the Winograd transforms, the
         transposed forms of train.py, and for the decoder and the fusion block their BatchNorm folds and statistics and their
@@ -298,6 +298,16 @@ class UAVSal(nn.Module):
         When one of `modules` is, or lies inside, `gauss_cb_layer` / `ob_cb_layer`, the prior record of every plan is dropped
         as well (`invalidate_priors`): the maps those nets left in the plans' arenas belong to the old weights, and a call with
         the same prior tensors must run them again (`cache_priors`).  Other modules leave the record alone.
+        `device=True` (keyword only): the repack itself runs on the GPU (`WeightCache.refresh_device`, csrc/repack.hip): one
+        launch on torch's CURRENT stream that reads the parameters where they lie and writes the same bytes the host path
+        writes, with no copy to or from the host once its table exists.  Everything else -- the version check, the dry pass
+        that raises before anything is touched, the replicas' bookkeeping, the prior record -- is as above.  Ordering: a plan
+        runs on the current stream, or (graphs) on the engine's own stream, which waits on the current stream before every
+        replay (`Engine.launch`: `_gstream.wait_stream(cur)`), so a repack launched here after `optimizer.step()` on the
+        same stream is complete before the next forward or backward reads a packed weight.  Refreshing while a
+        `RequestPipeline` has requests in flight is unsupported, as it is for the host path.  ValueError, before anything is written, when a
+        store of this model is on the CPU, or a parameter or buffer of `modules` is not a contiguous fp32 tensor on the
+        store's device -- a `channels_last` weight, or a model with packed weights on a second GPU: the host path takes both.
         Returns the number of packed tensors refreshed (0 when nothing was packed yet, or when the plans were dropped)."""
         from .weights import WeightCache
         if self._wversion is None or "_wtensors" not in self.__dict__:
@@ -309,9 +319,11 @@ class UAVSal(nn.Module):
             self._drop_engines()
             return 0
         caches = [WeightCache(dev, store) for dev, store in self._wshared.items()]
-        for c in caches:
-            c.refresh(mods, dry=True)                    # every key can be remade, or nothing is touched
-        n = sum(c.refresh(mods) for c in caches)
+        if device and any(c.device.type == "cpu" for c in caches):
+            raise ValueError("refresh_weights(device=True) needs packed weights on a GPU: this model holds a CPU store")
+        for c in caches:                                 # every key can be remade, or nothing is touched (the device path's dry
+            (c.refresh_device if device else c.refresh)(mods, dry=True)      # pass builds its table: the same walk, no host copy)
+        n = sum(c.refresh_device(mods) if device else c.refresh(mods) for c in caches)
         for m in [self] + list(self.__dict__.get("_stream_replicas") or []):
             if m._wversion is not None and "_wtensors" in m.__dict__:
                 m._wversion = m._weights_version()

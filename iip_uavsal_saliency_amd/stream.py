@@ -382,7 +382,7 @@ def validate_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
 def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_prior: torch.Tensor,
                    fix_map: torch.Tensor, fix_loc: torch.Tensor, optimizer, batch_size: int = 4,
                    model_size: Optional[tuple] = None, frame_layout: str = "CHW", bgr: bool = False,
-                   gaze_layout: Optional[str] = None, criterion=None, prepare=None, stages=("rnn",)):
+                   gaze_layout: Optional[str] = None, criterion=None, prepare=None, stages=("rnn",), refresh="host"):
     """The inner loop of the reference's `train` phase for one video (Demo_Train_Test.py:105-153), for the stage this package
     trains: the ConvTWA recurrence `model.rnn` (train.py).  Arguments, groups, skip rule, carried detached state and returned
     aggregates are `validate_video`'s (one loop serves both); every group that runs does
@@ -404,11 +404,15 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `"nets"` (last of all, only behind `"fuse"`, with or without `"fust"` / `"ctx"`; a model with the gauss or the ob prior):
     `recurrence_step(..., nets=True)` also sets the gradients of the prior nets `model.gauss_cb_layer` / `model.ob_cb_layer`,
     and the enabled nets' containers are refreshed as well (which makes the next call run them again on the priors it is
-    handed).  With every stage named, the optimiser may hold exactly the parameters the reference's does."""
+    handed).  With every stage named, the optimiser may hold exactly the parameters the reference's does.
+    `refresh`: `"host"` (the default) repacks the trained stages' weights on the host after every step; `"device"` repacks
+    them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host)."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
     stages = tuple(stages)
+    if refresh not in ("host", "device"):
+        raise ValueError("refresh must be 'host' or 'device', got %r" % (refresh,))
     allowed = [("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse"), ("rnn", "fuse", "fust"),
                ("rnn", "decoder", "fuse", "fust")]
     allowed += [s + ("ctx",) for s in allowed if "fuse" in s]
@@ -433,7 +437,10 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
                 mods.append(model.cxt_cb_prior)
         if "nets" in kw:
             mods.extend(_train.prior_nets(model).values())
-        model.refresh_weights(*mods)
+        if refresh == "device":
+            model.refresh_weights(*mods, device=True)
+        else:
+            model.refresh_weights(*mods)                  # (no keyword: a model-like object without `device=` keeps working)
         return loss, state
     return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,
                              bgr, gaze_layout, prepare, step)

@@ -197,6 +197,21 @@ class WeightCache:
             n += 1
         return n
 
+    def refresh_device(self, mods, dry=False):
+        """`refresh` without the host: every entry `refresh` would remake is remade by ONE launch of csrc/repack.hip on torch's
+        current stream, from the fp32 parameters and buffers where they lie on this device into the same packed tensors, to
+        the same bytes (the Winograd transforms: within one fp32 ulp).  The table of entries (repack.py) is built
+        and uploaded at the first call and kept in the store under a key `refresh` passes over; before every reuse the
+        addresses of every source and destination and the set of keys are compared with what it recorded, and it is rebuilt
+        when one differs.  Once the table exists a call copies nothing to or from the host and waits for nothing.
+        Raises what `refresh` raises, and ValueError -- before anything is written -- for what only the host path can do: a
+        CPU store, a parameter or buffer that is not fp32 ON THIS DEVICE (so a model whose packed weights live on two GPUs
+        cannot refresh the second store this way: its parameters are on one), or one that is not contiguous (a 3x3 weight kept
+        in `channels_last`).
+        `dry`: build and check the table, launch nothing.  Returns the number of entries refreshed, as `refresh` does."""
+        from . import repack
+        return repack.refresh(self, mods, dry)
+
     def _remake(self, kind, key, ms, mods):
         """The host tensors of one refreshable non-conv entry, in the order of the stored tuple."""
         if kind == "bn":

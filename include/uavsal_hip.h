@@ -1017,6 +1017,69 @@ int uavsal_ir_narrow_finish(const uavsal_ir_narrow_finish_desc* d, uavsal_stream
 int uavsal_frame_sum(const uavsal_frame_sum_desc* d, uavsal_stream_t stream);
 int uavsal_nets_sizeof_desc(int which);   /* 0 ir_narrow, 1 ir_narrow_finish, 2 frame_sum (uavsal_mp_sizeof_desc is closed at 1) */
 
+/* ---- repacking refreshed weights on the device (csrc/repack.hip) ---------------------------------------------------------
+ * After an optimiser step the packed copies of a module's weights are remade FROM the fp32 parameters and buffers where they
+ * lie INTO the packed device tensors that exist (launch plans hold their addresses): the bytes packing.py / weights.py make
+ * on the host, made by one launch.  uavsal_repack reads a table in DEVICE memory: `n_entries` uavsal_repack_entry, one per
+ * packed tensor, followed by n_entries + 1 int32 `first_block` (a prefix sum of ceil(units / 256); the last is `n_blocks`,
+ * the grid).  A workgroup finds its entry in the prefix array; a thread writes one unit of the destination, once.
+ *
+ * kind CONV (pack_conv_weight): the logical matrix m[n][k], n < Npad, k < Kpad, is 0 at n >= N or k >= C * taps; else with
+ *   c, tap from k (taps == 1: c = k; taps == 9: k = ((c / kt) * 9 + tap) * kt + c % kt), the row r = n (gi > 0, a ConvLSTM's
+ *   gate interleave: r = (n % 4) * gi + n / 4) falls into source s (rows[] are the cumulative row counts of up to
+ *   UAVSAL_REPACK_MAX_SRC weights side by side) at row r', and m = src[s][off + r' * sN + c * sC + (flip ? taps - 1 - tap : tap)]
+ *   (element strides: a plain weight has sN = Cin_full * taps, sC = taps, off = first channel of the slice * taps; the
+ *   transposed conv swaps sN and sC and sets flip).  With `sg` the value is fl32(m * s[c]), s[c] = fl32(sg[c] / sqrt(sv[c] +
+ *   seps)) folded in double -- one fp32 multiply.  Layouts (Kpad a multiple of kt: 16 for F32, 32 for the others and for the
+ *   32-float-K form of F32, which differs from F32 only through kt):
+ *     F32     float [Npad][Kpad]                                         unit = 4 consecutive k
+ *     F16X3   half  [Kpad/32][hi | lo][Npad][32], k order of a run permuted: position j holds k = 16 * ((j / 4) % 2) + 4 * (j / 8) + j % 4
+ *     F16X3I  half  [Kpad/32][Npad][hi 32 | lo 32], natural k order
+ *     F16X3J  half  [Kpad/16][Npad][hi 16 | lo 16], natural k order
+ *     BF16    bf16  [Kpad/32][Npad][32], permuted;  BF16X3  bf16 [Kpad/32][hi | lo][Npad][32], permuted
+ *   (unit = 8 consecutive halves).  The split: x = fl32(64 m), hi = half(x) to nearest even, lo = half(fl32(x - float(hi))) (the
+ *   difference is exact); bf16: the same without the 64.
+ * kind WINO (pack_wino_weight): float [P * P][Npad][Kpad], U[P i + l][o][c] = fl32(sum_jk G[i][j] g[j][k] G[l][k]) of the 3x3
+ *   taps g of (o, c), in double in ONE order: t[i][k] = (G[i][0] g[0][k] + G[i][1] g[1][k]) + G[i][2] g[2][k], then
+ *   U = (t[i][0] G[l][0] + t[i][1] G[l][1]) + t[i][2] G[l][2]; no product is fused with a sum.  G ([P][3], row-major in `G`)
+ *   comes from the caller.  Zero at o >= N or c >= C.  unit = one (o, c) of [Npad][Kpad].
+ * kind FOLD: float [Npad]; `layout` says which vector of the BatchNorms lying side by side (src = gamma, beta, mean, var,
+ *   eps; rows[] cumulative): SCALE g / sqrt(v + eps), BIAS b - m * scale (the unrounded scale), RSTD 1 / sqrt(v + eps), each in
+ *   double and rounded once, MEAN copied; channels N .. Npad hold `pad`.  unit = one channel.
+ * kind DW: float [9][N], tap-major, of depthwise weights [C_s][1][3][3] side by side.  kind COPY: `units` floats of src[0].
+ * Every divide and square root is the correctly rounded one.  The caller answers for the table: every pointer a device
+ * pointer to fp32 data of the stated extent, dst 16-byte aligned and as large as the layout says.  uavsal_repack itself
+ * checks only what it can see from the host: a non-null 16-byte aligned table, positive counts, n_blocks below
+ * UAVSAL_REPACK_MAX_BLOCKS. */
+#define UAVSAL_REPACK_MAX_SRC 4
+#define UAVSAL_REPACK_MAX_BLOCKS (1 << 24)  /* n_blocks at or above it: UAVSAL_ESHAPE (256 threads each, under 2^32 a launch) */
+enum { UAVSAL_REPACK_CONV = 0, UAVSAL_REPACK_WINO = 1, UAVSAL_REPACK_FOLD = 2, UAVSAL_REPACK_DW = 3, UAVSAL_REPACK_COPY = 4 };
+enum { UAVSAL_REPACK_F32 = 0, UAVSAL_REPACK_F16X3 = 1, UAVSAL_REPACK_F16X3I = 2, UAVSAL_REPACK_F16X3J = 3, UAVSAL_REPACK_BF16 = 4,
+       UAVSAL_REPACK_BF16X3 = 5 };
+enum { UAVSAL_REPACK_SCALE = 0, UAVSAL_REPACK_BIAS = 1, UAVSAL_REPACK_RSTD = 2, UAVSAL_REPACK_MEAN = 3 };
+
+typedef struct uavsal_repack_entry {
+    int32_t kind, layout;                   /* layout: the conv layout, or which vector a FOLD entry writes */
+    void* dst;
+    int64_t units;                          /* threads of this entry */
+    const float* src[UAVSAL_REPACK_MAX_SRC];        /* weights; FOLD: gamma */
+    const float* beta[UAVSAL_REPACK_MAX_SRC];
+    const float* mean[UAVSAL_REPACK_MAX_SRC];
+    const float* var[UAVSAL_REPACK_MAX_SRC];
+    double eps[UAVSAL_REPACK_MAX_SRC];
+    int32_t rows[UAVSAL_REPACK_MAX_SRC];    /* cumulative rows (channels) of the sources */
+    int32_t n_src;
+    int32_t N, C, taps, Npad, Kpad, kt, flip, gi;
+    int32_t P;                              /* WINO: r + 2 */
+    int64_t sN, sC, off;
+    const float* sg;  const float* sv;  double seps;        /* CONV: gamma, var, eps of the scale in the rows, or null */
+    float pad;  int32_t reserved;
+    double G[18];
+} uavsal_repack_entry;
+
+int uavsal_repack(const void* table, int n_entries, int n_blocks, uavsal_stream_t stream);
+int uavsal_repack_sizeof_desc(void);
+
 /* ---- launch plan: a recorded sequence of the calls above, run natively ------------ */
 typedef struct uavsal_plan uavsal_plan;
 

@@ -45,11 +45,17 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                64, ob0: 20 -> 120 -> 64) `train.narrow_block_param_grads` from given parts (two launches) and its first
                launch `uavsal_ir_narrow_grads` alone, with the slab count; `uavsal_frame_sum` of one 64-channel slice of
                g_cb; and `refresh_weights` over the six stages (refresh6);
+  refresh pairs beside every refresh case above its `_device` twin: the same in-place edit, then `refresh_weights(...,
+               device=True)` (csrc/repack.hip: one launch, no host copy); and at the end (or alone: --refresh-only) the
+               host and device refresh of 1, 4, 5 and 6 stages (refreshN_alt / refreshN_device_alt) and one whole six-stage
+               iteration -- step, `torch.optim.Adam.step`, refresh -- with either (iter6 / iter6_device), all alternated in
+               the same run, every run listed (`_all_ms`: the spread), with the device path's launches, entries and bytes and the
+               launch alone back to back (`refreshN_device_kernel_ms`);
   eager        torch autograd of the restated recurrence + decoder (float32, eval BatchNorm folded) on the same device,
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
 
-Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager]
+Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--frames 20 5]
 """
 import argparse
 import ctypes as C
@@ -163,19 +169,19 @@ def fuse_phases(res, m, x, cb, y_gaze, taps, grad_h, cache, iters, repeats, skip
             q.grad = None
         train.recurrence_step(m, x, cb, None, y_gaze, fuse=True)
 
-    def refresh_fuse():
+    def refresh_fuse(device=False):
         with torch.no_grad():
             rc.weight.mul_(1.0)
             for q in blk.parameters():
                 q.mul_(1.0)
-        m.refresh_weights(m.rnn, box)
+        m.refresh_weights(m.rnn, box, device=device)
     cases = {"block_bwd": lambda: train.block_backward(blk, x_in, grad_x, need_x_grad=False, cache=cache, grads=grads),
              "block_bwd_x": lambda: train.block_backward(blk, x_in, grad_x, cache=cache, grads=grads),
              "ir_bwd": lambda: train.ir_bwd(gd_, d_, e_, w9, s2),
              "ir_sums": lambda: train.ir_sums(gd_, d_, e_, ga_, gon),
              "pix_gemm_w1": lambda: train.pix_gemm(ga_, xn, out=g1, row_scale=s1, w=pw.weight.detach(), rowdot=rd1),
              "pix_gemm_w3": lambda: train.pix_gemm(gon, d_, out=g3, row_scale=s3, w=pl.weight.detach(), rowdot=rd3),
-             "refresh_fuse": refresh_fuse}
+             "refresh_fuse": refresh_fuse, "refresh_fuse_device": lambda: refresh_fuse(True)}
     for k, fn in cases.items():
         res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
     alt = {"step": [], "step_fuse": []}                      # the two steps alternated in the same run
@@ -242,17 +248,17 @@ def fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats):
             q.grad = None
         train.recurrence_step(m, x, cb, None, y_gaze, decoder=True, fuse=True, fust=True)
 
-    def refresh4():
+    def refresh4(device=False):
         with torch.no_grad():
             for q in trained:
                 q.mul_(1.0)
-        m.refresh_weights(m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer)
+        m.refresh_weights(m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer, device=device)
     cases = {"fust_output_grad": lambda: train.fust_output_grad(m, fu, cb192, grad_fu, cache=cache),
              "fust_block_bwd": lambda: train.block_backward(fb, st, g, need_x_grad=False, cache=cache, grads=grads),
              "ir_bwd_s2": lambda: train.ir_bwd_s2(ip["gd"], ip["d"], ip["e"], w9, s2),
              "bilinear_bwd": lambda: train.bilinear_bwd(g_up, B, parts["g_ctx2"].shape[1], parts["g_ctx2"].shape[2], src_mod=B),
              "tsum_bwd": lambda: train.tsum_bwd(grad_fu.permute(0, 2, 3, 1)[..., :256], parts["g_sum"], m.time_dims),
-             "refresh4": refresh4}
+             "refresh4": refresh4, "refresh4_device": lambda: refresh4(True)}
     for k, fn in cases.items():
         res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
     alt = {"step3": [], "step4": []}                         # the two steps alternated in the same run
@@ -291,14 +297,14 @@ def ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats):
             train.recurrence_step(m, x, cb, None, y_gaze, decoder=True, fuse=True, **kw)
         return run
 
-    def refresh5():
+    def refresh5(device=False):
         with torch.no_grad():
             for q in trained:
                 q.mul_(1.0)
-        m.refresh_weights(*boxes)
+        m.refresh_weights(*boxes, device=device)
     cases = {"prior_path_frozen": lambda: train.fust_output_grad(m, fu, cb192, grad_fu, cache=cache),
              "prior_path_trained": lambda: train.prior_path_backward(m, fu, cb192, grad_fu, cache=cache, grads=grads),
-             "refresh5": refresh5}
+             "refresh5": refresh5, "refresh5_device": lambda: refresh5(True)}
     shapes = {}
     for name, blk in blocks.items():
         key = {"fucb_layer.0": "fucb", "cxt_cb_prior.1": "ctx1", "cxt_cb_prior.0": "ctx0"}[name]
@@ -369,12 +375,13 @@ def nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
                 train.prior_net_backward(net, c, go, cache=cache)
         return run
 
-    def refresh6():
+    def refresh6(device=False):
         with torch.no_grad():
             for q in trained:
                 q.mul_(1.0)
-        m.refresh_weights(*boxes)
+        m.refresh_weights(*boxes, device=device)
     cases = {"nets_backward": backward(True), "nets_backward_frames": backward(False), "refresh6": refresh6,
+             "refresh6_device": lambda: refresh6(True),
              "frame_sum": lambda: train.frame_sum(g_cb[..., :64])}
     for i, (name, net) in enumerate(nets.items()):
         key = name.split("_")[0] + "0"
@@ -405,9 +412,65 @@ def nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
         q.grad = None
 
 
-def bench(T, iters, repeats, dev, skip_eager):
+def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
+    """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
+    from iip_uavsal_saliency_amd import repack
+    nets = tuple(train.prior_nets(m).values())
+    sets = {1: (m.rnn,), 4: (m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer)}
+    sets[5] = sets[4] + (m.fucb_layer, m.cxt_cb_prior)
+    sets[6] = sets[5] + nets
+    trained = [q for mod in sets[6] for q in mod.parameters()]
+    kw = dict(decoder=True, fuse=True, fust=True, ctx=True, nets=True)
+    for q in trained:
+        q.grad = None
+    train.recurrence_step(m, x, cb, None, y_gaze, **kw)           # the store holds every packed form a six-stage step reads
+
+    def refresher(boxes, device):
+        mine = [q for mod in boxes for q in mod.parameters()]
+
+        def run():
+            with torch.no_grad():
+                for q in mine:
+                    q.mul_(1.0)
+            m.refresh_weights(*boxes, device=device)
+        return run
+    opt = torch.optim.Adam(trained, lr=1e-4, betas=(0.9, 0.999), weight_decay=5e-5)
+
+    def iteration(device):
+        def run():
+            opt.zero_grad()
+            train.recurrence_step(m, x, cb, None, y_gaze, **kw)
+            opt.step()
+            m.refresh_weights(*sets[6], device=device)
+        return run
+    runs = {}
+    for n, boxes in sets.items():
+        runs["refresh%d_alt" % n], runs["refresh%d_device_alt" % n] = refresher(boxes, False), refresher(boxes, True)
+    runs["iter6"], runs["iter6_device"] = iteration(False), iteration(True)
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # every pair alternated in the same run, every run listed
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    store = m._wshared[str(x.device)]
+    for n, boxes in sets.items():                             # what one device refresh is: launches, entries, bytes written
+        rec = store[(repack.TABLE_KIND, tuple(sorted(id(s) for b in boxes for s in b.modules())))]
+        res["refresh%d_device_launches" % n] = 1 if rec.table is not None else 0
+        res["refresh%d_device_entries" % n], res["refresh%d_device_blocks" % n] = rec.n_entries, rec.blocks
+        res["refresh%d_device_bytes" % n], res["refresh%d_keys" % n] = rec.bytes_written, rec.count
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)       # the launch alone, back to back: the kernel's own time
+        res["refresh%d_device_kernel_ms" % n] = 1e3 * best_of(lambda rec=rec: L.check(L.load().uavsal_repack(
+            C.c_void_p(rec.table.data_ptr()), rec.n_entries, rec.blocks, stream), "uavsal_repack"), 4 * iters, repeats)
+    for q in trained:
+        q.grad = None
+
+
+def bench(T, iters, repeats, dev, skip_eager, refresh_only=False):
     H, W, h, w = 360, 640, 45, 80
-    m = UAVSal(time_dims=5)
+    m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
     m = m.to(dev).eval()
     x = torch.from_numpy(synth.normalize_frames(synth.synth_frames_u8(T, H, W, 3))).to(dev)
@@ -421,6 +484,10 @@ def bench(T, iters, repeats, dev, skip_eager):
     cache = WeightCache(torch.device(dev), m._wshared.setdefault(str(torch.device(dev)), {}))
     taps = {train.fuse_block(m)[1]: None}                    # the fusion block's input is read back on request
     out, _ = m(x, cb, None, taps=taps)
+    if refresh_only:
+        res = {"T": T}
+        refresh_phases(res, m, x, cb, y_gaze, iters, repeats)
+        return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
     pred = out.detach().requires_grad_(True)
@@ -433,10 +500,10 @@ def bench(T, iters, repeats, dev, skip_eager):
     h0n = torch.zeros((1, h, w, 256), device=dev)
     gw = torch.empty_like(rc.weight)
 
-    def refresh():
+    def refresh(device=False):
         with torch.no_grad():
             rc.weight.mul_(1.0)
-        m.refresh_weights(m.rnn)
+        m.refresh_weights(m.rnn, device=device)
 
     def step():
         rc.weight.grad = None
@@ -469,24 +536,24 @@ def bench(T, iters, repeats, dev, skip_eager):
             q.grad = None
         train.recurrence_step(m, x, cb, None, y_gaze, decoder=True)
 
-    def refresh_dec():
+    def refresh_dec(device=False):
         with torch.no_grad():
             rc.weight.mul_(1.0)
             for q in blk.parameters():
                 q.mul_(1.0)
-        m.refresh_weights(m.rnn, blk)
+        m.refresh_weights(m.rnn, blk, device=device)
     res = {"T": T}
     cases = {"forward": lambda: m(x, cb, None, taps={}),
              "dec_grad": lambda: train.decoder_input_grad(m.conv_out_st, h_seq, g_y, cache=cache, y=out),
              "twa_backward": lambda: train.twa_backward(x_seq, h_seq, None, rc.weight.detach(), grad_h, out=gw, cache=cache, module=rc),
              "wgrad": lambda: train.twa_wgrad(dz, xn, hn, h0n, out=gw),
-             "step": step, "refresh": refresh,
+             "step": step, "refresh": refresh, "refresh_device": lambda: refresh(True),
              "dec_bwd_grad": lambda: train.decoder_backward(blk, h_seq, g_y, cache=cache, y=out, grads=dgrads),
              "dec_bwd_kernel": lambda: train.dec_bwd(g_y, y_, e_, d_, s1, w9, s2, w3, s3),
              "pix_gemm": lambda: train.pix_gemm(ga_, hn, out=g1, row_scale=s1, w=pw.weight.detach(), rowdot=rowdot),
              "dec_sums": lambda: train.dec_sums(g_y, y_, e_, d_, ga_, w3, s3),
              "dec_finish": lambda: L.check(lib.uavsal_dec_finish(C.byref(fin), stream), "uavsal_dec_finish"),
-             "refresh_dec": refresh_dec}
+             "refresh_dec": refresh_dec, "refresh_dec_device": lambda: refresh_dec(True)}
     for k, fn in cases.items():
         res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
     alt = {"step": [], "step_dec": []}                       # the two steps alternated in the same run
@@ -518,6 +585,7 @@ def bench(T, iters, repeats, dev, skip_eager):
     fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+    refresh_phases(res, m, x, cb, y_gaze, iters, repeats)
     if not skip_eager:
         try:
             run = eager_step(m, taps["prefuse"], torch.zeros((1, 256, h, w), device=dev), g_y)
@@ -535,9 +603,12 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--skip-eager", action="store_true")
+    ap.add_argument("--refresh-only", action="store_true", help="only the refresh / iteration pairs (refresh_phases)")
+    ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
-    out = {"device": torch.cuda.get_device_name(0), "map": [45, 80], "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager) for T in (20, 5)]}
+    out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
+           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only) for T in a.frames]}
     print(json.dumps(out))
 
 
