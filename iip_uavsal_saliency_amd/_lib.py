@@ -430,6 +430,10 @@ SYMBOLS = [
     ("uavsal_plan_add_fused_ir", C.c_int, [C.c_void_p, C.POINTER(FusedIrDesc)]),
     ("uavsal_wino_input", C.c_int, [C.POINTER(WinoDesc), C.c_void_p]),
     ("uavsal_wino_output", C.c_int, [C.POINTER(WinoDesc), C.c_void_p]),
+    ("uavsal_wino_output_zero_h", C.c_int, [C.POINTER(WinoDesc), C.c_void_p]),
+    ("uavsal_wino_seam", C.c_int, [C.POINTER(WinoDesc), C.POINTER(WinoDesc), C.c_void_p]),
+    ("uavsal_wino_seam_zero_h", C.c_int, [C.POINTER(WinoDesc), C.POINTER(WinoDesc), C.c_void_p]),
+    ("uavsal_wino_seam_check", C.c_int, [C.POINTER(WinoDesc), C.POINTER(WinoDesc)]),
     ("uavsal_plan_add_wino_input", C.c_int, [C.c_void_p, C.POINTER(WinoDesc)]),
     ("uavsal_plan_add_wino_output", C.c_int, [C.c_void_p, C.POINTER(WinoDesc)]),
     ("uavsal_plan_add_copy", C.c_int, [C.c_void_p, C.POINTER(CopyDesc)]),
@@ -459,6 +463,9 @@ SYMBOLS = [
     ("uavsal_plan_last_launches", C.c_int, [C.c_void_p]),
     ("uavsal_plan_frame_repeat", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("uavsal_plan_frame_repeat_workgroups", C.c_int, [C.c_void_p, C.c_int]),
+    ("uavsal_plan_seam", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("uavsal_plan_zero_state", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("uavsal_plan_mode_report", C.c_int, [C.c_void_p, C.POINTER(C.c_int * 4)]),
     ("uavsal_plan_graph_build", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_graph_launch", C.c_int, [C.c_void_p, C.c_void_p]),
     ("uavsal_plan_time", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),

@@ -84,6 +84,13 @@ struct uavsal_plan {
     int fr_pw = -1, fr_dw = -1, fr_mod = 0, fr_div = 0;
     bool fr_on = false;
     int fr_wg[2] = {0, 0};
+    // recurrence modes (uavsal_plan_seam / uavsal_plan_zero_state): seam_next[i] = i + 1 when op i is the output transform of a
+    // registered, switched-on pair (else absent / -1); the ops of the zero initial state and whether the next runs apply it;
+    // what the most recent run did (uavsal_plan_mode_report)
+    std::vector<int> seam_next;
+    int zs_first = -1, zs_last = -1, zs_xin = -1, zs_gemm = -1, zs_xout = -1;
+    bool zs_on = false;
+    int mode_seams = 0, mode_elided = 0, mode_kernels = 0;
 };
 
 extern "C" uavsal_plan* uavsal_plan_create(void) { return new (std::nothrow) uavsal_plan(); }
@@ -278,6 +285,21 @@ static int run_range(uavsal_plan* p, int first, int last, uavsal_stream_t stream
         fr = cs == hipStreamCaptureStatusNone && !(a.group >= 0 && ((goff >> a.group) & 1u)) && !(b.group >= 0 && ((goff >> b.group) & 1u)) &&
              uavsal_conv_repeat_pair(&a.u.conv, &b.u.conv, p->fr_mod, p->fr_div) == 1;
     }
+    // recurrence modes: runs of the plan proper outside a capture, where the range holds every op concerned (a seam: both
+    // transforms; the zero state: the state layouts, if the plan has any, and the three ops of step 0) and no group switch
+    // leaves one of them out
+    bool modes = repeat && (p->zs_on || !p->seam_next.empty());
+    if (modes) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+        modes = cs == hipStreamCaptureStatusNone;
+    }
+    const uint32_t moff = masked ? p->groups_off : 0u;
+    auto masked_out = [&](int i) { return p->ops[i].group >= 0 && ((moff >> p->ops[i].group) & 1u); };
+    bool zs = modes && p->zs_on && p->zs_xin >= first && p->zs_xout < last && (p->zs_first < 0 || (p->zs_first >= first && p->zs_last < last)) &&
+              !masked_out(p->zs_xin) && !masked_out(p->zs_gemm) && !masked_out(p->zs_xout);
+    for (int i = p->zs_first; zs && i >= 0 && i <= p->zs_last; ++i) zs = !masked_out(i);
+    if (repeat && first == 0) p->mode_seams = p->mode_elided = p->mode_kernels = 0;
     // lanes are honoured only when the whole plan runs; a sub-range (per-op timing) is launched flat
     const bool lanes = p->lanes_on && first == 0 && last == n;
     const uint32_t off = masked ? p->groups_off : 0u;
@@ -303,12 +325,31 @@ static int run_range(uavsal_plan* p, int first, int last, uavsal_stream_t stream
         uavsal_stream_t s = (lanes && op.lane > 0) ? (uavsal_stream_t)p->side[op.lane] : stream;
         if (lanes && op.lane > 0 && !p->side[op.lane]) return UAVSAL_ESTATE;    // op on a lane that was never forked
         int e;
+        if (zs && ((p->zs_first >= 0 && i >= p->zs_first && i <= p->zs_last) || i == p->zs_xin || i == p->zs_gemm)) {
+            ++p->mode_elided;                // (an elided op still counts as launched: last_launches does not move with the modes)
+            ++*launched;
+            continue;
+        }
+        const bool seam = modes && i < (int)p->seam_next.size() && p->seam_next[i] == i + 1 && i + 1 < last && !masked_out(i + 1) &&
+                          p->ops[i + 1].lane == op.lane;
+        if (seam) {
+            const bool zh = zs && i == p->zs_xout;
+            e = zh ? uavsal_wino_seam_zero_h(&op.u.wino, &p->ops[i + 1].u.wino, s) : uavsal_wino_seam(&op.u.wino, &p->ops[i + 1].u.wino, s);
+            if (e) return e;
+            ++p->mode_seams; ++p->mode_kernels;
+            *launched += 2;
+            ++i;                             // the input transform went with it
+            continue;
+        }
         if (repeat && (i == p->fr_pw || i == p->fr_dw))
             e = uavsal_conv_gemm_mapped(&op.u.conv, s, fr ? p->fr_mod : 0, fr ? p->fr_div : 0, &p->fr_wg[i == p->fr_dw]);
+        else if (zs && i == p->zs_xout)
+            e = uavsal_wino_output_zero_h(&op.u.wino, s);
         else
             e = run_op(op, s);
         if (e) return e;
         ++*launched;
+        if (repeat) ++p->mode_kernels;
     }
     if (last == n) {       // the run that ends the plan (its guard op) -- whole, or the second part of a run issued in two ranges
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -343,6 +384,49 @@ extern "C" int uavsal_plan_frame_repeat(uavsal_plan* p, int op_pw, int op_dwpl, 
     return p->fr_on ? 1 : 0;
 }
 
+// Recurrence modes (include/uavsal_hip.h).  A pair is accepted when the two ops are neighbours on one lane and the seam launch
+// takes their descriptors (uavsal_wino_seam_check); the descriptors are looked at again by every launch.
+extern "C" int uavsal_plan_seam(uavsal_plan* p, int op_xout, int op_xin, int on) {
+    const int n = p ? (int)p->ops.size() : 0;
+    if (!p || op_xout < 0 || op_xin < 0 || op_xout >= n || op_xin >= n) return UAVSAL_EINVAL;
+    if (p->ops[op_xout].kind != OP_WINO_OUT || p->ops[op_xin].kind != OP_WINO_IN) return UAVSAL_EINVAL;
+    if ((int)p->seam_next.size() < n) p->seam_next.resize(n, -1);
+    p->seam_next[op_xout] = -1;
+    if (!on || p->exec || op_xin != op_xout + 1 || p->ops[op_xin].lane != p->ops[op_xout].lane ||
+        uavsal_wino_seam_check(&p->ops[op_xout].u.wino, &p->ops[op_xin].u.wino) != 0)
+        return 0;
+    p->seam_next[op_xout] = op_xin;
+    return 1;
+}
+
+extern "C" int uavsal_plan_zero_state(uavsal_plan* p, int op_state_in_first, int op_state_in_last, int op_xin0, int op_gemm0,
+                                      int op_xout0, int on) {
+    const int n = p ? (int)p->ops.size() : 0;
+    if (!p || op_xin0 < 0 || op_gemm0 != op_xin0 + 1 || op_xout0 != op_gemm0 + 1 || op_xout0 >= n) return UAVSAL_EINVAL;
+    if ((op_state_in_first < 0) != (op_state_in_last < 0) || op_state_in_last < op_state_in_first || op_state_in_last >= op_xin0)
+        return UAVSAL_EINVAL;
+    const Op& xi = p->ops[op_xin0];
+    const Op& g = p->ops[op_gemm0];
+    const Op& xo = p->ops[op_xout0];
+    if (xi.kind != OP_WINO_IN || g.kind != OP_CONV || xo.kind != OP_WINO_OUT) return UAVSAL_EINVAL;
+    for (int i = op_state_in_first; i >= 0 && i <= op_state_in_last; ++i)
+        if (p->ops[i].kind != OP_LAYOUT) return UAVSAL_EINVAL;
+    p->zs_first = op_state_in_first; p->zs_last = op_state_in_last;
+    p->zs_xin = op_xin0; p->zs_gemm = op_gemm0; p->zs_xout = op_xout0;
+    // the three ops are one F(2x2) ConvTWA step: the input transform feeds the GEMM, the GEMM the output transform, and the
+    // state the input transform reads is the output transform's h_{t-1}
+    p->zs_on = on != 0 && !p->exec && xi.u.wino.R == 2 && xo.u.wino.R == 2 && xo.u.wino.epi == UAVSAL_EPI_TWA &&
+               xi.u.wino.n_seg == 0 && xi.u.wino.in == xo.u.wino.hprev && g.u.conv.a == xi.u.wino.out && g.u.conv.out == xo.u.wino.in &&
+               xi.lane == xo.lane && g.lane == xo.lane;
+    return p->zs_on ? 1 : 0;
+}
+
+extern "C" int uavsal_plan_mode_report(const uavsal_plan* p, int out[4]) {
+    if (!p || !out) return UAVSAL_EINVAL;
+    out[0] = p->mode_seams; out[1] = p->mode_elided; out[2] = p->mode_kernels; out[3] = 0;
+    return 0;
+}
+
 // workgroups that the pair's kernel (which = 0: the expand, 1: the depthwise-projection) started in the most recent
 // uavsal_plan_run that launched it, armed or not; 0 before any
 extern "C" int uavsal_plan_frame_repeat_workgroups(const uavsal_plan* p, int which) {
@@ -353,6 +437,8 @@ extern "C" int uavsal_plan_graph_build(uavsal_plan* p, uavsal_stream_t stream) {
     if (!p) return UAVSAL_EINVAL;
     if (p->exec) return 0;
     p->fr_on = false;          // (a captured graph holds the full launches)
+    p->zs_on = false;
+    p->seam_next.clear();
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) return (int)e;

@@ -13,6 +13,7 @@
 //
 //   uavsal_wino_input : NHWC activation -> V[P*P][Mp][C],  V_k[tile][c] = (B^T d B)_k        one thread = (tile, 4 channels)
 //   uavsal_wino_output: M[P*P][Mp][C]   -> NHWC output,    y = A^T m A, then BN / ReLU6 / residual or the ConvTWA update
+//   uavsal_wino_seam  : the output transform of one F(2x2) ConvTWA step and the input transform of the next as one launch
 // uavsal_wino_desc.R = 2: 2x2 output tiles, P = 4, sixteen planes, 2.25x fewer multiplications than direct convolution;
 // R = 4: 4x4 output tiles, P = 6, thirty-six planes, 4x fewer (interpolation points 0, +-1, +-2: coefficients up to 8, a
 // single conv is ~20x less accurate than direct fp32 -- 2e-5 against 1e-6 at K = 576 -- the saliency map moves by 5.3e-5).
@@ -166,19 +167,10 @@ __device__ __forceinline__ f32x4 sigmoid4(f32x4 z) {
     return g;
 }
 
+// y = A^T m A of one (tile, channel quad): `mi` = the quad in plane 0, planes `plane` floats apart
 template <int R>
-__global__ __launch_bounds__(256) void wino_output_kernel(const WinoK p) {
+__device__ __forceinline__ void wino_tile_out(const float* mi, size_t plane, f32x4 (&y)[R][R]) {
     constexpr int P = WinoT<R>::P;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= p.total) return;
-    const int c4 = (int)(idx % p.C4);
-    const long long tile = idx / p.C4;
-    const int tpi = p.ty * p.tx;
-    const int n = (int)(tile / tpi);
-    const int r = (int)(tile - (long long)n * tpi);
-    const int tyi = r / p.tx, txi = r - tyi * p.tx;
-    const float* mi = p.in + (size_t)tile * p.ldi + c4 * 4;
-    const size_t plane = (size_t)p.Mp * p.ldi;
     f32x4 s[R][P];                                       // s = A^T m, built column by column
 #pragma unroll
     for (int j = 0; j < P; ++j) {
@@ -189,9 +181,41 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoK p) {
 #pragma unroll
         for (int a = 0; a < R; ++a) s[a][j] = sc_[a];
     }
-    f32x4 y[R][R];
 #pragma unroll
     for (int a = 0; a < R; ++a) WinoT<R>::at(s[a], y[a]);
+}
+
+// the ConvTWA update of one pixel quad: gate = sigmoid(conv(h) + W_x x_t); h_t = gate x_t + (1 - gate) h_{t-1}.  One function
+// for every kernel that computes it, with the roundings spelled out (one product rounded, the other fused into the sum), so
+// that the output transform, its zero-h form and the seam kernel give the same bits whatever the compiler would contract
+__device__ __forceinline__ f32x4 twa_gate(f32x4 v, f32x4 pre, f32x4 xt, f32x4 hp) {
+    const f32x4 g = sigmoid4(v + pre);
+    f32x4 h;
+    h.x = fmaf(g.x, xt.x, __fmul_rn(1.f - g.x, hp.x)); h.y = fmaf(g.y, xt.y, __fmul_rn(1.f - g.y, hp.y));
+    h.z = fmaf(g.z, xt.z, __fmul_rn(1.f - g.z, hp.z)); h.w = fmaf(g.w, xt.w, __fmul_rn(1.f - g.w, hp.w));
+    return h;
+}
+
+// ZH ("zero h", EPI_TWA only): h_{t-1} is all +0, so V, M and y are +0 -- neither the M planes nor `hprev` are loaded
+template <int R, bool ZH>
+__global__ __launch_bounds__(256) void wino_output_kernel(const WinoK p) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.total) return;
+    const int c4 = (int)(idx % p.C4);
+    const long long tile = idx / p.C4;
+    const int tpi = p.ty * p.tx;
+    const int n = (int)(tile / tpi);
+    const int r = (int)(tile - (long long)n * tpi);
+    const int tyi = r / p.tx, txi = r - tyi * p.tx;
+    f32x4 y[R][R];
+    if (ZH) {
+#pragma unroll
+        for (int a = 0; a < R; ++a)
+#pragma unroll
+            for (int b = 0; b < R; ++b) y[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    } else {
+        wino_tile_out<R>(p.in + (size_t)tile * p.ldi + c4 * 4, (size_t)p.Mp * p.ldi, y);
+    }
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
     if (p.scale) {
         sc = *reinterpret_cast<const f32x4*>(p.scale + c4 * 4);
@@ -206,12 +230,12 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoK p) {
             if (yy >= p.H || xx >= p.W) continue;
             const size_t pix = (size_t)yy * p.W + xx;
             f32x4 v = y[a][b];
-            if (p.epi == UAVSAL_EPI_TWA) {      // gate = sigmoid(conv(h) + W_x x_t); h_t = gate x_t + (1 - gate) h_{t-1}
-                const f32x4 z = v + *reinterpret_cast<const f32x4*>(p.aux + ((size_t)n * p.aux_is + pix) * p.ldx + c4 * 4);
+            if (ZH || p.epi == UAVSAL_EPI_TWA) {
+                const f32x4 pre = *reinterpret_cast<const f32x4*>(p.aux + ((size_t)n * p.aux_is + pix) * p.ldx + c4 * 4);
                 const f32x4 xt = *reinterpret_cast<const f32x4*>(p.res + ((size_t)n * p.res_is + pix) * p.ldr + c4 * 4);
-                const f32x4 hp = *reinterpret_cast<const f32x4*>(p.hprev + ((size_t)n * p.h_is + pix) * p.ldh + c4 * 4);
-                const f32x4 g = sigmoid4(z);
-                v = g * xt + (1.f - g) * hp;
+                const f32x4 hp = ZH ? (f32x4){0.f, 0.f, 0.f, 0.f}
+                                    : *reinterpret_cast<const f32x4*>(p.hprev + ((size_t)n * p.h_is + pix) * p.ldh + c4 * 4);
+                v = twa_gate(v, pre, xt, hp);
             } else {
                 v.x = __builtin_amdgcn_fmed3f(fmaf(v.x, sc.x, bi.x), lo, hi); v.y = __builtin_amdgcn_fmed3f(fmaf(v.y, sc.y, bi.y), lo, hi);
                 v.z = __builtin_amdgcn_fmed3f(fmaf(v.z, sc.z, bi.z), lo, hi); v.w = __builtin_amdgcn_fmed3f(fmaf(v.w, sc.w, bi.w), lo, hi);
@@ -219,6 +243,102 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoK p) {
             }
             *reinterpret_cast<f32x4*>(p.out + ((size_t)n * p.out_is + pix) * p.ldo + c4 * 4) = v;
         }
+}
+
+// Seam of the F(2x2) ConvTWA recurrence (uavsal_wino_seam): the output transform of step t (EPI_TWA, writes h_t into the history)
+// and the input transform of step t + 1 (reads h_t back, writes the V planes) as ONE launch, so h_t never makes the round trip
+// between two dependent launches.  A workgroup owns an 8x8-pixel block of one image and a slab of up to 16 channel quads:
+//   1. one thread per (tile, quad) computes h_t on the 6x6 output tiles that cover the block plus its one-pixel ring (the
+//      ring's h_t is computed again by the neighbours that own it: the same code on the same inputs, so the same bits) -- 576
+//      threads, so that every load of the launch is in flight at once --, stores its own 4x4 tiles' pixels to the history
+//      -- every element has one writer -- and keeps the 10x10 pixels in LDS, zeros outside the image;
+//   2. after one barrier the first 256 threads transform one (input tile, quad) each of the block's 4x4 input tiles from LDS.
+// Nothing a workgroup reads is written by another one in the same launch.  ZH: the zero-h form of step t (wino_output_kernel).
+struct SeamK {
+    WinoK o;                 // the output transform of step t
+    float* v;                // V planes of step t + 1: [16][Mp][ldv]
+    int ldv;
+    int bx, by, slabs;       // blocks per image row / column, channel slabs
+};
+// 4x4 tiles (8x8 pixels) and 16 quads: 6 x 10 blocks x 4 slabs = 240 workgroups on the 45x80 map of the one-clip step.  Measured
+// there against 4x8 tiles x 8 quads (same step time) and 8x8 tiles x 4 quads (slower): profiles/recurrence_seams.md
+constexpr int SEAM_TY = 4, SEAM_TX = 4;                    // 2x2 tiles of a block
+constexpr int SEAM_Q = 16;                                 // channel quads per slab
+constexpr int SEAM_PY = 2 * SEAM_TY + 2, SEAM_PX = 2 * SEAM_TX + 2;                         // pixels of a block with its ring
+constexpr int SEAM_NT = ((SEAM_TY + 2) * (SEAM_TX + 2) * SEAM_Q + 63) / 64 * 64;        // one thread per (tile with ring, quad)
+static_assert(SEAM_NT <= 1024 && SEAM_PY * SEAM_PX * SEAM_Q * 16 <= 65536, "seam block");
+
+template <bool ZH>
+__global__ __launch_bounds__(SEAM_NT) void wino_seam_kernel(const SeamK k) {
+    __shared__ f32x4 hs[SEAM_PY * SEAM_PX * SEAM_Q];    // [pixel][quad]
+    const WinoK& p = k.o;
+    int b = blockIdx.x;
+    const int slab = b % k.slabs; b /= k.slabs;
+    const int bxi = b % k.bx; b /= k.bx;
+    const int byi = b % k.by;
+    const int n = b / k.by;
+    const int q0 = slab * SEAM_Q;
+    const int S = min(SEAM_Q, p.C4 - q0);               // quads of this slab
+    const size_t mplane = (size_t)p.Mp * p.ldi;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int it = threadIdx.x; it < (SEAM_TY + 2) * (SEAM_TX + 2) * S; it += SEAM_NT) {
+        const int q = it % S, lt = it / S;
+        const int lty = lt / (SEAM_TX + 2), ltx = lt - lty * (SEAM_TX + 2);
+        const int tyi = SEAM_TY * byi - 1 + lty, txi = SEAM_TX * bxi - 1 + ltx;
+        const bool real = tyi >= 0 && tyi < p.ty && txi >= 0 && txi < p.tx;
+        const int c4 = q0 + q;
+        f32x4 y[2][2] = {{zero, zero}, {zero, zero}};
+        if (real && !ZH) {
+            const size_t tile = ((size_t)n * p.ty + tyi) * p.tx + txi;
+            wino_tile_out<2>(p.in + tile * p.ldi + c4 * 4, mplane, y);
+        }
+        const bool own = lty >= 1 && lty <= SEAM_TY && ltx >= 1 && ltx <= SEAM_TX;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int ly = 2 * lty + a - 1, lx = 2 * ltx + c - 1;       // in the window (pixel 0 = the block's first - 1)
+                if (ly < 0 || ly >= SEAM_PY || lx < 0 || lx >= SEAM_PX) continue;
+                const int yy = 2 * tyi + a, xx = 2 * txi + c;
+                f32x4 h = zero;
+                if (real && yy < p.H && xx < p.W) {
+                    const size_t pix = (size_t)yy * p.W + xx;
+                    const f32x4 pre = *reinterpret_cast<const f32x4*>(p.aux + ((size_t)n * p.aux_is + pix) * p.ldx + c4 * 4);
+                    const f32x4 xt = *reinterpret_cast<const f32x4*>(p.res + ((size_t)n * p.res_is + pix) * p.ldr + c4 * 4);
+                    const f32x4 hp = ZH ? zero : *reinterpret_cast<const f32x4*>(p.hprev + ((size_t)n * p.h_is + pix) * p.ldh + c4 * 4);
+                    h = twa_gate(y[a][c], pre, xt, hp);
+                    if (own) *reinterpret_cast<f32x4*>(p.out + ((size_t)n * p.out_is + pix) * p.ldo + c4 * 4) = h;
+                }
+                hs[(ly * SEAM_PX + lx) * SEAM_Q + q] = h;
+            }
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < SEAM_TY * SEAM_TX * S; it += SEAM_NT) {
+        const int q = it % S, lt = it / S;
+        const int ity = lt / SEAM_TX, itx = lt - ity * SEAM_TX;
+        const int tyi = SEAM_TY * byi + ity, txi = SEAM_TX * bxi + itx;
+        if (tyi >= p.ty || txi >= p.tx) continue;
+        f32x4 t[4][4];                                   // as wino_input_kernel: B^T d column by column, then (.) B row by row
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f32x4 col[4], tc[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) col[i] = hs[((2 * ity + i) * SEAM_PX + 2 * itx + j) * SEAM_Q + q];
+            WinoT<2>::bt(col, tc);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t[i][j] = tc[i];
+        }
+        const size_t tile = ((size_t)n * p.ty + tyi) * p.tx + txi;
+        float* o = k.v + tile * k.ldv + (q0 + q) * 4;
+        const size_t plane = (size_t)p.Mp * k.ldv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f32x4 v[4];
+            WinoT<2>::bt(t[i], v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(o + (size_t)(4 * i + j) * plane) = v[j];
+        }
+    }
 }
 
 int fill(const uavsal_wino_desc* d, WinoK& k, bool input) {
@@ -299,7 +419,56 @@ extern "C" int uavsal_wino_output(const uavsal_wino_desc* d, uavsal_stream_t str
     WinoK k;
     const int e = fill(d, k, false);
     if (e) return e;
-    if (d->R == 4) hipLaunchKernelGGL(wino_output_kernel<4>, dim3((unsigned)((k.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
-    else hipLaunchKernelGGL(wino_output_kernel<2>, dim3((unsigned)((k.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+    if (d->R == 4) hipLaunchKernelGGL((wino_output_kernel<4, false>), dim3((unsigned)((k.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL((wino_output_kernel<2, false>), dim3((unsigned)((k.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
     return uavsal_launch_status();
+}
+
+extern "C" int uavsal_wino_output_zero_h(const uavsal_wino_desc* d, uavsal_stream_t stream) {
+    WinoK k;
+    const int e = fill(d, k, false);
+    if (e) return e;
+    if (d->R != 2 || d->epi != UAVSAL_EPI_TWA) return UAVSAL_ESHAPE;
+    hipLaunchKernelGGL((wino_output_kernel<2, true>), dim3((unsigned)((k.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+    return uavsal_launch_status();
+}
+
+// 0 and `s` filled when `xout` / `xin` are the output transform of an F(2x2) ConvTWA step and the input transform of the next
+static int fill_seam(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin, SeamK& s) {
+    WinoK ki;
+    int e = fill(xout, s.o, false);
+    if (!e) e = fill(xin, ki, true);
+    if (e) return e;
+    if (xout->R != 2 || xin->R != 2 || xout->epi != UAVSAL_EPI_TWA || xout->scale || xout->act != UAVSAL_ACT_NONE || ki.nseg)
+        return UAVSAL_ESHAPE;
+    if (xin->in != xout->out || ki.in_is != s.o.out_is || ki.ldi != s.o.ldo || ki.n_img != s.o.n_img || ki.H != s.o.H ||
+        ki.W != s.o.W || ki.C4 != s.o.C4 || ki.Mp != s.o.Mp)
+        return UAVSAL_ESHAPE;
+    s.v = ki.out; s.ldv = ki.ldo;
+    s.by = (s.o.ty + SEAM_TY - 1) / SEAM_TY; s.bx = (s.o.tx + SEAM_TX - 1) / SEAM_TX; s.slabs = (s.o.C4 + SEAM_Q - 1) / SEAM_Q;
+    if ((long long)s.o.n_img * s.by * s.bx * s.slabs > 0x7fffffffLL) return UAVSAL_ESHAPE;
+    return 0;
+}
+
+extern "C" int uavsal_wino_seam_check(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin) {
+    SeamK s;
+    return fill_seam(xout, xin, s);
+}
+
+static int launch_seam(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin, uavsal_stream_t stream, bool zero_h) {
+    SeamK s;
+    const int e = fill_seam(xout, xin, s);
+    if (e) return e;
+    const dim3 grid((unsigned)(s.o.n_img * s.by * s.bx * s.slabs));
+    if (zero_h) hipLaunchKernelGGL(wino_seam_kernel<true>, grid, dim3(SEAM_NT), 0, (hipStream_t)stream, s);
+    else hipLaunchKernelGGL(wino_seam_kernel<false>, grid, dim3(SEAM_NT), 0, (hipStream_t)stream, s);
+    return uavsal_launch_status();
+}
+
+extern "C" int uavsal_wino_seam(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin, uavsal_stream_t stream) {
+    return launch_seam(xout, xin, stream, false);
+}
+
+extern "C" int uavsal_wino_seam_zero_h(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin, uavsal_stream_t stream) {
+    return launch_seam(xout, xin, stream, true);
 }

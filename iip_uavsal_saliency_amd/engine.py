@@ -316,9 +316,121 @@ class Engine:
             self._fr = (pw, dwpl) + ((N // self.ctx_T, 1) if self.ctx_mode == "tile" else (N, self.ctx_T))
         self._fr_idx = None                  # source frame of every frame, on the device (built by the first miss)
         self.repeat_armed = False            # did the most recent run apply the mode?
+        self._plan_recurrence_modes()
         self.use_lanes = bool(use_lanes)
         L.check(self.lib.uavsal_plan_enable_lanes(self.plan, 1 if self.use_lanes else 0), "plan_enable_lanes")
         self._graph_ready = False
+
+    # ------------------------------------------------------------------ recurrence modes
+    @staticmethod
+    def _extent(v):
+        """(first byte, one past the last) of the whole buffer a view lies in; None for a buffer outside the arena and the
+        engine's own allocations (the caller's)."""
+        t = v.t
+        if isinstance(t, _ArenaRef):
+            lo = t.arena.buf.data_ptr() + 4 * t.off
+            return lo, lo + 4 * t.numel_
+        if isinstance(t, torch.Tensor):
+            return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+        return None
+
+    def seam_conflicts(self, prev, nxt):
+        """Names of the buffers the output transform of step `prev` reads or writes that the V planes of step `nxt` overlap
+        (Recorder.twa_steps entries): a seam launch writes those planes while it runs that transform, so any is a refusal."""
+        v = self._extent(nxt["v"])
+        bad = []
+        for k in ("m", "out", "a", "x", "pre"):
+            e = self._extent(prev[k])
+            if v is None or (e is not None and e[0] < v[1] and v[0] < e[1]):
+                bad.append(k)
+        return bad
+
+    def _plan_recurrence_modes(self):
+        """At plan build: which run-time modes of the native plan this plan can take.  `_seams`: the (xout of step t, xin of
+        step t + 1) op pairs of an F(2x2) ConvTWA recurrence that are neighbours in the plan (a debug plan has poison fills
+        between them) and whose V planes overlap nothing the output transform touches in the planned arena.  `_zs`: the ops
+        of a zero initial state (state layouts first / last or -1, step 0's xin / gemm / xout).  Launch-loop plans only, and
+        not the debug plans (`model.arena_debug`), which are there to run every recorded op; the pairs are handed to the
+        native plan in front of the first run (`_arm_modes`)."""
+        self._seams, self._zs = [], None
+        self._seams_on = None                # what the native plan was told last (None: nothing yet)
+        self._zs_rec = None                  # zero test of a caller's state tensor: dict(base, sig, zero = (event, pinned word) | bool)
+        self.zero_armed = False
+        steps = self.rec.twa_steps
+        if self.lstm or not self.inplace or self.arena_debug or not steps or any(s["r"] != 2 for s in steps):
+            return
+        for a, b in zip(steps, steps[1:]):
+            if b["xin"] == a["xout"] + 1 and not self.seam_conflicts(a, b):
+                self._seams.append((a["xout"], b["xin"]))
+        lay = [i for i, m in enumerate(self.ops_meta) if m.get("name") == "state.in"]
+        s0 = steps[0]
+        if s0["gemm"] == s0["xin"] + 1 and s0["xout"] == s0["gemm"] + 1:
+            self._zs = ((lay[0], lay[-1]) if lay else (-1, -1)) + (s0["xin"], s0["gemm"], s0["xout"])
+
+    def _state_is_zero(self, state) -> bool:
+        """Is the state this call binds known to be all +0 bits?  None is (the engine's own zeros, never written).  A caller's
+        tensor goes by object and version, like the prior cache: the first call with it starts a device-side test of its bit
+        pattern into a pinned host word behind an event and runs in full -- nobody waits; a later call with the same object
+        and version says yes once the event is over and the word says zero.  -0.0 is not zero here: (1 - g) * -0 has the
+        other sign."""
+        if state is None:
+            return True
+        try:
+            base = state._base if state._base is not None else state
+            sig = (state.data_ptr(), tuple(state.shape), tuple(state.stride()), state._version)
+        except RuntimeError:
+            return False
+        if state.dtype != torch.float32 or state.device != self.device:
+            return False
+        r = self._zs_rec
+        if r is not None and r["base"] is base and r["sig"] == sig:
+            if isinstance(r["zero"], tuple):
+                ev, word = r["zero"]
+                if not ev.query():
+                    return False
+                r["zero"] = bool(word[0])
+            return r["zero"]
+        src = state if state.is_contiguous() else state.contiguous()
+        ok = (src.view(torch.int32) == 0).all()
+        word = torch.zeros(1, dtype=torch.bool).pin_memory()
+        word.copy_(ok.reshape(1), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._zs_rec = dict(base=base, sig=sig, zero=(ev, word))
+        return False
+
+    def invalidate_zero_state(self):
+        """Forget what is known about the caller's state tensor: the next call with it runs in full and tests it again."""
+        self._zs_rec = None
+
+    def _arm_modes(self, zero):
+        """In front of a call's launches: hands the seam pairs to the native plan (when `model.fuse_seams`, default on, changes)
+        and switches the zero-state mode on for this run when `zero` (the state step 0 reads is all +0 bits) and
+        `model.skip_zero_state` (default on).  `_disarm_modes` follows the launches."""
+        self.zero_armed = False
+        want = bool(getattr(self.model, "fuse_seams", True))
+        if self._seams and want != self._seams_on:
+            for xo, xi in self._seams:
+                r = self.lib.uavsal_plan_seam(self.plan, xo, xi, 1 if want else 0)
+                if r < 0:
+                    L.check(r, "plan_seam")
+            self._seams_on = want
+        if zero and self._zs is not None and bool(getattr(self.model, "skip_zero_state", True)):
+            r = self.lib.uavsal_plan_zero_state(self.plan, *self._zs, 1)
+            if r < 0:
+                L.check(r, "plan_zero_state")
+            self.zero_armed = r == 1
+
+    def _disarm_modes(self):
+        """Behind a call's launches: whatever runs next on another state, or as ranges of its own, runs step 0 in full."""
+        if self.zero_armed:
+            self.lib.uavsal_plan_zero_state(self.plan, *self._zs, 0)
+
+    def mode_report(self):
+        """(seam pairs fused, ops left out by the zero state, launch calls issued) of the most recent run of the plan."""
+        out = (C.c_int * 4)()
+        L.check(self.lib.uavsal_plan_mode_report(self.plan, C.byref(out)), "plan_mode_report")
+        return int(out[0]), int(out[1]), int(out[2])
 
     def __del__(self):
         try:
@@ -429,12 +541,15 @@ class Engine:
         pairs = [(state, self.h_view, self.state_in, "h0")]
         if self.c_view is not None:
             pairs.append((cstate, self.c_view, self.cstate_in, "c0"))
+        self._resident_zero = False
         for t, view, stage, name in pairs:
             if self._is_resident(t, view):
                 continue
             buf = self.named[name]
             if t is None:
                 buf.t.zero_()
+                if name == "h0":
+                    self._resident_zero = True           # a reset: step 0 reads all-zero bits
                 continue
             stage.copy_(t.reshape(stage.shape))
             d = L.LayoutDesc()
@@ -505,11 +620,16 @@ class Engine:
             else:
                 self.stage_inputs(x, cb0, cb1, state, cstate)
             self._arm_repeat(skip)
+            modes = self.inplace and bool(self._seams or self._zs)      # (a plan without either: nothing to look at)
+            if modes:
+                self._arm_modes(self._resident_zero if self.persistent else self._state_is_zero(state))
             with self.priors.launches():
                 try:
                     self.launch()
                 finally:
                     self._disarm_repeat()
+                    if modes:
+                        self._disarm_modes()
             if self.sync_errors:
                 self.check(wait=True)
             if not self._first_run_verified and self.split_mode:
@@ -584,7 +704,11 @@ class Engine:
                         mine.zero_()
                     elif prev is not None and prev is not self:
                         mine.copy_(prev.named[name].t)
-                L.check(self.lib.uavsal_plan_run(self.plan, split, -1, self._stream()), "plan_run(tail)")
+                self._arm_modes(bool(reset))
+                try:
+                    L.check(self.lib.uavsal_plan_run(self.plan, split, -1, self._stream()), "plan_run(tail)")
+                finally:
+                    self._disarm_modes()
         return out
 
     def check(self, wait=True):

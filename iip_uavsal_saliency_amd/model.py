@@ -201,6 +201,13 @@ class UAVSal(nn.Module):
         # kernel through `data_ptr()`, `tensor.data`) are NOT seen: call `invalidate_priors()` after those.  False: every call
         # runs them.
         self.cache_priors = True
+        # Run-time modes of the F(2x2) ConvTWA recurrence of a launch-loop plan, both bit-identical to the
+        # recorded launches.  `fuse_seams`: the output transform of step t and the input transform of step t + 1 run as one
+        # launch.  `skip_zero_state`: a call whose initial state is all +0 bits -- None, or a caller's tensor that an earlier
+        # call with the same object and version tested on the device -- leaves the state layout, step 0's input transform and
+        # its GEMM out.  Writes behind torch's back (see `cache_priors`): `invalidate_state()`.
+        self.fuse_seams = True
+        self.skip_zero_state = True
         # Activations of a plan live in ONE arena per plan, placed by liveness (first / last use over the recorded launches; a
         # use on a side lane counts from the lane's fork to its join): memory per call follows the largest set of tensors that
         # is live at once, not the number of layers (720x1280, 4 x 16 frames: 14.7 GB instead of 42.6).  False: one allocation
@@ -341,6 +348,13 @@ class UAVSal(nn.Module):
         for m in [self] + list(self.__dict__.get("_stream_replicas") or []):
             for eng in list(m._engines.values()):
                 eng.drop_prior_record()
+
+    def invalidate_state(self):
+        """Forget what the plans know about the caller's initial state tensor (`skip_zero_state`): the next call with it runs
+        in full and tests it again."""
+        for m in [self] + list(self.__dict__.get("_stream_replicas") or []):
+            for eng in list(m._engines.values()):
+                eng.invalidate_zero_state()
 
     def _weights_version(self):
         return sum(t._version for t in self._wtensors)

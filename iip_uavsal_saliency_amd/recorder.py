@@ -87,6 +87,10 @@ class Recorder:
         self.prior_ops: List[int] = []          # ops of the prior group (lane PRIOR_LANE, its fork and its join)
         # bind table: (caller name, op index, ABI slot, byte offset) of every caller-side address in a descriptor
         self.binds: List[tuple] = []
+        # ConvTWA steps recorded as Winograd triples, in order: dict(name, r, xin / gemm / xout op indices, and the views the
+        # output transform touches: v, m, out, a = h_{t-1}, x, pre) -- what the engine's recurrence modes go by
+        self.twa_steps: List[dict] = []
+        self._twa_prev = None                   # (op index of the last twa step's output transform, the views it touched)
         if not dry:
             self.plan = C.c_void_p(self.lib.uavsal_plan_create())
             if not self.plan:
@@ -416,6 +420,11 @@ class Recorder:
         self._meta(kind="wino_in", name=name + ".xin", flops=0.0, bytes=4.0 * n * hw * cin + 4.0 * float(pp) * tiles * cin)
         self.op_args[-1].update(triple=name + ".xout")
         self.arena.touch(a, v)
+        if twa is not None and r == 2 and self._twa_prev is not None and self._twa_prev[0] == self.arena.lop - 1:
+            # a seam launch (uavsal_plan_seam) writes this step's V planes while it still runs the previous step's output
+            # transform: everything that op reads or writes stays live one op longer, so V is never placed on it
+            self.arena.touch(*self._twa_prev[1])
+        xin_op = len(self.ops_meta) - 1
         if not self.dry:
             wi = L.WinoDesc()
             wi.inp, wi.ldi, wi.in_img_stride = a.ptr, a.ld, st.get("a", hw)
@@ -441,6 +450,10 @@ class Recorder:
             self._add(self.lib.uavsal_plan_add_conv, d, "plan_add_conv(%s)" % name)
         self._meta(kind="wino_out", name=name + ".xout", flops=0.0, bytes=4.0 * (float(pp) * tiles * cout + n * hw * cout))
         self.arena.touch(mm, out, *(twa or ()), *((a,) if twa is not None else ()))
+        if twa is not None:
+            self._twa_prev = (self.arena.lop, (mm, out, twa[0], twa[1], a))
+            self.twa_steps.append(dict(name=name, r=r, xin=xin_op, gemm=len(self.ops_meta) - 2, xout=len(self.ops_meta) - 1,
+                                       v=v, m=mm, out=out, a=a, x=twa[0], pre=twa[1]))
         if out.key is not None and self.dry:
             self.no_shadow.add(out.key)            # the output transform does not write split shadows
         if not self.dry:

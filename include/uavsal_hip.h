@@ -387,6 +387,20 @@ typedef struct uavsal_wino_desc {
 
 int uavsal_wino_input(const uavsal_wino_desc* d, uavsal_stream_t stream);
 int uavsal_wino_output(const uavsal_wino_desc* d, uavsal_stream_t stream);
+/* The output transform of an F(2x2) ConvTWA step whose previous state is all +0 bits: M and y are then +0 as well, so neither
+ * the M planes nor `hprev` are loaded (both must still be named); bit-identical to uavsal_wino_output on such a state with
+ * finite weights.  UAVSAL_ESHAPE unless R = 2 and epi = UAVSAL_EPI_TWA. */
+int uavsal_wino_output_zero_h(const uavsal_wino_desc* d, uavsal_stream_t stream);
+/* Seam of the F(2x2) ConvTWA recurrence: uavsal_wino_output(xout) followed by uavsal_wino_input(xin) as ONE launch that writes
+ * exactly the bytes the two launches write, bit for bit -- h_t into `xout->out` and the V planes (rows of real tiles) into
+ * `xin->out` -- without reading h_t back.  Taken when `xout` is an EPI_TWA output transform without scale / bias / activation
+ * and `xin` the input transform of the next step: R = 2 in both, xin->in == xout->out with the same row stride, image stride,
+ * n_img, H, W, C and Mp, no segments.  Anything else is refused and nothing is launched: the status the transforms themselves
+ * give for a bad descriptor (UAVSAL_EINVAL, UAVSAL_EALIGN: C % 4 != 0, ...), else UAVSAL_ESHAPE (R = 4, an affine epilogue,
+ * two transforms that are not consecutive).  _check: the same answer without a launch.  _zero_h: step t in the zero-h form. */
+int uavsal_wino_seam(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin, uavsal_stream_t stream);
+int uavsal_wino_seam_zero_h(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin, uavsal_stream_t stream);
+int uavsal_wino_seam_check(const uavsal_wino_desc* xout, const uavsal_wino_desc* xin);
 
 /* Sum over groups of T consecutive images (model.py:357-358): out[b] = sum_t in[b*T+t]. */
 typedef struct uavsal_tsum_desc {
@@ -1160,6 +1174,26 @@ int uavsal_plan_last_launches(const uavsal_plan* p);
  * recent uavsal_plan_run that launched it, in full or not. */
 int uavsal_plan_frame_repeat(uavsal_plan* p, int op_pw, int op_dwpl, int src_mod, int src_div, int on);
 int uavsal_plan_frame_repeat_workgroups(const uavsal_plan* p, int which);
+/* Recurrence modes: run-time modes of the F(2x2) ConvTWA steps of a recorded plan, in the manner of frame repeat -- they apply
+ * to uavsal_plan_run outside a stream capture and only to a range that holds every op concerned; any other range, the per-op
+ * timer and a captured graph run the recorded ops in full.  Outputs are bit-identical either way.
+ * plan_seam: registers (on = 1) or drops (0) the pair `op_xout` (output transform of step t) / `op_xin` (input transform of
+ *   step t + 1); while registered, a run whose range holds both issues uavsal_wino_seam in their place.  Returns 1 when
+ *   registered, 0 when not (on == 0; another op between the two or different lanes; descriptors uavsal_wino_seam refuses; a
+ *   built graph), negative on bad arguments.  The caller answers for the memory: the V planes of step t + 1 must not overlap
+ *   anything op_xout reads or writes (the engine checks its arena before it registers a pair).
+ * plan_zero_state: names the layouts that stage the caller's initial state (ops op_state_in_first .. op_state_in_last,
+ *   inclusive; -1, -1: the plan has none, the state is resident) and the three ops of step 0, and switches the mode on / off
+ *   for the runs that follow.  While on -- the caller vouches that the state step 0 reads is all +0 bits -- a run whose range
+ *   holds them leaves the layouts, the input transform and the GEMM out and launches the output transform in the zero-h form
+ *   (uavsal_wino_output_zero_h, or the seam's).  Returns 1 / 0 as above (0 also for a step that is not F(2x2) ConvTWA).
+ *   Not covered: non-finite recurrent weights (0 * inf), which the full path turns into NaN.
+ * Neither mode moves uavsal_plan_last_launches: an op served by a seam launch or left out still counts.
+ * plan_mode_report: what the most recent run did -- out[0] seam pairs fused, out[1] ops left out by the zero state, out[2]
+ *   launch calls actually issued for plan ops (one per op that ran, one per fused pair), out[3] reserved (0). */
+int uavsal_plan_seam(uavsal_plan* p, int op_xout, int op_xin, int on);
+int uavsal_plan_zero_state(uavsal_plan* p, int op_state_in_first, int op_state_in_last, int op_xin0, int op_gemm0, int op_xout0, int on);
+int uavsal_plan_mode_report(const uavsal_plan* p, int out[4]);
 /* capture the whole plan into a hipGraph once, then replay it */
 int uavsal_plan_graph_build(uavsal_plan* p, uavsal_stream_t stream);
 int uavsal_plan_graph_launch(uavsal_plan* p, uavsal_stream_t stream);
