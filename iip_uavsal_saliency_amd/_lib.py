@@ -333,6 +333,25 @@ class FrameSumDesc(C.Structure):
 NARROW_CHUNK = 32             # UAVSAL_NARROW_CHUNK: pixels whose G1 / G3 products uavsal_ir_narrow_grads adds in fp32 (csrc/train_nets.hip)
 NETS_DESC_TYPES = [IrNarrowDesc, IrNarrowFinishDesc, FrameSumDesc]      # sized by uavsal_nets_sizeof_desc
 
+
+class CbrSumsDesc(C.Structure):
+    _fields_ = [("g", _f), ("ldg", C.c_int32), ("y", _f), ("ldy", C.c_int32), ("gp", _f),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
+
+
+class CbrFinishDesc(C.Structure):
+    _fields_ = [("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("rowdot", C.c_void_p), ("r", _f), ("mu", _f),
+                ("g_gamma", _f), ("g_beta", _f), ("C", C.c_int32), ("slabs", C.c_int32), ("accumulate", C.c_int32)]
+
+
+class TdiffBwdDesc(C.Structure):
+    _fields_ = [("g", _f), ("ldg", C.c_int32), ("r", _f), ("ldr", C.c_int32), ("out", _f), ("ldo", C.c_int32),
+                ("n_img", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("seq_len", C.c_int32)]
+
+
+ST_DESC_TYPES = [CbrSumsDesc, CbrFinishDesc, TdiffBwdDesc]      # sized by uavsal_st_sizeof_desc (csrc/train_st.hip)
+
 REPACK_MAX_SRC = 4            # UAVSAL_REPACK_MAX_SRC: weights / BatchNorms side by side in one entry (csrc/repack.hip)
 REPACK_CONV, REPACK_WINO, REPACK_FOLD, REPACK_DW, REPACK_COPY = range(5)
 REPACK_LAYOUT = {"f32": 0, "f32k32": 0, "f16x3": 1, "f16x3i": 2, "f16x3j": 3, "bf16": 4, "bf16x3": 5}
@@ -419,6 +438,13 @@ SYMBOLS = [
     ("uavsal_ir_narrow_finish", C.c_int, [C.POINTER(IrNarrowFinishDesc), C.c_void_p]),
     ("uavsal_frame_sum", C.c_int, [C.POINTER(FrameSumDesc), C.c_void_p]),
     ("uavsal_nets_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_cbr_sums_workspace_bytes", C.c_int64, [C.POINTER(CbrSumsDesc)]),
+    ("uavsal_cbr_sums_slabs", C.c_int, [C.POINTER(CbrSumsDesc)]),
+    ("uavsal_cbr_sums_slab_rows", C.c_int, [C.POINTER(CbrSumsDesc)]),
+    ("uavsal_cbr_sums", C.c_int, [C.POINTER(CbrSumsDesc), C.c_void_p]),
+    ("uavsal_cbr_finish", C.c_int, [C.POINTER(CbrFinishDesc), C.c_void_p]),
+    ("uavsal_tdiff_bwd", C.c_int, [C.POINTER(TdiffBwdDesc), C.c_void_p]),
+    ("uavsal_st_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_repack", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("uavsal_repack_sizeof_desc", C.c_int, []),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
@@ -503,7 +529,8 @@ def load():
     for sizeof, types in ((lib.uavsal_prior_sizeof_desc, PRIOR_DESC_TYPES), (lib.uavsal_train_sizeof_desc, TRAIN_DESC_TYPES),
                           (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES),
                           (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES),
-                          (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES)):
+                          (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES),
+                          (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

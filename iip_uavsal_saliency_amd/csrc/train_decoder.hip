@@ -3,7 +3,8 @@
 //
 // 1. uavsal_pix_gemm: out[m][n] = row_scale[m] sum over pixels p of A[p][m] B[p][n].  The tile loop of uavsal_twa_wgrad
 //    (csrc/pix_gemm_tile.h: 128 x 128 tiles, 32-pixel K steps, chains of at most UAVSAL_WGRAD_CHAIN products, a second fp32
-//    register tile per share) with plain pitched rows as both operands.  M and N are multiples of 64: the last tile of either
+//    register tile per share) with plain pitched rows as both operands.  M and N are multiples of 64 (a 32-wide side goes to the
+//    sibling pix_gemm32_kernel below): the last tile of either
 //    may be half empty (its loader hands the tile loop zeros, nothing at or behind row M / column N is read or written).  K
 //    split by the same rule: ceil(M / 128) ceil(N / 128) tiles, about 1024 workgroups.  M = 1536, N = 256 is 24 tiles, at
 //    most 42 shares: T = 20 at 45 x 80 (71 chunks) runs 36 shares of 2 chunks.  Partial tiles [share][M][N] -> a second
@@ -78,6 +79,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
             }
 }
 
+// The sibling for a 32-wide side (an ST block's 32 x 256, 256 x 32, 32 x 384; pg_narrow below): a WAVE owns one whole 32 x 32 output
+// tile -- one v_mfma_f32_32x32x2_f32 accumulator (its 64-cycle dependent latency equals its issue interval, so one chain per
+// wave does not by itself idle the pipe), no half of a padded tile is multiplied -- and reads its operands from
+// global memory in the MFMA's own layout (lane l: pixel p + (l >> 5), column (l & 31) of the tile: two 128-byte rows per
+// operand and instruction), kLoads pixel pairs in flight; no LDS, no barrier.  Four tiles to a workgroup (tile = 4 blockIdx.x
+// + wave, mt fastest; here k.mt_n, k.nt_n count 32-wide tiles).  Chunks, chains, shares and the workspace as above.
+// Measured (profiles/train_st.md, 20 frames of 45 x 80): 0.083 ms for 32 x 256 and 256 x 32, 0.100 ms for 32 x 384 with the
+// reduction launch, 14-18 TFLOP/s where the 128 x 128 tile kernel reaches 53 at 256 x 256: the loads are not pipelined under
+// the MFMAs (16 loads, a wait, 8 dependent MFMAs) and the K split gives 142-213 workgroups.  The three calls are 0.27 ms of a
+// 7.4 ms block backward; a pipelined loader is the next step if that share ever matters.
+constexpr int kLoads = 8;
+
+__global__ __launch_bounds__(256) void pix_gemm32_kernel(const PgK k) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tile = (int)blockIdx.x * 4 + wave, share = blockIdx.y;
+    if (tile >= k.mt_n * k.nt_n) return;                       // uniform over the wave; the kernel has no barrier
+    const int mt = tile % k.mt_n, nt = tile / k.mt_n;
+    const int half = lane >> 5, col = lane & 31;
+
+    const long long p0 = (long long)share * k.cps * UAVSAL_WGRAD_CHAIN;
+    long long p1 = p0 + (long long)k.cps * UAVSAL_WGRAD_CHAIN;
+    if (p1 > k.K) p1 = k.K;
+    const float* ap = k.a + mt * 32 + col;
+    const float* bp = k.b + nt * 32 + col;
+
+    f32x16 tot, acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { tot[r] = 0.f; acc[r] = 0.f; }
+    for (long long c0 = p0; c0 < p1; c0 += UAVSAL_WGRAD_CHAIN) {      // a chain: at most UAVSAL_WGRAD_CHAIN products
+        long long c1 = c0 + UAVSAL_WGRAD_CHAIN;
+        if (c1 > p1) c1 = p1;
+        for (long long q = c0; q < c1; q += 2 * kLoads) {
+            float av[kLoads], bv[kLoads];
+#pragma unroll
+            for (int u = 0; u < kLoads; ++u) {
+                const long long g = q + 2 * u + half;
+                const bool ok = g < c1;                                 // rows at and behind p1 are zeros and never read
+                av[u] = ok ? ap[g * k.lda] : 0.f;
+                bv[u] = ok ? bp[g * k.ldb] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < kLoads; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
+        }
+        tot += acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    }
+    float* w = k.ws + (long long)share * k.M * k.N;           // ws [share][m][n]
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        w[(long long)m * k.N + nt * 32 + col] = tot[r];
+    }
+}
+
 // the 256 doubles of `red` summed in a fixed tree; the result in red[0]
 __device__ __forceinline__ void tree256(double* red) {
     for (int s = 128; s > 0; s >>= 1) {
@@ -108,8 +164,26 @@ __global__ __launch_bounds__(256) void pix_gemm_reduce_kernel(const PgK k) {
     if (threadIdx.x == 0) k.rowdot[m] = red[0];
 }
 
+// a 32-wide side (M == 32 or N == 32, the other a multiple of 32 from kNarrowMin to kNarrowMax): pix_gemm32_kernel.  At
+// least one whole workgroup of four tiles; every tile of the wide side reads the narrow operand again, which is what the
+// shapes of an ST block (256, 384) want.  Narrower and wider ones stay refused, as they always were: the cap only has to
+// keep out what re-reading the narrow operand per tile would make slow (1920 x 32 is 60 tiles); 512 is the next power of two
+// above the widest shape in use, not a tuned value
+constexpr int kNarrowMin = 128, kNarrowMax = 512;
+bool pg_narrow(int M, int N) {
+    const int wide = M > N ? M : N;
+    return (M == 32 || N == 32) && !(wide % 32) && wide >= kNarrowMin && wide <= kNarrowMax;
+}
+bool pg_shape_ok(int M, int N) { return pg_narrow(M, N) || (!(M % (kTile / 2)) && !(N % (kTile / 2))); }
+
 bool pg_plan(const uavsal_pix_gemm_desc* d, PgK& k) {
-    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || (d->M % (kTile / 2)) || (d->N % (kTile / 2))) return false;
+    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || !pg_shape_ok(d->M, d->N)) return false;
+    if (pg_narrow(d->M, d->N)) {
+        const long long tiles = (long long)(d->M / 32) * (d->N / 32);
+        if ((long long)d->M * d->N > 0x7fffffffll || (tiles + 3) / 4 > 65535) return false;
+        k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = d->M / 32; k.nt_n = d->N / 32;
+        return pixgemm::split(k.K, (int)((tiles + 3) / 4), k.cps, k.shares);
+    }
     const int mt_n = (d->M + kTile - 1) / kTile, nt_n = (d->N + kTile - 1) / kTile;
     if ((long long)d->M * d->N > 0x7fffffffll || (long long)mt_n * nt_n > 65535) return false;
     k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = mt_n; k.nt_n = nt_n;
@@ -292,7 +366,7 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     if (!d || !d->a || !d->b || !d->ws || !d->out) return UAVSAL_EINVAL;
     if (d->K <= 0 || d->M <= 0 || d->N <= 0) return UAVSAL_EINVAL;
     if (d->rowdot && !d->w) return UAVSAL_EINVAL;
-    if ((d->M % (kTile / 2)) || (d->N % (kTile / 2))) return UAVSAL_ESHAPE;
+    if (!pg_shape_ok(d->M, d->N)) return UAVSAL_ESHAPE;
     PgK k;
     if (!pg_plan(d, k)) return UAVSAL_ESHAPE;
     if (d->ws_bytes < uavsal_pix_gemm_workspace_bytes(d)) return UAVSAL_EINVAL;
@@ -304,7 +378,10 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     k.lda = d->lda; k.ldb = d->ldb; k.ldw = d->ldw; k.ldo = d->ldo;
     k.accumulate = d->accumulate != 0;
     const dim3 grid((unsigned)(k.mt_n * k.nt_n), (unsigned)k.shares);
-    if (k.M % kTile) hipLaunchKernelGGL(pix_gemm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, k);
+    if (pg_narrow(k.M, k.N))
+        hipLaunchKernelGGL(pix_gemm32_kernel, dim3((unsigned)((k.mt_n * k.nt_n + 3) / 4), (unsigned)k.shares), dim3(256), 0,
+                           (hipStream_t)stream, k);
+    else if (k.M % kTile) hipLaunchKernelGGL(pix_gemm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, k);
     else hipLaunchKernelGGL(pix_gemm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, k);
     hipLaunchKernelGGL(pix_gemm_reduce_kernel, dim3((unsigned)k.M), dim3(256), 0, (hipStream_t)stream, k);
     return uavsal_launch_status();

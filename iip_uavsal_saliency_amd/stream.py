@@ -405,6 +405,9 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `recurrence_step(..., nets=True)` also sets the gradients of the prior nets `model.gauss_cb_layer` / `model.ob_cb_layer`,
     and the enabled nets' containers are refreshed as well (which makes the next call run them again on the priors it is
     handed).  With every stage named, the optimiser may hold exactly the parameters the reference's does.
+    `"st"` (the very last stage, only behind `"fuse"` and, in a model with priors, `"fust"`): `recurrence_step(..., st=True)`
+    also sets the gradients of the ST blocks `model.st_layer` -- frozen in the reference's own `train()`, the first thing to
+    unfreeze on a new dataset -- and `model.st_layer` is refreshed as well.
     `refresh`: `"host"` (the default) repacks the trained stages' weights on the host after every step; `"device"` repacks
     them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host)."""
     from . import losses as _losses
@@ -417,9 +420,11 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
                ("rnn", "decoder", "fuse", "fust")]
     allowed += [s + ("ctx",) for s in allowed if "fuse" in s]
     allowed += [s + ("nets",) for s in allowed if "fuse" in s]
+    allowed += [s + ("st",) for s in allowed if "fuse" in s and ("fust" in s or not getattr(model, "num_cb", 0))]
     if stages not in allowed:
         raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
-                         "'fuse' (then 'ctx', then 'nets', behind 'fuse' too), got %r" % (stages,))
+                         "'fuse' (then 'ctx', then 'nets', behind 'fuse' too; 'st' the very last, behind 'fuse' and, in a "
+                         "model with priors, 'fust'), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
@@ -437,6 +442,8 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
                 mods.append(model.cxt_cb_prior)
         if "nets" in kw:
             mods.extend(_train.prior_nets(model).values())
+        if "st" in kw:
+            mods.append(model.st_layer)
         if refresh == "device":
             model.refresh_weights(*mods, device=True)
         else:

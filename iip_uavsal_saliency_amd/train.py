@@ -24,8 +24,13 @@ with M a multiple of 64) and stride 2 (`uavsal_ir_sums_s2`).  And a sixth, the l
 nets `model.gauss_cb_layer` / `model.ob_cb_layer` (`recurrence_step(nets=True)`, `prior_net_backward`): block 1 of either is a
 shape the walk above takes, block 0 (8 -> 48 -> 64, 20 -> 120 -> 64) goes through `narrow_block_param_grads`
 (csrc/train_nets.hip: `uavsal_ir_narrow_grads`, `uavsal_ir_narrow_finish`, and `uavsal_frame_sum` for priors that are one map
-for every frame).  With all six, a step sets the gradient of every parameter the reference's optimiser holds (`sfnet` and
-`st_layer` are frozen there too); BatchNorm in eval mode remains the documented difference.
+for every frame).  With all six, a step sets the gradient of every parameter the reference's optimiser holds by default
+(`sfnet` and `st_layer` are frozen there: Demo_Train_Test.py:58-62).  And a seventh, what deleting the reference's lines 61-62
+gives: the ST blocks `model.st_layer` (`recurrence_step(st=True)`, `st_block_backward`): the two inverted-residual blocks of an
+ST block go through the walks above (`block_param_grads` takes the temporal sub-block's 64 -> 384 -> 32, `uavsal_pix_gemm` its
+32-wide side), the three 1x1 conv + BatchNorm + ReLU6 stages through `cbr_backward` and the temporal difference through
+`tdiff_bwd` (csrc/train_st.hip: `uavsal_cbr_sums`, `uavsal_cbr_finish`, `uavsal_tdiff_bwd`).  The backbone `sfnet` stays frozen;
+BatchNorm in eval mode remains the documented difference.
 
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
@@ -371,9 +376,10 @@ def _param_grad_parts(block):
                            "(expand 1x1, depthwise 3x3, projection 1x1)")
     pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
     hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
-    if cout % 64 or hid % 64 or cin % 64:
-        raise RuntimeError("block_param_grads needs Cout %% 64 == 0, hidden %% 64 == 0 and Cin %% 64 == 0, got %d -> %d -> %d"
-                           % (cin, hid, cout))
+    narrow = cout == 32 and 128 <= hid <= 512                       # an ST block's sub_conv, 64 -> 384 -> 32 (uavsal_pix_gemm's 32-wide side)
+    if (cout % 64 and not narrow) or hid % 64 or cin % 64:
+        raise RuntimeError("block_param_grads needs Cout %% 64 == 0 (or Cout == 32 with 128 <= hidden <= 512), hidden %% 64 == 0 "
+                           "and Cin %% 64 == 0, got %d -> %d -> %d" % (cin, hid, cout))
     if stride == 2 and block.use_res_connect:
         raise RuntimeError("block_param_grads: a block with stride 2 has no residual")
     if block.training:
@@ -491,7 +497,8 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
     gives for the reference's `dwBlock` (include/uavsal_hip.h states the formulas); `out`: such a dict of dense tensors to
     write into, or (`accumulate`) to add to.  Nothing of the forward is recomputed; six launches (two pixel GEMMs with their
     reductions -- `ga` x `x` for W1, `grad_out` x `d` for W3 --, channel sums, finalise) on the current stream, no
-    synchronisation.  Accepted: Co % 64 == 0, Ch % 64 == 0, Cin % 64 == 0 (`block_backward`, which recomputes `e` and `d`
+    synchronisation.  Accepted: Co % 64 == 0 -- or Co == 32 with 128 <= Ch <= 512, the temporal sub-block of an ST block
+    (64 -> 384 -> 32), whose W3 product is the pixel GEMM's 32-wide side --, Ch % 64 == 0, Cin % 64 == 0 (`block_backward`, which recomputes `e` and `d`
     itself, keeps to stride 1 and Co % 128 == 0)."""
     lib = L.load()
     pw, pwbn, dwc, dwbn, pl, plbn = _param_grad_parts(block)
@@ -561,6 +568,12 @@ def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None,
     (+ `grad_out` when the block has the residual) from one Ch -> Cin GEMM of the same kind.  `parts` receives `e`, `d`,
     `gd`, `ga` (dense NHWC).  A block in training mode raises: the BatchNorms use their running statistics (which are not
     updated), as everywhere in this package."""
+    return _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate)
+
+
+def _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, ed=None, res=None):
+    """`block_backward`; `ed`: the block's `(e, d)` when the caller has recomputed them; `res`: an NHWC tensor the `grad_x` GEMM
+    adds where the block has no residual (`st_block_backward`)."""
     lib = L.load()
     pw, pwbn, dwc, dwbn, pl, plbn = _block_parts(block)
     hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
@@ -570,12 +583,12 @@ def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None,
     _block_grad_tensors(block, grads, accumulate)                    # raise before anything is launched
     with torch.cuda.device(dev):
         cache = cache or WeightCache(dev, {})
-        e, dd = _block_recompute(lib, cache, block, xn)
+        e, dd = ed or _block_recompute(lib, cache, block, xn)
         gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
         ga = ir_bwd(gd, dd, e, *cache.depthwise(dwc, dwbn)[:2])
         g = None
         if need_x_grad:
-            g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else None)
+            g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else res)
         grads = block_param_grads(block, xn.permute(0, 3, 1, 2), e, dd, go.permute(0, 3, 1, 2), gd=gd, ga=ga, cache=cache,
                                   out=grads, accumulate=accumulate)
         if parts is not None:
@@ -993,6 +1006,220 @@ def prior_net_backward(net, cb, grad_out, cache=None, parts=None, grads=None, ac
     return grads
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# The ST blocks (csrc/train_st.hip): 1x1 conv + BatchNorm + ReLU6 stages, the adjoint of the temporal difference
+ST_CBR_PARAMS = ("0.weight", "1.weight", "1.bias")                   # a BasicConv2d 1x1: W, gamma, beta
+ST_BLOCK_PARTS = (("stconv_sp.spconv.", BLOCK_PARAMS), ("stconv_te.reduce_conv.", ST_CBR_PARAMS),
+                  ("stconv_te.sub_conv.", BLOCK_PARAMS), ("stconv_te.last_conv.", ST_CBR_PARAMS), ("stconv_last.", ST_CBR_PARAMS))
+ST_BLOCK_PARAMS = tuple(p + n for p, names in ST_BLOCK_PARTS for n in names)      # the 27 names, in named_parameters() order
+
+
+def cbr_sums(g, y):
+    """`uavsal_cbr_sums` on the current stream: `g`, `y` NHWC views `[N,h,w,C]` of the same pixels (channel slices are read in
+    place) -> `(gp, ws, slabs)`: `gp = g * 1[0 < y < 6]` dense NHWC and the per-slab channel sums (float64 `[slab][C]`) that
+    `uavsal_cbr_finish` takes."""
+    lib = L.load()
+    gptr, ldg, *gs = _nhwc_view(g)
+    yptr, ldy, *ys = _nhwc_view(y)
+    if gs != ys or g.device != y.device:
+        raise RuntimeError("cbr_sums: g and y must have one shape [n,h,w,C] on one device")
+    n, hh, ww, c = gs
+    gp = torch.empty((n, hh, ww, c), dtype=torch.float32, device=g.device)
+    k = L.CbrSumsDesc()
+    k.g, k.ldg, k.y, k.ldy, k.gp = gptr, ldg, yptr, ldy, gp.data_ptr()
+    k.n_img, k.H, k.W, k.C = n, hh, ww, c
+    nbytes = int(lib.uavsal_cbr_sums_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_cbr_sums")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=g.device)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    L.check(lib.uavsal_cbr_sums(C.byref(k), _stream(g)), "uavsal_cbr_sums")
+    return gp, ws, int(lib.uavsal_cbr_sums_slabs(C.byref(k)))
+
+
+def tdiff_bwd(g_dif, r, seq_len):
+    """`uavsal_tdiff_bwd` on the current stream: the adjoint of `ops.tdiff` fused with the ReLU6 mask of the stage that made
+    its input.  `g_dif` `[N,h,w,2C]` = d loss / d dif, `r` `[N,h,w,C]` the difference's input (NHWC views, channel slices are
+    read in place), `seq_len` frames per sequence -> `gp_r` dense NHWC `[N,h,w,C]` = `1[0 < r < 6]` times the gradient with
+    respect to `r`."""
+    lib = L.load()
+    gptr, ldg, *gs = _nhwc_view(g_dif)
+    rptr, ldr, n, hh, ww, c = _nhwc_view(r)
+    if gs != [n, hh, ww, 2 * c] or g_dif.device != r.device:
+        raise RuntimeError("tdiff_bwd: g_dif must be [%d,%d,%d,%d] on the device of r" % (n, hh, ww, 2 * c))
+    out = torch.empty((n, hh, ww, c), dtype=torch.float32, device=r.device)
+    k = L.TdiffBwdDesc()
+    k.g, k.ldg, k.r, k.ldr, k.out, k.ldo = gptr, ldg, rptr, ldr, out.data_ptr(), c
+    k.n_img, k.HW, k.C, k.seq_len = n, hh * ww, c, int(seq_len)
+    L.check(lib.uavsal_tdiff_bwd(C.byref(k), _stream(r)), "uavsal_tdiff_bwd")
+    return out
+
+
+def _cbr_parts(conv, bn):
+    if (not isinstance(conv, torch.nn.Conv2d) or not isinstance(bn, torch.nn.BatchNorm2d) or conv.kernel_size != (1, 1)
+            or conv.stride != (1, 1) or conv.groups != 1 or conv.bias is not None):
+        raise RuntimeError("cbr_backward takes the 1x1 conv (no bias, stride 1) and the BatchNorm of a BasicConv2d")
+    cout, cin = conv.weight.shape[:2]
+    if cout % 32 or cin % 32:
+        raise RuntimeError("cbr_backward needs Cout %% 32 == 0 and Cin %% 32 == 0, got %d -> %d" % (cin, cout))
+    if bn.training:
+        raise RuntimeError("the BatchNorm uses its running statistics: call model.eval()")
+    return cin, cout
+
+
+def _cbr_grad_tensors(conv, bn, out, accumulate):
+    params = dict(zip(ST_CBR_PARAMS, (conv.weight, bn.weight, bn.bias)))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `grads`")
+        out = {n: torch.empty_like(q, memory_format=torch.contiguous_format) for n, q in params.items()}
+    for n, q in params.items():
+        t = out.get(n)
+        if (not torch.is_tensor(t) or t.shape != q.shape or t.dtype != torch.float32 or t.device != q.device
+                or not t.is_contiguous()):
+            raise RuntimeError("grads[%r] must be a dense float32 tensor of the parameter's shape on its device" % n)
+    return params, out
+
+
+def cbr_backward(conv, bn, x, y, grad_out, need_x_grad=True, cache=None, grads=None, accumulate=False):
+    """Backward of ONE 1x1 conv + BatchNorm + ReLU6 (`BasicConv2d`, eval mode: the BatchNorm on its running statistics, which
+    are not updated), teacher-forced: `x` `[N,Cin,h,w]` its input, `y` an NHWC view `[N,h,w,C]` of its own activation (before
+    any residual is added), `grad_out` `[N,C,h,w]` = d loss / d output.  Returns `(grad_x [N,Cin,h,w] | None, grads)`; `grads`
+    keyed by `ST_CBR_PARAMS` (W, gamma, beta), the values `torch.autograd` gives, written into the given dict of dense tensors or
+    with `accumulate` added to it.  `uavsal_cbr_sums` forms `gp = grad_out * 1[0 < y < 6]` and its channel sums,
+    `uavsal_pix_gemm` `s[c] G[c][j]` and the row dots, `uavsal_cbr_finish` beta and gamma (from the UNSCALED sums), and
+    `grad_x = gp . (diag(s) W)` is one GEMM whose transposed weights carry s in their rows (`WeightCache.conv_t_scaled`).
+    Accepted: Cin % 32 == 0, C % 32 == 0.  Four launches (+ the GEMM), on the current stream, no synchronisation."""
+    return _cbr_backward(conv, bn, x, y, grad_out, need_x_grad, cache, grads, accumulate)
+
+
+def _cbr_backward(conv, bn, x, y, grad_out, need_x_grad, cache, grads, accumulate, res=None):
+    """`cbr_backward`; `res`: an NHWC tensor the `grad_x` GEMM adds (`st_block_backward`)."""
+    lib = L.load()
+    cin, cout = _cbr_parts(conv, bn)
+    xn = _nhwc(x, "x", cin)
+    go = _block_grad_out(grad_out, xn, cout)
+    dev = xn.device
+    if (not torch.is_tensor(y) or y.dtype != torch.float32 or y.device != dev or tuple(y.shape) != tuple(go.shape)):
+        raise RuntimeError("y must be a float32 NHWC view %r on the device of x" % (tuple(go.shape),))
+    params, grads = _cbr_grad_tensors(conv, bn, grads, accumulate)
+    if any(q.device != dev or not q.is_contiguous() for q in params.values()):
+        raise RuntimeError("the parameters must be dense tensors on the device of `x`")
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        s = cache.affine(bn, cout)[0]
+        r, mu = cache.bn_stats(bn)
+        gp, ws, slabs = cbr_sums(go, y)
+        rowdot = torch.empty(cout, dtype=torch.float64, device=dev)
+        pix_gemm(gp, xn, out=grads[ST_CBR_PARAMS[0]], row_scale=s, w=conv.weight.detach(), rowdot=rowdot, accumulate=accumulate)
+        k = L.CbrFinishDesc()
+        k.ws, k.ws_bytes, k.rowdot, k.r, k.mu = ws.data_ptr(), ws.numel() * 8, rowdot.data_ptr(), r.data_ptr(), mu.data_ptr()
+        k.g_gamma, k.g_beta = grads[ST_CBR_PARAMS[1]].data_ptr(), grads[ST_CBR_PARAMS[2]].data_ptr()
+        k.C, k.slabs, k.accumulate = cout, slabs, int(bool(accumulate))
+        L.check(lib.uavsal_cbr_finish(C.byref(k), _stream(xn)), "uavsal_cbr_finish")
+        g = _conv(lib, cache, gp, conv, cin, 1, tscale=bn, res=res) if need_x_grad else None
+    return (g.permute(0, 3, 1, 2) if need_x_grad else None), grads
+
+
+def _st_parts(block):
+    """The sub-modules of an `STBlock` `st_block_backward` covers, or a RuntimeError."""
+    sp, te, last = getattr(block, "stconv_sp", None), getattr(block, "stconv_te", None), getattr(block, "stconv_last", None)
+    if sp is None or te is None or last is None or not hasattr(sp, "spconv"):
+        raise RuntimeError("st_block_backward takes an STBlock (model.st_layer[i])")
+    if str(getattr(block, "fu_type", "sum")).lower() != "sum":
+        raise RuntimeError("st_block_backward covers fu_type='sum' only, got fu_type=%r" % (block.fu_type,))
+    if block.training:
+        raise RuntimeError("the ST block's BatchNorms use their running statistics: call model.eval()")
+    if sp.spconv.use_res_connect or te.sub_conv.use_res_connect:
+        raise RuntimeError("st_block_backward: spconv and sub_conv have no residual in an STBlock")
+    return sp.spconv, te.reduce_conv, te.sub_conv, te.last_conv, last
+
+
+def _st_grad_tensors(block, out, accumulate):
+    params = dict(block.named_parameters())
+    if sorted(params) != sorted(ST_BLOCK_PARAMS):
+        raise RuntimeError("the ST block's parameters must be %r" % (ST_BLOCK_PARAMS,))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `grads`")
+        out = {n: torch.empty_like(params[n], memory_format=torch.contiguous_format) for n in ST_BLOCK_PARAMS}
+    for n in ST_BLOCK_PARAMS:
+        t, q = out.get(n), params[n]
+        if (not torch.is_tensor(t) or t.shape != q.shape or t.dtype != torch.float32 or t.device != q.device
+                or not t.is_contiguous()):
+            raise RuntimeError("grads[%r] must be a dense float32 tensor of the parameter's shape on its device" % n)
+    return params, out
+
+
+def st_block_backward(block, x, grad_out, seq_len=None, need_x_grad=True, cache=None, parts=None, grads=None, accumulate=False):
+    """Backward of an ST block that is TRAINED (`model.st_layer[i]`, reference model.py:163-249; eval mode: every BatchNorm on
+    its running statistics, which are not updated): `x` `[N,256,h,w]` its input, `grad_out` `[N,256,h,w]` = d loss / d output,
+    `seq_len` the frames per sequence of the temporal difference (default: all N -- `forward()`; one clip's T for
+    `forward_clips`).  Returns `(grad_x [N,256,h,w] | None, grads)`, `grads` keyed by the block's 27 parameter names
+    (`ST_BLOCK_PARAMS`), written into the given dict of dense tensors or with `accumulate` added to it.
+        x_sp = spconv(x);  r = ReLU6(BN(W_r x));  dif = tdiff(r);  t1 = sub_conv(dif);  a_te = ReLU6(BN(W_l t1));
+        o = ReLU6(BN(W_last (x_sp + a_te)));  out = x + o
+    The intermediates are recomputed by the forward's own launches, each once (`a_te` and `o` WITHOUT the residual their
+    launches add in the plan: the ReLU6 masks are those of the stages' own activations; `x_sp + a_te` is one `uavsal_tsum_bwd`
+    launch with T = 1, the fp32 sum the plan's epilogue forms).  The walk: `stconv_last` (`cbr_backward`), the spatial branch
+    (`block_backward` on `spconv`), `last_conv` (`cbr_backward`), `sub_conv` (the input-gradient walk + `block_param_grads`),
+    `tdiff_bwd`, `reduce_conv` (`cbr_backward`; the mask is already in `tdiff_bwd`'s output, applying it again changes no
+    bit).  `grad_x = (grad_out + spconv's) + reduce_conv's`: each GEMM adds what is already there.  `need_x_grad=False` (block
+    0: the backbone is frozen) leaves the two GEMMs out.  `parts` receives every intermediate (NHWC): `e_sp`, `d_sp`, `x_sp`,
+    `r`, `dif`, `e_te`, `d_te`, `t1`, `a_te`, `ssum`, `o`, `g_sum`, `g_t1`, `g_dif`, `gp_r`, `gx_sp` and `sp` / `sub`, the two
+    blocks' `dict(e=, d=, gd=, ga=)`.  A block in training mode, `fu_type != 'sum'` or CPU tensors raise."""
+    lib = L.load()
+    spc, red, sub, lastc, stl = _st_parts(block)
+    p_sub = _input_grad_parts(sub)
+    _param_grad_parts(sub)
+    p_sp = _block_parts(spc)
+    for cv in (red, lastc, stl):
+        _cbr_parts(cv[0], cv[1])
+    cin = spc.cin
+    xn = _nhwc(x, "x", cin)
+    go = _block_grad_out(grad_out, xn, stl[0].weight.shape[0])
+    N, hh, ww, _ = xn.shape
+    seq_len = N if seq_len is None else int(seq_len)
+    if seq_len < 2 or N % seq_len:
+        raise RuntimeError("seq_len must be at least 2 and divide the %d frames, got %r" % (N, seq_len))
+    dev = xn.device
+    _, grads = _st_grad_tensors(block, grads, accumulate)                # raise before anything is launched
+    sub_g = lambda prefix, names: {n: grads[prefix + n] for n in names}   # noqa: E731
+    g_sp, g_red, g_sub, g_last, g_stl = (sub_g(p, names) for p, names in ST_BLOCK_PARTS)
+    nchw = lambda t: t.permute(0, 3, 1, 2)                                # noqa: E731
+    from .ops import tdiff as _tdiff
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        # ---- the forward's intermediates
+        e_sp, d_sp = _block_recompute(lib, cache, spc, xn, 1, p_sp)
+        x_sp = _conv(lib, cache, d_sp, p_sp[4], p_sp[4].weight.shape[0], 1, bn=p_sp[5])
+        r = _conv(lib, cache, xn, red[0], red[0].weight.shape[0], 1, bn=red[1], act=L.ACT_RELU6)
+        dif = _tdiff(r, seq_len)
+        e_te, d_te = _block_recompute(lib, cache, sub, dif, 1, p_sub)
+        t1 = _conv(lib, cache, d_te, p_sub[4], p_sub[4].weight.shape[0], 1, bn=p_sub[5])
+        a_te = _conv(lib, cache, t1, lastc[0], lastc[0].weight.shape[0], 1, bn=lastc[1], act=L.ACT_RELU6)
+        ssum = tsum_bwd(a_te, x_sp, 1)
+        o = _conv(lib, cache, ssum, stl[0], stl[0].weight.shape[0], 1, bn=stl[1], act=L.ACT_RELU6)
+        # ---- the walk back
+        g_sum, _ = cbr_backward(stl[0], stl[1], nchw(ssum), o, nchw(go), cache=cache, grads=g_stl, accumulate=accumulate)
+        pt_sp = {}
+        gx, _ = _block_backward(spc, nchw(xn), g_sum, need_x_grad, cache, pt_sp, g_sp, accumulate, ed=(e_sp, d_sp), res=go)
+        g_t1, _ = cbr_backward(lastc[0], lastc[1], nchw(t1), a_te, g_sum, cache=cache, grads=g_last, accumulate=accumulate)
+        g_t1n = g_t1.permute(0, 2, 3, 1)
+        pt_sub = {}
+        g_dif = _input_grad(lib, cache, sub, p_sub, dif, g_t1n, ed=(e_te, d_te), parts=pt_sub)
+        block_param_grads(sub, nchw(dif), e_te, d_te, g_t1, gd=pt_sub["gd"], ga=pt_sub["ga"], cache=cache, out=g_sub,
+                          accumulate=accumulate)
+        gp_r = tdiff_bwd(g_dif, r, seq_len)
+        g, _ = _cbr_backward(red[0], red[1], nchw(xn), r, nchw(gp_r), need_x_grad, cache, g_red, accumulate,
+                             res=gx.permute(0, 2, 3, 1) if need_x_grad else None)
+        if parts is not None:
+            parts.update(e_sp=e_sp, d_sp=d_sp, x_sp=x_sp, r=r, dif=dif, e_te=e_te, d_te=d_te, t1=t1, a_te=a_te, ssum=ssum, o=o,
+                         g_sum=g_sum.permute(0, 2, 3, 1), g_t1=g_t1n, g_dif=g_dif, gp_r=gp_r,
+                         gx_sp=gx.permute(0, 2, 3, 1) if need_x_grad else None, sp=pt_sp, sub=pt_sub)
+    return g, grads
+
+
 def twa_gate_bwd(g, carry, z, x, hprev, need_dx=False):
     """`uavsal_twa_gate_bwd` on NHWC tensors `[1,h,w,256]` (`g`, `x`, `hprev` may be channel slices; `carry` dense or None):
     returns `(dz, carry_out, dx | None)`, dense."""
@@ -1128,7 +1355,8 @@ def _param_grad_tensors(blk):
     return {n: q.grad for n, q in params.items()}, acc
 
 
-def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False):
+def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False,
+                    st=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -1161,7 +1389,14 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     them, `model.dedupe_priors and model._static(cb0, cb1, 1)` with more than one frame -- ran each net on ONE frame whose
     output every frame reads: the slice is summed over the frames (`frame_sum`) and the backward runs on one frame too; else
     it runs over all N frames.  Refresh `model.gauss_cb_layer` / `model.ob_cb_layer` afterwards as well (which also drops the
-    engines' prior records, `model.refresh_weights`)."""
+    engines' prior records, `model.refresh_weights`).
+    `st=True` (needs `fuse=True`, and `fust=True` as well in a model with priors: the gradient must reach `fust_layer[0]`'s
+    input): the ST blocks `model.st_layer` are trained as well -- what a user of the reference gets by deleting the two lines
+    that freeze them (Demo_Train_Test.py:61-62).  The `block_backward` of `model.fust_layer[0]` also returns the gradient of
+    its input, and `st_block_backward` walks from the last ST block to the first over the `st{i}` and `sfnet` taps (one
+    sequence of all the call's frames, as `forward()` runs them; no input gradient at block 0: the backbone `sfnet` stays
+    frozen), setting -- or adding to -- the `.grad` of the 27 parameters of every block.  Refresh `model.st_layer` afterwards
+    as well.  A call without `st` runs the launches, and copies the taps, it always ran."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
@@ -1175,6 +1410,9 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if nets and not (fuse and prior_nets(model)):
         raise RuntimeError("nets=True needs fuse=True and a model with the gauss or the ob prior (bias_type [0,0,1] and [0,0,0] "
                            "have no prior net)")
+    if st and not (fuse and (fust or not getattr(model, "num_cb", 0))):
+        raise RuntimeError("st=True needs fuse=True, and in a model with priors fust=True as well (the gradient reaches "
+                           "model.st_layer through model.fust_layer[0]'s input)")
     if model.training:
         raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
     if model.precision != "f32":
@@ -1186,7 +1424,7 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     taps = {src: None} if fuse else {}                               # (fu320 is read back on request only: engine.TAPS_ON_REQUEST)
     if fust or ctx or nets:
         taps["cb192"] = None                                         # (likewise)
-    out, st = model(x, cb, in_state, taps=taps)
+    out, h_last = model(x, cb, in_state, taps=taps)
     pred = out.detach().requires_grad_(True)
     with torch.enable_grad():
         loss = criterion(pred, y_gaze)
@@ -1210,9 +1448,9 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if fuse:
         grads, acc = _param_grad_tensors(blk)
         fu = taps[src].contiguous(memory_format=cl)
-        grad_fu, _ = block_backward(blk, fu, grad_x, need_x_grad=bool(fust or ctx or nets), cache=cache, grads=grads,
+        grad_fu, _ = block_backward(blk, fu, grad_x, need_x_grad=bool(fust or ctx or nets or st), cache=cache, grads=grads,
                                     accumulate=acc)
-        g_cb = None
+        g_cb, g_st = None, grad_fu                                   # (without priors the fuse stage IS fust_layer[0])
         if ctx:
             pg = {n: _param_grad_tensors(b) for n, b in prior_path_blocks(model).items()}
             g, _, *g_cb = prior_path_backward(model, fu, taps["cb192"], grad_fu, cache=cache, grads={n: v[0] for n, v in pg.items()},
@@ -1237,6 +1475,12 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
         if fust:
             fb = model.fust_layer[0]
             grads, acc = _param_grad_tensors(fb)
-            block_backward(fb, taps["st%d" % (len(model.st_layer) - 1)].contiguous(memory_format=cl), g, need_x_grad=False,
-                           cache=cache, grads=grads, accumulate=acc)
-    return loss.detach(), out, [st[0].detach()]
+            g_st, _ = block_backward(fb, taps["st%d" % (len(model.st_layer) - 1)].contiguous(memory_format=cl), g,
+                                     need_x_grad=bool(st), cache=cache, grads=grads, accumulate=acc)
+        if st:
+            for i in range(len(model.st_layer) - 1, -1, -1):         # one sequence of all frames, as forward() runs them
+                grads, acc = _param_grad_tensors(model.st_layer[i])
+                xin = taps["st%d" % (i - 1)] if i else taps["sfnet"]
+                g_st, _ = st_block_backward(model.st_layer[i], xin.contiguous(memory_format=cl), g_st, seq_len=x.shape[0],
+                                            need_x_grad=i > 0, cache=cache, grads=grads, accumulate=acc)
+    return loss.detach(), out, [h_last[0].detach()]

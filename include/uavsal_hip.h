@@ -767,13 +767,21 @@ int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd 
  *
  * uavsal_pix_gemm: out[m][n] = fl(row_scale[m] G[m][n]) (+ the old value with `accumulate`), G[m][n] = sum over the K
  *   pixels p of a[p][m] b[p][n]; row p of a / b at p * lda / p * ldb floats (channel slices are read in place).  M and N
- *   multiples of 64 (else UAVSAL_ESHAPE; the last M tile and the last N tile may be half empty: nothing at or behind row
+ *   multiples of 64 (multiples of 32: below; the last M tile and the last N tile may be half empty: nothing at or behind row
  *   M or column N is read, written or enters rowdot).  The tile loop and the K split of uavsal_twa_wgrad: chunks of
  *   UAVSAL_WGRAD_CHAIN pixels, shares of whole chunks for about 1024 workgroups over the ceil(M / 128) ceil(N / 128) tiles, partial
  *   tiles in `ws`; a second launch sums the shares in share order in double and rounds once.  row_scale NULL = 1.
  *   rowdot (optional, [M] doubles) = sum_n w[m][n] G[m][n] in double in a fixed order, w rows ldw floats apart.
  *   No atomics: two calls return the same bits.  TWO launches, no allocation.  UAVSAL_EALIGN: a, b, ws not 16-byte
  *   aligned or lda / ldb not a multiple of 4.
+ *   M == 32 or N == 32, the other side a multiple of 32 from 128 to 512 (the 32-wide sides of an ST block: 32 x 256, 256 x 32, 32 x 384): a sibling
+ *   kernel behind the same entry point, in which a WAVE owns one whole 32 x 32 tile (one v_mfma_f32_32x32x2_f32 accumulator,
+ *   no padded half tile, operands read from global memory in the MFMA's own layout, not pipelined under the MFMAs: 14-18
+ *   TFLOP/s measured at 20 frames of 45 x 80, profiles/train_st.md), four tiles to a workgroup; the same
+ *   chunks, chains, shares rule (over ceil((M / 32)(N / 32) / 4) workgroups per share), workspace layout, reduction launch,
+ *   row_scale, rowdot and accumulate.  Every call with M and N multiples of 64 keeps the kernel, grid, workspace and bits it
+ *   had.  Anything else (96 x 64: no side is 32 wide and one is no multiple of 64; 32 x 64: less than one workgroup of
+ *   four tiles; 1920 x 32: wider than 512): UAVSAL_ESHAPE, as before.
  * uavsal_dec_sums: per slab of picture rows the partial sums S3, G3, S2, Gd, S1 -> `ws` (doubles), from gy (pitched as in
  *   uavsal_dec_bwd_desc), y dense [n_img][H][W], e, d, ga dense [n_img][H][W][C], C % 256 == 0 (else UAVSAL_ESHAPE).
  *   delta3 and delta2 are formed in fp32 exactly as uavsal_dec_bwd forms them; every product is accumulated in double.
@@ -1030,6 +1038,66 @@ int uavsal_ir_narrow_grads(const uavsal_ir_narrow_desc* d, uavsal_stream_t strea
 int uavsal_ir_narrow_finish(const uavsal_ir_narrow_finish_desc* d, uavsal_stream_t stream);
 int uavsal_frame_sum(const uavsal_frame_sum_desc* d, uavsal_stream_t stream);
 int uavsal_nets_sizeof_desc(int which);   /* 0 ir_narrow, 1 ir_narrow_finish, 2 frame_sum (uavsal_mp_sizeof_desc is closed at 1) */
+
+/* ---- fine-tuning the ST blocks: conv + BN + ReLU6 sums, the adjoint of the temporal difference (csrc/train_st.hip) --------
+ * An ST block (model.py:163-249) with x [N][256]:  x_sp = spconv(x);  r = ReLU6(BN(W_r x)) (256 -> 32);  dif = tdiff(r);
+ * t1 = sub_conv(dif) (64 -> 384 -> 32);  a_te = ReLU6(BN(W_l t1)) (32 -> 256);  o = ReLU6(BN(W_last (x_sp + a_te)));
+ * out = x + o.  The two inverted-residual blocks go through the block backward above (uavsal_pix_gemm takes their 32-wide
+ * sides); the three 1x1 conv + BatchNorm + ReLU6 stages y = ReLU6(s (W x) + b), in eval mode, with m6(v) = 1[0 < v < 6],
+ *     gp[p][c] = g[p][c] m6(y[p][c])     S[c] = sum_p gp[p][c]     G[c][j] = sum_p gp[p][c] x[p][j]
+ * have the gradients
+ *     W[c][j]: s[c] G[c][j]    beta: S    gamma[c]: r[c] (sum_j W[c][j] G[c][j] - mu[c] S[c])    x: gp . (diag(s) W)
+ * (G, the row scale and the row dot from uavsal_pix_gemm(gp, x); the gamma gradient from the UNSCALED sums).
+ *
+ * uavsal_cbr_sums: g rows of C floats ldg floats apart (a channel slice is read in place) = d loss / d output; y rows ldy
+ *   floats apart = the stage's own activation (before any residual is added); writes gp dense [n_img H W][C] and per slab
+ *   of picture rows the partial sums S -> `ws` ([slab][C] doubles), every term added in double.  A slab is a run of whole
+ *   picture rows counted through all images, about 512 pixels and at most 256 slabs (the rule of uavsal_ir_sums;
+ *   uavsal_cbr_sums_slabs / _slab_rows): a function of the shape alone, no atomics, bit-reproducible.  C % 32 == 0 (else
+ *   UAVSAL_ESHAPE); ldg, ldy multiples of 4 and 16-byte aligned pointers (else UAVSAL_EALIGN).  ONE launch.
+ * uavsal_cbr_finish: sums the slabs in slab order in double and writes beta: S and gamma[c]: r[c] (rowdot[c] - mu[c] S[c]),
+ *   each rounded once, overwritten or (`accumulate`) added to.  rowdot: uavsal_pix_gemm's, with w = W.  ONE launch.
+ * uavsal_tdiff_bwd: the adjoint of uavsal_tdiff fused with the ReLU6 mask of the stage that made its input.  g rows of 2 C
+ *   floats ldg floats apart = d loss / d dif, P_i = g[i][:C], Q_i = g[i][C:]; r rows ldr floats apart = uavsal_tdiff's input;
+ *   out rows ldo floats apart.  For frame j of a sequence of L = seq_len frames (n_img % L == 0, L >= 2; nothing crosses a
+ *   sequence border), the at most six terms in this order, added in double and rounded once:
+ *     own frame:   j == 0: -P_0 + Q_0;   j == L-1: +P_j - Q_j;   else +P_j + Q_j
+ *     frame j - 1: j - 1 == 0: +P_0 - Q_0;   0 < j - 1: -Q_{j-1}                (j >= 1)
+ *     frame j + 1: j + 1 == L-1: -P_{j+1} + Q_{j+1};   j + 1 < L-1: -P_{j+1}    (j <= L-2)
+ *   (frame 0 takes the first rule and frame L-1 the last, L == 2 included), then out[j] = m6(r[j]) * that sum.  A gather:
+ *   bit-reproducible.  C, ldg, ldr, ldo multiples of 4, 16-byte aligned pointers (else UAVSAL_EALIGN); seq_len < 2 or
+ *   n_img % seq_len != 0: UAVSAL_ESHAPE.  ONE launch.
+ */
+typedef struct uavsal_cbr_sums_desc {
+    const float* g;  int32_t ldg;           /* [n_img * H * W] rows of C floats */
+    const float* y;  int32_t ldy;           /* [n_img * H * W] rows of C floats */
+    float* gp;                              /* dense [n_img][H][W][C] */
+    double* ws;  int64_t ws_bytes;
+    int32_t n_img, H, W, C;
+} uavsal_cbr_sums_desc;
+
+typedef struct uavsal_cbr_finish_desc {
+    const double* ws;  int64_t ws_bytes;
+    const double* rowdot;                   /* [C] */
+    const float* r;  const float* mu;       /* [C] */
+    float* g_gamma;  float* g_beta;         /* [C] */
+    int32_t C, slabs, accumulate;
+} uavsal_cbr_finish_desc;
+
+typedef struct uavsal_tdiff_bwd_desc {
+    const float* g;  int32_t ldg;           /* [n_img * HW] rows of 2 C floats */
+    const float* r;  int32_t ldr;           /* [n_img * HW] rows of C floats */
+    float* out;      int32_t ldo;           /* [n_img * HW] rows of C floats */
+    int32_t n_img, HW, C, seq_len;
+} uavsal_tdiff_bwd_desc;
+
+int64_t uavsal_cbr_sums_workspace_bytes(const uavsal_cbr_sums_desc* d);
+int uavsal_cbr_sums_slabs(const uavsal_cbr_sums_desc* d);           /* slabs of that call (no launch) */
+int uavsal_cbr_sums_slab_rows(const uavsal_cbr_sums_desc* d);       /* picture rows per slab */
+int uavsal_cbr_sums(const uavsal_cbr_sums_desc* d, uavsal_stream_t stream);
+int uavsal_cbr_finish(const uavsal_cbr_finish_desc* d, uavsal_stream_t stream);
+int uavsal_tdiff_bwd(const uavsal_tdiff_bwd_desc* d, uavsal_stream_t stream);
+int uavsal_st_sizeof_desc(int which);     /* 0 cbr_sums, 1 cbr_finish, 2 tdiff_bwd (uavsal_nets_sizeof_desc is closed at 3) */
 
 /* ---- repacking refreshed weights on the device (csrc/repack.hip) ---------------------------------------------------------
  * After an optimiser step the packed copies of a module's weights are remade FROM the fp32 parameters and buffers where they

@@ -45,6 +45,18 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                64, ob0: 20 -> 120 -> 64) `train.narrow_block_param_grads` from given parts (two launches) and its first
                launch `uavsal_ir_narrow_grads` alone, with the slab count; `uavsal_frame_sum` of one 64-channel slice of
                g_cb; and `refresh_weights` over the six stages (refresh6);
+  st           the ST blocks trained too, the seventh stage (`model.st_layer`, 27 parameters per block): the six-stage step
+               (step6b) and the same with `st=True` (step7), alternated in the same run, every run listed (the spread);
+               `train.st_block_backward` of the last block (st_block_bwd_x: with the input gradient) and of block 0
+               (st_block_bwd: without); and per launch family at a block's shapes, from the tensors the walk hands out:
+               the forward's recompute (st_recompute: the nine launches), the spatial branch's `train.block_backward`
+               (st_spconv_bwd), the sub-block's input-gradient walk and `train.block_param_grads` at 64 -> 384 -> 32
+               (st_sub_walk, st_sub_param_grads), `train.cbr_backward` of the three 1x1 stages (st_cbr_last 256 -> 256,
+               st_cbr_te_last 32 -> 256, st_cbr_reduce 256 -> 32), `uavsal_cbr_sums` alone at 256 and at 32 channels (GB/s
+               from g, y read and gp written), `uavsal_tdiff_bwd` alone (GB/s from g_dif, r read and gp_r written), the
+               pixel GEMM with its reduction at 256 x 256 (the 128 x 128 tile kernel) and at the three 32-wide shapes
+               (st_pix_gemm_32x256, _256x32, _32x384: the sibling kernel; shares and TFLOP/s), and `refresh_weights` over
+               the seven stages on the host and on the device (refresh7, refresh7_device).  Alone: --st-only;
   refresh pairs beside every refresh case above its `_device` twin: the same in-place edit, then `refresh_weights(...,
                device=True)` (csrc/repack.hip: one launch, no host copy); and at the end (or alone: --refresh-only) the
                host and device refresh of 1, 4, 5 and 6 stages (refreshN_alt / refreshN_device_alt) and one whole six-stage
@@ -55,7 +67,7 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
 
-Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--frames 20 5]
+Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--frames 20 5]
 """
 import argparse
 import ctypes as C
@@ -412,6 +424,110 @@ def nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
         q.grad = None
 
 
+def st_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
+    """the phases of the trained ST blocks (model.st_layer), the seventh stage, added to `res`"""
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    nets = tuple(train.prior_nets(m).values())
+    boxes = (m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer, m.fucb_layer, m.cxt_cb_prior) + nets + (m.st_layer,)
+    trained = [q for mod in boxes for q in mod.parameters()]
+    kw6 = dict(decoder=True, fuse=True, fust=True, ctx=True, nets=True)
+    taps = {}
+    m(x, cb, None, taps=taps)
+    n_st = len(m.st_layer)
+    blk = m.st_layer[n_st - 1]
+    x_in = (taps["st%d" % (n_st - 2)] if n_st > 1 else taps["sfnet"]).contiguous(memory_format=cl)
+    x0 = taps["sfnet"].contiguous(memory_format=cl)
+    go = (torch.randn_like(x_in) / x_in[0].numel()).contiguous(memory_format=cl)      # (timing only: any gradient of the right shape)
+    T = x_in.shape[0]
+    pt = {}
+    _, grads = train.st_block_backward(blk, x_in, go, seq_len=T, cache=cache, parts=pt)
+    _, grads0 = train.st_block_backward(m.st_layer[0], x0, go, seq_len=T, need_x_grad=False, cache=cache)
+    nchw = lambda t: t.permute(0, 3, 1, 2)                     # noqa: E731
+    te = blk.stconv_te
+    xn, gon = x_in.permute(0, 2, 3, 1), go.permute(0, 2, 3, 1)
+    n_pix = xn.shape[0] * xn.shape[1] * xn.shape[2]
+    sub = {n: grads["stconv_te.sub_conv." + n] for n in train.BLOCK_PARAMS}
+    spg = {n: grads["stconv_sp.spconv." + n] for n in train.BLOCK_PARAMS}
+    cbr = {k: {n: grads[p + n] for n in train.ST_CBR_PARAMS}
+           for k, p in (("last", "stconv_last."), ("te_last", "stconv_te.last_conv."), ("reduce", "stconv_te.reduce_conv."))}
+    p_sub = train._input_grad_parts(te.sub_conv)
+
+    def recompute():
+        train._block_recompute(lib, cache, blk.stconv_sp.spconv, xn)
+        train._conv(lib, cache, pt["d_sp"], blk.stconv_sp.spconv.conv[2], 256, 1, bn=blk.stconv_sp.spconv.conv[3])
+        train._conv(lib, cache, xn, te.reduce_conv[0], 32, 1, bn=te.reduce_conv[1], act=L.ACT_RELU6)
+        ops.tdiff(pt["r"], T)
+        train._block_recompute(lib, cache, te.sub_conv, pt["dif"], 1, p_sub)
+        train._conv(lib, cache, pt["d_te"], p_sub[4], 32, 1, bn=p_sub[5])
+        train._conv(lib, cache, pt["t1"], te.last_conv[0], 256, 1, bn=te.last_conv[1], act=L.ACT_RELU6)
+        train.tsum_bwd(pt["a_te"], pt["x_sp"], 1)
+        train._conv(lib, cache, pt["ssum"], blk.stconv_last[0], 256, 1, bn=blk.stconv_last[1], act=L.ACT_RELU6)
+
+    def stepper(**kw):
+        def run():
+            for q in trained:
+                q.grad = None
+            train.recurrence_step(m, x, cb, None, y_gaze, **kw6, **kw)
+        return run
+
+    def refresh7(device=False):
+        with torch.no_grad():
+            for q in trained:
+                q.mul_(1.0)
+        m.refresh_weights(*boxes, device=device)
+    gems = {}
+    for tag, (a, b, M, N) in (("256x256", (pt["g_sum"], pt["ssum"], 256, 256)), ("32x256", (pt["gp_r"], xn, 32, 256)),
+                              ("256x32", (pt["g_sum"], pt["t1"], 256, 32)), ("32x384", (pt["g_t1"], pt["d_te"], 32, 384))):
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+        rd = torch.empty(M, dtype=torch.float64, device=dev)
+        w = torch.randn((M, N), dtype=torch.float32, device=dev)
+        rsc = torch.ones(M, dtype=torch.float32, device=dev)
+        gems[tag] = (M, N, lambda a=a, b=b, out=out, rd=rd, w=w, rsc=rsc: train.pix_gemm(a, b, out=out, row_scale=rsc, w=w, rowdot=rd))
+    cases = {"st_block_bwd_x": lambda: train.st_block_backward(blk, x_in, go, seq_len=T, cache=cache, grads=grads),
+             "st_block_bwd": lambda: train.st_block_backward(m.st_layer[0], x0, go, seq_len=T, need_x_grad=False, cache=cache, grads=grads0),
+             "st_recompute": recompute,
+             "st_spconv_bwd": lambda: train._block_backward(blk.stconv_sp.spconv, x_in, nchw(pt["g_sum"]), True, cache, None, spg, False,
+                                                            ed=(pt["e_sp"], pt["d_sp"]), res=gon),
+             "st_sub_walk": lambda: train._input_grad(lib, cache, te.sub_conv, p_sub, pt["dif"], pt["g_t1"], ed=(pt["e_te"], pt["d_te"])),
+             "st_sub_param_grads": lambda: train.block_param_grads(te.sub_conv, nchw(pt["dif"]), pt["e_te"], pt["d_te"], nchw(pt["g_t1"]),
+                                                                   gd=pt["sub"]["gd"], ga=pt["sub"]["ga"], cache=cache, out=sub),
+             "st_cbr_last": lambda: train.cbr_backward(blk.stconv_last[0], blk.stconv_last[1], nchw(pt["ssum"]), pt["o"], go, cache=cache,
+                                                       grads=cbr["last"]),
+             "st_cbr_te_last": lambda: train.cbr_backward(te.last_conv[0], te.last_conv[1], nchw(pt["t1"]), pt["a_te"], nchw(pt["g_sum"]),
+                                                          cache=cache, grads=cbr["te_last"]),
+             "st_cbr_reduce": lambda: train._cbr_backward(te.reduce_conv[0], te.reduce_conv[1], x_in, pt["r"], nchw(pt["gp_r"]), True, cache,
+                                                          cbr["reduce"], False, res=pt["gx_sp"]),
+             "st_cbr_sums_256": lambda: train.cbr_sums(gon, pt["o"]),
+             "st_cbr_sums_32": lambda: train.cbr_sums(pt["gp_r"], pt["r"]),
+             "st_tdiff_bwd": lambda: train.tdiff_bwd(pt["g_dif"], pt["r"], T),
+             "refresh7": refresh7, "refresh7_device": lambda: refresh7(True)}
+    for tag, (_, _, fn) in gems.items():
+        cases["st_pix_gemm_" + tag] = fn
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    for tag, (M, N, _) in gems.items():
+        gd = L.PixGemmDesc()
+        gd.K, gd.M, gd.N = n_pix, M, N
+        res["st_pix_gemm_%s_shares" % tag] = int(lib.uavsal_pix_gemm_shares(C.byref(gd)))
+        res["st_pix_gemm_%s_tflops" % tag] = 2.0 * M * N * n_pix / (res["st_pix_gemm_%s_ms" % tag] * 1e-3) / 1e12
+    res["st_cbr_sums_256_gbs"] = 3.0 * 256 * 4 * n_pix / (res["st_cbr_sums_256_ms"] * 1e-3) / 1e9
+    res["st_cbr_sums_32_gbs"] = 3.0 * 32 * 4 * n_pix / (res["st_cbr_sums_32_ms"] * 1e-3) / 1e9
+    res["st_tdiff_bwd_gbs"] = 4.0 * 32 * 4 * n_pix / (res["st_tdiff_bwd_ms"] * 1e-3) / 1e9
+    runs = {"step6b": stepper(), "step7": stepper(st=True)}
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # the two steps alternated in the same run
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    for q in trained:
+        q.grad = None
+
+
 def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
     """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
     from iip_uavsal_saliency_amd import repack
@@ -468,7 +584,7 @@ def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
         q.grad = None
 
 
-def bench(T, iters, repeats, dev, skip_eager, refresh_only=False):
+def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
@@ -487,6 +603,10 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False):
     if refresh_only:
         res = {"T": T}
         refresh_phases(res, m, x, cb, y_gaze, iters, repeats)
+        return res
+    if st_only:
+        res = {"T": T}
+        st_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
         return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -585,6 +705,7 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False):
     fust_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+    st_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
     refresh_phases(res, m, x, cb, y_gaze, iters, repeats)
     if not skip_eager:
         try:
@@ -604,11 +725,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--skip-eager", action="store_true")
     ap.add_argument("--refresh-only", action="store_true", help="only the refresh / iteration pairs (refresh_phases)")
+    ap.add_argument("--st-only", action="store_true", help="only the phases of the seventh stage (st_phases)")
     ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
     out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
-           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only) for T in a.frames]}
+           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only) for T in a.frames]}
     print(json.dumps(out))
 
 
