@@ -352,6 +352,24 @@ class TdiffBwdDesc(C.Structure):
 
 ST_DESC_TYPES = [CbrSumsDesc, CbrFinishDesc, TdiffBwdDesc]      # sized by uavsal_st_sizeof_desc (csrc/train_st.hip)
 
+
+class Conv3WgradDesc(C.Structure):
+    _fields_ = [("g", _f), ("x", _f), ("ldx", C.c_int32), ("row_scale", _f), ("w", _f), ("rowdot", C.c_void_p),
+                ("ws", _f), ("ws_bytes", C.c_int64), ("out", _f),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Co", C.c_int32), ("Ci", C.c_int32),
+                ("accumulate", C.c_int32)]
+
+
+class IrBwdDilDesc(C.Structure):
+    _fields_ = IrBwdDesc._fields_ + [("dil", C.c_int32)]
+
+
+class IrSumsDilDesc(C.Structure):
+    _fields_ = IrSumsDesc._fields_ + [("dil", C.c_int32)]
+
+
+SRF_DESC_TYPES = [Conv3WgradDesc, IrBwdDilDesc, IrSumsDilDesc]  # sized by uavsal_srf_sizeof_desc (csrc/train_srf.hip)
+
 REPACK_MAX_SRC = 4            # UAVSAL_REPACK_MAX_SRC: weights / BatchNorms side by side in one entry (csrc/repack.hip)
 REPACK_CONV, REPACK_WINO, REPACK_FOLD, REPACK_DW, REPACK_COPY = range(5)
 REPACK_LAYOUT = {"f32": 0, "f32k32": 0, "f16x3": 1, "f16x3i": 2, "f16x3j": 3, "bf16": 4, "bf16x3": 5}
@@ -445,6 +463,15 @@ SYMBOLS = [
     ("uavsal_cbr_finish", C.c_int, [C.POINTER(CbrFinishDesc), C.c_void_p]),
     ("uavsal_tdiff_bwd", C.c_int, [C.POINTER(TdiffBwdDesc), C.c_void_p]),
     ("uavsal_st_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_conv3_wgrad_workspace_bytes", C.c_int64, [C.POINTER(Conv3WgradDesc)]),
+    ("uavsal_conv3_wgrad_shares", C.c_int, [C.POINTER(Conv3WgradDesc)]),
+    ("uavsal_conv3_wgrad", C.c_int, [C.POINTER(Conv3WgradDesc), C.c_void_p]),
+    ("uavsal_ir_bwd_dil", C.c_int, [C.POINTER(IrBwdDilDesc), C.c_void_p]),
+    ("uavsal_ir_sums_dil_workspace_bytes", C.c_int64, [C.POINTER(IrSumsDilDesc)]),
+    ("uavsal_ir_sums_dil_slabs", C.c_int, [C.POINTER(IrSumsDilDesc)]),
+    ("uavsal_ir_sums_dil_slab_rows", C.c_int, [C.POINTER(IrSumsDilDesc)]),
+    ("uavsal_ir_sums_dil", C.c_int, [C.POINTER(IrSumsDilDesc), C.c_void_p]),
+    ("uavsal_srf_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_repack", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("uavsal_repack_sizeof_desc", C.c_int, []),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
@@ -530,7 +557,7 @@ def load():
                           (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES),
                           (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES),
                           (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES),
-                          (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES)):
+                          (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES), (lib.uavsal_srf_sizeof_desc, SRF_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

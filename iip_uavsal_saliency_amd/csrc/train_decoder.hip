@@ -168,11 +168,14 @@ __global__ __launch_bounds__(256) void pix_gemm_reduce_kernel(const PgK k) {
 // least one whole workgroup of four tiles; every tile of the wide side reads the narrow operand again, which is what the
 // shapes of an ST block (256, 384) want.  Narrower and wider ones stay refused, as they always were: the cap only has to
 // keep out what re-reading the narrow operand per tile would make slow (1920 x 32 is 60 tiles); 512 is the next power of two
-// above the widest shape in use, not a tuned value
+// above the widest shape in use, not a tuned value.  The same kernel takes M a multiple of 64 with N an ODD multiple of 32
+// under the same cap (the SRF-Net head's conv_lv3 64 x 32 -- two tiles, two idle waves -- and conv_lv4 128 x 96): the 128 x 128
+// tile kernel cannot end a tile at column 32 or 96.
 constexpr int kNarrowMin = 128, kNarrowMax = 512;
 bool pg_narrow(int M, int N) {
     const int wide = M > N ? M : N;
-    return (M == 32 || N == 32) && !(wide % 32) && wide >= kNarrowMin && wide <= kNarrowMax;
+    if ((M == 32 || N == 32) && !(wide % 32) && wide >= kNarrowMin && wide <= kNarrowMax) return true;
+    return !(M % 64) && (N % 64) == 32 && M <= kNarrowMax && N <= kNarrowMax;
 }
 bool pg_shape_ok(int M, int N) { return pg_narrow(M, N) || (!(M % (kTile / 2)) && !(N % (kTile / 2))); }
 

@@ -408,6 +408,9 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `"st"` (the very last stage, only behind `"fuse"` and, in a model with priors, `"fust"`): `recurrence_step(..., st=True)`
     also sets the gradients of the ST blocks `model.st_layer` -- frozen in the reference's own `train()`, the first thing to
     unfreeze on a new dataset -- and `model.st_layer` is refreshed as well.
+    `"srf"` (the very last stage of all, only behind `"st"`): `recurrence_step(..., srf=True)` also sets the gradients of the
+    SRF-Net head `train.srf_head(model)` -- everything in `model.sfnet` but the ImageNet `features` -- and those eight modules
+    are refreshed as well.
     `refresh`: `"host"` (the default) repacks the trained stages' weights on the host after every step; `"device"` repacks
     them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host)."""
     from . import losses as _losses
@@ -421,10 +424,11 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     allowed += [s + ("ctx",) for s in allowed if "fuse" in s]
     allowed += [s + ("nets",) for s in allowed if "fuse" in s]
     allowed += [s + ("st",) for s in allowed if "fuse" in s and ("fust" in s or not getattr(model, "num_cb", 0))]
+    allowed += [s + ("srf",) for s in allowed if "st" in s]
     if stages not in allowed:
         raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
                          "'fuse' (then 'ctx', then 'nets', behind 'fuse' too; 'st' the very last, behind 'fuse' and, in a "
-                         "model with priors, 'fust'), got %r" % (stages,))
+                         "model with priors, 'fust'; only 'srf' may follow 'st'), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
@@ -444,6 +448,8 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
             mods.extend(_train.prior_nets(model).values())
         if "st" in kw:
             mods.append(model.st_layer)
+        if "srf" in kw:
+            mods.extend(_train.srf_head(model))
         if refresh == "device":
             model.refresh_weights(*mods, device=True)
         else:

@@ -29,8 +29,11 @@ for every frame).  With all six, a step sets the gradient of every parameter the
 gives: the ST blocks `model.st_layer` (`recurrence_step(st=True)`, `st_block_backward`): the two inverted-residual blocks of an
 ST block go through the walks above (`block_param_grads` takes the temporal sub-block's 64 -> 384 -> 32, `uavsal_pix_gemm` its
 32-wide side), the three 1x1 conv + BatchNorm + ReLU6 stages through `cbr_backward` and the temporal difference through
-`tdiff_bwd` (csrc/train_st.hip: `uavsal_cbr_sums`, `uavsal_cbr_finish`, `uavsal_tdiff_bwd`).  The backbone `sfnet` stays frozen;
-BatchNorm in eval mode remains the documented difference.
+`tdiff_bwd` (csrc/train_st.hip: `uavsal_cbr_sums`, `uavsal_cbr_finish`, `uavsal_tdiff_bwd`).  And an eighth: the head of the backbone
+`sfnet` -- everything in it the reference initialises itself (`recurrence_step(srf=True)`, `srf_head`, `srf_head_backward`): its 1x1
+stages go through `cbr_backward`, its dilated ASPP branches through `block_param_grads` (csrc/train_srf.hip: `uavsal_ir_bwd_dil`,
+`uavsal_ir_sums_dil`) and the dense 3x3 `conv_last` through `conv3_backward` (`uavsal_conv3_wgrad`).  Only the ImageNet MobileNetV2
+`sfnet.features` stay frozen; BatchNorm in eval mode remains the documented difference.
 
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
@@ -370,12 +373,17 @@ def _param_grad_parts(block):
     `_block_parts` takes, and stride 2 and Cout % 64 == 0 besides (the blocks of the multi-prior path), or a RuntimeError."""
     seq = getattr(block, "conv", None)
     stride = getattr(block, "stride", None)
+    dil = getattr(block, "dilation", None)
     if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4 or stride not in (1, 2)
-            or getattr(block, "dilation", None) != 1 or seq[1][0].stride != (stride, stride) or seq[1][0].dilation != (1, 1)):
-        raise RuntimeError("block_param_grads takes a dwBlock with an expand conv, stride 1 or 2 and dilation 1 "
-                           "(expand 1x1, depthwise 3x3, projection 1x1)")
+            or not isinstance(dil, int) or dil < 1 or (dil > 1 and stride != 1)
+            or seq[1][0].stride != (stride, stride) or seq[1][0].dilation != (dil, dil)):
+        raise RuntimeError("block_param_grads takes a dwBlock with an expand conv, stride 1 or 2 and dilation 1, or stride 1 and "
+                           "a dilation above 1 (expand 1x1, depthwise 3x3, projection 1x1)")
     pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
     hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    if dil > 1 and cout % 128:                                      # the ASPP branches of the SRF-Net head: 320 -> 1920 -> 256
+        raise RuntimeError("block_param_grads takes a dilated block with Cout %% 128 == 0 only, got %d -> %d -> %d, dilation %d"
+                           % (cin, hid, cout, dil))
     narrow = cout == 32 and 128 <= hid <= 512                       # an ST block's sub_conv, 64 -> 384 -> 32 (uavsal_pix_gemm's 32-wide side)
     if (cout % 64 and not narrow) or hid % 64 or cin % 64:
         raise RuntimeError("block_param_grads needs Cout %% 64 == 0 (or Cout == 32 with 128 <= hidden <= 512), hidden %% 64 == 0 "
@@ -485,6 +493,55 @@ def ir_sums_s2(gd, d, e, ga, go):
     return ws, int(lib.uavsal_ir_sums_s2_slabs(C.byref(k)))
 
 
+def ir_bwd_dil(gd, d, e, wd9, s2, dil):
+    """`uavsal_ir_bwd_dil` on the current stream: `ir_bwd` for a depthwise 3x3 with stride 1 and dilation `dil` >= 1 (the ASPP
+    branches of the SRF-Net head): `gd`, `d`, `e` dense NHWC `[T,h,w,C]` -> `ga` = d loss / d a1, dense NHWC."""
+    lib = L.load()
+    _dense_nhwc("ir_bwd_dil", "gd, d, e", gd, d, e)
+    if gd.shape != d.shape or e.shape != d.shape or any(t.device != e.device for t in (gd, d)):
+        raise RuntimeError("ir_bwd_dil: gd, d, e must have one shape on one device")
+    if not isinstance(dil, int) or dil < 1:
+        raise RuntimeError("ir_bwd_dil: the dilation must be an integer >= 1, got %r" % (dil,))
+    T, hh, ww, c = e.shape
+    for name, t, n in (("wd9", wd9, 9 * c), ("s2", s2, c)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == e.device and t.is_contiguous() and t.numel() >= n):
+            raise RuntimeError("ir_bwd_dil: %s must be a dense float32 tensor of at least %d elements on the device of e" % (name, n))
+    ga = torch.empty_like(e)
+    k = L.IrBwdDilDesc()
+    k.gd, k.d, k.e, k.wd9, k.s2, k.ga = gd.data_ptr(), d.data_ptr(), e.data_ptr(), wd9.data_ptr(), s2.data_ptr(), ga.data_ptr()
+    k.n_img, k.H, k.W, k.C, k.dil = T, hh, ww, c, dil
+    L.check(lib.uavsal_ir_bwd_dil(C.byref(k), _stream(e)), "uavsal_ir_bwd_dil")
+    return ga
+
+
+def ir_sums_dil(gd, d, e, ga, go, dil):
+    """`uavsal_ir_sums_dil` on the current stream -> `(ws, slabs)`: `ir_sums` for a depthwise 3x3 with stride 1 and dilation
+    `dil` >= 1, in the same workspace layout.  `gd`, `d`, `e`, `ga` dense NHWC `[T,h,w,Ch]`; `go` an NHWC view `[T,h,w,Co]` of
+    the same pixels (a channel slice is read in place)."""
+    lib = L.load()
+    _dense_nhwc("ir_sums_dil", "gd, d, e, ga", gd, d, e, ga)
+    if not all(t.shape == e.shape and t.device == e.device for t in (gd, d, ga)):
+        raise RuntimeError("ir_sums_dil: gd, d, e, ga must have one shape on one device")
+    if not isinstance(dil, int) or dil < 1:
+        raise RuntimeError("ir_sums_dil: the dilation must be an integer >= 1, got %r" % (dil,))
+    T, hh, ww, c = e.shape
+    if not torch.is_tensor(go) or go.dtype != torch.float32 or go.device != e.device:
+        raise RuntimeError("ir_sums_dil: go must be a float32 tensor on the device of e")
+    gp, ldgo, *gs = _nhwc_view(go)
+    if gs[:3] != [T, hh, ww]:
+        raise RuntimeError("ir_sums_dil: go must cover the pixels of e")
+    k = L.IrSumsDilDesc()
+    k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
+    k.n_img, k.H, k.W, k.Ch, k.Co, k.dil = T, hh, ww, c, gs[3], dil
+    nbytes = int(lib.uavsal_ir_sums_dil_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_ir_sums_dil")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    L.check(lib.uavsal_ir_sums_dil(C.byref(k), _stream(e)), "uavsal_ir_sums_dil")
+    return ws, int(lib.uavsal_ir_sums_dil_slabs(C.byref(k)))
+
+
 def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, out=None, accumulate=False):
     """The gradients of the nine parameters of an inverted-residual `block` (a `dwBlock` with an expand conv, stride 1 or 2,
     dilation 1, with or without the residual; eval mode: the BatchNorms on their running statistics, which are not updated)
@@ -499,11 +556,13 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
     reductions -- `ga` x `x` for W1, `grad_out` x `d` for W3 --, channel sums, finalise) on the current stream, no
     synchronisation.  Accepted: Co % 64 == 0 -- or Co == 32 with 128 <= Ch <= 512, the temporal sub-block of an ST block
     (64 -> 384 -> 32), whose W3 product is the pixel GEMM's 32-wide side --, Ch % 64 == 0, Cin % 64 == 0 (`block_backward`, which recomputes `e` and `d`
-    itself, keeps to stride 1 and Co % 128 == 0)."""
+    itself, keeps to stride 1 and Co % 128 == 0).  A block with stride 1 and a DILATED depthwise conv (the ASPP branches of the
+    SRF-Net head, 320 -> 1920 -> 256 at dilation 6 / 12 / 18) is taken with Co % 128 == 0: `uavsal_ir_bwd_dil` and
+    `uavsal_ir_sums_dil` stand in for the undilated launches, everything else is the same."""
     lib = L.load()
     pw, pwbn, dwc, dwbn, pl, plbn = _param_grad_parts(block)
     hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
-    stride = dwc.stride[0]
+    stride, dil = dwc.stride[0], dwc.dilation[0]
     xn = _nhwc(x, "x", cin)
     T, hh, ww, _ = xn.shape
     ho, wo = (hh - 1) // stride + 1, (ww - 1) // stride + 1
@@ -524,13 +583,13 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
         if gd is None:
             gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
         if ga is None:
-            ga = (ir_bwd if stride == 1 else ir_bwd_s2)(gd, d, e, w9, s2)
+            ga = ir_bwd_dil(gd, d, e, w9, s2, dil) if dil > 1 else (ir_bwd if stride == 1 else ir_bwd_s2)(gd, d, e, w9, s2)
         (r1, mu1), (r2, mu2), (r3, mu3) = (cache.bn_stats(b) for b in (pwbn, dwbn, plbn))
         rd1 = torch.empty(hid, dtype=torch.float64, device=dev)
         rd3 = torch.empty(cout, dtype=torch.float64, device=dev)
         pix_gemm(ga, xn, out=out[BLOCK_PARAMS[0]], row_scale=s1, w=pw.weight.detach(), rowdot=rd1, accumulate=accumulate)
         pix_gemm(go, d, out=out[BLOCK_PARAMS[6]], row_scale=s3, w=pl.weight.detach(), rowdot=rd3, accumulate=accumulate)
-        ws, slabs = (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go)
+        ws, slabs = ir_sums_dil(gd, d, e, ga, go, dil) if dil > 1 else (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go)
         k = L.IrFinishDesc()
         k.ws, k.ws_bytes, k.rowdot1, k.rowdot3 = ws.data_ptr(), ws.numel() * 8, rd1.data_ptr(), rd3.data_ptr()
         k.wd, k.s2 = dwc.weight.data_ptr(), s2.data_ptr()
@@ -542,9 +601,10 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
     return out
 
 
-def _block_recompute(lib, cache, block, x, stride=1, prt=None):
+def _block_recompute(lib, cache, block, x, stride=1, prt=None, dilation=1):
     """`e`, `d` (dense NHWC) from the NHWC `x` by the forward's own launches (expand conv, `uavsal_dw3x3`); `stride` 2: `d` is
-    `[T, (h-1)/2+1, (w-1)/2+1, Ch]`.  `prt`: the block's parts when the caller has checked them (`_input_grad_parts`)."""
+    `[T, (h-1)/2+1, (w-1)/2+1, Ch]`.  `prt`: the block's parts when the caller has checked them (`_input_grad_parts`);
+    `dilation`: that of the depthwise conv (stride 1: `srf_head_backward`)."""
     pw, pwbn, dwc, dwbn, _, _ = prt or _block_parts(block)
     T, hh, ww, _ = x.shape
     hid = pw.weight.shape[0]
@@ -554,7 +614,7 @@ def _block_recompute(lib, cache, block, x, stride=1, prt=None):
     q = L.DwDesc()
     q.inp, q.ldi, q.w9c, q.scale, q.bias = e.data_ptr(), hid, w9.data_ptr(), s2.data_ptr(), b2.data_ptr()
     q.out, q.ldo = dd.data_ptr(), hid
-    q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, stride, 1, L.ACT_RELU6
+    q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, hid, stride, dilation, L.ACT_RELU6
     L.check(lib.uavsal_dw3x3(C.byref(q), _stream(x)), "uavsal_dw3x3")
     return e, dd
 
@@ -1220,6 +1280,240 @@ def st_block_backward(block, x, grad_out, seq_len=None, need_x_grad=True, cache=
     return g, grads
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# The SRF-Net head (model.sfnet without its MobileNetV2 `features`): an eighth stage (csrc/train_srf.hip)
+SRF_HEAD = ("conv_lv3", "conv_lv4", "lv5_aspp1", "lv5_aspp2", "lv5_aspp3", "lv5_aspp4", "conv_lv5", "conv_last")
+SRF_HEAD_BLOCKS = ("lv5_aspp2", "lv5_aspp3", "lv5_aspp4")           # the dilated inverted-residual branches; the rest conv + BN + ReLU6
+SRF_HEAD_PARAMS = tuple("%s.%s" % (m, n) for m in SRF_HEAD                 # the 42 names, relative to sfnet, in named_parameters() order
+                        for n in (BLOCK_PARAMS if m in SRF_HEAD_BLOCKS else ST_CBR_PARAMS))
+
+
+def srf_head(model):
+    """The eight trainable modules of the SRF-Net head, in `SRF_HEAD` order: what the reference initialises itself in
+    `uavsal_srfnet_aspp` (model.py:120-131).  Hand their parameters to the optimiser and the modules to
+    `model.refresh_weights(*train.srf_head(model))` -- never `model.sfnet` itself, whose frozen `features` hold fused blocks and
+    the stem, which cannot be refreshed in place."""
+    sf = getattr(model, "sfnet", model)
+    return [getattr(sf, n) for n in SRF_HEAD]
+
+
+def conv3_wgrad(g, x, out=None, row_scale=None, w=None, rowdot=None, accumulate=False):
+    """`uavsal_conv3_wgrad` on the current stream: `g` dense NHWC `[n,h,w,Co]`, `x` an NHWC view `[n,h,w,Ci]` of the same pixels
+    (a channel slice is read in place) -> `out[co][ci][ky][kx] = row_scale[co] sum_p g[p][co] x[p + (ky-1, kx-1)][ci]` (dense
+    `[Co,Ci,3,3]`, zero outside the picture, never across frames; `accumulate`: added to `out`), and with `w` `[Co,Ci,3,3]` and
+    `rowdot` (float64 `[Co]`) `rowdot[co] = sum w[co] G[co]`.  Co % 128 == 0, Ci % 64 == 0.  Two launches, no synchronisation."""
+    lib = L.load()
+    _dense_nhwc("conv3_wgrad", "g", g)
+    xp, ldx, *xs = _nhwc_view(x)
+    n, hh, ww, co = g.shape
+    if xs[:3] != [n, hh, ww] or x.device != g.device:
+        raise RuntimeError("conv3_wgrad: g and x must cover the same pixels on one device")
+    ci, dev = xs[3], g.device
+    if co % 128 or ci % 64:
+        raise RuntimeError("conv3_wgrad takes Co %% 128 == 0 and Ci %% 64 == 0, got Co = %d, Ci = %d" % (co, ci))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `out`")
+        out = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (co, ci, 3, 3) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError("out must be a dense float32 [%d,%d,3,3] tensor on the device" % (co, ci))
+    k = L.Conv3WgradDesc()
+    k.g, k.x, k.ldx = g.data_ptr(), xp, ldx
+    k.n_img, k.H, k.W, k.Co, k.Ci, k.accumulate = n, hh, ww, co, ci, int(bool(accumulate))
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or row_scale.device != dev or row_scale.numel() < co or not row_scale.is_contiguous():
+            raise RuntimeError("row_scale must be a dense float32 vector of at least %d elements on the device" % co)
+        k.row_scale = row_scale.data_ptr()
+    if rowdot is not None:
+        if (w is None or tuple(w.shape) != (co, ci, 3, 3) or not w.is_contiguous() or w.dtype != torch.float32 or w.device != dev
+                or rowdot.dtype != torch.float64 or rowdot.numel() != co or not rowdot.is_contiguous() or rowdot.device != dev):
+            raise RuntimeError("rowdot needs a dense float32 `w` [%d,%d,3,3] and a dense float64 [%d] on the device" % (co, ci, co))
+        k.w, k.rowdot = w.data_ptr(), rowdot.data_ptr()
+    nbytes = int(lib.uavsal_conv3_wgrad_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_conv3_wgrad")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    k.ws, k.ws_bytes, k.out = ws.data_ptr(), nbytes, out.data_ptr()
+    L.check(lib.uavsal_conv3_wgrad(C.byref(k), _stream(g)), "uavsal_conv3_wgrad")
+    return out
+
+
+def _conv3_parts(conv, bn):
+    if (not isinstance(conv, torch.nn.Conv2d) or not isinstance(bn, torch.nn.BatchNorm2d) or conv.kernel_size != (3, 3)
+            or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1
+            or conv.bias is not None):
+        raise RuntimeError("conv3_backward takes the dense 3x3 conv (no bias, stride 1, padding 1, dilation 1, one group) and the "
+                           "BatchNorm of a BasicConv2d")
+    cout, cin = conv.weight.shape[:2]
+    if cout % 128 or cin % 64:
+        raise RuntimeError("conv3_backward needs Cout %% 128 == 0 and Cin %% 64 == 0, got %d -> %d" % (cin, cout))
+    if bn.training:
+        raise RuntimeError("the BatchNorm uses its running statistics: call model.eval()")
+    return cin, cout
+
+
+def conv3_backward(conv, bn, x, y, grad_out, need_x_grad=True, cache=None, grads=None, accumulate=False):
+    """`cbr_backward` for a dense 3x3 conv + BatchNorm + ReLU6 (the head's `conv_last`; eval mode, teacher-forced): `x`
+    `[N,Cin,h,w]` its input, `y` an NHWC view `[N,h,w,C]` of its activation, `grad_out` `[N,C,h,w]`.  Returns
+    `(grad_x [N,Cin,h,w] | None, grads)`, `grads` keyed by `ST_CBR_PARAMS`.  `uavsal_cbr_sums` forms `gp` and its channel sums,
+    `uavsal_conv3_wgrad` `s[c] G[c][j][ky][kx]` and the row dots, `uavsal_cbr_finish` beta and gamma, and `grad_x` is one 3x3
+    GEMM with the flipped, transposed weights that carry s in their rows.  Accepted: C % 128 == 0, Cin % 64 == 0."""
+    lib = L.load()
+    cin, cout = _conv3_parts(conv, bn)
+    xn = _nhwc(x, "x", cin)
+    go = _block_grad_out(grad_out, xn, cout)
+    dev = xn.device
+    if (not torch.is_tensor(y) or y.dtype != torch.float32 or y.device != dev or tuple(y.shape) != tuple(go.shape)):
+        raise RuntimeError("y must be a float32 NHWC view %r on the device of x" % (tuple(go.shape),))
+    params, grads = _cbr_grad_tensors(conv, bn, grads, accumulate)
+    if any(q.device != dev or not q.is_contiguous() for q in params.values()):
+        raise RuntimeError("the parameters must be dense tensors on the device of `x`")
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        s = cache.affine(bn, cout)[0]
+        r, mu = cache.bn_stats(bn)
+        gp, ws, slabs = cbr_sums(go, y)
+        rowdot = torch.empty(cout, dtype=torch.float64, device=dev)
+        conv3_wgrad(gp, xn, out=grads[ST_CBR_PARAMS[0]], row_scale=s, w=conv.weight.detach(), rowdot=rowdot, accumulate=accumulate)
+        k = L.CbrFinishDesc()
+        k.ws, k.ws_bytes, k.rowdot, k.r, k.mu = ws.data_ptr(), ws.numel() * 8, rowdot.data_ptr(), r.data_ptr(), mu.data_ptr()
+        k.g_gamma, k.g_beta = grads[ST_CBR_PARAMS[1]].data_ptr(), grads[ST_CBR_PARAMS[2]].data_ptr()
+        k.C, k.slabs, k.accumulate = cout, slabs, int(bool(accumulate))
+        L.check(lib.uavsal_cbr_finish(C.byref(k), _stream(xn)), "uavsal_cbr_finish")
+        g = _conv(lib, cache, gp, conv, cin, 9, tscale=bn) if need_x_grad else None
+    return (g.permute(0, 3, 1, 2) if need_x_grad else None), grads
+
+
+def _resize(x, ho, wo, out):
+    """`uavsal_bilinear_ac` on the current stream, no synchronisation: the NHWC `x` resized (`align_corners`) into the NHWC
+    view `out` `[n,ho,wo,C]` (a channel slice is written in place)."""
+    lib = L.load()
+    ip, ldi, n, h, w, c = _nhwc_view(x)
+    op, ldo, *_ = _nhwc_view(out)
+    d = L.BilinearDesc()
+    d.inp, d.ldi, d.Hi, d.Wi, d.out, d.ldo, d.Ho, d.Wo = ip, ldi, h, w, op, ldo, ho, wo
+    d.n_out, d.C, d.src_mod, d.src_div = n, c, n, 1
+    L.check(lib.uavsal_bilinear_ac(C.byref(d), _stream(x)), "uavsal_bilinear_ac")
+
+
+def _srf_parts(sfnet):
+    """The head's modules checked: `(lv3, lv4, aspp1, [(branch, parts, dilation)] * 3, lv5, last)`, or a RuntimeError."""
+    if not all(hasattr(sfnet, n) for n in SRF_HEAD):
+        raise RuntimeError("srf_head_backward takes model.sfnet (an uavsal_srfnet_aspp)")
+    if sfnet.training:
+        raise RuntimeError("the head's BatchNorms use their running statistics: call model.eval()")
+    lv3, lv4, a1, lv5, last = (getattr(sfnet, n) for n in ("conv_lv3", "conv_lv4", "lv5_aspp1", "conv_lv5", "conv_last"))
+    for cv in (lv3, lv4, a1, lv5):
+        _cbr_parts(cv[0], cv[1])
+    _conv3_parts(last[0], last[1])
+    branches = []
+    for n in SRF_HEAD_BLOCKS:
+        b = getattr(sfnet, n)
+        prt = _param_grad_parts(b)
+        if b.use_res_connect or b.stride != 1:
+            raise RuntimeError("srf_head_backward: the ASPP branch %s has stride 1 and no residual" % n)
+        branches.append((b, prt, prt[2].dilation[0]))
+    return lv3, lv4, a1, branches, lv5, last
+
+
+def _srf_grad_tensors(sfnet, out, accumulate):
+    params = dict(sfnet.named_parameters())
+    if any(n not in params for n in SRF_HEAD_PARAMS):
+        raise RuntimeError("the head's parameters must be %r" % (SRF_HEAD_PARAMS,))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `grads`")
+        out = {n: torch.empty_like(params[n], memory_format=torch.contiguous_format) for n in SRF_HEAD_PARAMS}
+    for n in SRF_HEAD_PARAMS:
+        t, q = out.get(n), params[n]
+        if (not torch.is_tensor(t) or t.shape != q.shape or t.dtype != torch.float32 or t.device != q.device
+                or not t.is_contiguous()):
+            raise RuntimeError("grads[%r] must be a dense float32 tensor of the parameter's shape on its device" % n)
+    return params, out
+
+
+def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, grads=None, accumulate=False):
+    """Backward of the SRF-Net head that is TRAINED (`model.sfnet` behind its frozen `features`, reference model.py:139-158;
+    eval mode: every BatchNorm on its running statistics, which are not updated): `c3` `[N,32,h,w]`, `c4` `[N,96,h4,w4]`, `c5`
+    `[N,320,h5,w5]` the backbone taps, `y` `[N,256,h,w]` the head's output (`taps["sfnet"]`, `conv_last`'s own activation),
+    `grad_out` `[N,256,h,w]` = d loss / d `y`.  Returns `grads`, keyed by the 42 parameter names relative to `sfnet`
+    (`SRF_HEAD_PARAMS`), written into the given dict of dense tensors or with `accumulate` added to it.  No input gradient is
+    formed for `c3` / `c4` / `c5`: the features stay frozen.
+        a1 = CBR(lv5_aspp1, c5);  a_b = BN(W3 ReLU6(BN(dw_dil(CBR(expand, c5)))))  (b = 2, 3, 4; dilation 6, 12, 18)
+        x5 = CBR(conv_lv5, cat[a1, a2, a3, a4]);  x4 = CBR(conv_lv4, c4);  x3 = CBR(conv_lv3, c3)
+        y = CBR3x3(conv_last, cat[up(x5), up(x4), x3])
+    The intermediates are recomputed by the forward's own launches, each once.  The walk: `conv_last` (`conv3_backward`), the
+    two upsamples (`bilinear_bwd`), `conv_lv3`, `conv_lv4`, `conv_lv5` (`cbr_backward`; only `conv_lv5` forms its input
+    gradient), `lv5_aspp1` (`cbr_backward`) and the three dilated branches (one 256 -> 1920 GEMM with s3 in its rows,
+    `uavsal_ir_bwd_dil`, `block_param_grads`).  `parts` receives every intermediate (NHWC): `a1`, `e2..4`, `d2..4`, `a2..4`,
+    `aspp`, `x5`, `x4`, `x3`, `cat`, `g_cat`, `g_x5`, `g_x4`, `g_aspp`, `gd2..4`, `ga2..4`.  A head in training mode or CPU tensors
+    raise."""
+    lib = L.load()
+    lv3, lv4, a1m, branches, lv5, last = _srf_parts(sfnet)
+    c3n, c4n, c5n = (_nhwc(t, nm, cv[0].weight.shape[1]) for t, nm, cv in ((c3, "c3", lv3), (c4, "c4", lv4), (c5, "c5", a1m)))
+    N, hh, ww, _ = c3n.shape
+    if c4n.shape[0] != N or c5n.shape[0] != N or any(t.device != c3n.device for t in (c4n, c5n)):
+        raise RuntimeError("c3, c4, c5 must hold the same frames on one device")
+    cout = last[0].weight.shape[0]
+    go = _block_grad_out(grad_out, c3n, cout)
+    yn = _nhwc(y, "y", cout)
+    if yn.shape != go.shape or yn.device != go.device:
+        raise RuntimeError("y must be [%d,%d,%d,%d] on the device of c3" % (N, cout, hh, ww))
+    dev = c3n.device
+    _, grads = _srf_grad_tensors(sfnet, grads, accumulate)               # raise before anything is launched
+    sub_g = lambda m, names: {n: grads["%s.%s" % (m, n)] for n in names}  # noqa: E731
+    nchw = lambda t: t.permute(0, 3, 1, 2)                                # noqa: E731
+    cbr = lambda cv, x: _conv(lib, cache, x, cv[0], cv[0].weight.shape[0], 1, bn=cv[1], act=L.ACT_RELU6)               # noqa: E731
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        # ---- the forward's intermediates
+        a = [cbr(a1m, c5n)]
+        eds = []
+        for b, prt, dil in branches:
+            e, d = _block_recompute(lib, cache, b, c5n, 1, prt, dil)
+            eds.append((e, d))
+            a.append(_conv(lib, cache, d, prt[4], prt[4].weight.shape[0], 1, bn=prt[5]))
+        aspp = torch.cat(a, 3)
+        x5, x4, x3 = cbr(lv5, aspp), cbr(lv4, c4n), cbr(lv3, c3n)
+        n5, n4, n3 = x5.shape[3], x4.shape[3], x3.shape[3]
+        cat = torch.empty((N, hh, ww, n5 + n4 + n3), dtype=torch.float32, device=dev)
+        _resize(x5, hh, ww, cat[..., :n5])
+        _resize(x4, hh, ww, cat[..., n5:n5 + n4])
+        cat[..., n5 + n4:].copy_(x3)
+        # ---- the walk back
+        g_cat, _ = conv3_backward(last[0], last[1], nchw(cat), yn, nchw(go), cache=cache, grads=sub_g("conv_last", ST_CBR_PARAMS),
+                                  accumulate=accumulate)
+        g_cat = g_cat.permute(0, 2, 3, 1)
+        g_x5 = bilinear_bwd(g_cat[..., :n5], N, x5.shape[1], x5.shape[2])
+        g_x4 = bilinear_bwd(g_cat[..., n5:n5 + n4], N, x4.shape[1], x4.shape[2])
+        cbr_backward(lv3[0], lv3[1], nchw(c3n), x3, nchw(g_cat[..., n5 + n4:]), need_x_grad=False, cache=cache,
+                     grads=sub_g("conv_lv3", ST_CBR_PARAMS), accumulate=accumulate)
+        cbr_backward(lv4[0], lv4[1], nchw(c4n), x4, nchw(g_x4), need_x_grad=False, cache=cache,
+                     grads=sub_g("conv_lv4", ST_CBR_PARAMS), accumulate=accumulate)
+        g_aspp, _ = cbr_backward(lv5[0], lv5[1], nchw(aspp), x5, nchw(g_x5), cache=cache, grads=sub_g("conv_lv5", ST_CBR_PARAMS),
+                                 accumulate=accumulate)
+        g_aspp = g_aspp.permute(0, 2, 3, 1)
+        w1 = a[0].shape[3]
+        cbr_backward(a1m[0], a1m[1], nchw(c5n), a[0], nchw(g_aspp[..., :w1]), need_x_grad=False, cache=cache,
+                     grads=sub_g("lv5_aspp1", ST_CBR_PARAMS), accumulate=accumulate)
+        gds, gas = [], []
+        for i, ((b, prt, dil), (e, d)) in enumerate(zip(branches, eds)):
+            wb = prt[4].weight.shape[0]
+            gb = g_aspp[..., w1 + i * wb:w1 + (i + 1) * wb]
+            gd = _conv(lib, cache, gb, prt[4], prt[0].weight.shape[0], 1, tscale=prt[5])
+            ga = ir_bwd_dil(gd, d, e, *cache.depthwise(prt[2], prt[3])[:2], dil)
+            block_param_grads(b, nchw(c5n), e, d, nchw(gb), gd=gd, ga=ga, cache=cache, out=sub_g(SRF_HEAD_BLOCKS[i], BLOCK_PARAMS),
+                              accumulate=accumulate)
+            gds.append(gd)
+            gas.append(ga)
+        if parts is not None:
+            parts.update(a1=a[0], aspp=aspp, x5=x5, x4=x4, x3=x3, cat=cat, g_cat=g_cat, g_x5=g_x5, g_x4=g_x4, g_aspp=g_aspp)
+            for i in range(len(branches)):
+                parts.update({"e%d" % (i + 2): eds[i][0], "d%d" % (i + 2): eds[i][1], "a%d" % (i + 2): a[i + 1],
+                              "gd%d" % (i + 2): gds[i], "ga%d" % (i + 2): gas[i]})
+    return grads
+
+
 def twa_gate_bwd(g, carry, z, x, hprev, need_dx=False):
     """`uavsal_twa_gate_bwd` on NHWC tensors `[1,h,w,256]` (`g`, `x`, `hprev` may be channel slices; `carry` dense or None):
     returns `(dz, carry_out, dx | None)`, dense."""
@@ -1356,7 +1650,7 @@ def _param_grad_tensors(blk):
 
 
 def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False,
-                    st=False):
+                    st=False, srf=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -1396,7 +1690,13 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     its input, and `st_block_backward` walks from the last ST block to the first over the `st{i}` and `sfnet` taps (one
     sequence of all the call's frames, as `forward()` runs them; no input gradient at block 0: the backbone `sfnet` stays
     frozen), setting -- or adding to -- the `.grad` of the 27 parameters of every block.  Refresh `model.st_layer` afterwards
-    as well.  A call without `st` runs the launches, and copies the taps, it always ran."""
+    as well.  A call without `st` runs the launches, and copies the taps, it always ran.
+    `srf=True` (needs `st=True`, and so everything `st` needs): the SRF-Net head `srf_head(model)` is trained as well -- every
+    parameter of `model.sfnet` the reference initialises itself; only the ImageNet `features` stay frozen.  ST block 0 is then
+    walked with `need_x_grad=True`, and `srf_head_backward` carries its input gradient (d loss / d `taps["sfnet"]`) over the
+    `c3` / `c4` / `c5` taps to the head's 42 parameters (`.grad` set, or added to); no gradient is formed for the taps
+    themselves.  Refresh `*train.srf_head(model)` afterwards as well (not `model.sfnet`: its fused backbone blocks and the stem
+    cannot be refreshed in place).  A call without `srf` runs the launches, and copies the taps, it always ran."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
@@ -1413,6 +1713,9 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if st and not (fuse and (fust or not getattr(model, "num_cb", 0))):
         raise RuntimeError("st=True needs fuse=True, and in a model with priors fust=True as well (the gradient reaches "
                            "model.st_layer through model.fust_layer[0]'s input)")
+    if srf and not st:
+        raise RuntimeError("srf=True needs st=True (and what st needs): the gradient reaches model.sfnet's head through the "
+                           "input of model.st_layer[0]")
     if model.training:
         raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
     if model.precision != "f32":
@@ -1482,5 +1785,13 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
                 grads, acc = _param_grad_tensors(model.st_layer[i])
                 xin = taps["st%d" % (i - 1)] if i else taps["sfnet"]
                 g_st, _ = st_block_backward(model.st_layer[i], xin.contiguous(memory_format=cl), g_st, seq_len=x.shape[0],
-                                            need_x_grad=i > 0, cache=cache, grads=grads, accumulate=acc)
+                                            need_x_grad=i > 0 or bool(srf), cache=cache, grads=grads, accumulate=acc)
+        if srf:
+            hp = dict(model.sfnet.named_parameters())
+            acc = any(hp[n].grad is not None for n in SRF_HEAD_PARAMS)
+            for n in SRF_HEAD_PARAMS:
+                if hp[n].grad is None:
+                    hp[n].grad = (torch.zeros_like if acc else torch.empty_like)(hp[n], memory_format=torch.contiguous_format)
+            srf_head_backward(model.sfnet, taps["c3"], taps["c4"], taps["c5"], taps["sfnet"], g_st, cache=cache,
+                              grads={n: hp[n].grad for n in SRF_HEAD_PARAMS}, accumulate=acc)
     return loss.detach(), out, [h_last[0].detach()]

@@ -780,8 +780,10 @@ int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd 
  *   TFLOP/s measured at 20 frames of 45 x 80, profiles/train_st.md), four tiles to a workgroup; the same
  *   chunks, chains, shares rule (over ceil((M / 32)(N / 32) / 4) workgroups per share), workspace layout, reduction launch,
  *   row_scale, rowdot and accumulate.  Every call with M and N multiples of 64 keeps the kernel, grid, workspace and bits it
- *   had.  Anything else (96 x 64: no side is 32 wide and one is no multiple of 64; 32 x 64: less than one workgroup of
- *   four tiles; 1920 x 32: wider than 512): UAVSAL_ESHAPE, as before.
+ *   had.  The same kernel takes M a multiple of 64 with N an odd multiple of 32, neither above 512 (the 1x1 convs of the
+ *   SRF-Net head on c3 and c4: 64 x 32, 128 x 96); a last workgroup with fewer than four tiles leaves its other waves idle.
+ *   Anything else (96 x 64: M is no multiple of 64; 32 x 64, 32 x 32: a 32-wide M below 128 columns; 1920 x 32: wider than
+ *   512): UAVSAL_ESHAPE, as before.
  * uavsal_dec_sums: per slab of picture rows the partial sums S3, G3, S2, Gd, S1 -> `ws` (doubles), from gy (pitched as in
  *   uavsal_dec_bwd_desc), y dense [n_img][H][W], e, d, ga dense [n_img][H][W][C], C % 256 == 0 (else UAVSAL_ESHAPE).
  *   delta3 and delta2 are formed in fp32 exactly as uavsal_dec_bwd forms them; every product is accumulated in double.
@@ -1098,6 +1100,70 @@ int uavsal_cbr_sums(const uavsal_cbr_sums_desc* d, uavsal_stream_t stream);
 int uavsal_cbr_finish(const uavsal_cbr_finish_desc* d, uavsal_stream_t stream);
 int uavsal_tdiff_bwd(const uavsal_tdiff_bwd_desc* d, uavsal_stream_t stream);
 int uavsal_st_sizeof_desc(int which);     /* 0 cbr_sums, 1 cbr_finish, 2 tdiff_bwd (uavsal_nets_sizeof_desc is closed at 3) */
+
+/* ---- fine-tuning the SRF-Net head: a dense 3x3 weight gradient, the dilated depthwise backward (csrc/train_srf.hip) --------
+ * The head of model.sfnet (model.py:120-158) behind the frozen MobileNetV2 features: three 1x1 conv + BatchNorm + ReLU6
+ * stages on c3 / c4 / c5 and one on the 1024-wide ASPP concat (uavsal_cbr_sums, uavsal_pix_gemm, uavsal_cbr_finish above;
+ * uavsal_pix_gemm takes their 64 x 32 and 128 x 96), three dilated inverted-residual blocks 320 -> 1920 -> 256 (dilation 6,
+ * 12, 18; the block backward above with the two kernels below in place of uavsal_ir_bwd / uavsal_ir_sums) and the dense 3x3
+ * conv_last 448 -> 256 + BatchNorm + ReLU6, whose stage is the cbr stage above with G[co][ci][ky][kx] in place of G[c][j].
+ *
+ * uavsal_conv3_wgrad: out[co][ci][ky][kx] = fl(row_scale[co] G[co][ci][ky][kx]) (+ the old value with `accumulate`),
+ *   G[co][ci][ky][kx] = sum over images and pixels p of g[p][co] x[p + (ky-1, kx-1)][ci], zero outside the picture, never
+ *   across frames.  g dense [n_img][H][W][Co]; x rows of Ci floats ldx floats apart (a channel slice is read in place); out
+ *   the parameter's own [Co][Ci][3][3].  row_scale NULL = 1.  rowdot (optional, [Co] doubles) = sum over ci, ky, kx of
+ *   w[co][ci][ky][kx] G[co][ci][ky][kx] (w dense like out) in double in a fixed order: uavsal_pix_gemm's contract, so
+ *   uavsal_cbr_finish forms the gamma gradient.  The tile loop, chunks, chains and K split of uavsal_twa_wgrad: 128 x 128
+ *   tiles of ONE tap, (Co / 128) * 9 * ceil(Ci / 128) of them, shares of whole chunks of UAVSAL_WGRAD_CHAIN pixels, partial
+ *   tiles [share][co][tap][ci] in `ws`; a second launch (a workgroup per co) sums the shares in share order in double and
+ *   rounds once.  Co % 128 == 0 and Ci % 64 == 0 (else UAVSAL_ESHAPE; the last tile of a tap may be half empty: nothing at
+ *   or behind column Ci is read, written or enters rowdot); g, x, ws 16-byte aligned, ldx a multiple of 4 (else
+ *   UAVSAL_EALIGN).  No atomics: two calls return the same bits.  TWO launches, no allocation.
+ * uavsal_ir_bwd_dil / uavsal_ir_sums_dil: uavsal_ir_bwd / uavsal_ir_sums for a depthwise 3x3 with stride 1, padding dil and
+ *   dilation dil >= 1 (else UAVSAL_EINVAL): the taps lie at p -/+ dil (k - (1,1)),
+ *     ga[p][c]      = 1[0 < e[p][c] < 6] s2[c] sum over taps k of wd[k][c] delta2[p - dil (k - (1,1))][c]
+ *     Gd[c][ky][kx] = sum delta2[p][c] e[p + dil (ky-1, kx-1)][c]
+ *   with delta2 = gd 1[0 < d < 6] formed in fp32 as uavsal_ir_bwd forms it, the sum over the taps in the order k = 8 .. 0 of
+ *   wd, then * s2, then the mask by e.  A lane owns four channels of ONE pixel and nine bounds-checked taps (the 2 x 2
+ *   patch with a 4 x 4 halo of the undilated kernels gives nothing at a dilation of 6 to 18 on a 1/32-scale map).  The sums'
+ *   slabs, workspace layout and byte count are those of uavsal_ir_sums for the same shape (uavsal_ir_sums_dil_slabs /
+ *   _slab_rows / _workspace_bytes), so uavsal_ir_finish takes the workspace as it is.  C % 4 == 0 (uavsal_ir_bwd_dil, else
+ *   UAVSAL_EALIGN), Ch % 64 == 0 (uavsal_ir_sums_dil, else UAVSAL_ESHAPE).  ONE launch each, no atomics, bit-reproducible.
+ */
+typedef struct uavsal_conv3_wgrad_desc {
+    const float* g;                         /* dense [n_img][H][W][Co] */
+    const float* x;      int32_t ldx;       /* [n_img * H * W] rows of Ci floats */
+    const float* row_scale;                 /* [Co] or NULL */
+    const float* w;                         /* dense [Co][Ci][3][3] (needed with rowdot) */
+    double* rowdot;                         /* [Co] or NULL */
+    float* ws;  int64_t ws_bytes;
+    float* out;                             /* [Co][Ci][3][3] */
+    int32_t n_img, H, W, Co, Ci, accumulate;
+} uavsal_conv3_wgrad_desc;
+
+typedef struct uavsal_ir_bwd_dil_desc {
+    const float* gd;  const float* d;  const float* e;
+    const float* wd9;  const float* s2;
+    float* ga;
+    int32_t n_img, H, W, C, dil;
+} uavsal_ir_bwd_dil_desc;
+
+typedef struct uavsal_ir_sums_dil_desc {
+    const float* gd;  const float* d;  const float* e;  const float* ga;
+    const float* go;  int32_t ldgo;         /* [n_img * H * W] rows of Co floats */
+    double* ws;  int64_t ws_bytes;
+    int32_t n_img, H, W, Ch, Co, dil;
+} uavsal_ir_sums_dil_desc;
+
+int64_t uavsal_conv3_wgrad_workspace_bytes(const uavsal_conv3_wgrad_desc* d);
+int uavsal_conv3_wgrad_shares(const uavsal_conv3_wgrad_desc* d);    /* K shares per tile of that call (no launch) */
+int uavsal_conv3_wgrad(const uavsal_conv3_wgrad_desc* d, uavsal_stream_t stream);
+int uavsal_ir_bwd_dil(const uavsal_ir_bwd_dil_desc* d, uavsal_stream_t stream);
+int64_t uavsal_ir_sums_dil_workspace_bytes(const uavsal_ir_sums_dil_desc* d);
+int uavsal_ir_sums_dil_slabs(const uavsal_ir_sums_dil_desc* d);     /* slabs of that call (no launch) */
+int uavsal_ir_sums_dil_slab_rows(const uavsal_ir_sums_dil_desc* d); /* picture rows per slab */
+int uavsal_ir_sums_dil(const uavsal_ir_sums_dil_desc* d, uavsal_stream_t stream);
+int uavsal_srf_sizeof_desc(int which);    /* 0 conv3_wgrad, 1 ir_bwd_dil, 2 ir_sums_dil (uavsal_st_sizeof_desc is closed at 3) */
 
 /* ---- repacking refreshed weights on the device (csrc/repack.hip) ---------------------------------------------------------
  * After an optimiser step the packed copies of a module's weights are remade FROM the fp32 parameters and buffers where they

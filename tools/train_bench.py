@@ -57,6 +57,16 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                pixel GEMM with its reduction at 256 x 256 (the 128 x 128 tile kernel) and at the three 32-wide shapes
                (st_pix_gemm_32x256, _256x32, _32x384: the sibling kernel; shares and TFLOP/s), and `refresh_weights` over
                the seven stages on the host and on the device (refresh7, refresh7_device).  Alone: --st-only;
+  srf          the SRF-Net head trained too, the eighth stage (`train.srf_head`, 42 parameters): the seven-stage step (step7b)
+               and the same with `srf=True` (step8), alternated in the same run, every run listed (the spread);
+               `train.srf_head_backward` alone (srf_head_bwd) and per launch family at the head's shapes, from the tensors the
+               walk hands out: `train.conv3_backward` of `conv_last` (srf_conv_last_bwd), `uavsal_conv3_wgrad` alone at
+               [256,448,3,3] beside `uavsal_twa_wgrad` at the same K (srf_conv3_wgrad, srf_twa_wgrad_same_k: 72 tiles and the
+               same loop; TFLOP/s of the useful and of the issued products), `uavsal_cbr_sums` at 256 channels, the resize's
+               adjoint, `train.cbr_backward` of `conv_lv3`, `conv_lv4`, `conv_lv5`, one dilated branch's
+               `train.block_param_grads` with `uavsal_ir_bwd_dil` and `uavsal_ir_sums_dil` alone, the pixel GEMM at 64 x 32,
+               128 x 96 (the wave-per-tile kernel) and 256 x 1024, and `refresh_weights` over the eight stages on the host and
+               on the device (refresh8, refresh8_device).  Alone: --srf-only;
   refresh pairs beside every refresh case above its `_device` twin: the same in-place edit, then `refresh_weights(...,
                device=True)` (csrc/repack.hip: one launch, no host copy); and at the end (or alone: --refresh-only) the
                host and device refresh of 1, 4, 5 and 6 stages (refreshN_alt / refreshN_device_alt) and one whole six-stage
@@ -67,7 +77,7 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
 
-Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--frames 20 5]
+Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--srf-only] [--frames 20 5]
 """
 import argparse
 import ctypes as C
@@ -528,6 +538,103 @@ def st_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
         q.grad = None
 
 
+def srf_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
+    """the phases of the trained SRF-Net head (train.srf_head), the eighth stage, added to `res`"""
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    nets = tuple(train.prior_nets(m).values())
+    head = tuple(train.srf_head(m))
+    boxes = (m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer, m.fucb_layer, m.cxt_cb_prior) + nets + (m.st_layer,) + head
+    trained = [q for mod in boxes for q in mod.parameters()]
+    kw7 = dict(decoder=True, fuse=True, fust=True, ctx=True, nets=True, st=True)
+    taps = {}
+    m(x, cb, None, taps=taps)
+    c3, c4, c5, y = (taps[k].contiguous(memory_format=cl) for k in ("c3", "c4", "c5", "sfnet"))
+    go = (torch.randn_like(y) / y[0].numel()).contiguous(memory_format=cl)      # (timing only: any gradient of the right shape)
+    pt = {}
+    grads = train.srf_head_backward(m.sfnet, c3, c4, c5, y, go, cache=cache, parts=pt)
+    sf = m.sfnet
+    nchw = lambda t: t.permute(0, 3, 1, 2)                     # noqa: E731
+    yn, gon = y.permute(0, 2, 3, 1), go.permute(0, 2, 3, 1)
+    T, hh, ww, _ = yn.shape
+    n_pix, n5 = T * hh * ww, T * c5.shape[2] * c5.shape[3]
+    sub = lambda name, names: {n: grads["%s.%s" % (name, n)] for n in names}      # noqa: E731
+    gp, _, _ = train.cbr_sums(gon, yn)
+    b2 = sf.lv5_aspp2
+    prt = train._param_grad_parts(b2)
+    w9, s2 = cache.depthwise(prt[2], prt[3])[:2]
+    # uavsal_twa_wgrad at the same K, 72 tiles and the same loop: the recurrence's own operands stand in (256-wide x, h, h0)
+    tw = [torch.randn((T, hh, ww, 256), device=dev) for _ in range(3)] + [torch.zeros((1, hh, ww, 256), device=dev)]
+    gw_twa = torch.empty((256, 512, 3, 3), device=dev)
+    gw_c3 = torch.empty_like(sf.conv_last[0].weight)
+
+    def stepper(**kw):
+        def run():
+            for q in trained:
+                q.grad = None
+            train.recurrence_step(m, x, cb, None, y_gaze, **kw7, **kw)
+        return run
+
+    def refresh8(device=False):
+        with torch.no_grad():
+            for q in trained:
+                q.mul_(1.0)
+        m.refresh_weights(*boxes, device=device)
+    gems = {}
+    for tag, (a, b, M, N) in (("64x32", (pt["g_cat"][..., 384:], c3.permute(0, 2, 3, 1), 64, 32)),
+                              ("128x96", (pt["g_x4"], c4.permute(0, 2, 3, 1), 128, 96)),
+                              ("256x1024", (pt["g_x5"], pt["aspp"], 256, 1024))):
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+        gems[tag] = (M, N, a.shape[0] * a.shape[1] * a.shape[2], lambda a=a, b=b, out=out: train.pix_gemm(a, b, out=out))
+    cases = {"srf_head_bwd": lambda: train.srf_head_backward(sf, c3, c4, c5, y, go, cache=cache, grads=grads),
+             "srf_conv_last_bwd": lambda: train.conv3_backward(sf.conv_last[0], sf.conv_last[1], nchw(pt["cat"]), yn, go, cache=cache,
+                                                               grads=sub("conv_last", train.ST_CBR_PARAMS)),
+             "srf_conv3_wgrad": lambda: train.conv3_wgrad(gp, pt["cat"], out=gw_c3),
+             "srf_twa_wgrad_same_k": lambda: train.twa_wgrad(tw[0], tw[1], tw[2], tw[3], out=gw_twa),
+             "srf_cbr_sums_256": lambda: train.cbr_sums(gon, yn),
+             "srf_bilinear_bwd_256": lambda: train.bilinear_bwd(pt["g_cat"][..., :256], T, c5.shape[2], c5.shape[3]),
+             "srf_cbr_lv3": lambda: train.cbr_backward(sf.conv_lv3[0], sf.conv_lv3[1], c3, pt["x3"], nchw(pt["g_cat"][..., 384:]),
+                                                       need_x_grad=False, cache=cache, grads=sub("conv_lv3", train.ST_CBR_PARAMS)),
+             "srf_cbr_lv4": lambda: train.cbr_backward(sf.conv_lv4[0], sf.conv_lv4[1], c4, pt["x4"], nchw(pt["g_x4"]), need_x_grad=False,
+                                                       cache=cache, grads=sub("conv_lv4", train.ST_CBR_PARAMS)),
+             "srf_cbr_lv5": lambda: train.cbr_backward(sf.conv_lv5[0], sf.conv_lv5[1], nchw(pt["aspp"]), pt["x5"], nchw(pt["g_x5"]),
+                                                       cache=cache, grads=sub("conv_lv5", train.ST_CBR_PARAMS)),
+             "srf_aspp_branch_param_grads": lambda: train.block_param_grads(b2, c5, pt["e2"], pt["d2"], nchw(pt["g_aspp"][..., 256:512]),
+                                                                            gd=pt["gd2"], ga=pt["ga2"], cache=cache,
+                                                                            out=sub("lv5_aspp2", train.BLOCK_PARAMS)),
+             "srf_ir_bwd_dil": lambda: train.ir_bwd_dil(pt["gd2"], pt["d2"], pt["e2"], w9, s2, b2.dilation),
+             "srf_ir_sums_dil": lambda: train.ir_sums_dil(pt["gd2"], pt["d2"], pt["e2"], pt["ga2"], pt["g_aspp"][..., 256:512], b2.dilation),
+             "refresh8": refresh8, "refresh8_device": lambda: refresh8(True)}
+    for tag, (_, _, _, fn) in gems.items():
+        cases["srf_pix_gemm_" + tag] = fn
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    for tag, (M, N, K, _) in gems.items():
+        gd = L.PixGemmDesc()
+        gd.K, gd.M, gd.N = K, M, N
+        res["srf_pix_gemm_%s_shares" % tag] = int(lib.uavsal_pix_gemm_shares(C.byref(gd)))
+        res["srf_pix_gemm_%s_tflops" % tag] = 2.0 * M * N * K / (res["srf_pix_gemm_%s_ms" % tag] * 1e-3) / 1e12
+    d = L.Conv3WgradDesc()
+    d.n_img, d.H, d.W, d.Co, d.Ci = T, hh, ww, 256, 448
+    res["srf_conv3_wgrad_shares"] = int(lib.uavsal_conv3_wgrad_shares(C.byref(d)))
+    res["srf_conv3_wgrad_tflops"] = 2.0 * 256 * 9 * 448 * n_pix / (res["srf_conv3_wgrad_ms"] * 1e-3) / 1e12
+    res["srf_conv3_wgrad_issued_tflops"] = 2.0 * 256 * 9 * 512 * n_pix / (res["srf_conv3_wgrad_ms"] * 1e-3) / 1e12
+    res["srf_twa_wgrad_same_k_tflops"] = 2.0 * 256 * 9 * 512 * n_pix / (res["srf_twa_wgrad_same_k_ms"] * 1e-3) / 1e12
+    res["srf_ir_bwd_dil_gbs"] = 4.0 * 1920 * 4 * n5 / (res["srf_ir_bwd_dil_ms"] * 1e-3) / 1e9
+    runs = {"step7b": stepper(), "step8": stepper(srf=True)}
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # the two steps alternated in the same run
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    for q in trained:
+        q.grad = None
+
+
 def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
     """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
     from iip_uavsal_saliency_amd import repack
@@ -584,7 +691,7 @@ def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
         q.grad = None
 
 
-def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False):
+def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
@@ -607,6 +714,10 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False)
     if st_only:
         res = {"T": T}
         st_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+        return res
+    if srf_only:
+        res = {"T": T}
+        srf_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
         return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -706,6 +817,7 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False)
     ctx_phases(res, m, x, cb, y_gaze, grad_h, cache, iters, repeats)
     nets_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
     st_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+    srf_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
     refresh_phases(res, m, x, cb, y_gaze, iters, repeats)
     if not skip_eager:
         try:
@@ -726,11 +838,12 @@ def main():
     ap.add_argument("--skip-eager", action="store_true")
     ap.add_argument("--refresh-only", action="store_true", help="only the refresh / iteration pairs (refresh_phases)")
     ap.add_argument("--st-only", action="store_true", help="only the phases of the seventh stage (st_phases)")
+    ap.add_argument("--srf-only", action="store_true", help="only the phases of the eighth stage (srf_phases)")
     ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
     out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
-           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only) for T in a.frames]}
+           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only) for T in a.frames]}
     print(json.dumps(out))
 
 
