@@ -243,7 +243,8 @@ TRAIN_DESC_TYPES = [TwaGateDesc, TwaWgradDesc, DecBwdDesc]        # sized by uav
 class PixGemmDesc(C.Structure):
     _fields_ = [("a", _f), ("lda", C.c_int32), ("b", _f), ("ldb", C.c_int32), ("row_scale", _f),
                 ("w", _f), ("ldw", C.c_int32), ("rowdot", C.c_void_p), ("ws", _f), ("ws_bytes", C.c_int64),
-                ("out", _f), ("ldo", C.c_int32), ("K", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("accumulate", C.c_int32)]
+                ("out", _f), ("ldo", C.c_int32), ("K", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("accumulate", C.c_int32),
+                ("tails32", C.c_int32)]
 
 
 class DecSumsDesc(C.Structure):

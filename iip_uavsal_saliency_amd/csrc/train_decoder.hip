@@ -4,7 +4,8 @@
 // 1. uavsal_pix_gemm: out[m][n] = row_scale[m] sum over pixels p of A[p][m] B[p][n].  The tile loop of uavsal_twa_wgrad
 //    (csrc/pix_gemm_tile.h: 128 x 128 tiles, 32-pixel K steps, chains of at most UAVSAL_WGRAD_CHAIN products, a second fp32
 //    register tile per share) with plain pitched rows as both operands.  M and N are multiples of 64 (a 32-wide side goes to the
-//    sibling pix_gemm32_kernel below): the last tile of either
+//    sibling pix_gemm32_kernel below; with the descriptor's tails32 every other multiple of 32 is taken too, by THIS kernel with
+//    quarter-tile tails and shares of 128-pixel units: pg_short_ok below): the last tile of either
 //    may be half empty (its loader hands the tile loop zeros, nothing at or behind row M / column N is read or written).  K
 //    split by the same rule: ceil(M / 128) ceil(N / 128) tiles, about 1024 workgroups.  M = 1536, N = 256 is 24 tiles, at
 //    most 42 shares: T = 20 at 45 x 80 (71 chunks) runs 36 shares of 2 chunks.  Partial tiles [share][M][N] -> a second
@@ -40,11 +41,13 @@ struct PgK {
     double* rowdot;
     float *ws, *out;
     long long K;
+    long long spp;                               // pixels of one share: cps * UAVSAL_WGRAD_CHAIN, or (tails32) whole kShortUnit's
     int lda, ldb, ldw, ldo, M, N, mt_n, nt_n;
     int cps, shares, accumulate;
 };
 
-// kMTail: M % 128 == 64, the last M tile is half empty.  Without it the kernel is the instruction stream it was before M
+// kMTail: M % 128 != 0, the last M tile is half empty (or, with tails32, a quarter or three quarters: the loader's test is per
+// thread, four columns at lc, and M and N are multiples of 4, so it holds for any tail; so does the row guard of the store).  Without it the kernel is the instruction stream it was before M
 // tails existed (the A loader's test and the row guard fold away): the calls with whole M tiles keep their bits and their time.
 template <bool kMTail>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void pix_gemm_kernel(const PgK k) {
@@ -54,15 +57,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
     const int lc = (threadIdx.x & 31) * 4;
 
-    const long long p0 = (long long)share * k.cps * UAVSAL_WGRAD_CHAIN;
-    long long p1 = p0 + (long long)k.cps * UAVSAL_WGRAD_CHAIN;
+    const long long p0 = (long long)share * k.spp;
+    long long p1 = p0 + k.spp;
     if (p1 > k.K) p1 = k.K;
 
     f32x16 tot[2][2];
     const float* arow = k.a + mt * kTile + lc;
     const float* brow = k.b + nt * kTile + lc;
-    const bool bok = nt * kTile + lc < k.N;                   // N % 64 == 0: the last N tile may be half empty
-    const bool aok = !kMTail || mt * kTile + lc < k.M;        // M % 64 == 0: and so may the last M tile
+    const bool bok = nt * kTile + lc < k.N;                   // N % 32 == 0: the last N tile may end at any quarter
+    const bool aok = !kMTail || mt * kTile + lc < k.M;        // M % 32 == 0: and so may the last M tile
     pixgemm::tile_loop(p0, p1,
         [&](long long g) { return aok ? arow + g * k.lda : nullptr; },
         [&](long long g) { return bok ? brow + g * k.ldb : nullptr; }, tot);
@@ -98,8 +101,8 @@ __global__ __launch_bounds__(256) void pix_gemm32_kernel(const PgK k) {
     const int mt = tile % k.mt_n, nt = tile / k.mt_n;
     const int half = lane >> 5, col = lane & 31;
 
-    const long long p0 = (long long)share * k.cps * UAVSAL_WGRAD_CHAIN;
-    long long p1 = p0 + (long long)k.cps * UAVSAL_WGRAD_CHAIN;
+    const long long p0 = (long long)share * k.spp;
+    long long p1 = p0 + k.spp;
     if (p1 > k.K) p1 = k.K;
     const float* ap = k.a + mt * 32 + col;
     const float* bp = k.b + nt * 32 + col;
@@ -179,18 +182,49 @@ bool pg_narrow(int M, int N) {
 }
 bool pg_shape_ok(int M, int N) { return pg_narrow(M, N) || (!(M % (kTile / 2)) && !(N % (kTile / 2))); }
 
+// tails32 (uavsal_pix_gemm_desc: opt-in, the weight gradients of the MobileNetV2 blocks 8..17 -- 576 x 96, 960 x 160, 96 x 384,
+// 96 x 576, 160 x 576, 160 x 960): every M, N multiple of 32 that the rules above refuse goes to pix_gemm_kernel<true>, whose
+// last tile of either side may end at any quarter.  Their K is short (20 frames of 12 x 20 are 4800 pixels: under five chunks,
+// on 3 to 16 tiles), so a share is a whole number of kShortUnit pixels, not of chunks, for about kShortWGs workgroups (two
+// resident per CU): 960 x 160 at K = 4800 runs 16 tiles x 19 shares of 256 pixels = 304 workgroups where whole chunks give
+// 80.  A share's chains still end every UAVSAL_WGRAD_CHAIN products counted from the share's first pixel.
+constexpr int kShortUnit = 128, kShortWGs = 512;
+bool pg_short_ok(int M, int N) { return M > 0 && N > 0 && !(M % 32) && !(N % 32) && !pg_shape_ok(M, N); }
+
+bool pg_split_short(long long K, int tiles, long long& spp, int& shares_out) {
+    const long long units = (K + kShortUnit - 1) / kShortUnit;
+    long long want = kShortWGs / tiles;
+    if (want < 1) want = 1;
+    if (want > units) want = units;
+    const long long ups = (units + want - 1) / want;
+    const long long shares = (units + ups - 1) / ups;
+    if (ups > 0x7fffffffll / kShortUnit || shares > 65535) return false;
+    spp = ups * kShortUnit; shares_out = (int)shares;
+    return true;
+}
+
 bool pg_plan(const uavsal_pix_gemm_desc* d, PgK& k) {
-    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0 || !pg_shape_ok(d->M, d->N)) return false;
-    if (pg_narrow(d->M, d->N)) {
+    if (!d || d->K <= 0 || d->M <= 0 || d->N <= 0) return false;
+    const bool is_short = d->tails32 && pg_short_ok(d->M, d->N);
+    if (!is_short && !pg_shape_ok(d->M, d->N)) return false;
+    if (!is_short && pg_narrow(d->M, d->N)) {
         const long long tiles = (long long)(d->M / 32) * (d->N / 32);
         if ((long long)d->M * d->N > 0x7fffffffll || (tiles + 3) / 4 > 65535) return false;
         k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = d->M / 32; k.nt_n = d->N / 32;
-        return pixgemm::split(k.K, (int)((tiles + 3) / 4), k.cps, k.shares);
+        if (!pixgemm::split(k.K, (int)((tiles + 3) / 4), k.cps, k.shares)) return false;
+        k.spp = (long long)k.cps * UAVSAL_WGRAD_CHAIN;
+        return true;
     }
     const int mt_n = (d->M + kTile - 1) / kTile, nt_n = (d->N + kTile - 1) / kTile;
     if ((long long)d->M * d->N > 0x7fffffffll || (long long)mt_n * nt_n > 65535) return false;
     k.K = d->K; k.M = d->M; k.N = d->N; k.mt_n = mt_n; k.nt_n = nt_n;
-    return pixgemm::split(k.K, k.mt_n * nt_n, k.cps, k.shares);
+    if (is_short) {
+        k.cps = 0;
+        return pg_split_short(k.K, mt_n * nt_n, k.spp, k.shares);
+    }
+    if (!pixgemm::split(k.K, k.mt_n * nt_n, k.cps, k.shares)) return false;
+    k.spp = (long long)k.cps * UAVSAL_WGRAD_CHAIN;
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ channel sums
@@ -369,7 +403,8 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     if (!d || !d->a || !d->b || !d->ws || !d->out) return UAVSAL_EINVAL;
     if (d->K <= 0 || d->M <= 0 || d->N <= 0) return UAVSAL_EINVAL;
     if (d->rowdot && !d->w) return UAVSAL_EINVAL;
-    if (!pg_shape_ok(d->M, d->N)) return UAVSAL_ESHAPE;
+    const bool is_short = d->tails32 && pg_short_ok(d->M, d->N);
+    if (!is_short && !pg_shape_ok(d->M, d->N)) return UAVSAL_ESHAPE;
     PgK k;
     if (!pg_plan(d, k)) return UAVSAL_ESHAPE;
     if (d->ws_bytes < uavsal_pix_gemm_workspace_bytes(d)) return UAVSAL_EINVAL;
@@ -381,10 +416,10 @@ extern "C" int uavsal_pix_gemm(const uavsal_pix_gemm_desc* d, uavsal_stream_t st
     k.lda = d->lda; k.ldb = d->ldb; k.ldw = d->ldw; k.ldo = d->ldo;
     k.accumulate = d->accumulate != 0;
     const dim3 grid((unsigned)(k.mt_n * k.nt_n), (unsigned)k.shares);
-    if (pg_narrow(k.M, k.N))
+    if (!is_short && pg_narrow(k.M, k.N))
         hipLaunchKernelGGL(pix_gemm32_kernel, dim3((unsigned)((k.mt_n * k.nt_n + 3) / 4), (unsigned)k.shares), dim3(256), 0,
                            (hipStream_t)stream, k);
-    else if (k.M % kTile) hipLaunchKernelGGL(pix_gemm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, k);
+    else if (is_short || k.M % kTile) hipLaunchKernelGGL(pix_gemm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, k);
     else hipLaunchKernelGGL(pix_gemm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, k);
     hipLaunchKernelGGL(pix_gemm_reduce_kernel, dim3((unsigned)k.M), dim3(256), 0, (hipStream_t)stream, k);
     return uavsal_launch_status();

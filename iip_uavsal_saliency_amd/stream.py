@@ -411,6 +411,9 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `"srf"` (the very last stage of all, only behind `"st"`): `recurrence_step(..., srf=True)` also sets the gradients of the
     SRF-Net head `train.srf_head(model)` -- everything in `model.sfnet` but the ImageNet `features` -- and those eight modules
     are refreshed as well.
+    `"backbone"` (only behind `"srf"`): `recurrence_step(..., backbone=True)` also sets the gradients of the deep backbone
+    `train.backbone_blocks(model)` -- MobileNetV2 `features[8:18]` -- and those ten modules are refreshed as well;
+    `features[0..7]` stay frozen.
     `refresh`: `"host"` (the default) repacks the trained stages' weights on the host after every step; `"device"` repacks
     them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host)."""
     from . import losses as _losses
@@ -425,10 +428,11 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     allowed += [s + ("nets",) for s in allowed if "fuse" in s]
     allowed += [s + ("st",) for s in allowed if "fuse" in s and ("fust" in s or not getattr(model, "num_cb", 0))]
     allowed += [s + ("srf",) for s in allowed if "st" in s]
+    allowed += [s + ("backbone",) for s in allowed if "srf" in s]
     if stages not in allowed:
         raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
                          "'fuse' (then 'ctx', then 'nets', behind 'fuse' too; 'st' the very last, behind 'fuse' and, in a "
-                         "model with priors, 'fust'; only 'srf' may follow 'st'), got %r" % (stages,))
+                         "model with priors, 'fust'; only 'srf' may follow 'st', only 'backbone' 'srf'), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
@@ -450,6 +454,8 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
             mods.append(model.st_layer)
         if "srf" in kw:
             mods.extend(_train.srf_head(model))
+        if "backbone" in kw:
+            mods.extend(_train.backbone_blocks(model))
         if refresh == "device":
             model.refresh_weights(*mods, device=True)
         else:

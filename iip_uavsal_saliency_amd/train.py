@@ -32,8 +32,11 @@ ST block go through the walks above (`block_param_grads` takes the temporal sub-
 `tdiff_bwd` (csrc/train_st.hip: `uavsal_cbr_sums`, `uavsal_cbr_finish`, `uavsal_tdiff_bwd`).  And an eighth: the head of the backbone
 `sfnet` -- everything in it the reference initialises itself (`recurrence_step(srf=True)`, `srf_head`, `srf_head_backward`): its 1x1
 stages go through `cbr_backward`, its dilated ASPP branches through `block_param_grads` (csrc/train_srf.hip: `uavsal_ir_bwd_dil`,
-`uavsal_ir_sums_dil`) and the dense 3x3 `conv_last` through `conv3_backward` (`uavsal_conv3_wgrad`).  Only the ImageNet MobileNetV2
-`sfnet.features` stay frozen; BatchNorm in eval mode remains the documented difference.
+`uavsal_ir_sums_dil`) and the dense 3x3 `conv_last` through `conv3_backward` (`uavsal_conv3_wgrad`).  And a ninth: the deep
+backbone, MobileNetV2 `features[8:18]` (`recurrence_step(backbone=True)`, `backbone_blocks`, `backbone_backward`): the head also
+hands out the gradients of its `c4` / `c5` taps and the ten blocks at 1/16 and 1/32 resolution go through `block_backward(
+backbone=True)` (their widths are multiples of 32: `uavsal_pix_gemm` with `tails32`).  Only `features[0..7]` and the stem stay
+frozen; BatchNorm in eval mode remains the documented difference.
 
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
@@ -190,10 +193,12 @@ DECODER_PARAMS = ("conv.0.0.weight", "conv.0.1.weight", "conv.0.1.bias", "conv.1
                   "conv.2.weight", "conv.3.weight", "conv.3.bias")      # W1, gamma1, beta1, Wd, gamma2, beta2, W3, gamma3, beta3
 
 
-def pix_gemm(a, b, out=None, row_scale=None, w=None, rowdot=None, accumulate=False):
+def pix_gemm(a, b, out=None, row_scale=None, w=None, rowdot=None, accumulate=False, tails32=False):
     """`uavsal_pix_gemm` on the current stream: `a` `[..., M]`, `b` `[..., N]` NHWC tensors of the same pixels (channel slices
     are read in place) -> `out[m][n] = row_scale[m] sum_p a[p][m] b[p][n]` (dense `[M, N]`; `accumulate`: added to `out`), and
-    with `w` `[M, N]` and `rowdot` (float64 `[M]`) `rowdot[m] = sum_n w[m][n] G[m][n]`.  Two launches, no synchronisation."""
+    with `w` `[M, N]` and `rowdot` (float64 `[M]`) `rowdot[m] = sum_n w[m][n] G[m][n]`.  Two launches, no synchronisation.
+    `tails32=True`: every M, N multiple of 32 the default call refuses is taken too (the weight gradients of the backbone
+    blocks: quarter-tile tails, shares of 128-pixel units; include/uavsal_hip.h); what the default takes keeps its bits."""
     lib = L.load()
     ap, lda, *sa = _nhwc_view(a)
     bp, ldb, *sb = _nhwc_view(b)
@@ -210,6 +215,7 @@ def pix_gemm(a, b, out=None, row_scale=None, w=None, rowdot=None, accumulate=Fal
     k = L.PixGemmDesc()
     k.a, k.lda, k.b, k.ldb = ap, lda, bp, ldb
     k.K, k.M, k.N, k.accumulate = sa[0] * sa[1] * sa[2], M, N, int(bool(accumulate))
+    k.tails32 = int(bool(tails32))
     if row_scale is not None:
         if row_scale.dtype != torch.float32 or row_scale.device != dev or row_scale.numel() < M or not row_scale.is_contiguous():
             raise RuntimeError("row_scale must be a dense float32 vector of at least %d elements on the device" % M)
@@ -351,8 +357,11 @@ def decoder_backward(block, h_seq, grad_out, cache=None, y=None, parts=None, gra
 BLOCK_PARAMS = DECODER_PARAMS                                        # a dwBlock with an expand conv: the same nine names
 
 
-def _block_parts(block):
-    """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual block the block backward covers, or a RuntimeError."""
+def _block_parts(block, backbone=False):
+    """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual block the block backward covers, or a RuntimeError.
+    `backbone`: the shapes of MobileNetV2 `features[8:18]` instead (`_param_grad_parts`)."""
+    if backbone:
+        return _param_grad_parts(block, True)
     seq = getattr(block, "conv", None)
     if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4 or getattr(block, "stride", None) != 1
             or getattr(block, "dilation", None) != 1 or seq[1][0].stride != (1, 1) or seq[1][0].dilation != (1, 1)):
@@ -368,12 +377,30 @@ def _block_parts(block):
     return pw, pwbn, dwc, dwbn, pl, plbn
 
 
-def _param_grad_parts(block):
+def _param_grad_parts(block, backbone=False):
     """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual block whose nine gradients `block_param_grads` forms: what
-    `_block_parts` takes, and stride 2 and Cout % 64 == 0 besides (the blocks of the multi-prior path), or a RuntimeError."""
+    `_block_parts` takes, and stride 2 and Cout % 64 == 0 besides (the blocks of the multi-prior path), or a RuntimeError.
+    `backbone`: Cin % 32 == 0, hidden % 64 == 0, Cout % 32 == 0 at dilation 1 instead, stride 1 (with or without the residual)
+    or 2 -- MobileNetV2 `features[8:18]`.  `model_feature.InvertedResidual` and `dwBlock` are the same module to this code:
+    the same `conv` Sequential, the same nine parameter names (`BLOCK_PARAMS`), which is checked here."""
     seq = getattr(block, "conv", None)
     stride = getattr(block, "stride", None)
     dil = getattr(block, "dilation", None)
+    if backbone:
+        if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4
+                or tuple(n for n, _ in block.named_parameters()) != BLOCK_PARAMS):
+            raise RuntimeError("the backbone backward takes an inverted-residual block with an expand conv (expand 1x1, depthwise "
+                               "3x3, projection 1x1: features[2..17]), not features[1] or the stem")
+        if stride not in (1, 2) or dil != 1 or seq[1][0].stride != (stride, stride) or seq[1][0].dilation != (1, 1):
+            raise RuntimeError("the backbone backward takes stride 1 or 2 at dilation 1 (a dilated block with stride 2 is not covered)")
+        pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
+        hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+        if cout % 32 or hid % 64 or cin % 32:
+            raise RuntimeError("the backbone backward needs Cout %% 32 == 0, hidden %% 64 == 0 and Cin %% 32 == 0, got %d -> %d -> %d"
+                               % (cin, hid, cout))
+        if block.training:
+            raise RuntimeError("the block's BatchNorms use their running statistics: call model.eval()")
+        return pw, pwbn, dwc, dwbn, pl, plbn
     if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4 or stride not in (1, 2)
             or not isinstance(dil, int) or dil < 1 or (dil > 1 and stride != 1)
             or seq[1][0].stride != (stride, stride) or seq[1][0].dilation != (dil, dil)):
@@ -542,7 +569,7 @@ def ir_sums_dil(gd, d, e, ga, go, dil):
     return ws, int(lib.uavsal_ir_sums_dil_slabs(C.byref(k)))
 
 
-def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, out=None, accumulate=False):
+def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, out=None, accumulate=False, backbone=False):
     """The gradients of the nine parameters of an inverted-residual `block` (a `dwBlock` with an expand conv, stride 1 or 2,
     dilation 1, with or without the residual; eval mode: the BatchNorms on their running statistics, which are not updated)
     from given tensors, teacher-forced: `x` `[T,Cin,h,w]` the block's input, `e` dense NHWC `[T,h,w,Ch]` its expanded and `d`
@@ -558,9 +585,12 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
     (64 -> 384 -> 32), whose W3 product is the pixel GEMM's 32-wide side --, Ch % 64 == 0, Cin % 64 == 0 (`block_backward`, which recomputes `e` and `d`
     itself, keeps to stride 1 and Co % 128 == 0).  A block with stride 1 and a DILATED depthwise conv (the ASPP branches of the
     SRF-Net head, 320 -> 1920 -> 256 at dilation 6 / 12 / 18) is taken with Co % 128 == 0: `uavsal_ir_bwd_dil` and
-    `uavsal_ir_sums_dil` stand in for the undilated launches, everything else is the same."""
+    `uavsal_ir_sums_dil` stand in for the undilated launches, everything else is the same.
+    `backbone=True`: Cin % 32 == 0, Ch % 64 == 0, Co % 32 == 0 at dilation 1, stride 1 or 2, instead -- the blocks of MobileNetV2
+    `features[8:18]` (64 -> 384 -> 64 / 96, 96 -> 576 -> 96 / 160, 160 -> 960 -> 160 / 320): the two pixel GEMMs run with
+    `tails32` (quarter-tile tails, shares of 128-pixel units), everything else is the same six launches."""
     lib = L.load()
-    pw, pwbn, dwc, dwbn, pl, plbn = _param_grad_parts(block)
+    pw, pwbn, dwc, dwbn, pl, plbn = _param_grad_parts(block, backbone)
     hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
     stride, dil = dwc.stride[0], dwc.dilation[0]
     xn = _nhwc(x, "x", cin)
@@ -587,8 +617,10 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
         (r1, mu1), (r2, mu2), (r3, mu3) = (cache.bn_stats(b) for b in (pwbn, dwbn, plbn))
         rd1 = torch.empty(hid, dtype=torch.float64, device=dev)
         rd3 = torch.empty(cout, dtype=torch.float64, device=dev)
-        pix_gemm(ga, xn, out=out[BLOCK_PARAMS[0]], row_scale=s1, w=pw.weight.detach(), rowdot=rd1, accumulate=accumulate)
-        pix_gemm(go, d, out=out[BLOCK_PARAMS[6]], row_scale=s3, w=pl.weight.detach(), rowdot=rd3, accumulate=accumulate)
+        pix_gemm(ga, xn, out=out[BLOCK_PARAMS[0]], row_scale=s1, w=pw.weight.detach(), rowdot=rd1, accumulate=accumulate,
+                 tails32=backbone)
+        pix_gemm(go, d, out=out[BLOCK_PARAMS[6]], row_scale=s3, w=pl.weight.detach(), rowdot=rd3, accumulate=accumulate,
+                 tails32=backbone)
         ws, slabs = ir_sums_dil(gd, d, e, ga, go, dil) if dil > 1 else (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go)
         k = L.IrFinishDesc()
         k.ws, k.ws_bytes, k.rowdot1, k.rowdot3 = ws.data_ptr(), ws.numel() * 8, rd1.data_ptr(), rd3.data_ptr()
@@ -619,7 +651,7 @@ def _block_recompute(lib, cache, block, x, stride=1, prt=None, dilation=1):
     return e, dd
 
 
-def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None, grads=None, accumulate=False):
+def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None, grads=None, accumulate=False, backbone=False):
     """Backward of an inverted-residual `block` that is TRAINED (the blocks `block_param_grads` covers): `x` `[T,Cin,h,w]` its
     input, `grad_out` `[T,Co,h,w]` = d loss / d output.  Returns `(grad_x [T,Cin,h,w] | None, grads)` with `grads` the dict
     of `block_param_grads` (written into `grads`, or with `accumulate` added to it, when given).  `e` and `d` are recomputed
@@ -627,32 +659,33 @@ def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None,
     carry s3 in their rows (`WeightCache.conv_t_scaled`), `ga` comes from `uavsal_ir_bwd`, and `grad_x = ga . (diag(s1) W1)`
     (+ `grad_out` when the block has the residual) from one Ch -> Cin GEMM of the same kind.  `parts` receives `e`, `d`,
     `gd`, `ga` (dense NHWC).  A block in training mode raises: the BatchNorms use their running statistics (which are not
-    updated), as everywhere in this package."""
-    return _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate)
+    updated), as everywhere in this package.
+    `backbone=True`: a block of MobileNetV2 `features[8:18]` instead (Cin % 32 == 0, hidden % 64 == 0, Cout % 32 == 0, with or
+    without the residual, stride 1 or 2): with stride 2 `grad_out` is `[T,Co,(h-1)//2+1,(w-1)//2+1]`, the depthwise conv is
+    recomputed with its stride, `ga` comes from `uavsal_ir_bwd_s2`, the sums from `uavsal_ir_sums_s2`, and `grad_x` runs
+    over the input grid -- the walk `prior_path_backward` makes through its stride-2 blocks (`_input_grad`: one copy)."""
+    return _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, backbone=backbone)
 
 
-def _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, ed=None, res=None):
+def _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, ed=None, res=None, backbone=False):
     """`block_backward`; `ed`: the block's `(e, d)` when the caller has recomputed them; `res`: an NHWC tensor the `grad_x` GEMM
-    adds where the block has no residual (`st_block_backward`)."""
+    adds where the block has no residual (`st_block_backward`, `backbone_backward`)."""
     lib = L.load()
-    pw, pwbn, dwc, dwbn, pl, plbn = _block_parts(block)
-    hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+    prt = _block_parts(block, backbone)
+    pw, dwc, pl = prt[0], prt[2], prt[4]
+    cin, cout = pw.weight.shape[1], pl.weight.shape[0]
     xn = _nhwc(x, "x", cin)
-    go = _block_grad_out(grad_out, xn, cout)
+    go = _block_grad_out(grad_out, xn, cout, dwc.stride[0])
     dev = xn.device
     _block_grad_tensors(block, grads, accumulate)                    # raise before anything is launched
     with torch.cuda.device(dev):
         cache = cache or WeightCache(dev, {})
-        e, dd = ed or _block_recompute(lib, cache, block, xn)
-        gd = _conv(lib, cache, go, pl, hid, 1, tscale=plbn)
-        ga = ir_bwd(gd, dd, e, *cache.depthwise(dwc, dwbn)[:2])
-        g = None
-        if need_x_grad:
-            g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else res)
-        grads = block_param_grads(block, xn.permute(0, 3, 1, 2), e, dd, go.permute(0, 3, 1, 2), gd=gd, ga=ga, cache=cache,
-                                  out=grads, accumulate=accumulate)
+        pt = {}
+        g = _input_grad(lib, cache, block, prt, xn, go, ed=ed, parts=pt, need_x_grad=need_x_grad, res=res)
+        grads = block_param_grads(block, xn.permute(0, 3, 1, 2), pt["e"], pt["d"], go.permute(0, 3, 1, 2), gd=pt["gd"], ga=pt["ga"],
+                                  cache=cache, out=grads, accumulate=accumulate, backbone=backbone)
         if parts is not None:
-            parts.update(e=e, d=dd, gd=gd, ga=ga)
+            parts.update(pt)
     return (g.permute(0, 3, 1, 2) if need_x_grad else None), grads
 
 
@@ -733,9 +766,11 @@ def _input_grad_parts(block):
     return pw, pwbn, dwc, dwbn, pl, plbn
 
 
-def _input_grad(lib, cache, block, prt, xn, go, ed=None, parts=None, need_x_grad=True):
+def _input_grad(lib, cache, block, prt, xn, go, ed=None, parts=None, need_x_grad=True, res=None):
     """`block_input_grad` on checked NHWC views; `ed`: the block's `(e, d)` when the caller has them.  `need_x_grad=False`:
-    only `parts` is wanted (the operands of the block's parameter gradients), the last GEMM is left out and None returned."""
+    only `parts` is wanted (the operands of the block's parameter gradients), the last GEMM is left out and None returned.
+    `res`: an NHWC tensor on the input grid that the last GEMM adds where the block has no residual.  The one walk through a
+    block, trained (`_block_backward`) or frozen, stride 1 or 2."""
     pw, pwbn, dwc, dwbn, pl, plbn = prt
     hid, cin = pw.weight.shape[:2]
     stride = dwc.stride[0]
@@ -744,7 +779,7 @@ def _input_grad(lib, cache, block, prt, xn, go, ed=None, parts=None, need_x_grad
     ga = (ir_bwd if stride == 1 else ir_bwd_s2)(gd, dd, e, *cache.depthwise(dwc, dwbn)[:2])
     g = None
     if need_x_grad:
-        g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else None)
+        g = _conv(lib, cache, ga, pw, cin, 1, tscale=pwbn, res=go if block.use_res_connect else res)
     if parts is not None:
         parts.update(e=e, d=dd, gd=gd, ga=ga)
     return g
@@ -1432,7 +1467,7 @@ def _srf_grad_tensors(sfnet, out, accumulate):
     return params, out
 
 
-def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, grads=None, accumulate=False):
+def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, grads=None, accumulate=False, need_tap_grads=False):
     """Backward of the SRF-Net head that is TRAINED (`model.sfnet` behind its frozen `features`, reference model.py:139-158;
     eval mode: every BatchNorm on its running statistics, which are not updated): `c3` `[N,32,h,w]`, `c4` `[N,96,h4,w4]`, `c5`
     `[N,320,h5,w5]` the backbone taps, `y` `[N,256,h,w]` the head's output (`taps["sfnet"]`, `conv_last`'s own activation),
@@ -1447,7 +1482,13 @@ def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, gr
     gradient), `lv5_aspp1` (`cbr_backward`) and the three dilated branches (one 256 -> 1920 GEMM with s3 in its rows,
     `uavsal_ir_bwd_dil`, `block_param_grads`).  `parts` receives every intermediate (NHWC): `a1`, `e2..4`, `d2..4`, `a2..4`,
     `aspp`, `x5`, `x4`, `x3`, `cat`, `g_cat`, `g_x5`, `g_x4`, `g_aspp`, `gd2..4`, `ga2..4`.  A head in training mode or CPU tensors
-    raise."""
+    raise.
+    `need_tap_grads=True` (the backbone stage, `backbone_backward`): returns `(grads, g_c4, g_c5)`, the gradients of the `c4`
+    `[N,96,h4,w4]` and `c5` `[N,320,h5,w5]` taps as well.  `g_c4` is `conv_lv4`'s input gradient (`cbr_backward` forms it);
+    `g_c5` is the sum of `lv5_aspp1`'s input gradient and the three branches' `ga_b . (diag(s1) W1_b)`, each one GEMM with the
+    transposed scaled expand weights whose `res=` operand is the sum so far: no pass over the sum of its own.  `c3` gets no
+    gradient (its producers stay frozen).  The 42 parameter gradients are the default call's, bit for bit; the default call
+    runs the launches it always ran."""
     lib = L.load()
     lv3, lv4, a1m, branches, lv5, last = _srf_parts(sfnet)
     c3n, c4n, c5n = (_nhwc(t, nm, cv[0].weight.shape[1]) for t, nm, cv in ((c3, "c3", lv3), (c4, "c4", lv4), (c5, "c5", a1m)))
@@ -1488,14 +1529,16 @@ def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, gr
         g_x4 = bilinear_bwd(g_cat[..., n5:n5 + n4], N, x4.shape[1], x4.shape[2])
         cbr_backward(lv3[0], lv3[1], nchw(c3n), x3, nchw(g_cat[..., n5 + n4:]), need_x_grad=False, cache=cache,
                      grads=sub_g("conv_lv3", ST_CBR_PARAMS), accumulate=accumulate)
-        cbr_backward(lv4[0], lv4[1], nchw(c4n), x4, nchw(g_x4), need_x_grad=False, cache=cache,
-                     grads=sub_g("conv_lv4", ST_CBR_PARAMS), accumulate=accumulate)
+        g_c4, _ = cbr_backward(lv4[0], lv4[1], nchw(c4n), x4, nchw(g_x4), need_x_grad=bool(need_tap_grads), cache=cache,
+                               grads=sub_g("conv_lv4", ST_CBR_PARAMS), accumulate=accumulate)
         g_aspp, _ = cbr_backward(lv5[0], lv5[1], nchw(aspp), x5, nchw(g_x5), cache=cache, grads=sub_g("conv_lv5", ST_CBR_PARAMS),
                                  accumulate=accumulate)
         g_aspp = g_aspp.permute(0, 2, 3, 1)
         w1 = a[0].shape[3]
-        cbr_backward(a1m[0], a1m[1], nchw(c5n), a[0], nchw(g_aspp[..., :w1]), need_x_grad=False, cache=cache,
-                     grads=sub_g("lv5_aspp1", ST_CBR_PARAMS), accumulate=accumulate)
+        g_c5, _ = cbr_backward(a1m[0], a1m[1], nchw(c5n), a[0], nchw(g_aspp[..., :w1]), need_x_grad=bool(need_tap_grads), cache=cache,
+                               grads=sub_g("lv5_aspp1", ST_CBR_PARAMS), accumulate=accumulate)
+        if need_tap_grads:
+            g_c5 = g_c5.permute(0, 2, 3, 1)
         gds, gas = [], []
         for i, ((b, prt, dil), (e, d)) in enumerate(zip(branches, eds)):
             wb = prt[4].weight.shape[0]
@@ -1506,11 +1549,108 @@ def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, gr
                               accumulate=accumulate)
             gds.append(gd)
             gas.append(ga)
+            if need_tap_grads:                                           # + ga_b . (diag(s1) W1_b), added to the sum so far
+                g_c5 = _conv(lib, cache, ga, prt[0], prt[0].weight.shape[1], 1, tscale=prt[1], res=g_c5)
         if parts is not None:
             parts.update(a1=a[0], aspp=aspp, x5=x5, x4=x4, x3=x3, cat=cat, g_cat=g_cat, g_x5=g_x5, g_x4=g_x4, g_aspp=g_aspp)
             for i in range(len(branches)):
                 parts.update({"e%d" % (i + 2): eds[i][0], "d%d" % (i + 2): eds[i][1], "a%d" % (i + 2): a[i + 1],
                               "gd%d" % (i + 2): gds[i], "ga%d" % (i + 2): gas[i]})
+    if need_tap_grads:
+        return grads, g_c4, nchw(g_c5)
+    return grads
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The deep backbone as a ninth stage: MobileNetV2 features[8:18] behind the frozen features[0:8]
+BACKBONE_FIRST, BACKBONE_END = 8, 18                                 # features[8:18]: the blocks at 1/16 and 1/32 resolution
+BACKBONE_C4 = 13                                                     # the block whose output is the c4 tap (c5: block 17)
+BACKBONE_PARAMS = tuple("%d.%s" % (i, n) for i in range(BACKBONE_FIRST, BACKBONE_END) for n in BLOCK_PARAMS)      # the 90 names
+
+
+def backbone_blocks(model):
+    """The ten trainable backbone blocks `model.sfnet.features.features[8:18]`, in forward order: 64 -> 384 -> 64 (three), 64 ->
+    384 -> 96, 96 -> 576 -> 96 (two) at 1/16 resolution, 96 -> 576 -> 160 with stride 2, 160 -> 960 -> 160 (two) and 160 -> 960
+    -> 320 at 1/32.  Hand their parameters to the optimiser and the modules to `model.refresh_weights(*train.backbone_blocks(
+    model))`: their packed forms (natural-layout fused entries or unfused launches) are remade in place.  `features[0..7]`
+    stay frozen: transposed-layout fused entries and the stem cannot be refreshed in place."""
+    sf = getattr(model, "sfnet", model)
+    return list(sf.features.features[BACKBONE_FIRST:BACKBONE_END])
+
+
+def _backbone_grad_tensors(features, out, accumulate):
+    params = {"%d.%s" % (i, n): q for i in range(BACKBONE_FIRST, BACKBONE_END) for n, q in features[i].named_parameters()}
+    if tuple(params) != BACKBONE_PARAMS:
+        raise RuntimeError("the backbone's parameters must be %r of features[%d:%d]" % (BLOCK_PARAMS, BACKBONE_FIRST, BACKBONE_END))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `grads`")
+        out = {n: torch.empty_like(q, memory_format=torch.contiguous_format) for n, q in params.items()}
+    for n, q in params.items():
+        t = out.get(n)
+        if (not torch.is_tensor(t) or t.shape != q.shape or t.dtype != torch.float32 or t.device != q.device
+                or not t.is_contiguous()):
+            raise RuntimeError("grads[%r] must be a dense float32 tensor of the parameter's shape on its device" % n)
+    return params, out
+
+
+def backbone_backward(features, c3, g_c4, g_c5, cache=None, parts=None, grads=None, accumulate=False):
+    """Backward of the backbone blocks that are TRAINED, `features[8:18]` of `features = model.sfnet.features.features` (eval
+    mode: every BatchNorm on its running statistics, which are not updated): `c3` `[N,32,h,w]` the 1/8-scale tap (the output
+    of the frozen `features[6]`), `g_c4` `[N,96,h4,w4]` and `g_c5` `[N,320,h5,w5]` the gradients of the `c4` / `c5` taps
+    (`srf_head_backward(need_tap_grads=True)`; `h4 = (h-1)//2+1`, `h5 = (h4-1)//2+1`).  Returns `grads`, keyed
+    `"<i>.<BLOCK_PARAMS name>"` (`BACKBONE_PARAMS`, 90 names), written into the given dict of dense tensors or with `accumulate`
+    added to it.
+    Recompute: `x7 .. x17` (`x_i` the output of `features[i]`) from `c3` by the forward's own UNFUSED launches -- expand conv,
+    `uavsal_dw3x3`, projection with the residual as its `res=` operand; block 7 (32 -> 192 -> 64, stride 2) is recomputed
+    frozen.  The recomputed `x13` / `x17` differ from the `c4` / `c5` taps only by the rounding between the fused and unfused
+    forward launches (blocks 7..13 may have run as fused entries), as the other stages' recomputes do from theirs.
+    Walk: from `g_c5` through blocks 17 .. 14 (`block_backward(backbone=True)`; block 14 has stride 2 and no residual, so its
+    `grad_x` GEMM adds `g_c4` as its `res=` operand), then blocks 13 .. 8; block 8 forms no input gradient.
+    `parts` receives `x7..x17`, `e8..e17`, `d8..d17`, `gd8..gd17`, `ga8..ga17` (dense NHWC) and `g8..g17`, the gradient of
+    each `x_i` the walk held (`g17` is `g_c5`, `g13` has `g_c4` added; no `g7`).  A block in training mode or CPU tensors raise."""
+    lib = L.load()
+    if not hasattr(features, "__getitem__") or len(features) < BACKBONE_END:
+        raise RuntimeError("backbone_backward takes model.sfnet.features.features (the MobileNetV2 Sequential)")
+    p7 = _input_grad_parts(features[BACKBONE_FIRST - 1])
+    prts = {i: _param_grad_parts(features[i], True) for i in range(BACKBONE_FIRST, BACKBONE_END)}
+    c3n = _nhwc(c3, "c3", p7[0].weight.shape[1])
+    N, hh, ww, _ = c3n.shape
+    dev = c3n.device
+    down = lambda v: (v - 1) // 2 + 1                                     # noqa: E731
+    nchw = lambda t: t.permute(0, 3, 1, 2)                                # noqa: E731
+    h4, w4 = down(hh), down(ww)
+    for nm, g, c, a, b in (("g_c4", g_c4, 96, h4, w4), ("g_c5", g_c5, 320, down(h4), down(w4))):
+        if (not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float32 or g.device != dev
+                or tuple(g.shape) != (N, prts[BACKBONE_C4 if nm == "g_c4" else BACKBONE_END - 1][4].weight.shape[0], a, b)):
+            raise RuntimeError("%s must be a float32 cuda tensor [%d,%d,%d,%d] on the device of c3" % (nm, N, c, a, b))
+    _, grads = _backbone_grad_tensors(features, grads, accumulate)       # raise before anything is launched
+    sub_g = lambda i: {n: grads["%d.%s" % (i, n)] for n in BLOCK_PARAMS}  # noqa: E731
+    g4 = _nhwc(g_c4, "g_c4")
+
+    def forward(blk, prt, x):
+        e, d = _block_recompute(lib, cache, blk, x, prt[2].stride[0], prt)
+        return e, d, _conv(lib, cache, d, prt[4], prt[4].weight.shape[0], 1, bn=prt[5], res=x if blk.use_res_connect else None)
+
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        xs, eds = {BACKBONE_FIRST - 2: c3n}, {}
+        xs[BACKBONE_FIRST - 1] = forward(features[BACKBONE_FIRST - 1], p7, c3n)[2]
+        for i in range(BACKBONE_FIRST, BACKBONE_END):
+            e, d, xs[i] = forward(features[i], prts[i], xs[i - 1])
+            eds[i] = (e, d)
+        g, gs, pts = g_c5, {}, {}
+        for i in range(BACKBONE_END - 1, BACKBONE_FIRST - 1, -1):
+            gs[i] = g
+            pts[i] = {}
+            g, _ = _block_backward(features[i], nchw(xs[i - 1]), g, i > BACKBONE_FIRST, cache, pts[i], sub_g(i), accumulate,
+                                   ed=eds[i], res=g4 if i == BACKBONE_C4 + 1 else None, backbone=True)
+        if parts is not None:
+            for i in range(BACKBONE_FIRST - 1, BACKBONE_END):
+                parts["x%d" % i] = xs[i]
+            for i in range(BACKBONE_FIRST, BACKBONE_END):
+                parts.update({"%s%d" % (k, i): v for k, v in pts[i].items()})
+                parts["g%d" % i] = _nhwc(gs[i], "g")
     return grads
 
 
@@ -1650,7 +1790,7 @@ def _param_grad_tensors(blk):
 
 
 def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False,
-                    st=False, srf=False):
+                    st=False, srf=False, backbone=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -1696,7 +1836,13 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     walked with `need_x_grad=True`, and `srf_head_backward` carries its input gradient (d loss / d `taps["sfnet"]`) over the
     `c3` / `c4` / `c5` taps to the head's 42 parameters (`.grad` set, or added to); no gradient is formed for the taps
     themselves.  Refresh `*train.srf_head(model)` afterwards as well (not `model.sfnet`: its fused backbone blocks and the stem
-    cannot be refreshed in place).  A call without `srf` runs the launches, and copies the taps, it always ran."""
+    cannot be refreshed in place).  A call without `srf` runs the launches, and copies the taps, it always ran.
+    `backbone=True` (needs `srf=True`, and so everything `srf` needs): the deep backbone `backbone_blocks(model)` --
+    MobileNetV2 `features[8:18]`, the ten blocks at 1/16 and 1/32 resolution -- is trained as well, what the reference's
+    unfrozen form does (Demo_Train_Test.py:58 freezes only "to improve the training speed").  `srf_head_backward` then also
+    returns the gradients of the `c4` / `c5` taps and `backbone_backward` walks blocks 17 .. 8 over the `c3` tap, setting -- or
+    adding to -- the `.grad` of their 90 parameters.  `features[0..7]` stay frozen.  Refresh `*train.backbone_blocks(model)`
+    afterwards as well.  A call without `backbone` runs the launches it always ran."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
@@ -1716,6 +1862,9 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if srf and not st:
         raise RuntimeError("srf=True needs st=True (and what st needs): the gradient reaches model.sfnet's head through the "
                            "input of model.st_layer[0]")
+    if backbone and not srf:
+        raise RuntimeError("backbone=True needs srf=True (and what srf needs): the gradient reaches the backbone blocks through "
+                           "the c4 / c5 taps of model.sfnet's head")
     if model.training:
         raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
     if model.precision != "f32":
@@ -1792,6 +1941,14 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
             for n in SRF_HEAD_PARAMS:
                 if hp[n].grad is None:
                     hp[n].grad = (torch.zeros_like if acc else torch.empty_like)(hp[n], memory_format=torch.contiguous_format)
-            srf_head_backward(model.sfnet, taps["c3"], taps["c4"], taps["c5"], taps["sfnet"], g_st, cache=cache,
-                              grads={n: hp[n].grad for n in SRF_HEAD_PARAMS}, accumulate=acc)
+            ret = srf_head_backward(model.sfnet, taps["c3"], taps["c4"], taps["c5"], taps["sfnet"], g_st, cache=cache,
+                                    grads={n: hp[n].grad for n in SRF_HEAD_PARAMS}, accumulate=acc, need_tap_grads=bool(backbone))
+        if backbone:
+            feats = model.sfnet.features.features
+            bp = {"%d.%s" % (i, n): q for i in range(BACKBONE_FIRST, BACKBONE_END) for n, q in feats[i].named_parameters()}
+            acc = any(q.grad is not None for q in bp.values())
+            for q in bp.values():
+                if q.grad is None:
+                    q.grad = (torch.zeros_like if acc else torch.empty_like)(q, memory_format=torch.contiguous_format)
+            backbone_backward(feats, taps["c3"], ret[1], ret[2], cache=cache, grads={n: q.grad for n, q in bp.items()}, accumulate=acc)
     return loss.detach(), out, [h_last[0].detach()]

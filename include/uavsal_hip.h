@@ -784,6 +784,17 @@ int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd 
  *   SRF-Net head on c3 and c4: 64 x 32, 128 x 96); a last workgroup with fewer than four tiles leaves its other waves idle.
  *   Anything else (96 x 64: M is no multiple of 64; 32 x 64, 32 x 32: a 32-wide M below 128 columns; 1920 x 32: wider than
  *   512): UAVSAL_ESHAPE, as before.
+ *   tails32 != 0 (opt-in; the field lies in what was the struct's tail padding, so a zeroed descriptor keeps every rule
+ *   above, every refusal included): any M, N multiple of 32 that those rules refuse is taken as well -- the W1 / W3 gradients
+ *   of MobileNetV2 blocks 8..17: 576 x 96, 960 x 160, 96 x 384, 96 x 576, 160 x 576, 160 x 960 -- by the 128 x 128 tile kernel,
+ *   whose last tile of either side may then end at ANY quarter (32, 64, 96 rows or columns; nothing at or behind row M or
+ *   column N is read, written or enters rowdot).  A shape the rules above take keeps its kernel, K split and bits with the
+ *   flag set.  The K split of these shapes only: K is short there (4800 to 18400 pixels on 3 to 16 tiles), so a share is a
+ *   whole number `ups` of UNITS of 128 pixels instead of chunks: units = ceil(K / 128), want = clamp(512 / tiles, 1, units)
+ *   with tiles = ceil(M / 128) ceil(N / 128), ups = ceil(units / want), shares = ceil(units / ups)
+ *   (uavsal_pix_gemm_shares returns it); share s owns pixels [s ups 128, (s + 1) ups 128) cut at K, its accumulation chains
+ *   end every UAVSAL_WGRAD_CHAIN products counted from its first pixel.  Workspace: shares * M * N floats, [share][M][N], as
+ *   for every other partition; the reduction launch, row_scale, rowdot and accumulate are the same code.
  * uavsal_dec_sums: per slab of picture rows the partial sums S3, G3, S2, Gd, S1 -> `ws` (doubles), from gy (pitched as in
  *   uavsal_dec_bwd_desc), y dense [n_img][H][W], e, d, ga dense [n_img][H][W][C], C % 256 == 0 (else UAVSAL_ESHAPE).
  *   delta3 and delta2 are formed in fp32 exactly as uavsal_dec_bwd forms them; every product is accumulated in double.
@@ -804,6 +815,7 @@ typedef struct uavsal_pix_gemm_desc {
     float* ws;  int64_t ws_bytes;
     float* out;  int32_t ldo;               /* [M] rows of N floats */
     int64_t K;  int32_t M, N, accumulate;
+    int32_t tails32;                        /* 0: the rules above.  1: every other M, N multiple of 32 is taken too (below) */
 } uavsal_pix_gemm_desc;
 
 typedef struct uavsal_dec_sums_desc {

@@ -67,6 +67,8 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                `train.block_param_grads` with `uavsal_ir_bwd_dil` and `uavsal_ir_sums_dil` alone, the pixel GEMM at 64 x 32,
                128 x 96 (the wave-per-tile kernel) and 256 x 1024, and `refresh_weights` over the eight stages on the host and
                on the device (refresh8, refresh8_device).  Alone: --srf-only;
+  backbone     the deep backbone trained too, the ninth stage (`train.backbone_blocks`, 90 parameters): `backbone_phases`' docstring.
+               Alone: --backbone-only;
   refresh pairs beside every refresh case above its `_device` twin: the same in-place edit, then `refresh_weights(...,
                device=True)` (csrc/repack.hip: one launch, no host copy); and at the end (or alone: --refresh-only) the
                host and device refresh of 1, 4, 5 and 6 stages (refreshN_alt / refreshN_device_alt) and one whole six-stage
@@ -77,7 +79,8 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                forward + backward from the same inputs, if torch's conv kernels run there.
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
 
-Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--srf-only] [--frames 20 5]
+Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--srf-only] [--backbone-only]
+        [--frames 20 5]
 """
 import argparse
 import ctypes as C
@@ -635,6 +638,78 @@ def srf_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
         q.grad = None
 
 
+def backbone_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
+    """the phases of the trained deep backbone (train.backbone_blocks: MobileNetV2 features[8:18]), the ninth stage, added to
+    `res`: the six weight-gradient shapes `uavsal_pix_gemm` takes with `tails32`, alone, at the K they have in the walk (1/16
+    scale: 23 x 40, 1/32: 12 x 20 per frame) beside 256 x 256 at the 1/16 K (ms, TFLOP/s, shares, workgroups);
+    `train.backbone_backward` alone; the eight-stage step (step8b) and the same with `backbone=True` (step9), and one whole
+    nine-stage iteration -- step, Adam, refresh -- with host and with device refresh (iter9 / iter9_device), all alternated in
+    the same run, every run listed (`_all_ms`: the spread)."""
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    nets = tuple(train.prior_nets(m).values())
+    boxes = ((m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer, m.fucb_layer, m.cxt_cb_prior) + nets + (m.st_layer,)
+             + tuple(train.srf_head(m)) + tuple(train.backbone_blocks(m)))
+    trained = [q for mod in boxes for q in mod.parameters()]
+    kw8 = dict(decoder=True, fuse=True, fust=True, ctx=True, nets=True, st=True, srf=True)
+    taps = {}
+    m(x, cb, None, taps=taps)
+    c3, c4, c5 = (taps[k].contiguous(memory_format=cl) for k in ("c3", "c4", "c5"))
+    T = c3.shape[0]
+    g4 = (torch.randn_like(c4) / c4[0].numel()).contiguous(memory_format=cl)      # (timing only: any gradient of the right shape)
+    g5 = (torch.randn_like(c5) / c5[0].numel()).contiguous(memory_format=cl)
+    feats = m.sfnet.features.features
+    grads = train.backbone_backward(feats, c3, g4, g5, cache=cache)
+    grids = {16: tuple(c4.shape[2:]), 32: tuple(c5.shape[2:])}
+    gems = {}
+    for M, N, scale in ((576, 96, 16), (960, 160, 32), (96, 384, 16), (96, 576, 16), (160, 576, 32), (160, 960, 32), (256, 256, 16)):
+        hh, ww = grids[scale]
+        a = 1e-2 * torch.randn((T, hh, ww, M), device=dev)
+        b = torch.randn((T, hh, ww, N), device=dev)
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+        gems["%dx%d" % (M, N)] = (M, N, T * hh * ww, lambda a=a, b=b, out=out: train.pix_gemm(a, b, out=out, tails32=True))
+    cases = {"backbone_bwd": lambda: train.backbone_backward(feats, c3, g4, g5, cache=cache, grads=grads)}
+    for tag, (_, _, _, fn) in gems.items():
+        cases["backbone_pix_gemm_" + tag] = fn
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+    for tag, (M, N, K, _) in gems.items():
+        gd = L.PixGemmDesc()
+        gd.K, gd.M, gd.N, gd.tails32 = K, M, N, 1
+        sh = int(lib.uavsal_pix_gemm_shares(C.byref(gd)))
+        res["backbone_pix_gemm_%s_K" % tag], res["backbone_pix_gemm_%s_shares" % tag] = K, sh
+        res["backbone_pix_gemm_%s_workgroups" % tag] = -(-M // 128) * -(-N // 128) * sh
+        res["backbone_pix_gemm_%s_tflops" % tag] = 2.0 * M * N * K / (res["backbone_pix_gemm_%s_ms" % tag] * 1e-3) / 1e12
+    opt = torch.optim.Adam(trained, lr=1e-4, betas=(0.9, 0.999), weight_decay=5e-5)
+
+    def stepper(**kw):
+        def run():
+            for q in trained:
+                q.grad = None
+            train.recurrence_step(m, x, cb, None, y_gaze, **kw8, **kw)
+        return run
+
+    def iteration(device):
+        def run():
+            opt.zero_grad()
+            train.recurrence_step(m, x, cb, None, y_gaze, backbone=True, **kw8)
+            opt.step()
+            m.refresh_weights(*boxes, device=device)
+        return run
+    runs = {"step8b": stepper(), "step9": stepper(backbone=True), "iter9": iteration(False), "iter9_device": iteration(True)}
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # alternated in the same run, every run listed
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    for q in trained:
+        q.grad = None
+
+
 def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
     """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
     from iip_uavsal_saliency_amd import repack
@@ -691,7 +766,7 @@ def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
         q.grad = None
 
 
-def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False):
+def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False, backbone_only=False):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
@@ -718,6 +793,10 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False,
     if srf_only:
         res = {"T": T}
         srf_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+        return res
+    if backbone_only:
+        res = {"T": T}
+        backbone_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
         return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -819,6 +898,7 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False,
     st_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
     srf_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
     refresh_phases(res, m, x, cb, y_gaze, iters, repeats)
+    backbone_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
     if not skip_eager:
         try:
             run = eager_step(m, taps["prefuse"], torch.zeros((1, 256, h, w), device=dev), g_y)
@@ -839,11 +919,13 @@ def main():
     ap.add_argument("--refresh-only", action="store_true", help="only the refresh / iteration pairs (refresh_phases)")
     ap.add_argument("--st-only", action="store_true", help="only the phases of the seventh stage (st_phases)")
     ap.add_argument("--srf-only", action="store_true", help="only the phases of the eighth stage (srf_phases)")
+    ap.add_argument("--backbone-only", action="store_true", help="only the phases of the ninth stage (backbone_phases)")
     ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
     out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
-           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only) for T in a.frames]}
+           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only, a.backbone_only)
+                     for T in a.frames]}
     print(json.dumps(out))
 
 
