@@ -270,10 +270,13 @@ class IrBwdDesc(C.Structure):
                 ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
 
 
+_IR_SUMS_FIELDS = [("gd", _f), ("d", _f), ("e", _f), ("ga", _f), ("go", _f), ("ldgo", C.c_int32),
+                   ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                   ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ch", C.c_int32), ("Co", C.c_int32)]
+
+
 class IrSumsDesc(C.Structure):
-    _fields_ = [("gd", _f), ("d", _f), ("e", _f), ("ga", _f), ("go", _f), ("ldgo", C.c_int32),
-                ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
-                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ch", C.c_int32), ("Co", C.c_int32)]
+    _fields_ = _IR_SUMS_FIELDS + [("ch16", C.c_int32)]         # ch16: in what was tail padding (the size did not change)
 
 
 class IrFinishDesc(C.Structure):
@@ -366,13 +369,24 @@ class IrBwdDilDesc(C.Structure):
 
 
 class IrSumsDilDesc(C.Structure):
-    _fields_ = IrSumsDesc._fields_ + [("dil", C.c_int32)]
+    _fields_ = _IR_SUMS_FIELDS + [("dil", C.c_int32)]
 
 
 SRF_DESC_TYPES = [Conv3WgradDesc, IrBwdDilDesc, IrSumsDilDesc]  # sized by uavsal_srf_sizeof_desc (csrc/train_srf.hip)
 
+
+class SkinnyWgradDesc(C.Structure):
+    _fields_ = [("a", _f), ("lda", C.c_int32), ("b", _f), ("ldb", C.c_int32), ("row_scale", _f),
+                ("w", _f), ("ldw", C.c_int32), ("rowdot", C.c_void_p), ("ws", _f), ("ws_bytes", C.c_int64),
+                ("out", _f), ("ldo", C.c_int32), ("K", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("accumulate", C.c_int32)]
+
+
+SKINNY_UNIT, SKINNY_SHARES = 128, 1024       # UAVSAL_SKINNY_UNIT, UAVSAL_SKINNY_SHARES: the K split of uavsal_skinny_wgrad
+SKINNY_MAX_NARROW, SKINNY_MAX_WIDE = 32, 192
+SHALLOW_DESC_TYPES = [SkinnyWgradDesc]      # sized by uavsal_shallow_sizeof_desc (csrc/train_shallow.hip)
+
 REPACK_MAX_SRC = 4            # UAVSAL_REPACK_MAX_SRC: weights / BatchNorms side by side in one entry (csrc/repack.hip)
-REPACK_CONV, REPACK_WINO, REPACK_FOLD, REPACK_DW, REPACK_COPY = range(5)
+REPACK_CONV, REPACK_WINO, REPACK_FOLD, REPACK_DW, REPACK_COPY, REPACK_COPY_T = range(6)
 REPACK_LAYOUT = {"f32": 0, "f32k32": 0, "f16x3": 1, "f16x3i": 2, "f16x3j": 3, "bf16": 4, "bf16x3": 5}
 REPACK_SCALE, REPACK_BIAS, REPACK_RSTD, REPACK_MEAN = range(4)
 
@@ -440,6 +454,7 @@ SYMBOLS = [
     ("uavsal_ir_sums_slab_rows", C.c_int, [C.POINTER(IrSumsDesc)]),
     ("uavsal_ir_sums", C.c_int, [C.POINTER(IrSumsDesc), C.c_void_p]),
     ("uavsal_ir_finish", C.c_int, [C.POINTER(IrFinishDesc), C.c_void_p]),
+    ("uavsal_ir_finish_c16", C.c_int, [C.POINTER(IrFinishDesc), C.c_void_p]),
     ("uavsal_block_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_ir_bwd_s2", C.c_int, [C.POINTER(IrBwdS2Desc), C.c_void_p]),
     ("uavsal_bilinear_ac_bwd", C.c_int, [C.POINTER(BilinearBwdDesc), C.c_void_p]),
@@ -473,6 +488,10 @@ SYMBOLS = [
     ("uavsal_ir_sums_dil_slab_rows", C.c_int, [C.POINTER(IrSumsDilDesc)]),
     ("uavsal_ir_sums_dil", C.c_int, [C.POINTER(IrSumsDilDesc), C.c_void_p]),
     ("uavsal_srf_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_skinny_wgrad_workspace_bytes", C.c_int64, [C.POINTER(SkinnyWgradDesc)]),
+    ("uavsal_skinny_wgrad_shares", C.c_int, [C.POINTER(SkinnyWgradDesc)]),
+    ("uavsal_skinny_wgrad", C.c_int, [C.POINTER(SkinnyWgradDesc), C.c_void_p]),
+    ("uavsal_shallow_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_repack", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("uavsal_repack_sizeof_desc", C.c_int, []),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
@@ -558,7 +577,8 @@ def load():
                           (lib.uavsal_train_decoder_sizeof_desc, TRAIN_DECODER_DESC_TYPES),
                           (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES),
                           (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES),
-                          (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES), (lib.uavsal_srf_sizeof_desc, SRF_DESC_TYPES)):
+                          (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES), (lib.uavsal_srf_sizeof_desc, SRF_DESC_TYPES),
+                          (lib.uavsal_shallow_sizeof_desc, SHALLOW_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

@@ -204,6 +204,11 @@ __global__ __launch_bounds__(kThreads) void repack_kernel(const uavsal_repack_en
         break;
     }
     case UAVSAL_REPACK_COPY: reinterpret_cast<float*>(e.dst)[u] = e.src[0][u]; break;
+    case UAVSAL_REPACK_COPY_T: {                        // [C][N] from src[0] = [N][C]: u = c * N + n
+        const int c = (int)(u / e.N), n = (int)(u - (long long)c * e.N);
+        reinterpret_cast<float*>(e.dst)[u] = e.src[0][(long long)n * e.C + c];
+        break;
+    }
     default: break;
     }
 }

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void ir_sums_kernel(const SumK p) {
 
     const int cg = blockIdx.y;
     const int c = cg * kGroup + lane * 4;
-    const bool live = c < p.Ch;                                // Ch % 64 == 0: a lane's four channels are all inside or all outside
+    const bool live = c < p.Ch;                                // Ch % 4 == 0: a lane's four channels are all inside or all outside
     double acc[kNS][4];
 #pragma unroll
     for (int j = 0; j < kNS; ++j)
@@ -190,8 +190,11 @@ __global__ __launch_bounds__(256) void ir_sums_kernel(const SumK p) {
     }
 }
 
+// the hidden widths taken: multiples of 64, or with the descriptor's ch16 of 16 (the kernel itself needs Ch % 4 == 0 only)
+inline int ch_step(int ch16) { return ch16 ? 16 : 64; }
+
 bool sums_plan(const uavsal_ir_sums_desc* d, SumK& k) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || (d->Ch % 64) || (d->Co % 4)) return false;
+    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || (d->Ch % ch_step(d->ch16)) || (d->Co % 4)) return false;
     k.cgroups = (d->Ch + kGroup - 1) / kGroup;
     if ((long long)d->H * d->W > 0x7fffffffll || k.cgroups + (d->Co + kGroup - 1) / kGroup > 65535) return false;
     k.H = d->H; k.W = d->W; k.Ch = d->Ch; k.Co = d->Co;
@@ -297,7 +300,7 @@ extern "C" int64_t uavsal_ir_sums_workspace_bytes(const uavsal_ir_sums_desc* d) 
 extern "C" int uavsal_ir_sums(const uavsal_ir_sums_desc* d, uavsal_stream_t stream) {
     if (!d || !d->gd || !d->d || !d->e || !d->ga || !d->go || !d->ws) return UAVSAL_EINVAL;
     if (d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0) return UAVSAL_EINVAL;
-    if (d->Ch % 64) return UAVSAL_ESHAPE;
+    if (d->Ch % ch_step(d->ch16)) return UAVSAL_ESHAPE;
     if ((d->Co & 3) || (d->ldgo & 3)) return UAVSAL_EALIGN;
     if (d->ldgo < d->Co) return UAVSAL_EINVAL;
     SumK k;
@@ -310,12 +313,12 @@ extern "C" int uavsal_ir_sums(const uavsal_ir_sums_desc* d, uavsal_stream_t stre
     return uavsal_launch_status();
 }
 
-extern "C" int uavsal_ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t stream) {
+static int ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t stream, int ch16) {
     if (!d || !d->ws || !d->rowdot1 || !d->rowdot3 || !d->wd || !d->s2 || !d->r1 || !d->mu1 || !d->r2 || !d->mu2 || !d->r3 ||
         !d->mu3 || !d->g_gamma1 || !d->g_beta1 || !d->g_wd || !d->g_gamma2 || !d->g_beta2 || !d->g_gamma3 || !d->g_beta3)
         return UAVSAL_EINVAL;
     if (d->Ch <= 0 || d->Co <= 0 || d->slabs <= 0) return UAVSAL_EINVAL;
-    if ((d->Ch % 64) || (d->Co & 3)) return UAVSAL_ESHAPE;
+    if ((d->Ch % ch_step(ch16)) || (d->Co & 3)) return UAVSAL_ESHAPE;
     if (d->ws_bytes < (int64_t)d->slabs * ((int64_t)kNS * d->Ch + d->Co) * (int64_t)sizeof(double)) return UAVSAL_EINVAL;
     const void* f4[] = {d->wd, d->s2, d->r1, d->mu1, d->r2, d->mu2, d->r3, d->mu3, d->g_gamma1, d->g_beta1, d->g_wd,
                         d->g_gamma2, d->g_beta2, d->g_gamma3, d->g_beta3};
@@ -332,3 +335,7 @@ extern "C" int uavsal_ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t 
     hipLaunchKernelGGL(ir_finish_kernel, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
     return uavsal_launch_status();
 }
+
+extern "C" int uavsal_ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t stream) { return ir_finish(d, stream, 0); }
+
+extern "C" int uavsal_ir_finish_c16(const uavsal_ir_finish_desc* d, uavsal_stream_t stream) { return ir_finish(d, stream, 1); }

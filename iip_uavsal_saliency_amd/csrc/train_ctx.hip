@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void ir_sums_s2_kernel(const Sum2K p) {
 
     const int cg = blockIdx.y;
     const int c = cg * kGroup + lane * 4;
-    const bool live = c < p.Ch;                                // Ch % 64 == 0: a lane's four channels are all inside or all outside
+    const bool live = c < p.Ch;                                // Ch % 4 == 0: a lane's four channels are all inside or all outside
     double acc[kNS][4];
 #pragma unroll
     for (int j = 0; j < kNS; ++j)
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void ir_sums_s2_kernel(const Sum2K p) {
 }
 
 bool sums2_plan(const uavsal_ir_sums_s2_desc* d, Sum2K& k) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || (d->Ch % 64) || (d->Co % 4)) return false;
+    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || (d->Ch % (d->ch16 ? 16 : 64)) || (d->Co % 4)) return false;
     k.cgroups = (d->Ch + kGroup - 1) / kGroup;
     if ((long long)d->H * d->W > 0x7fffffffll || k.cgroups + (d->Co + kGroup - 1) / kGroup > 65535) return false;
     k.H = d->H; k.W = d->W; k.Ho = (d->H - 1) / 2 + 1; k.Wo = (d->W - 1) / 2 + 1; k.Ch = d->Ch; k.Co = d->Co;
@@ -348,7 +348,7 @@ extern "C" int64_t uavsal_ir_sums_s2_workspace_bytes(const uavsal_ir_sums_s2_des
 extern "C" int uavsal_ir_sums_s2(const uavsal_ir_sums_s2_desc* d, uavsal_stream_t stream) {
     if (!d || !d->gd || !d->d || !d->e || !d->ga || !d->go || !d->ws) return UAVSAL_EINVAL;
     if (d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0) return UAVSAL_EINVAL;
-    if (d->Ch % 64) return UAVSAL_ESHAPE;
+    if (d->Ch % (d->ch16 ? 16 : 64)) return UAVSAL_ESHAPE;     // ch16: the opt-in of uavsal_ir_sums_desc (the kernel needs Ch % 4 == 0 only)
     if ((d->Co & 3) || (d->ldgo & 3)) return UAVSAL_EALIGN;
     if (d->ldgo < d->Co) return UAVSAL_EINVAL;
     Sum2K k;

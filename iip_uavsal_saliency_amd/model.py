@@ -292,7 +292,7 @@ class UAVSal(nn.Module):
 
     invalidate_engines = _drop_engines
 
-    def refresh_weights(self, *modules, device=False):
+    def refresh_weights(self, *modules, device=False, fused_t=False):
         """After an optimiser step on the parameters of `modules` (e.g. `model.rnn`, `model.conv_out_st`, `model.fucbst_layer`):
         repack every packed copy of their weights -- conv weights in every layout in use, the Winograd transforms, the
         transposed forms of train.py, and for the decoder and the fusion block their BatchNorm folds and statistics and their
@@ -315,6 +315,8 @@ class UAVSal(nn.Module):
         `RequestPipeline` has requests in flight is unsupported, as it is for the host path.  ValueError, before anything is written, when a
         store of this model is on the CPU, or a parameter or buffer of `modules` is not a contiguous fp32 tensor on the
         store's device -- a `channels_last` weight, or a model with packed weights on a second GPU: the host path takes both.
+        `fused_t=True` (keyword only, opt-in): transposed-layout fused blocks among `modules` (MobileNetV2 `features[2:8]`,
+        `train.shallow_blocks`) are remade in place too, on either path (`WeightCache.refresh`); without it they raise.
         Returns the number of packed tensors refreshed (0 when nothing was packed yet, or when the plans were dropped)."""
         from .weights import WeightCache
         if self._wversion is None or "_wtensors" not in self.__dict__:
@@ -328,9 +330,10 @@ class UAVSal(nn.Module):
         caches = [WeightCache(dev, store) for dev, store in self._wshared.items()]
         if device and any(c.device.type == "cpu" for c in caches):
             raise ValueError("refresh_weights(device=True) needs packed weights on a GPU: this model holds a CPU store")
+        kw = {"fused_t": True} if fused_t else {}
         for c in caches:                                 # every key can be remade, or nothing is touched (the device path's dry
-            (c.refresh_device if device else c.refresh)(mods, dry=True)      # pass builds its table: the same walk, no host copy)
-        n = sum(c.refresh_device(mods) if device else c.refresh(mods) for c in caches)
+            (c.refresh_device if device else c.refresh)(mods, dry=True, **kw)      # pass builds its table: the same walk, no host copy)
+        n = sum(c.refresh_device(mods, **kw) if device else c.refresh(mods, **kw) for c in caches)
         for m in [self] + list(self.__dict__.get("_stream_replicas") or []):
             if m._wversion is not None and "_wtensors" in m.__dict__:
                 m._wversion = m._weights_version()

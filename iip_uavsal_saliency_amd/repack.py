@@ -149,8 +149,19 @@ def _copy(key, dst, mod, name="weight"):
     return e
 
 
-def _fused(key, stored, blk):
-    """The natural-layout dictionary of a fused block, name by name as `weights._fused_host` makes it."""
+def _copy_t(key, dst, mod, name="weight"):
+    """A 1x1 conv weight [Cout][Cin] written transposed, [Cin][Cout]: what `weights._fused_host(blk, False)` holds."""
+    e = Entry(key, L.REPACK_COPY_T, dst)
+    e.src = [e.own(mod, name)]
+    e.N, e.C = int(e.src[0].shape[0]), int(e.src[0].shape[1])
+    e.units = e.N * e.C
+    e.nbytes = 4 * e.units
+    return e
+
+
+def _fused(key, stored, blk, natural=True):
+    """The dictionary of a fused block, name by name as `weights._fused_host` makes it: `natural` the 1x1 weights as the module
+    holds them, else transposed."""
     seq = list(blk.conv)
     pw, pwbn = (None, None) if blk.expand_ratio == 1 else (seq[0][0], seq.pop(0)[1])
     dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1], seq[2]
@@ -158,10 +169,11 @@ def _fused(key, stored, blk):
     if sorted(names) != sorted(stored):
         raise RuntimeError("a packed fused entry does not match its block any more: call model.invalidate_engines()")
     out = []
+    mat = _copy if natural else _copy_t
     if pw is not None:
-        out += [_copy(key, stored["w1"], pw)] + _affine(key, (stored["s1"], stored["b1"]), [pwbn])
+        out += [mat(key, stored["w1"], pw)] + _affine(key, (stored["s1"], stored["b1"]), [pwbn])
     out += [_dw(key, stored["wd"], [dwc])] + _affine(key, (stored["sd"], stored["bd"]), [dwbn])
-    return out + [_copy(key, stored["w2"], pl)] + _affine(key, (stored["s2"], stored["b2"]), [plbn])
+    return out + [mat(key, stored["w2"], pl)] + _affine(key, (stored["s2"], stored["b2"]), [plbn])
 
 
 def _of_key(store, key, ms, mods):
@@ -185,7 +197,7 @@ def _of_key(store, key, ms, mods):
         dwc, pl = ms
         return ([_dw(key, dst[0], [dwc])] + _affine(key, dst[1:3], [W._bn_after(mods, dwc)]) + [_copy(key, dst[3], pl)]
                 + _affine(key, dst[4:6], [W._bn_after(mods, pl)]))
-    return _fused(key, dst, W._block_of(mods, ms[0]))
+    return _fused(key, dst, W._block_of(mods, ms[0]), bool(key[2]))
 
 
 def touched_keys(store, mods):
@@ -193,15 +205,16 @@ def touched_keys(store, mods):
     return [k for k in store if isinstance(k, tuple) and k[0] != TABLE_KIND and any(isinstance(i, int) and i in mods for i in k[1:])]
 
 
-def entries(cache, mods):
+def entries(cache, mods, fused_t=False):
     """One `Entry` per packed tensor of every store entry whose key holds the id of a module in `mods` (id -> module), in the
     order `WeightCache.refresh` visits them; the keys they carry are the entries `refresh` counts.  Raises what `refresh`
     raises: NotImplementedError for a transposed-layout fused block or the stem, RuntimeError for a key that joins modules
-    not all given or whose neighbours (`_bn_after`, `_block_of`) are not among `mods`."""
+    not all given or whose neighbours (`_bn_after`, `_block_of`) are not among `mods`.  `fused_t=True`: a transposed-layout fused
+    block is taken as well (its 1x1 weights as COPY_T entries), as `WeightCache.refresh(fused_t=True)` takes it."""
     out = []
     for key in touched_keys(cache.store, mods):
         kind = key[0]
-        if kind not in W._REFRESH_IDS or (kind == "fused" and not key[2]):
+        if kind not in W._REFRESH_IDS or (kind == "fused" and not key[2] and not fused_t):
             raise NotImplementedError("packed %r weights cannot be refreshed in place: call model.invalidate_engines()" % (kind,))
         ids = W._REFRESH_IDS[kind](key)
         if not all(i in mods for i in ids):
@@ -271,9 +284,9 @@ class _Record:
     reads: each DISTINCT set of modules a caller refreshes leaves its own table and record there (a training loop has one), and
     nothing evicts one before the store itself is dropped (`model.invalidate_engines()`, a load, an edit of another module)."""
 
-    def __init__(self, cache, mods):
+    def __init__(self, cache, mods, fused_t=False):
         self.keys = touched_keys(cache.store, mods)
-        ents = entries(cache, mods)
+        ents = entries(cache, mods, fused_t)
         self.n_entries, self.count = len(ents), len(self.keys)
         self.owners = [(m, n, getattr(m, n).data_ptr()) for e in ents for m, n in e.owners]
         self.dsts = _dst_ptrs(cache.store, self.keys)
@@ -288,14 +301,14 @@ class _Record:
                 and self.dsts == _dst_ptrs(cache.store, self.keys))
 
 
-def refresh(cache, mods, dry=False):
+def refresh(cache, mods, dry=False, fused_t=False):
     """`WeightCache.refresh_device`: see there."""
     if cache.device.type == "cpu":
         raise ValueError("refresh_weights(device=True) needs packed weights on a GPU: this store is on the CPU")
-    key = (TABLE_KIND, tuple(sorted(mods)))
+    key = (TABLE_KIND, tuple(sorted(mods))) + ((True,) if fused_t else ())
     rec = cache.store.get(key)
     if rec is None or not rec.current(cache, mods):
-        rec = cache.store[key] = _Record(cache, mods)
+        rec = cache.store[key] = _Record(cache, mods, fused_t)
     if not dry and rec.table is not None:
         with torch.cuda.device(cache.device):
             stream = C.c_void_p(torch.cuda.current_stream(cache.device).cuda_stream)

@@ -413,7 +413,10 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     are refreshed as well.
     `"backbone"` (only behind `"srf"`): `recurrence_step(..., backbone=True)` also sets the gradients of the deep backbone
     `train.backbone_blocks(model)` -- MobileNetV2 `features[8:18]` -- and those ten modules are refreshed as well;
-    `features[0..7]` stay frozen.
+    `features[0..7]` stay frozen unless `"shallow"` follows.
+    `"shallow"` (only behind `"backbone"`): `recurrence_step(..., shallow=True)` also sets the gradients of the shallow backbone
+    `train.shallow_blocks(model)` -- MobileNetV2 `features[2:8]` -- and those six modules are refreshed as well, with
+    `fused_t=True` (their packed forms are transposed-layout fused entries); the stem and `features[1]` stay frozen.
     `refresh`: `"host"` (the default) repacks the trained stages' weights on the host after every step; `"device"` repacks
     them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host)."""
     from . import losses as _losses
@@ -429,10 +432,11 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     allowed += [s + ("st",) for s in allowed if "fuse" in s and ("fust" in s or not getattr(model, "num_cb", 0))]
     allowed += [s + ("srf",) for s in allowed if "st" in s]
     allowed += [s + ("backbone",) for s in allowed if "srf" in s]
+    allowed += [s + ("shallow",) for s in allowed if "backbone" in s]
     if stages not in allowed:
         raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
                          "'fuse' (then 'ctx', then 'nets', behind 'fuse' too; 'st' the very last, behind 'fuse' and, in a "
-                         "model with priors, 'fust'; only 'srf' may follow 'st', only 'backbone' 'srf'), got %r" % (stages,))
+                         "model with priors, 'fust'; only 'srf' may follow 'st', only 'backbone' 'srf', only 'shallow' 'backbone'), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
 
     def step(x, cb, state, y):
@@ -456,7 +460,10 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
             mods.extend(_train.srf_head(model))
         if "backbone" in kw:
             mods.extend(_train.backbone_blocks(model))
-        if refresh == "device":
+        if "shallow" in kw:
+            mods.extend(_train.shallow_blocks(model))
+            model.refresh_weights(*mods, device=refresh == "device", fused_t=True)
+        elif refresh == "device":
             model.refresh_weights(*mods, device=True)
         else:
             model.refresh_weights(*mods)                  # (no keyword: a model-like object without `device=` keeps working)

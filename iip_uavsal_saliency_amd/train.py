@@ -35,8 +35,12 @@ stages go through `cbr_backward`, its dilated ASPP branches through `block_param
 `uavsal_ir_sums_dil`) and the dense 3x3 `conv_last` through `conv3_backward` (`uavsal_conv3_wgrad`).  And a ninth: the deep
 backbone, MobileNetV2 `features[8:18]` (`recurrence_step(backbone=True)`, `backbone_blocks`, `backbone_backward`): the head also
 hands out the gradients of its `c4` / `c5` taps and the ten blocks at 1/16 and 1/32 resolution go through `block_backward(
-backbone=True)` (their widths are multiples of 32: `uavsal_pix_gemm` with `tails32`).  Only `features[0..7]` and the stem stay
-frozen; BatchNorm in eval mode remains the documented difference.
+backbone=True)` (their widths are multiples of 32: `uavsal_pix_gemm` with `tails32`).  And a tenth: the shallow backbone,
+`features[2:8]` (`recurrence_step(shallow=True)`, `shallow_blocks`, `shallow_backward`; csrc/train_shallow.hip): the head also
+hands out the gradient of its `c3` tap, the ninth stage that of block 7's output, and the six blocks at 1/4 to 1/16 resolution go
+through `block_backward(shallow=True)` (widths of 16 to 192: `skinny_wgrad` for the weight gradients `uavsal_pix_gemm` refuses,
+the channel sums with their Ch % 16 opt-in).  Only the stem and `features[1]` stay frozen; BatchNorm in eval mode remains the
+documented difference.
 
 New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
@@ -235,6 +239,47 @@ def pix_gemm(a, b, out=None, row_scale=None, w=None, rowdot=None, accumulate=Fal
     return out
 
 
+def skinny_wgrad(a, b, out=None, row_scale=None, w=None, rowdot=None, accumulate=False):
+    """`uavsal_skinny_wgrad` on the current stream: `pix_gemm`'s arguments and results for the skinny products it refuses,
+    M and N multiples of 8 with `min(M, N) <= 32` and `max(M, N) <= 192` (the 1x1 weight gradients of MobileNetV2
+    `features[2:8]`: 96 x 16, 144 x 24, 24 x 96, 24 x 144, 32 x 144).  One pass over both operands, a wave per share of the
+    pixels (csrc/train_shallow.hip; the partition is stated in include/uavsal_hip.h).  Two launches, no synchronisation."""
+    lib = L.load()
+    ap, lda, *sa = _nhwc_view(a)
+    bp, ldb, *sb = _nhwc_view(b)
+    M, N = sa[3], sb[3]
+    if sa[:3] != sb[:3] or a.device != b.device:
+        raise RuntimeError("skinny_wgrad: a and b must cover the same pixels on one device")
+    dev = a.device
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `out`")
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    if out.numel() != M * N or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError("out must be a dense float32 tensor of %d x %d elements on the device" % (M, N))
+    k = L.SkinnyWgradDesc()
+    k.a, k.lda, k.b, k.ldb = ap, lda, bp, ldb
+    k.K, k.M, k.N, k.accumulate = sa[0] * sa[1] * sa[2], M, N, int(bool(accumulate))
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or row_scale.device != dev or row_scale.numel() < M or not row_scale.is_contiguous():
+            raise RuntimeError("row_scale must be a dense float32 vector of at least %d elements on the device" % M)
+        k.row_scale = row_scale.data_ptr()
+    if rowdot is not None:
+        if (w is None or w.numel() != M * N or not w.is_contiguous() or w.dtype != torch.float32 or w.device != dev
+                or rowdot.dtype != torch.float64 or rowdot.numel() != M or not rowdot.is_contiguous() or rowdot.device != dev):
+            raise RuntimeError("rowdot needs a dense float32 `w` of %d x %d elements and a dense float64 [%d] on the device" % (M, N, M))
+        k.w, k.ldw, k.rowdot = w.data_ptr(), N, rowdot.data_ptr()
+    k.out, k.ldo = out.data_ptr(), N
+    nbytes = int(lib.uavsal_skinny_wgrad_workspace_bytes(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, "uavsal_skinny_wgrad")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    with torch.cuda.device(dev):
+        L.check(lib.uavsal_skinny_wgrad(C.byref(k), _stream(a)), "uavsal_skinny_wgrad")
+    return out
+
+
 def dec_sums(grad_out, y, e, d, ga, w3, s3):
     """`uavsal_dec_sums` on the current stream -> `(ws, slabs)`: the per-slab partial sums (float64, the layout of
     include/uavsal_hip.h) that `uavsal_dec_finish` takes.  Arguments as `dec_bwd`'s; `ga` dense NHWC like `e`."""
@@ -357,11 +402,11 @@ def decoder_backward(block, h_seq, grad_out, cache=None, y=None, parts=None, gra
 BLOCK_PARAMS = DECODER_PARAMS                                        # a dwBlock with an expand conv: the same nine names
 
 
-def _block_parts(block, backbone=False):
+def _block_parts(block, backbone=False, shallow=False):
     """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual block the block backward covers, or a RuntimeError.
-    `backbone`: the shapes of MobileNetV2 `features[8:18]` instead (`_param_grad_parts`)."""
-    if backbone:
-        return _param_grad_parts(block, True)
+    `backbone`: the shapes of MobileNetV2 `features[8:18]` instead, `shallow`: those of `features[2:8]` (`_param_grad_parts`)."""
+    if backbone or shallow:
+        return _param_grad_parts(block, backbone, shallow)
     seq = getattr(block, "conv", None)
     if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4 or getattr(block, "stride", None) != 1
             or getattr(block, "dilation", None) != 1 or seq[1][0].stride != (1, 1) or seq[1][0].dilation != (1, 1)):
@@ -377,15 +422,32 @@ def _block_parts(block, backbone=False):
     return pw, pwbn, dwc, dwbn, pl, plbn
 
 
-def _param_grad_parts(block, backbone=False):
+def _param_grad_parts(block, backbone=False, shallow=False):
     """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual block whose nine gradients `block_param_grads` forms: what
     `_block_parts` takes, and stride 2 and Cout % 64 == 0 besides (the blocks of the multi-prior path), or a RuntimeError.
     `backbone`: Cin % 32 == 0, hidden % 64 == 0, Cout % 32 == 0 at dilation 1 instead, stride 1 (with or without the residual)
     or 2 -- MobileNetV2 `features[8:18]`.  `model_feature.InvertedResidual` and `dwBlock` are the same module to this code:
-    the same `conv` Sequential, the same nine parameter names (`BLOCK_PARAMS`), which is checked here."""
+    the same `conv` Sequential, the same nine parameter names (`BLOCK_PARAMS`), which is checked here.
+    `shallow`: Cin % 8 == 0, hidden % 16 == 0, Cout % 8 == 0 at dilation 1, stride 1 or 2, an expand conv present -- MobileNetV2
+    `features[2:8]` (16 -> 96 -> 24, 24 -> 144 -> 24 / 32, 32 -> 192 -> 32 / 64); it takes what `backbone` takes as well."""
     seq = getattr(block, "conv", None)
     stride = getattr(block, "stride", None)
     dil = getattr(block, "dilation", None)
+    if shallow:
+        if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4
+                or tuple(n for n, _ in block.named_parameters()) != BLOCK_PARAMS):
+            raise RuntimeError("the shallow backward takes an inverted-residual block with an expand conv (expand 1x1, depthwise "
+                               "3x3, projection 1x1: features[2..17]), not features[1] or the stem")
+        if stride not in (1, 2) or dil != 1 or seq[1][0].stride != (stride, stride) or seq[1][0].dilation != (1, 1):
+            raise RuntimeError("the shallow backward takes stride 1 or 2 at dilation 1 (a dilated block with stride 2 is not covered)")
+        pw, pwbn, dwc, dwbn, pl, plbn = seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2], seq[3]
+        hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
+        if cout % 8 or hid % 16 or cin % 8:
+            raise RuntimeError("the shallow backward needs Cout %% 8 == 0, hidden %% 16 == 0 and Cin %% 8 == 0, got %d -> %d -> %d"
+                               % (cin, hid, cout))
+        if block.training:
+            raise RuntimeError("the block's BatchNorms use their running statistics: call model.eval()")
+        return pw, pwbn, dwc, dwbn, pl, plbn
     if backbone:
         if (seq is None or getattr(block, "expand_ratio", 1) == 1 or len(seq) != 4
                 or tuple(n for n, _ in block.named_parameters()) != BLOCK_PARAMS):
@@ -466,10 +528,11 @@ def ir_bwd(gd, d, e, wd9, s2):
     return ga
 
 
-def ir_sums(gd, d, e, ga, go):
+def ir_sums(gd, d, e, ga, go, ch16=False):
     """`uavsal_ir_sums` on the current stream -> `(ws, slabs)`: the per-slab partial sums (float64, the layout of
     include/uavsal_hip.h) that `uavsal_ir_finish` takes.  `gd`, `d`, `e`, `ga` dense NHWC `[T,h,w,Ch]`; `go` an NHWC view
-    `[T,h,w,Co]` of the same pixels (a channel slice is read in place)."""
+    `[T,h,w,Co]` of the same pixels (a channel slice is read in place).  `ch16=True`: any Ch % 16 == 0 is taken, not only
+    Ch % 64 == 0 (the descriptor's opt-in; `ir_finish(..., ch16=True)` takes the workspace)."""
     lib = L.load()
     if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
                 for t in (gd, d, e, ga)) or not all(t.shape == e.shape and t.device == e.device for t in (gd, d, ga))):
@@ -482,7 +545,7 @@ def ir_sums(gd, d, e, ga, go):
         raise RuntimeError("ir_sums: go must cover the pixels of e")
     k = L.IrSumsDesc()
     k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
-    k.n_img, k.H, k.W, k.Ch, k.Co = T, hh, ww, c, gs[3]
+    k.n_img, k.H, k.W, k.Ch, k.Co, k.ch16 = T, hh, ww, c, gs[3], int(bool(ch16))
     nbytes = int(lib.uavsal_ir_sums_workspace_bytes(C.byref(k)))
     if nbytes <= 0:
         L.check(-3, "uavsal_ir_sums")
@@ -492,10 +555,10 @@ def ir_sums(gd, d, e, ga, go):
     return ws, int(lib.uavsal_ir_sums_slabs(C.byref(k)))
 
 
-def ir_sums_s2(gd, d, e, ga, go):
+def ir_sums_s2(gd, d, e, ga, go, ch16=False):
     """`uavsal_ir_sums_s2` on the current stream -> `(ws, slabs)`: `ir_sums` for a depthwise 3x3 with stride 2, in the same
     workspace layout.  `e`, `ga` dense NHWC `[n,H,W,Ch]`; `gd`, `d` dense NHWC `[n,Ho,Wo,Ch]` with `Ho = (H-1)//2+1`,
-    `Wo = (W-1)//2+1`; `go` an NHWC view `[n,Ho,Wo,Co]` (a channel slice is read in place)."""
+    `Wo = (W-1)//2+1`; `go` an NHWC view `[n,Ho,Wo,Co]` (a channel slice is read in place).  `ch16`: as in `ir_sums`."""
     lib = L.load()
     _dense_nhwc("ir_sums_s2", "gd, d, e, ga", gd, d, e, ga)
     n, hh, ww, c = e.shape
@@ -510,7 +573,7 @@ def ir_sums_s2(gd, d, e, ga, go):
         raise RuntimeError("ir_sums_s2: go must cover the pixels of d")
     k = L.IrSumsS2Desc()
     k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
-    k.n_img, k.H, k.W, k.Ch, k.Co = n, hh, ww, c, gs[3]
+    k.n_img, k.H, k.W, k.Ch, k.Co, k.ch16 = n, hh, ww, c, gs[3], int(bool(ch16))
     nbytes = int(lib.uavsal_ir_sums_s2_workspace_bytes(C.byref(k)))
     if nbytes <= 0:
         L.check(-3, "uavsal_ir_sums_s2")
@@ -569,7 +632,15 @@ def ir_sums_dil(gd, d, e, ga, go, dil):
     return ws, int(lib.uavsal_ir_sums_dil_slabs(C.byref(k)))
 
 
-def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, out=None, accumulate=False, backbone=False):
+def _takes_pix_gemm(lib, M, N, K):
+    """Whether `uavsal_pix_gemm` with `tails32` takes an M x N product (a host query, no launch)."""
+    k = L.PixGemmDesc()
+    k.K, k.M, k.N, k.tails32 = K, M, N, 1
+    return int(lib.uavsal_pix_gemm_shares(C.byref(k))) > 0
+
+
+def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, out=None, accumulate=False, backbone=False,
+                      shallow=False):
     """The gradients of the nine parameters of an inverted-residual `block` (a `dwBlock` with an expand conv, stride 1 or 2,
     dilation 1, with or without the residual; eval mode: the BatchNorms on their running statistics, which are not updated)
     from given tensors, teacher-forced: `x` `[T,Cin,h,w]` the block's input, `e` dense NHWC `[T,h,w,Ch]` its expanded and `d`
@@ -588,9 +659,13 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
     `uavsal_ir_sums_dil` stand in for the undilated launches, everything else is the same.
     `backbone=True`: Cin % 32 == 0, Ch % 64 == 0, Co % 32 == 0 at dilation 1, stride 1 or 2, instead -- the blocks of MobileNetV2
     `features[8:18]` (64 -> 384 -> 64 / 96, 96 -> 576 -> 96 / 160, 160 -> 960 -> 160 / 320): the two pixel GEMMs run with
-    `tails32` (quarter-tile tails, shares of 128-pixel units), everything else is the same six launches."""
+    `tails32` (quarter-tile tails, shares of 128-pixel units), everything else is the same six launches.
+    `shallow=True`: Cin % 8 == 0, Ch % 16 == 0, Co % 8 == 0 at dilation 1, stride 1 or 2, instead -- the blocks of MobileNetV2
+    `features[2:8]` (16 -> 96 -> 24, 24 -> 144 -> 24 / 32, 32 -> 192 -> 32 / 64).  A weight-gradient product that
+    `uavsal_pix_gemm` takes (192 x 32, 32 x 192, 64 x 192) keeps that launch; the others (96 x 16, 144 x 24, 24 x 96, 24 x 144,
+    32 x 144) go to `skinny_wgrad`; the channel sums and the finalise run with their Ch % 16 opt-in.  The same six launches."""
     lib = L.load()
-    pw, pwbn, dwc, dwbn, pl, plbn = _param_grad_parts(block, backbone)
+    pw, pwbn, dwc, dwbn, pl, plbn = _param_grad_parts(block, backbone, shallow)
     hid, cin, cout = pw.weight.shape[0], pw.weight.shape[1], pl.weight.shape[0]
     stride, dil = dwc.stride[0], dwc.dilation[0]
     xn = _nhwc(x, "x", cin)
@@ -617,11 +692,18 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
         (r1, mu1), (r2, mu2), (r3, mu3) = (cache.bn_stats(b) for b in (pwbn, dwbn, plbn))
         rd1 = torch.empty(hid, dtype=torch.float64, device=dev)
         rd3 = torch.empty(cout, dtype=torch.float64, device=dev)
-        pix_gemm(ga, xn, out=out[BLOCK_PARAMS[0]], row_scale=s1, w=pw.weight.detach(), rowdot=rd1, accumulate=accumulate,
-                 tails32=backbone)
-        pix_gemm(go, d, out=out[BLOCK_PARAMS[6]], row_scale=s3, w=pl.weight.detach(), rowdot=rd3, accumulate=accumulate,
-                 tails32=backbone)
-        ws, slabs = ir_sums_dil(gd, d, e, ga, go, dil) if dil > 1 else (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go)
+        for a, b, name, s, wt, rd in ((ga, xn, BLOCK_PARAMS[0], s1, pw, rd1), (go, d, BLOCK_PARAMS[6], s3, pl, rd3)):
+            kw = dict(out=out[name], row_scale=s, w=wt.weight.detach(), rowdot=rd, accumulate=accumulate)
+            if shallow and not _takes_pix_gemm(lib, a.shape[-1], b.shape[-1], b.shape[0] * b.shape[1] * b.shape[2]):
+                skinny_wgrad(a, b, **kw)
+            else:
+                pix_gemm(a, b, tails32=backbone or shallow, **kw)
+        if dil > 1:
+            ws, slabs = ir_sums_dil(gd, d, e, ga, go, dil)
+        elif shallow:
+            ws, slabs = (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go, ch16=True)
+        else:
+            ws, slabs = (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go)
         k = L.IrFinishDesc()
         k.ws, k.ws_bytes, k.rowdot1, k.rowdot3 = ws.data_ptr(), ws.numel() * 8, rd1.data_ptr(), rd3.data_ptr()
         k.wd, k.s2 = dwc.weight.data_ptr(), s2.data_ptr()
@@ -629,7 +711,10 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
         (k.g_gamma1, k.g_beta1, k.g_wd, k.g_gamma2, k.g_beta2) = (out[n].data_ptr() for n in BLOCK_PARAMS[1:6])
         k.g_gamma3, k.g_beta3 = out[BLOCK_PARAMS[7]].data_ptr(), out[BLOCK_PARAMS[8]].data_ptr()
         k.Ch, k.Co, k.slabs, k.accumulate = hid, cout, slabs, int(bool(accumulate))
-        L.check(lib.uavsal_ir_finish(C.byref(k), _stream(xn)), "uavsal_ir_finish")
+        if shallow:
+            L.check(lib.uavsal_ir_finish_c16(C.byref(k), _stream(xn)), "uavsal_ir_finish_c16")
+        else:
+            L.check(lib.uavsal_ir_finish(C.byref(k), _stream(xn)), "uavsal_ir_finish")
     return out
 
 
@@ -651,7 +736,8 @@ def _block_recompute(lib, cache, block, x, stride=1, prt=None, dilation=1):
     return e, dd
 
 
-def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None, grads=None, accumulate=False, backbone=False):
+def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None, grads=None, accumulate=False, backbone=False,
+                   shallow=False):
     """Backward of an inverted-residual `block` that is TRAINED (the blocks `block_param_grads` covers): `x` `[T,Cin,h,w]` its
     input, `grad_out` `[T,Co,h,w]` = d loss / d output.  Returns `(grad_x [T,Cin,h,w] | None, grads)` with `grads` the dict
     of `block_param_grads` (written into `grads`, or with `accumulate` added to it, when given).  `e` and `d` are recomputed
@@ -663,15 +749,18 @@ def block_backward(block, x, grad_out, need_x_grad=True, cache=None, parts=None,
     `backbone=True`: a block of MobileNetV2 `features[8:18]` instead (Cin % 32 == 0, hidden % 64 == 0, Cout % 32 == 0, with or
     without the residual, stride 1 or 2): with stride 2 `grad_out` is `[T,Co,(h-1)//2+1,(w-1)//2+1]`, the depthwise conv is
     recomputed with its stride, `ga` comes from `uavsal_ir_bwd_s2`, the sums from `uavsal_ir_sums_s2`, and `grad_x` runs
-    over the input grid -- the walk `prior_path_backward` makes through its stride-2 blocks (`_input_grad`: one copy)."""
-    return _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, backbone=backbone)
+    over the input grid -- the walk `prior_path_backward` makes through its stride-2 blocks (`_input_grad`: one copy).
+    `shallow=True`: a block of MobileNetV2 `features[2:8]` instead (Cin % 8 == 0, hidden % 16 == 0, Cout % 8 == 0): the same
+    walk, with the skinny weight gradients and the Ch % 16 sums of `block_param_grads(shallow=True)`."""
+    return _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, backbone=backbone, shallow=shallow)
 
 
-def _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, ed=None, res=None, backbone=False):
+def _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumulate, ed=None, res=None, backbone=False,
+                    shallow=False):
     """`block_backward`; `ed`: the block's `(e, d)` when the caller has recomputed them; `res`: an NHWC tensor the `grad_x` GEMM
     adds where the block has no residual (`st_block_backward`, `backbone_backward`)."""
     lib = L.load()
-    prt = _block_parts(block, backbone)
+    prt = _block_parts(block, backbone, shallow)
     pw, dwc, pl = prt[0], prt[2], prt[4]
     cin, cout = pw.weight.shape[1], pl.weight.shape[0]
     xn = _nhwc(x, "x", cin)
@@ -683,7 +772,7 @@ def _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumu
         pt = {}
         g = _input_grad(lib, cache, block, prt, xn, go, ed=ed, parts=pt, need_x_grad=need_x_grad, res=res)
         grads = block_param_grads(block, xn.permute(0, 3, 1, 2), pt["e"], pt["d"], go.permute(0, 3, 1, 2), gd=pt["gd"], ga=pt["ga"],
-                                  cache=cache, out=grads, accumulate=accumulate, backbone=backbone)
+                                  cache=cache, out=grads, accumulate=accumulate, backbone=backbone, shallow=shallow)
         if parts is not None:
             parts.update(pt)
     return (g.permute(0, 3, 1, 2) if need_x_grad else None), grads
@@ -1326,8 +1415,8 @@ SRF_HEAD_PARAMS = tuple("%s.%s" % (m, n) for m in SRF_HEAD                 # the
 def srf_head(model):
     """The eight trainable modules of the SRF-Net head, in `SRF_HEAD` order: what the reference initialises itself in
     `uavsal_srfnet_aspp` (model.py:120-131).  Hand their parameters to the optimiser and the modules to
-    `model.refresh_weights(*train.srf_head(model))` -- never `model.sfnet` itself, whose frozen `features` hold fused blocks and
-    the stem, which cannot be refreshed in place."""
+    `model.refresh_weights(*train.srf_head(model))` -- never `model.sfnet` itself, whose frozen `features` hold the stem and
+    `features[1]`, which cannot be refreshed in place."""
     sf = getattr(model, "sfnet", model)
     return [getattr(sf, n) for n in SRF_HEAD]
 
@@ -1467,7 +1556,8 @@ def _srf_grad_tensors(sfnet, out, accumulate):
     return params, out
 
 
-def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, grads=None, accumulate=False, need_tap_grads=False):
+def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, grads=None, accumulate=False, need_tap_grads=False,
+                      need_c3_grad=False):
     """Backward of the SRF-Net head that is TRAINED (`model.sfnet` behind its frozen `features`, reference model.py:139-158;
     eval mode: every BatchNorm on its running statistics, which are not updated): `c3` `[N,32,h,w]`, `c4` `[N,96,h4,w4]`, `c5`
     `[N,320,h5,w5]` the backbone taps, `y` `[N,256,h,w]` the head's output (`taps["sfnet"]`, `conv_last`'s own activation),
@@ -1488,7 +1578,10 @@ def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, gr
     `g_c5` is the sum of `lv5_aspp1`'s input gradient and the three branches' `ga_b . (diag(s1) W1_b)`, each one GEMM with the
     transposed scaled expand weights whose `res=` operand is the sum so far: no pass over the sum of its own.  `c3` gets no
     gradient (its producers stay frozen).  The 42 parameter gradients are the default call's, bit for bit; the default call
-    runs the launches it always ran."""
+    runs the launches it always ran.
+    `need_c3_grad=True` (the shallow-backbone stage, `shallow_backward`): `g_c3` `[N,32,h,w]`, `conv_lv3`'s input gradient
+    (`cbr_backward` forms it: one more GEMM), is appended to what the call returns -- `(grads, g_c4, g_c5, g_c3)` with
+    `need_tap_grads`, `(grads, g_c3)` without.  Every other result keeps its launches and bits."""
     lib = L.load()
     lv3, lv4, a1m, branches, lv5, last = _srf_parts(sfnet)
     c3n, c4n, c5n = (_nhwc(t, nm, cv[0].weight.shape[1]) for t, nm, cv in ((c3, "c3", lv3), (c4, "c4", lv4), (c5, "c5", a1m)))
@@ -1527,8 +1620,8 @@ def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, gr
         g_cat = g_cat.permute(0, 2, 3, 1)
         g_x5 = bilinear_bwd(g_cat[..., :n5], N, x5.shape[1], x5.shape[2])
         g_x4 = bilinear_bwd(g_cat[..., n5:n5 + n4], N, x4.shape[1], x4.shape[2])
-        cbr_backward(lv3[0], lv3[1], nchw(c3n), x3, nchw(g_cat[..., n5 + n4:]), need_x_grad=False, cache=cache,
-                     grads=sub_g("conv_lv3", ST_CBR_PARAMS), accumulate=accumulate)
+        g_c3, _ = cbr_backward(lv3[0], lv3[1], nchw(c3n), x3, nchw(g_cat[..., n5 + n4:]), need_x_grad=bool(need_c3_grad), cache=cache,
+                               grads=sub_g("conv_lv3", ST_CBR_PARAMS), accumulate=accumulate)
         g_c4, _ = cbr_backward(lv4[0], lv4[1], nchw(c4n), x4, nchw(g_x4), need_x_grad=bool(need_tap_grads), cache=cache,
                                grads=sub_g("conv_lv4", ST_CBR_PARAMS), accumulate=accumulate)
         g_aspp, _ = cbr_backward(lv5[0], lv5[1], nchw(aspp), x5, nchw(g_x5), cache=cache, grads=sub_g("conv_lv5", ST_CBR_PARAMS),
@@ -1556,9 +1649,10 @@ def srf_head_backward(sfnet, c3, c4, c5, y, grad_out, cache=None, parts=None, gr
             for i in range(len(branches)):
                 parts.update({"e%d" % (i + 2): eds[i][0], "d%d" % (i + 2): eds[i][1], "a%d" % (i + 2): a[i + 1],
                               "gd%d" % (i + 2): gds[i], "ga%d" % (i + 2): gas[i]})
-    if need_tap_grads:
-        return grads, g_c4, nchw(g_c5)
-    return grads
+    ret = (grads, g_c4, nchw(g_c5)) if need_tap_grads else (grads,)
+    if need_c3_grad:
+        ret += (g_c3,)
+    return ret if len(ret) > 1 else grads
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1572,8 +1666,8 @@ def backbone_blocks(model):
     """The ten trainable backbone blocks `model.sfnet.features.features[8:18]`, in forward order: 64 -> 384 -> 64 (three), 64 ->
     384 -> 96, 96 -> 576 -> 96 (two) at 1/16 resolution, 96 -> 576 -> 160 with stride 2, 160 -> 960 -> 160 (two) and 160 -> 960
     -> 320 at 1/32.  Hand their parameters to the optimiser and the modules to `model.refresh_weights(*train.backbone_blocks(
-    model))`: their packed forms (natural-layout fused entries or unfused launches) are remade in place.  `features[0..7]`
-    stay frozen: transposed-layout fused entries and the stem cannot be refreshed in place."""
+    model))`: their packed forms (natural-layout fused entries or unfused launches) are remade in place.  `features[2:8]`
+    are the next stage (`shallow_blocks`); the stem and `features[1]` stay frozen."""
     sf = getattr(model, "sfnet", model)
     return list(sf.features.features[BACKBONE_FIRST:BACKBONE_END])
 
@@ -1594,7 +1688,7 @@ def _backbone_grad_tensors(features, out, accumulate):
     return params, out
 
 
-def backbone_backward(features, c3, g_c4, g_c5, cache=None, parts=None, grads=None, accumulate=False):
+def backbone_backward(features, c3, g_c4, g_c5, cache=None, parts=None, grads=None, accumulate=False, need_x_grad=False):
     """Backward of the backbone blocks that are TRAINED, `features[8:18]` of `features = model.sfnet.features.features` (eval
     mode: every BatchNorm on its running statistics, which are not updated): `c3` `[N,32,h,w]` the 1/8-scale tap (the output
     of the frozen `features[6]`), `g_c4` `[N,96,h4,w4]` and `g_c5` `[N,320,h5,w5]` the gradients of the `c4` / `c5` taps
@@ -1608,7 +1702,10 @@ def backbone_backward(features, c3, g_c4, g_c5, cache=None, parts=None, grads=No
     Walk: from `g_c5` through blocks 17 .. 14 (`block_backward(backbone=True)`; block 14 has stride 2 and no residual, so its
     `grad_x` GEMM adds `g_c4` as its `res=` operand), then blocks 13 .. 8; block 8 forms no input gradient.
     `parts` receives `x7..x17`, `e8..e17`, `d8..d17`, `gd8..gd17`, `ga8..ga17` (dense NHWC) and `g8..g17`, the gradient of
-    each `x_i` the walk held (`g17` is `g_c5`, `g13` has `g_c4` added; no `g7`).  A block in training mode or CPU tensors raise."""
+    each `x_i` the walk held (`g17` is `g_c5`, `g13` has `g_c4` added; no `g7`).  A block in training mode or CPU tensors raise.
+    `need_x_grad=True` (the shallow-backbone stage, `shallow_backward`): block 8 forms its input gradient too (one more GEMM)
+    and the call returns `(grads, g_x7)`, `g_x7` `[N,64,h4,w4]` the gradient of block 7's output; `parts` then holds it as `g7`.
+    The 90 gradients keep their launches and bits."""
     lib = L.load()
     if not hasattr(features, "__getitem__") or len(features) < BACKBONE_END:
         raise RuntimeError("backbone_backward takes model.sfnet.features.features (the MobileNetV2 Sequential)")
@@ -1643,12 +1740,156 @@ def backbone_backward(features, c3, g_c4, g_c5, cache=None, parts=None, grads=No
         for i in range(BACKBONE_END - 1, BACKBONE_FIRST - 1, -1):
             gs[i] = g
             pts[i] = {}
-            g, _ = _block_backward(features[i], nchw(xs[i - 1]), g, i > BACKBONE_FIRST, cache, pts[i], sub_g(i), accumulate,
+            g, _ = _block_backward(features[i], nchw(xs[i - 1]), g, i > BACKBONE_FIRST or bool(need_x_grad), cache, pts[i], sub_g(i), accumulate,
                                    ed=eds[i], res=g4 if i == BACKBONE_C4 + 1 else None, backbone=True)
         if parts is not None:
             for i in range(BACKBONE_FIRST - 1, BACKBONE_END):
                 parts["x%d" % i] = xs[i]
             for i in range(BACKBONE_FIRST, BACKBONE_END):
+                parts.update({"%s%d" % (k, i): v for k, v in pts[i].items()})
+                parts["g%d" % i] = _nhwc(gs[i], "g")
+            if need_x_grad:
+                parts["g%d" % (BACKBONE_FIRST - 1)] = _nhwc(g, "g")
+    return (grads, g) if need_x_grad else grads
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The shallow backbone as a tenth stage: MobileNetV2 features[2:8] behind the frozen stem and features[1]
+SHALLOW_FIRST, SHALLOW_END = 2, 8                                    # features[2:8]: the blocks at 1/4, 1/8 and (block 7's output) 1/16
+SHALLOW_C3 = 6                                                       # the block whose output is the c3 tap
+SHALLOW_PARAMS = tuple("%d.%s" % (i, n) for i in range(SHALLOW_FIRST, SHALLOW_END) for n in BLOCK_PARAMS)         # the 54 names
+
+
+def shallow_blocks(model):
+    """The six trainable shallow backbone blocks `model.sfnet.features.features[2:8]`, in forward order: 16 -> 96 -> 24 with
+    stride 2, 24 -> 144 -> 24 at 1/4 resolution, 24 -> 144 -> 32 with stride 2, 32 -> 192 -> 32 (two) at 1/8, 32 -> 192 -> 64
+    with stride 2.  Hand their parameters to the optimiser and the modules to `model.refresh_weights(*train.shallow_blocks(
+    model), fused_t=True)`: their packed forms are transposed-layout fused entries, which that keyword remakes in place.  The
+    stem and `features[1]` (the one block without an expand conv) stay frozen."""
+    sf = getattr(model, "sfnet", model)
+    return list(sf.features.features[SHALLOW_FIRST:SHALLOW_END])
+
+
+def _shallow_grad_tensors(features, out, accumulate):
+    params = {"%d.%s" % (i, n): q for i in range(SHALLOW_FIRST, SHALLOW_END) for n, q in features[i].named_parameters()}
+    if tuple(params) != SHALLOW_PARAMS:
+        raise RuntimeError("the shallow backbone's parameters must be %r of features[%d:%d]" % (BLOCK_PARAMS, SHALLOW_FIRST, SHALLOW_END))
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate needs `grads`")
+        out = {n: torch.empty_like(q, memory_format=torch.contiguous_format) for n, q in params.items()}
+    for n, q in params.items():
+        t = out.get(n)
+        if (not torch.is_tensor(t) or t.shape != q.shape or t.dtype != torch.float32 or t.device != q.device
+                or not t.is_contiguous()):
+            raise RuntimeError("grads[%r] must be a dense float32 tensor of the parameter's shape on its device" % n)
+    return params, out
+
+
+def _stem_forward(lib, cache, stem, x):
+    """`features[0]` (conv 3x3 stride 2 + BatchNorm + ReLU6) on the frames `x` `[N,3,H,W]` (fp32, or uint8 RGB that the kernel
+    normalises on load) -> NHWC `[N,(H-1)//2+1,(W-1)//2+1,32]`: the forward's own `uavsal_stem_conv`, no synchronisation."""
+    from .synth import IMAGENET_MEAN, IMAGENET_STD
+    n, _, H, W = x.shape
+    out = torch.empty((n, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 32), dtype=torch.float32, device=x.device)
+    ws, s, b = cache.stem(stem[0], stem[1])
+    d = L.StemDesc()
+    if x.dtype == torch.uint8:
+        d.inp, d.in_u8 = None, x.data_ptr()
+    else:
+        d.inp, d.in_u8 = x.data_ptr(), None
+    d.w, d.scale, d.bias, d.out, d.ldo = ws.data_ptr(), s.data_ptr(), b.data_ptr(), out.data_ptr(), 32
+    d.n_img, d.H, d.W = n, H, W
+    for i in range(3):
+        d.mean[i], d.stdv[i] = IMAGENET_MEAN[i], IMAGENET_STD[i]
+    L.check(lib.uavsal_stem_conv(C.byref(d), _stream(out)), "uavsal_stem_conv")
+    return out
+
+
+def _fused_forward(lib, cache, blk, x):
+    """One FROZEN small-channel inverted-residual block as the forward's one launch (`uavsal_fused_ir`, transposed-layout
+    weights from `cache.fused_block`): `x` NHWC -> its output NHWC.  No synchronisation."""
+    ip, ldi, n, h, w, cin = _nhwc_view(x)
+    dwc = list(blk.conv)[0 if blk.expand_ratio == 1 else 1][0]
+    hid, cout, stride = dwc.weight.shape[0], blk.conv[-2].weight.shape[0], dwc.stride[0]
+    out = torch.empty((n, (h - 1) // stride + 1, (w - 1) // stride + 1, cout), dtype=torch.float32, device=x.device)
+    d = L.FusedIrDesc()
+    d.inp, d.ldi = ip, ldi
+    d.n_img, d.H, d.W, d.Cin, d.hidden, d.Cout, d.stride, d.tile = n, h, w, cin, hid, cout, stride, 0
+    d.w1 = (1 << 20) if blk.expand_ratio != 1 else None
+    if int(lib.uavsal_fused_ir_supported(C.byref(d))) != 1:
+        raise RuntimeError("no transposed-layout fused instance for (Cin, hidden, Cout, stride) = %s" % ((cin, hid, cout, stride),))
+    ws = cache.fused_block(blk, False)
+    if blk.expand_ratio != 1:
+        d.w1, d.scale1, d.bias1 = ws["w1"].data_ptr(), ws["s1"].data_ptr(), ws["b1"].data_ptr()
+    else:
+        d.w1 = None
+    d.wd, d.scale_d, d.bias_d = ws["wd"].data_ptr(), ws["sd"].data_ptr(), ws["bd"].data_ptr()
+    d.w2, d.scale2, d.bias2 = ws["w2"].data_ptr(), ws["s2"].data_ptr(), ws["b2"].data_ptr()
+    if blk.use_res_connect:
+        d.res, d.ldr = ip, ldi
+    d.out, d.ldo = out.data_ptr(), cout
+    L.check(lib.uavsal_fused_ir(C.byref(d), _stream(x)), "uavsal_fused_ir")
+    return out
+
+
+def shallow_backward(features, x, g_c3, g_x7, cache=None, parts=None, grads=None, accumulate=False):
+    """Backward of the shallow backbone blocks that are TRAINED, `features[2:8]` of `features = model.sfnet.features.features`
+    (eval mode: every BatchNorm on its running statistics, which are not updated): `x` `[N,3,H,W]` the model's input frames as
+    `recurrence_step` receives them, `g_c3` `[N,32,h,w]` the gradient of the `c3` tap (`srf_head_backward(need_c3_grad=True)`;
+    `h` is `H` halved three times, each time `(v-1)//2+1`) and `g_x7` `[N,64,h4,w4]` the gradient of block 7's output
+    (`backbone_backward(need_x_grad=True)`).  Returns `grads`, keyed `"<i>.<BLOCK_PARAMS name>"` (`SHALLOW_PARAMS`, 54 names),
+    written into the given dict of dense tensors or with `accumulate` added to it.
+    Recompute: `x0` by the stem's launch and `x1` by `features[1]`'s one fused launch, both frozen; then `x2 .. x7` and every
+    block's `(e, d)` by the forward's own UNFUSED launches (expand conv, `uavsal_dw3x3`, projection with the residual as its
+    `res=` operand), as `backbone_backward` does -- block 7 a second time, here trained.
+    Walk: `g_x7` enters block 7 (stride 2, no residual), whose `grad_x` GEMM adds `g_c3` as its `res=` operand; blocks 6 and 5
+    (residual), 4 (stride 2), 3 (residual) and 2, which forms no input gradient (`block_backward(shallow=True)`).
+    `parts` receives `x0..x7`, `e2..e7`, `d2..d7`, `gd2..gd7`, `ga2..ga7` (dense NHWC) and `g2..g7`, the gradient of each `x_i`
+    the walk held (`g7` is `g_x7`, `g6` has `g_c3` added).  A block in training mode or CPU tensors raise."""
+    lib = L.load()
+    if not hasattr(features, "__getitem__") or len(features) < SHALLOW_END:
+        raise RuntimeError("shallow_backward takes model.sfnet.features.features (the MobileNetV2 Sequential)")
+    prts = {i: _param_grad_parts(features[i], False, True) for i in range(SHALLOW_FIRST, SHALLOW_END)}
+    stem, f1 = features[0], features[1]
+    if stem.training or f1.training:
+        raise RuntimeError("the stem and features[1] are frozen: their BatchNorms are folded in eval mode (call model.eval())")
+    if (not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4 or x.shape[1] != 3 or x.dtype not in (torch.float32, torch.uint8)):
+        raise RuntimeError("x must be the input frames, a float32 (or uint8) cuda tensor [N,3,H,W] (no CPU fallback)")
+    dev = x.device
+    down = lambda v: (v - 1) // 2 + 1                                     # noqa: E731
+    nchw = lambda t: t.permute(0, 3, 1, 2)                                # noqa: E731
+    N = x.shape[0]
+    h3, w3 = down(down(down(x.shape[2]))), down(down(down(x.shape[3])))
+    for nm, g, i, a, b in (("g_c3", g_c3, SHALLOW_C3, h3, w3), ("g_x7", g_x7, SHALLOW_END - 1, down(h3), down(w3))):
+        c = prts[i][4].weight.shape[0]
+        if (not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float32 or g.device != dev or tuple(g.shape) != (N, c, a, b)):
+            raise RuntimeError("%s must be a float32 cuda tensor [%d,%d,%d,%d] on the device of x" % (nm, N, c, a, b))
+    _, grads = _shallow_grad_tensors(features, grads, accumulate)        # raise before anything is launched
+    sub_g = lambda i: {n: grads["%d.%s" % (i, n)] for n in BLOCK_PARAMS}  # noqa: E731
+    g3 = _nhwc(g_c3, "g_c3")
+
+    def forward(blk, prt, xin):
+        e, d = _block_recompute(lib, cache, blk, xin, prt[2].stride[0], prt)
+        return e, d, _conv(lib, cache, d, prt[4], prt[4].weight.shape[0], 1, bn=prt[5], res=xin if blk.use_res_connect else None)
+
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        xs, eds = {0: _stem_forward(lib, cache, stem, x.contiguous())}, {}
+        xs[1] = _fused_forward(lib, cache, f1, xs[0])
+        for i in range(SHALLOW_FIRST, SHALLOW_END):
+            e, d, xs[i] = forward(features[i], prts[i], xs[i - 1])
+            eds[i] = (e, d)
+        g, gs, pts = g_x7, {}, {}
+        for i in range(SHALLOW_END - 1, SHALLOW_FIRST - 1, -1):
+            gs[i] = g
+            pts[i] = {}
+            g, _ = _block_backward(features[i], nchw(xs[i - 1]), g, i > SHALLOW_FIRST, cache, pts[i], sub_g(i), accumulate,
+                                   ed=eds[i], res=g3 if i == SHALLOW_C3 + 1 else None, shallow=True)
+        if parts is not None:
+            for i in range(SHALLOW_END):
+                parts["x%d" % i] = xs[i]
+            for i in range(SHALLOW_FIRST, SHALLOW_END):
                 parts.update({"%s%d" % (k, i): v for k, v in pts[i].items()})
                 parts["g%d" % i] = _nhwc(gs[i], "g")
     return grads
@@ -1790,7 +2031,7 @@ def _param_grad_tensors(blk):
 
 
 def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False,
-                    st=False, srf=False, backbone=False):
+                    st=False, srf=False, backbone=False, shallow=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -1835,14 +2076,20 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     parameter of `model.sfnet` the reference initialises itself; only the ImageNet `features` stay frozen.  ST block 0 is then
     walked with `need_x_grad=True`, and `srf_head_backward` carries its input gradient (d loss / d `taps["sfnet"]`) over the
     `c3` / `c4` / `c5` taps to the head's 42 parameters (`.grad` set, or added to); no gradient is formed for the taps
-    themselves.  Refresh `*train.srf_head(model)` afterwards as well (not `model.sfnet`: its fused backbone blocks and the stem
-    cannot be refreshed in place).  A call without `srf` runs the launches, and copies the taps, it always ran.
+    themselves.  Refresh `*train.srf_head(model)` afterwards as well (not `model.sfnet`: the stem and `features[1]` cannot be
+    refreshed in place, and the transposed-layout fused blocks only with `fused_t=True`).  A call without `srf` runs the launches, and copies the taps, it always ran.
     `backbone=True` (needs `srf=True`, and so everything `srf` needs): the deep backbone `backbone_blocks(model)` --
     MobileNetV2 `features[8:18]`, the ten blocks at 1/16 and 1/32 resolution -- is trained as well, what the reference's
     unfrozen form does (Demo_Train_Test.py:58 freezes only "to improve the training speed").  `srf_head_backward` then also
     returns the gradients of the `c4` / `c5` taps and `backbone_backward` walks blocks 17 .. 8 over the `c3` tap, setting -- or
-    adding to -- the `.grad` of their 90 parameters.  `features[0..7]` stay frozen.  Refresh `*train.backbone_blocks(model)`
-    afterwards as well.  A call without `backbone` runs the launches it always ran."""
+    adding to -- the `.grad` of their 90 parameters.  `features[0..7]` stay frozen (`features[2:8]` unless `shallow` is given).
+    Refresh `*train.backbone_blocks(model)` afterwards as well.  A call without `backbone` runs the launches it always ran.
+    `shallow=True` (needs `backbone=True`, and so everything `backbone` needs): the shallow backbone `shallow_blocks(model)` --
+    MobileNetV2 `features[2:8]`, the six blocks with an expand conv in front of the c3 tap and behind it -- is trained as well.
+    `srf_head_backward` then also returns the gradient of the `c3` tap, `backbone_backward` the gradient of block 7's output,
+    and `shallow_backward` walks blocks 7 .. 2 over the input frames `x`, setting -- or adding to -- the `.grad` of their 54
+    parameters.  Only the stem and `features[1]` stay frozen.  Refresh `*train.shallow_blocks(model)` with `fused_t=True`
+    afterwards as well.  A call without `shallow` runs the launches it always ran."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
     if getattr(model, "rnn_type", "twa") != "twa":
@@ -1865,6 +2112,9 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if backbone and not srf:
         raise RuntimeError("backbone=True needs srf=True (and what srf needs): the gradient reaches the backbone blocks through "
                            "the c4 / c5 taps of model.sfnet's head")
+    if shallow and not backbone:
+        raise RuntimeError("shallow=True needs backbone=True (and what backbone needs): the gradient reaches the shallow blocks "
+                           "through the c3 tap of model.sfnet's head and the input of features[8]")
     if model.training:
         raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
     if model.precision != "f32":
@@ -1942,7 +2192,8 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
                 if hp[n].grad is None:
                     hp[n].grad = (torch.zeros_like if acc else torch.empty_like)(hp[n], memory_format=torch.contiguous_format)
             ret = srf_head_backward(model.sfnet, taps["c3"], taps["c4"], taps["c5"], taps["sfnet"], g_st, cache=cache,
-                                    grads={n: hp[n].grad for n in SRF_HEAD_PARAMS}, accumulate=acc, need_tap_grads=bool(backbone))
+                                    grads={n: hp[n].grad for n in SRF_HEAD_PARAMS}, accumulate=acc, need_tap_grads=bool(backbone),
+                                    **({"need_c3_grad": True} if shallow else {}))
         if backbone:
             feats = model.sfnet.features.features
             bp = {"%d.%s" % (i, n): q for i in range(BACKBONE_FIRST, BACKBONE_END) for n, q in feats[i].named_parameters()}
@@ -1950,5 +2201,13 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
             for q in bp.values():
                 if q.grad is None:
                     q.grad = (torch.zeros_like if acc else torch.empty_like)(q, memory_format=torch.contiguous_format)
-            backbone_backward(feats, taps["c3"], ret[1], ret[2], cache=cache, grads={n: q.grad for n, q in bp.items()}, accumulate=acc)
+            bret = backbone_backward(feats, taps["c3"], ret[1], ret[2], cache=cache, grads={n: q.grad for n, q in bp.items()},
+                                     accumulate=acc, **({"need_x_grad": True} if shallow else {}))
+        if shallow:
+            sp = {"%d.%s" % (i, n): q for i in range(SHALLOW_FIRST, SHALLOW_END) for n, q in feats[i].named_parameters()}
+            acc = any(q.grad is not None for q in sp.values())
+            for q in sp.values():
+                if q.grad is None:
+                    q.grad = (torch.zeros_like if acc else torch.empty_like)(q, memory_format=torch.contiguous_format)
+            shallow_backward(feats, x, ret[3], bret[1], cache=cache, grads={n: q.grad for n, q in sp.items()}, accumulate=acc)
     return loss.detach(), out, [h_last[0].detach()]

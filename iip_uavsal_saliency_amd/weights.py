@@ -142,7 +142,7 @@ class WeightCache:
         running mean -- what the gradient of the BatchNorm's weight needs beside the fold (train.decoder_param_grads)."""
         return self._get(("bnstat", id(bn)), lambda: self._up(*_bn_stats(bn)))
 
-    def refresh(self, mods, dry=False):
+    def refresh(self, mods, dry=False, fused_t=False):
         """Repack, INTO THE EXISTING DEVICE TENSORS, every entry whose key holds the id of a module in `mods` (id -> module)
         from the module's current parameters: launch plans that recorded the tensors' addresses stay valid.  Conv weights in
         every layout, their Winograd transforms and transposed forms, BatchNorm folds (with their identity padding) and
@@ -153,19 +153,22 @@ class WeightCache:
         a depthwise entry's key holds its conv alone: its BatchNorm is the module that follows the conv in the container
         that holds both, which must be in `mods` too (pass the block, not the conv).
         `dry`: only check that every such entry can be remade (raise otherwise), pack and copy nothing.
+        `fused_t=True` (opt-in): a transposed-layout fused block (csrc/fused_ir.hip: the 1x1 weights as [Cin][Cout] -- MobileNetV2
+        `features[1:8]`) whose block is among `mods` is remade in place as well, from `_fused_host(blk, False)`, and checked in
+        the dry pass like the natural-layout ones.  Without it such an entry raises, as it always did; the stem raises either way.
         Returns the number of entries refreshed (that would be)."""
         n = 0
         for key in list(self.store):
             if not isinstance(key, tuple) or not any(isinstance(i, int) and i in mods for i in key[1:]):
                 continue
             kind = key[0]
-            if kind not in _REFRESH_IDS or (kind == "fused" and not key[2]):
+            if kind not in _REFRESH_IDS or (kind == "fused" and not key[2] and not fused_t):
                 raise NotImplementedError("packed %r weights cannot be refreshed in place: call model.invalidate_engines()" % (kind,))
             ids = _REFRESH_IDS[kind](key)
             if not all(i in mods for i in ids):
                 raise RuntimeError("a packed %r entry joins several modules: refresh all of them together" % (kind,))
             if kind == "fused":
-                new = _fused_host(_block_of(mods, mods[key[1]]), True)           # raises in the dry pass when the block is missing
+                new = _fused_host(_block_of(mods, mods[key[1]]), bool(key[2]))   # raises in the dry pass when the block is missing
                 if sorted(new) != sorted(self.store[key]):
                     raise RuntimeError("a packed fused entry does not match its block any more: call model.invalidate_engines()")
                 if not dry:
@@ -197,7 +200,7 @@ class WeightCache:
             n += 1
         return n
 
-    def refresh_device(self, mods, dry=False):
+    def refresh_device(self, mods, dry=False, fused_t=False):
         """`refresh` without the host: every entry `refresh` would remake is remade by ONE launch of csrc/repack.hip on torch's
         current stream, from the fp32 parameters and buffers where they lie on this device into the same packed tensors, to
         the same bytes (the Winograd transforms: within one fp32 ulp).  The table of entries (repack.py) is built
@@ -208,9 +211,10 @@ class WeightCache:
         CPU store, a parameter or buffer that is not fp32 ON THIS DEVICE (so a model whose packed weights live on two GPUs
         cannot refresh the second store this way: its parameters are on one), or one that is not contiguous (a 3x3 weight kept
         in `channels_last`).
-        `dry`: build and check the table, launch nothing.  Returns the number of entries refreshed, as `refresh` does."""
+        `dry`: build and check the table, launch nothing.  Returns the number of entries refreshed, as `refresh` does.
+        `fused_t`: as in `refresh`; the transposed 1x1 weights are written by the same launch (entry kind COPY_T)."""
         from . import repack
-        return repack.refresh(self, mods, dry)
+        return repack.refresh(self, mods, dry, fused_t)
 
     def _remake(self, kind, key, ms, mods):
         """The host tensors of one refreshable non-conv entry, in the order of the stored tuple."""

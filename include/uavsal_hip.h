@@ -879,6 +879,12 @@ int uavsal_train_decoder_sizeof_desc(int which);  /* 0 pix_gemm, 1 dec_sums, 2 d
  * uavsal_ir_finish: sums the slabs in slab order in double and writes gamma1, beta1 [Ch], Wd [Ch][3][3], gamma2, beta2
  *   [Ch], gamma3, beta3 [Co] in the parameters' own layouts, each rounded once, overwritten or (`accumulate`) added to.
  *   rowdot1 [Ch]: uavsal_pix_gemm's with w = W1; rowdot3 [Co]: with w = W3.  wd is the parameter [Ch][3][3].  ONE launch.
+ * ch16 != 0 (uavsal_ir_sums_desc and uavsal_ir_sums_s2_desc; opt-in, the field lies in what was the structs' tail padding, so a
+ *   zeroed descriptor keeps every rule above, the refusal included): any Ch % 16 == 0 is taken -- the hidden widths 96 and 144
+ *   of MobileNetV2 features[2:5].  The same kernels, slabs, workspace layout and summation order: a lane owns four channels,
+ *   so the lanes behind Ch / 4 of the last channel group idle (at Ch = 96, 24 of 64 work); a Ch the default rule takes
+ *   keeps its launch and bits with the flag set.  uavsal_ir_finish_c16 is uavsal_ir_finish for such a workspace: Ch % 16 == 0
+ *   where uavsal_ir_finish wants Ch % 64 == 0, every other rule, the kernel and the order of the sums the same.
  * block_param_grads is SIX launches (two GEMMs with their reductions, sums, finish); block_backward adds the recomputation
  * of e and d (two), gd, uavsal_ir_bwd and, when wanted, gx.
  */
@@ -896,6 +902,7 @@ typedef struct uavsal_ir_sums_desc {
     const float* go;  int32_t ldgo;         /* [n_img * H * W] rows of Co floats */
     double* ws;  int64_t ws_bytes;
     int32_t n_img, H, W, Ch, Co;
+    int32_t ch16;                           /* 0: Ch % 64 == 0.  1: any Ch % 16 == 0 is taken (below); in what was tail padding */
 } uavsal_ir_sums_desc;
 
 typedef struct uavsal_ir_finish_desc {
@@ -912,6 +919,7 @@ int uavsal_ir_sums_slabs(const uavsal_ir_sums_desc* d);         /* slabs of that
 int uavsal_ir_sums_slab_rows(const uavsal_ir_sums_desc* d);     /* picture rows per slab */
 int uavsal_ir_sums(const uavsal_ir_sums_desc* d, uavsal_stream_t stream);
 int uavsal_ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t stream);
+int uavsal_ir_finish_c16(const uavsal_ir_finish_desc* d, uavsal_stream_t stream);     /* Ch % 16 == 0 */
 int uavsal_block_sizeof_desc(int which);  /* 0 ir_bwd, 1 ir_sums, 2 ir_finish (uavsal_train_decoder_sizeof_desc is closed at 3) */
 
 /* ---- input gradients of the frozen context-prior path (csrc/train_ctx.hip) ----------------------------------------------
@@ -989,6 +997,7 @@ typedef struct uavsal_ir_sums_s2_desc {
     const float* go;  int32_t ldgo;         /* [n_img * Ho * Wo] rows of Co floats */
     double* ws;  int64_t ws_bytes;
     int32_t n_img, H, W, Ch, Co;
+    int32_t ch16;                           /* as in uavsal_ir_sums_desc */
 } uavsal_ir_sums_s2_desc;
 
 int64_t uavsal_ir_sums_s2_workspace_bytes(const uavsal_ir_sums_s2_desc* d);
@@ -1177,6 +1186,53 @@ int uavsal_ir_sums_dil_slab_rows(const uavsal_ir_sums_dil_desc* d); /* picture r
 int uavsal_ir_sums_dil(const uavsal_ir_sums_dil_desc* d, uavsal_stream_t stream);
 int uavsal_srf_sizeof_desc(int which);    /* 0 conv3_wgrad, 1 ir_bwd_dil, 2 ir_sums_dil (uavsal_st_sizeof_desc is closed at 3) */
 
+/* ---- fine-tuning the shallow backbone: the skinny weight-gradient GEMM (csrc/train_shallow.hip) ---------------------------
+ * The 1x1 weight gradients of MobileNetV2 features[2:8] that uavsal_pix_gemm refuses: 96 x 16, 144 x 24, 24 x 96, 24 x 144 and
+ * 32 x 144 over 72,000 to 1,152,000 pixels at 20 frames of 360 x 640.  Under 30 flop per operand byte: the memory sets the
+ * time, so the kernel makes ONE pass over both operands and multiplies no padded 128 x 128 tile.
+ *
+ * uavsal_skinny_wgrad: uavsal_pix_gemm's contract -- out[m][n] = fl(row_scale[m] G[m][n]) (+ the old value with
+ *   `accumulate`), G[m][n] = sum over the K pixels p of a[p][m] b[p][n]; row p of a / b at p * lda / p * ldb floats (channel
+ *   slices are read in place); row_scale NULL = 1; rowdot (optional, [M] doubles) = sum_n w[m][n] G[m][n] in double in a fixed
+ *   order, w rows ldw floats apart -- for M and N multiples of 8 with min(M, N) <= 32 and max(M, N) <= 192 (else
+ *   UAVSAL_ESHAPE).  Nothing at or behind column M of a, column N of b, row M or column N of out / w is read or written.
+ *   The partition: the K pixels are cut into UNITS of UAVSAL_SKINNY_UNIT = 128; units = ceil(K / 128),
+ *   want = min(UAVSAL_SKINNY_SHARES, units), ups = ceil(units / want), shares = ceil(units / ups) (uavsal_skinny_wgrad_shares
+ *   returns it: a function of K alone, at most UAVSAL_SKINNY_SHARES = 1024, one wave per SIMD of 256 CUs).  Share s owns the
+ *   pixels [s ups 128, (s + 1) ups 128) cut at K and is the work of ONE wave, which holds the whole M x N result: the narrow
+ *   side in one 32-wide MFMA tile (its columns from min(M, N) on are zeros in registers, never read), the wide side in
+ *   ceil(max(M, N) / 32) tiles, the last cut at its width in the same way.  The wave reads its pixels two at a time in the
+ *   layout of v_mfma_f32_32x32x2_f32 (128 contiguous bytes per tile and pixel; every operand byte is fetched once) and adds
+ *   pixel pair after pixel pair, in pixel order, to one fp32 accumulator per tile; an accumulation chain ends every
+ *   UAVSAL_WGRAD_CHAIN products counted from the share's first pixel and is added in fp32 to the share's total.  The totals
+ *   go to `ws` as [share][M][N] floats (uavsal_skinny_wgrad_workspace_bytes: shares * M * N * 4).  A second launch, one
+ *   workgroup per row m, sums them in double in a FIXED order that depends on the shape alone: with g = floor(1024 / N)
+ *   groups and spg = ceil(shares / g), group j adds the shares [j spg, (j + 1) spg) cut at `shares` in share order, then the
+ *   groups are added in group order; the sum is scaled, rounded once and stored; rowdot's N products meet in a fixed tree.
+ *   No atomics: two calls return the same bits.  TWO launches, no allocation.  UAVSAL_EALIGN: a, b, ws not 16-byte aligned
+ *   or lda / ldb not a multiple of 4; UAVSAL_EINVAL: a null operand, ws_bytes too small, a pitch below its width, rowdot
+ *   without w. */
+#define UAVSAL_SKINNY_UNIT 128
+#define UAVSAL_SKINNY_SHARES 1024
+#define UAVSAL_SKINNY_MAX_NARROW 32
+#define UAVSAL_SKINNY_MAX_WIDE 192
+
+typedef struct uavsal_skinny_wgrad_desc {
+    const float* a;  int32_t lda;           /* [K] rows of M floats */
+    const float* b;  int32_t ldb;           /* [K] rows of N floats */
+    const float* row_scale;                 /* [M] or NULL */
+    const float* w;  int32_t ldw;           /* [M] rows of N floats (needed with rowdot) */
+    double* rowdot;                         /* [M] or NULL */
+    float* ws;  int64_t ws_bytes;
+    float* out;  int32_t ldo;               /* [M] rows of N floats */
+    int64_t K;  int32_t M, N, accumulate;
+} uavsal_skinny_wgrad_desc;
+
+int64_t uavsal_skinny_wgrad_workspace_bytes(const uavsal_skinny_wgrad_desc* d);
+int uavsal_skinny_wgrad_shares(const uavsal_skinny_wgrad_desc* d);  /* K shares of that call (no launch); 0: refused */
+int uavsal_skinny_wgrad(const uavsal_skinny_wgrad_desc* d, uavsal_stream_t stream);
+int uavsal_shallow_sizeof_desc(int which);    /* 0 skinny_wgrad (uavsal_srf_sizeof_desc is closed at 3) */
+
 /* ---- repacking refreshed weights on the device (csrc/repack.hip) ---------------------------------------------------------
  * After an optimiser step the packed copies of a module's weights are remade FROM the fp32 parameters and buffers where they
  * lie INTO the packed device tensors that exist (launch plans hold their addresses): the bytes packing.py / weights.py make
@@ -1207,13 +1263,16 @@ int uavsal_srf_sizeof_desc(int which);    /* 0 conv3_wgrad, 1 ir_bwd_dil, 2 ir_s
  *   eps; rows[] cumulative): SCALE g / sqrt(v + eps), BIAS b - m * scale (the unrounded scale), RSTD 1 / sqrt(v + eps), each in
  *   double and rounded once, MEAN copied; channels N .. Npad hold `pad`.  unit = one channel.
  * kind DW: float [9][N], tap-major, of depthwise weights [C_s][1][3][3] side by side.  kind COPY: `units` floats of src[0].
+ * kind COPY_T: float [C][N], the transpose of src[0] = [N][C] (a 1x1 conv weight [Cout][Cin] as the small-channel fused block
+ *   kernel holds it, [Cin][Cout]: csrc/fused_ir.hip); unit = one element of the destination, units = N * C.
  * Every divide and square root is the correctly rounded one.  The caller answers for the table: every pointer a device
  * pointer to fp32 data of the stated extent, dst 16-byte aligned and as large as the layout says.  uavsal_repack itself
  * checks only what it can see from the host: a non-null 16-byte aligned table, positive counts, n_blocks below
  * UAVSAL_REPACK_MAX_BLOCKS. */
 #define UAVSAL_REPACK_MAX_SRC 4
 #define UAVSAL_REPACK_MAX_BLOCKS (1 << 24)  /* n_blocks at or above it: UAVSAL_ESHAPE (256 threads each, under 2^32 a launch) */
-enum { UAVSAL_REPACK_CONV = 0, UAVSAL_REPACK_WINO = 1, UAVSAL_REPACK_FOLD = 2, UAVSAL_REPACK_DW = 3, UAVSAL_REPACK_COPY = 4 };
+enum { UAVSAL_REPACK_CONV = 0, UAVSAL_REPACK_WINO = 1, UAVSAL_REPACK_FOLD = 2, UAVSAL_REPACK_DW = 3, UAVSAL_REPACK_COPY = 4,
+       UAVSAL_REPACK_COPY_T = 5 };
 enum { UAVSAL_REPACK_F32 = 0, UAVSAL_REPACK_F16X3 = 1, UAVSAL_REPACK_F16X3I = 2, UAVSAL_REPACK_F16X3J = 3, UAVSAL_REPACK_BF16 = 4,
        UAVSAL_REPACK_BF16X3 = 5 };
 enum { UAVSAL_REPACK_SCALE = 0, UAVSAL_REPACK_BIAS = 1, UAVSAL_REPACK_RSTD = 2, UAVSAL_REPACK_MEAN = 3 };

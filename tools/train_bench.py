@@ -69,6 +69,8 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                on the device (refresh8, refresh8_device).  Alone: --srf-only;
   backbone     the deep backbone trained too, the ninth stage (`train.backbone_blocks`, 90 parameters): `backbone_phases`' docstring.
                Alone: --backbone-only;
+  shallow      the shallow backbone trained too, the tenth stage (`train.shallow_blocks`, 54 parameters): `shallow_phases`' docstring.
+               Alone: --shallow-only;
   refresh pairs beside every refresh case above its `_device` twin: the same in-place edit, then `refresh_weights(...,
                device=True)` (csrc/repack.hip: one launch, no host copy); and at the end (or alone: --refresh-only) the
                host and device refresh of 1, 4, 5 and 6 stages (refreshN_alt / refreshN_device_alt) and one whole six-stage
@@ -80,7 +82,7 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
 
 Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--srf-only] [--backbone-only]
-        [--frames 20 5]
+        [--shallow-only] [--frames 20 5]
 """
 import argparse
 import ctypes as C
@@ -710,6 +712,92 @@ def backbone_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
         q.grad = None
 
 
+def shallow_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
+    """the phases of the trained shallow backbone (train.shallow_blocks: MobileNetV2 features[2:8]), the tenth stage, added to
+    `res`: the five weight-gradient shapes `uavsal_skinny_wgrad` takes, alone with their reduce launch, at the K they have in
+    the walk (ms, operand bytes / time as a fraction of 8 TB/s, shares) beside the only way the parent forms them -- operands
+    zero-padded to multiples of 32 in torch (not timed), then `train.pix_gemm(tails32=True)` (`_padded_ms`);
+    `train.shallow_backward` alone; the nine-stage step (step9b) and the same with `shallow=True` (step10), and one whole
+    ten-stage iteration -- step, Adam, refresh -- with host and with device refresh (iter10 / iter10_device), all alternated in
+    the same run, every run listed (`_all_ms`: the spread); the peak device memory of the ten-stage step."""
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    nets = tuple(train.prior_nets(m).values())
+    boxes = ((m.rnn, m.conv_out_st, m.fucbst_layer, m.fust_layer, m.fucb_layer, m.cxt_cb_prior) + nets + (m.st_layer,)
+             + tuple(train.srf_head(m)) + tuple(train.backbone_blocks(m)) + tuple(train.shallow_blocks(m)))
+    trained = [q for mod in boxes for q in mod.parameters()]
+    kw9 = dict(decoder=True, fuse=True, fust=True, ctx=True, nets=True, st=True, srf=True, backbone=True)
+    taps = {}
+    m(x, cb, None, taps=taps)
+    c3, c4 = (taps[k].contiguous(memory_format=cl) for k in ("c3", "c4"))
+    T, H, W = x.shape[0], x.shape[2], x.shape[3]
+    down = lambda v: (v - 1) // 2 + 1                                     # noqa: E731
+    g3 = (torch.randn_like(c3) / c3[0].numel()).contiguous(memory_format=cl)      # (timing only: any gradient of the right shape)
+    g7 = (torch.randn((T, 64) + tuple(c4.shape[2:]), device=dev) / c4[0].numel()).contiguous(memory_format=cl)
+    feats = m.sfnet.features.features
+    grads = train.shallow_backward(feats, x, g3, g7, cache=cache)
+    grids = {2: (down(H), down(W)), 4: (down(down(H)), down(down(W))), 8: tuple(c3.shape[2:])}
+    gems = {}
+    pad32 = lambda t: F.pad(t, (0, -t.shape[-1] % 32))                    # noqa: E731
+    for M, N, scale in ((96, 16, 2), (144, 24, 4), (24, 96, 4), (24, 144, 4), (32, 144, 8)):
+        hh, ww = grids[scale]
+        a = 1e-2 * torch.randn((T, hh, ww, M), device=dev)
+        b = torch.randn((T, hh, ww, N), device=dev)
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+        ap, bp = pad32(a), pad32(b)
+        outp = torch.empty((ap.shape[-1], bp.shape[-1]), dtype=torch.float32, device=dev)
+        gems["%dx%d" % (M, N)] = (M, N, T * hh * ww, lambda a=a, b=b, out=out: train.skinny_wgrad(a, b, out=out),
+                                  lambda a=ap, b=bp, out=outp: train.pix_gemm(a, b, out=out, tails32=True))
+    res["shallow_bwd_ms"] = 1e3 * best_of(lambda: train.shallow_backward(feats, x, g3, g7, cache=cache, grads=grads), iters, repeats)
+    for tag, (M, N, K, fn, fnp) in gems.items():                          # the pair alternated, every run listed
+        per_call(fn, 2), per_call(fnp, 2)
+        mine, theirs = [], []
+        for _ in range(repeats):
+            mine.append(1e3 * per_call(fn, 4 * iters))
+            theirs.append(1e3 * per_call(fnp, 4 * iters))
+        gd = L.SkinnyWgradDesc()
+        gd.K, gd.M, gd.N = K, M, N
+        k = "shallow_skinny_wgrad_" + tag
+        res[k + "_ms"], res[k + "_all_ms"], res[k + "_padded_ms"], res[k + "_padded_all_ms"] = min(mine), mine, min(theirs), theirs
+        res[k + "_K"], res[k + "_shares"] = K, int(lib.uavsal_skinny_wgrad_shares(C.byref(gd)))
+        res[k + "_of_8TBs"] = (M + N) * K * 4 / (min(mine) * 1e-3) / 8e12
+    del gems
+    opt = torch.optim.Adam(trained, lr=1e-4, betas=(0.9, 0.999), weight_decay=5e-5)
+
+    def stepper(**kw):
+        def run():
+            for q in trained:
+                q.grad = None
+            train.recurrence_step(m, x, cb, None, y_gaze, **kw9, **kw)
+        return run
+
+    def iteration(device):
+        def run():
+            opt.zero_grad()
+            train.recurrence_step(m, x, cb, None, y_gaze, shallow=True, **kw9)
+            opt.step()
+            m.refresh_weights(*boxes, device=device, fused_t=True)
+        return run
+    runs = {"step9b": stepper(), "step10": stepper(shallow=True), "iter10": iteration(False), "iter10_device": iteration(True)}
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # alternated in the same run, every run listed
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    for name, fn in (("step9b", runs["step9b"]), ("step10", runs["step10"])):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        fn()
+        torch.cuda.synchronize()
+        res[name + "_peak_MB"] = torch.cuda.max_memory_allocated(dev) / 1e6
+    for q in trained:
+        q.grad = None
+
+
 def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
     """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
     from iip_uavsal_saliency_amd import repack
@@ -766,7 +854,8 @@ def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
         q.grad = None
 
 
-def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False, backbone_only=False):
+def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False, backbone_only=False,
+          shallow_only=False):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
@@ -797,6 +886,10 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False,
     if backbone_only:
         res = {"T": T}
         backbone_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+        return res
+    if shallow_only:
+        res = {"T": T}
+        shallow_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
         return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -920,11 +1013,12 @@ def main():
     ap.add_argument("--st-only", action="store_true", help="only the phases of the seventh stage (st_phases)")
     ap.add_argument("--srf-only", action="store_true", help="only the phases of the eighth stage (srf_phases)")
     ap.add_argument("--backbone-only", action="store_true", help="only the phases of the ninth stage (backbone_phases)")
+    ap.add_argument("--shallow-only", action="store_true", help="only the phases of the tenth stage (shallow_phases)")
     ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
     out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
-           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only, a.backbone_only)
+           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only, a.backbone_only, a.shallow_only)
                      for T in a.frames]}
     print(json.dumps(out))
 
