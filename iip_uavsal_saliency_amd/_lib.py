@@ -240,6 +240,18 @@ class DecBwdDesc(C.Structure):
 
 TRAIN_DESC_TYPES = [TwaGateDesc, TwaWgradDesc, DecBwdDesc]        # sized by uavsal_train_sizeof_desc
 
+
+class LstmScanDesc(C.Structure):
+    _fields_ = [("cc", _f), ("c0", _f), ("c_seq", _f), ("n_pix", C.c_int64), ("T", C.c_int32), ("C", C.c_int32)]
+
+
+class LstmGateDesc(C.Structure):
+    _fields_ = [("g", _f), ("ldg", C.c_int32), ("carry_h", _f), ("carry_c", _f), ("cc", _f), ("c", _f), ("c_prev", _f),
+                ("dcc", _f), ("carry_c_out", _f), ("n_pix", C.c_int64), ("C", C.c_int32)]
+
+
+LSTM_DESC_TYPES = [LstmScanDesc, LstmGateDesc]                    # sized by uavsal_lstm_sizeof_desc (csrc/train_lstm.hip)
+
 class PixGemmDesc(C.Structure):
     _fields_ = [("a", _f), ("lda", C.c_int32), ("b", _f), ("ldb", C.c_int32), ("row_scale", _f),
                 ("w", _f), ("ldw", C.c_int32), ("rowdot", C.c_void_p), ("ws", _f), ("ws_bytes", C.c_int64),
@@ -439,6 +451,9 @@ SYMBOLS = [
     ("uavsal_twa_wgrad", C.c_int, [C.POINTER(TwaWgradDesc), C.c_void_p]),
     ("uavsal_dec_bwd", C.c_int, [C.POINTER(DecBwdDesc), C.c_void_p]),
     ("uavsal_train_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_lstm_scan", C.c_int, [C.POINTER(LstmScanDesc), C.c_void_p]),
+    ("uavsal_lstm_gate_bwd", C.c_int, [C.POINTER(LstmGateDesc), C.c_void_p]),
+    ("uavsal_lstm_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_pix_gemm_workspace_bytes", C.c_int64, [C.POINTER(PixGemmDesc)]),
     ("uavsal_pix_gemm_shares", C.c_int, [C.POINTER(PixGemmDesc)]),
     ("uavsal_pix_gemm", C.c_int, [C.POINTER(PixGemmDesc), C.c_void_p]),
@@ -578,7 +593,7 @@ def load():
                           (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES),
                           (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES),
                           (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES), (lib.uavsal_srf_sizeof_desc, SRF_DESC_TYPES),
-                          (lib.uavsal_shallow_sizeof_desc, SHALLOW_DESC_TYPES)):
+                          (lib.uavsal_shallow_sizeof_desc, SHALLOW_DESC_TYPES), (lib.uavsal_lstm_sizeof_desc, LSTM_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

@@ -418,7 +418,10 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `train.shallow_blocks(model)` -- MobileNetV2 `features[2:8]` -- and those six modules are refreshed as well, with
     `fused_t=True` (their packed forms are transposed-layout fused entries); the stem and `features[1]` stay frozen.
     `refresh`: `"host"` (the default) repacks the trained stages' weights on the host after every step; `"device"` repacks
-    them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host)."""
+    them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host).
+    A `UAVSAL_LSTM` model (`rnn_type == "lstm"`) is trained the same way: the step is `recurrence_step(..., lstm=True)`
+    (`train.lstm_backward`), the carried state is `[(h.detach(), c.detach())]` as in `validate_video`, and `stages`, their
+    order rules and `refresh` are unchanged -- `"rnn"` is then the ConvLSTM's `[1024,512,3,3]` weight."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
@@ -438,10 +441,15 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
                          "'fuse' (then 'ctx', then 'nets', behind 'fuse' too; 'st' the very last, behind 'fuse' and, in a "
                          "model with priors, 'fust'; only 'srf' may follow 'st', only 'backbone' 'srf', only 'shallow' 'backbone'), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
+    lstm = getattr(model, "rnn_type", "twa") == "lstm"
+    if lstm:
+        kw["lstm"] = True                                 # (a ConvTWA model's call keeps the keywords it always had)
 
     def step(x, cb, state, y):
         optimizer.zero_grad()
         loss, _, state = _train.recurrence_step(model, x, cb, state, y, criterion, **kw)
+        if lstm:                                          # the ConvLSTM carries (h, c), as in validate_video
+            state = [(state[0].detach(), state[1].detach())]
         optimizer.step()
         mods = [model.rnn] + ([model.conv_out_st] if "decoder" in kw else [])
         if "fuse" in kw:

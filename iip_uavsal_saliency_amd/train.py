@@ -42,7 +42,14 @@ through `block_backward(shallow=True)` (widths of 16 to 192: `skinny_wgrad` for 
 the channel sums with their Ch % 16 opt-in).  Only the stem and `features[1]` stay frozen; BatchNorm in eval mode remains the
 documented difference.
 
-New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`.  Everything else is one
+The second model, `UAVSAL_LSTM` (the reference's ConvLSTM ablation, model_convlstm.py:111-126: `cc_t = conv3x3(W, cat[x_t, h_{t-1}])`,
+`i, f, o = sigmoid`, `g = tanh`, `c_t = f c_{t-1} + i g`, `h_t = o tanh(c_t)`; `W` `[1024,512,3,3]`), is trained through the same step
+with `recurrence_step(lstm=True)`: `lstm_backward` stands where `twa_backward` stands (csrc/train_lstm.hip: `uavsal_lstm_scan` recomputes
+the cell-state history in one launch, `uavsal_lstm_gate_bwd` is one step of the walk; the weight gradient is `uavsal_conv3_wgrad` at
+1024 x 512), and every stage above works unchanged behind it -- they hang off the recurrence's `grad_x` and `grad_h`.
+
+New launches (csrc/train.hip): `uavsal_dec_bwd`, `uavsal_twa_gate_bwd`, `uavsal_twa_wgrad`; (csrc/train_lstm.hip): `uavsal_lstm_scan`,
+`uavsal_lstm_gate_bwd`.  Everything else is one
 `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's own table, with repacked weights.
 Tensors are float32 on the GPU with the logical shape `[T, C, h, w]`; a channels-last tensor (NHWC in memory, or a channel
 slice of one) is read in place, anything else is copied once.  Returned gradients are channels-last.  `f32` only; one
@@ -2010,6 +2017,125 @@ def twa_backward(x_seq, h_seq, h0, weight, grad_h, need_x_grad=False, out=None, 
     return gw, (dx.permute(0, 3, 1, 2) if need_x_grad else None), carry.permute(0, 3, 1, 2)
 
 
+def _dense(name, what, t, shape, dev):
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == tuple(shape)
+            and t.is_contiguous()):
+        raise RuntimeError("%s: %s must be a dense float32 %r tensor on the device" % (name, what, list(shape)))
+
+
+def lstm_scan(cc, c0=None):
+    """`uavsal_lstm_scan` on the current stream: `cc` dense NHWC `[T,h,w,4C]` (rows gate * C + c, gates i, f, o, g), `c0` dense
+    `[1,h,w,C]` or None (zeros) -> the cell-state history `c_seq` dense `[T,h,w,C]`, `c_t = f c_{t-1} + i g`.  One launch."""
+    lib = L.load()
+    if not torch.is_tensor(cc) or not cc.is_cuda or cc.dim() != 4 or cc.shape[3] % 4:
+        raise RuntimeError("lstm_scan: cc must be a dense float32 cuda tensor [T,h,w,4C] (no CPU fallback)")
+    T, hh, ww, c4 = cc.shape
+    c = c4 // 4
+    _dense("lstm_scan", "cc", cc, cc.shape, cc.device)
+    if c0 is not None:
+        _dense("lstm_scan", "c0", c0, (1, hh, ww, c), cc.device)
+    cs = torch.empty((T, hh, ww, c), dtype=torch.float32, device=cc.device)
+    k = L.LstmScanDesc()
+    k.cc, k.c0, k.c_seq = cc.data_ptr(), (c0.data_ptr() if c0 is not None else None), cs.data_ptr()
+    k.n_pix, k.T, k.C = hh * ww, T, c
+    with torch.cuda.device(cc.device):
+        L.check(lib.uavsal_lstm_scan(C.byref(k), _stream(cc)), "uavsal_lstm_scan")
+    return cs
+
+
+def lstm_gate_bwd(g, carry_h, carry_c, cc, c, c_prev, dcc=None, carry_c_out=None):
+    """`uavsal_lstm_gate_bwd` on NHWC tensors: `g` `[1,h,w,C]` (may be a channel slice), `carry_h`, `carry_c` dense or None,
+    `cc` dense `[1,h,w,4C]`, `c`, `c_prev` dense `[1,h,w,C]` -> `(dcc [1,h,w,4C], carry_c_out [1,h,w,C])`, dense; written into
+    `dcc` / `carry_c_out` when given (`carry_c_out` may be `carry_c`)."""
+    lib = L.load()
+    gp, ldg, n, hh, ww, ch = _nhwc_view(g)
+    dev = g.device
+    for name, t in (("carry_h", carry_h), ("carry_c", carry_c), ("c", c), ("c_prev", c_prev), ("carry_c_out", carry_c_out)):
+        if t is not None or name in ("c", "c_prev"):
+            _dense("lstm_gate_bwd", name, t, (n, hh, ww, ch), dev)
+    _dense("lstm_gate_bwd", "cc", cc, (n, hh, ww, 4 * ch), dev)
+    if dcc is None:
+        dcc = torch.empty((n, hh, ww, 4 * ch), dtype=torch.float32, device=dev)
+    _dense("lstm_gate_bwd", "dcc", dcc, (n, hh, ww, 4 * ch), dev)
+    if carry_c_out is None:
+        carry_c_out = torch.empty((n, hh, ww, ch), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lstm_gate(lib, gp, ldg, carry_h, carry_c, cc, c, c_prev, dcc, carry_c_out, n * hh * ww, ch, _stream(g))
+    return dcc, carry_c_out
+
+
+def _lstm_gate(lib, gp, ldg, carry_h, carry_c, cc, c, c_prev, dcc, co, n_pix, ch, st):
+    k = L.LstmGateDesc()
+    k.g, k.ldg = gp, ldg
+    k.carry_h = carry_h.data_ptr() if carry_h is not None else None
+    k.carry_c = carry_c.data_ptr() if carry_c is not None else None
+    k.cc, k.c, k.c_prev, k.dcc, k.carry_c_out = cc.data_ptr(), c.data_ptr(), c_prev.data_ptr(), dcc.data_ptr(), co.data_ptr()
+    k.n_pix, k.C = n_pix, ch
+    L.check(lib.uavsal_lstm_gate_bwd(C.byref(k), st), "uavsal_lstm_gate_bwd")
+
+
+def lstm_backward(x_seq, h_seq, h0, c0, weight, grad_h, need_x_grad=False, out=None, accumulate=False, cache=None, module=None,
+                  parts=None):
+    """Back-propagation through time over one ConvLSTM sequence (`UAVSAL_LSTM`; reference model_convlstm.py:111-126, no bias,
+    one layer): the counterpart of `twa_backward`.  `x_seq` `[T,256,h,w]` the recurrence input, `h_seq` `[T,256,h,w]` its
+    output history, `h0`, `c0` `[1,256,h,w]` the state it started from (None = zeros), `weight` `[1024,512,3,3]` (rows
+    gate * 256 + c, gates i, f, o, g), `grad_h` `[T,256,h,w]` the gradient of the loss with respect to every `h_t` (the carried
+    part excluded; the returned state is detached, so nothing arrives at `c_t` directly).
+    Returns `(grad_weight [1024,512,3,3], grad_x [T,256,h,w] | None, grad_h0 [1,256,h,w], grad_c0 [1,256,h,w])`; `out` /
+    `accumulate`: the weight gradient is written to `out` or added to it (`.grad +=`).
+    The pre-activations `cc` are recomputed from the known history by two batched 3x3 convs over all frames and the cell
+    states from them by ONE `uavsal_lstm_scan`, so the forward stays what it is (no new tap, no arena change) and only the
+    carry runs step by step: per step one `uavsal_lstm_gate_bwd` (which keeps `carry_c`) and one 3x3 conv 1024 -> 256 with
+    flip(W_h)^T.  `grad_x` is one such conv with flip(W_x)^T over all frames, the weight gradient one `uavsal_conv3_wgrad`
+    (Co = 1024, Ci = 512) over `cat[x, h_prev]`.
+    `cache` + `module`: take the packed forms of the weight from a `WeightCache` under the id of `module` (the conv that
+    owns `weight`); default: packed on the host for this call.  `parts`: a dict that receives `cc`, `c_seq`, `dcc` (NHWC;
+    tests)."""
+    lib = L.load()
+    x = _nhwc(x_seq, "x_seq", HID)
+    h = _nhwc(h_seq, "h_seq", HID)
+    G = _nhwc(grad_h, "grad_h", HID)
+    T, hh, ww, _ = x.shape
+    if h.shape != x.shape or G.shape != x.shape:
+        raise RuntimeError("x_seq, h_seq and grad_h must have one shape [T,256,h,w]")
+    dev = x.device
+    if (not torch.is_tensor(weight) or tuple(weight.shape) != (4 * HID, 2 * HID, 3, 3) or weight.dtype != torch.float32
+            or weight.device != dev):
+        raise RuntimeError("weight must be the float32 [1024,512,3,3] ConvLSTM weight on the device")
+    with torch.cuda.device(dev):
+        st0 = []
+        for name, s in (("h0", h0), ("c0", c0)):
+            if s is None:
+                st0.append(torch.zeros((1, hh, ww, HID), dtype=torch.float32, device=dev))
+            else:
+                s = _nhwc(s, name, HID).contiguous()
+                if tuple(s.shape) != (1, hh, ww, HID):
+                    raise RuntimeError("%s must be [1,256,%d,%d]" % (name, hh, ww))
+                st0.append(s)
+        h0n, c0n = st0
+        if cache is None or module is None:
+            cache, module = WeightCache(dev, {}), types.SimpleNamespace(weight=weight)
+        st = _stream(x)
+        hprev = torch.cat([h0n, h[:T - 1]], 0)                       # h_{t-1} of every frame, dense
+        cc = _conv(lib, cache, x, module, 4 * HID, 9, wslice=(0, HID))
+        cc = _conv(lib, cache, hprev, module, 4 * HID, 9, wslice=(HID, 2 * HID), res=cc)
+        cs = lstm_scan(cc, c0n if c0 is not None else None)
+        dcc = torch.empty_like(cc)
+        cbuf = torch.empty((1, hh, ww, HID), dtype=torch.float32, device=dev)
+        carry = None
+        hw = hh * ww
+        gp, ldg, *_ = _nhwc_view(G)
+        for t in range(T - 1, -1, -1):
+            _lstm_gate(lib, gp + 4 * t * hw * ldg, ldg, carry, cbuf if carry is not None else None, cc[t], cs[t],
+                       cs[t - 1] if t else c0n, dcc[t], cbuf, hw, HID, st)
+            carry = _conv(lib, cache, dcc[t:t + 1], module, HID, 9, wslice=(HID, 2 * HID), transposed=True)
+        dx = _conv(lib, cache, dcc, module, HID, 9, wslice=(0, HID), transposed=True) if need_x_grad else None
+        gw = conv3_wgrad(dcc, torch.cat([x, hprev], 3), out=out, accumulate=accumulate)
+        if parts is not None:
+            parts.update(cc=cc, c_seq=cs, dcc=dcc)
+    return gw, (dx.permute(0, 3, 1, 2) if need_x_grad else None), carry.permute(0, 3, 1, 2), cbuf.permute(0, 3, 1, 2)
+
+
 def fuse_block(model):
     """The block that produces the recurrence's input (the `prefuse` tap), and the name of the tap that holds ITS input:
     `model.fucbst_layer[0]` reading `fu320` with any prior enabled, else `model.fust_layer[0]` reading the last ST block's
@@ -2031,13 +2157,13 @@ def _param_grad_tensors(blk):
 
 
 def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False,
-                    st=False, srf=False, backbone=False, shallow=False):
+                    st=False, srf=False, backbone=False, shallow=False, lstm=False):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
     and no other parameter touched.  Returns `(loss, out, [h_last.detach()])`, the forward's contract plus the loss.
     The model is in eval mode (every other stage is frozen, its BatchNorms folded); a model in training mode, CPU tensors,
-    a precision other than 'f32' or `UAVSAL_LSTM` raise.  After `optimizer.step()` call `model.refresh_weights(model.rnn)`.
+    a precision other than 'f32' or -- without `lstm=True` -- `UAVSAL_LSTM` raise.  After `optimizer.step()` call `model.refresh_weights(model.rnn)`.
     `decoder=True`: the decoder `model.conv_out_st` is trained too (`decoder_backward`): its nine parameters' `.grad` are set
     as well, or added to, and the recurrence receives that path's `grad_h`; afterwards call
     `model.refresh_weights(model.rnn, model.conv_out_st)`.  The BatchNorms still use their running statistics.
@@ -2089,11 +2215,22 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     `srf_head_backward` then also returns the gradient of the `c3` tap, `backbone_backward` the gradient of block 7's output,
     and `shallow_backward` walks blocks 7 .. 2 over the input frames `x`, setting -- or adding to -- the `.grad` of their 54
     parameters.  Only the stem and `features[1]` stay frozen.  Refresh `*train.shallow_blocks(model)` with `fused_t=True`
-    afterwards as well.  A call without `shallow` runs the launches it always ran."""
+    afterwards as well.  A call without `shallow` runs the launches it always ran.
+    `lstm=True` (opt-in, for a `UAVSAL_LSTM` model; with a ConvTWA model it raises before any launch): the recurrence is the
+    reference's ConvLSTM ablation.  `in_state` is None or `[(h, c)]`, the forward runs through the plan as it always did, and
+    `lstm_backward` stands where `twa_backward` stands (csrc/train_lstm.hip: `uavsal_lstm_scan`, `uavsal_lstm_gate_bwd`; the
+    weight gradient is `uavsal_conv3_wgrad` at 1024 x 512), setting -- or adding to -- the `.grad` of the `[1024,512,3,3]`
+    `rnn_conv.weight`.  Every other keyword works unchanged behind it: the stages hang off the recurrence's `grad_x` and
+    `grad_h`, which are the same tensors in both models.  Returns `(loss, out, [h_last.detach(), c_last.detach()])`, the
+    forward's contract for this model; refresh `model.rnn` as usual.  Without the keyword a `UAVSAL_LSTM` model raises, as it
+    always did, and a `UAVSal` call runs the launches it always ran."""
     from . import losses as _losses
     criterion = criterion or _losses.loss_fu
-    if getattr(model, "rnn_type", "twa") != "twa":
+    is_lstm = getattr(model, "rnn_type", "twa") != "twa"
+    if is_lstm and not lstm:
         raise RuntimeError("recurrence_step covers the ConvTWA recurrence, not UAVSAL_LSTM")
+    if lstm and not is_lstm:
+        raise RuntimeError("lstm=True is for a UAVSAL_LSTM model (the ConvLSTM recurrence); this model's recurrence is ConvTWA")
     if fust and not (fuse and getattr(model, "num_cb", 0)):
         raise RuntimeError("fust=True needs fuse=True and a model with at least one prior (without priors the fuse stage "
                            "already is model.fust_layer[0])")
@@ -2145,8 +2282,13 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     had = w.grad is not None
     if not had:
         w.grad = torch.empty_like(w, memory_format=torch.contiguous_format)
-    _, grad_x, _ = twa_backward(x_seq, h_seq, h0, w.detach(), grad_h, need_x_grad=bool(fuse), out=w.grad, accumulate=had,
-                                cache=cache, module=rc)
+    if lstm:
+        h0, c0 = (None, None) if h0 is None else h0
+        _, grad_x, _, _ = lstm_backward(x_seq, h_seq, h0, c0, w.detach(), grad_h, need_x_grad=bool(fuse), out=w.grad,
+                                        accumulate=had, cache=cache, module=rc)
+    else:
+        _, grad_x, _ = twa_backward(x_seq, h_seq, h0, w.detach(), grad_h, need_x_grad=bool(fuse), out=w.grad, accumulate=had,
+                                    cache=cache, module=rc)
     if fuse:
         grads, acc = _param_grad_tensors(blk)
         fu = taps[src].contiguous(memory_format=cl)
@@ -2210,4 +2352,4 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
                 if q.grad is None:
                     q.grad = (torch.zeros_like if acc else torch.empty_like)(q, memory_format=torch.contiguous_format)
             shallow_backward(feats, x, ret[3], bret[1], cache=cache, grads={n: q.grad for n, q in sp.items()}, accumulate=acc)
-    return loss.detach(), out, [h_last[0].detach()]
+    return loss.detach(), out, [t.detach() for t in h_last]

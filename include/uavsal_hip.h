@@ -745,6 +745,52 @@ int uavsal_twa_wgrad(const uavsal_twa_wgrad_desc* d, uavsal_stream_t stream);
 int uavsal_dec_bwd(const uavsal_dec_bwd_desc* d, uavsal_stream_t stream);
 int uavsal_train_sizeof_desc(int which);  /* 0 twa_gate, 1 twa_wgrad, 2 dec_bwd (uavsal_sizeof_desc's list is closed at 20) */
 
+/* ---- fine-tuning the ConvLSTM recurrence of UAVSAL_LSTM: backward of model.rnn (csrc/train_lstm.hip) -------------------
+ * All activations NHWC fp32, one sequence per call, C hidden channels (C % 4 == 0, else UAVSAL_EALIGN; the model builds 256).
+ * Notation: W = [W_x | W_h] [4C][2C][3][3], rows gate * C + c in gate order i, f, o, g (model_convlstm.py:111-126, no bias):
+ *   cc_t = conv3x3(W, cat[x_t, h_{t-1}]),  i, f, o = sigmoid(cc_i, cc_f, cc_o),  g = tanh(cc_g),
+ *   c_t = f c_{t-1} + i g,  h_t = o tanh(c_t).
+ * `cc` and `dcc` are dense rows of 4C floats per pixel in that gate-major order: [gate][c] (what uavsal_conv_gemm writes for
+ * the weight as the module holds it; the forward plan's own packed form interleaves the gates and is not read here).
+ *
+ * uavsal_lstm_scan: the cell-state history from the pre-activations of all frames, ONE launch: c_seq[t] = f_t c_{t-1} + i_t g_t
+ *   for t = 0 .. T-1 with c_{-1} = c0 (NULL = zeros).  A lane owns four channels of one pixel and walks t itself.
+ *
+ * uavsal_lstm_gate_bwd: one step of back-propagation through time, element-wise, ONE launch.  With gh = G_t + carry_h (the
+ *   direct gradient of h_t plus what step t+1 hands back through W_h; NULL = none), carry_c what step t+1 hands back through
+ *   its forget gate (NULL = none) and tc = tanh(c_t):
+ *     dc = carry_c + gh o (1 - tc^2)
+ *     dcc_i = dc g i (1 - i),  dcc_f = dc c_{t-1} f (1 - f),  dcc_o = gh tc o (1 - o),  dcc_g = dc i (1 - g^2)
+ *     carry_c_out = dc f
+ *   The gates are recomputed from cc_t; s (1 - s) = e / (1 + e)^2 with e = exp(-|z|) and 1 - tanh^2 = 4 e2 / (1 + e2)^2 with
+ *   e2 = exp(-2|z|), so every factor keeps its relative accuracy in a saturated gate.  Rows of G are `ldg` floats apart (a
+ *   channel slice is read in place); everything else is dense.  carry_c_out may be `carry_c`; no other output may alias an
+ *   input.  UAVSAL_EALIGN: C % 4, ldg % 4 or a pointer not 16-byte aligned; UAVSAL_EINVAL: a missing pointer, a size <= 0,
+ *   ldg < C; UAVSAL_ESHAPE: more elements than one launch indexes.  No atomics, no allocation: two calls return the same bits.
+ */
+typedef struct uavsal_lstm_scan_desc {
+    const float* cc;                        /* dense [T][n_pix][4C] */
+    const float* c0;                        /* dense [n_pix][C] or NULL */
+    float* c_seq;                           /* dense [T][n_pix][C] */
+    int64_t n_pix;  int32_t T, C;
+} uavsal_lstm_scan_desc;
+
+typedef struct uavsal_lstm_gate_desc {
+    const float* g;      int32_t ldg;       /* G_t */
+    const float* carry_h;                   /* dense [n_pix][C] or NULL */
+    const float* carry_c;                   /* dense [n_pix][C] or NULL */
+    const float* cc;                        /* dense [n_pix][4C]: cc_t */
+    const float* c;                         /* dense [n_pix][C]: c_t */
+    const float* c_prev;                    /* dense [n_pix][C]: c_{t-1} */
+    float* dcc;                             /* dense [n_pix][4C] */
+    float* carry_c_out;                     /* dense [n_pix][C] */
+    int64_t n_pix;  int32_t C;
+} uavsal_lstm_gate_desc;
+
+int uavsal_lstm_scan(const uavsal_lstm_scan_desc* d, uavsal_stream_t stream);
+int uavsal_lstm_gate_bwd(const uavsal_lstm_gate_desc* d, uavsal_stream_t stream);
+int uavsal_lstm_sizeof_desc(int which);   /* 0 lstm_scan, 1 lstm_gate (additions: UAVSAL_ABI_VERSION stays 20) */
+
 /* ---- fine-tuning the decoder conv_out_st: its nine parameter gradients (csrc/train_decoder.hip) -----------------------
  * The decoder in eval mode, r = 1 / sqrt(var + eps), s = gamma r, b = beta - mu s per BatchNorm:
  *     u1 = W1 h, a1 = s1 u1 + b1, e = ReLU6(a1);  u2 = dw3x3(Wd, e), a2 = s2 u2 + b2, d = ReLU6(a2);

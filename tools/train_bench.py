@@ -71,6 +71,8 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                Alone: --backbone-only;
   shallow      the shallow backbone trained too, the tenth stage (`train.shallow_blocks`, 54 parameters): `shallow_phases`' docstring.
                Alone: --shallow-only;
+  lstm         the second model, `UAVSAL_LSTM`, trained through `recurrence_step(lstm=True)`: `lstm_phases`' docstring.
+               Only with --lstm-only (a second model is built for it);
   refresh pairs beside every refresh case above its `_device` twin: the same in-place edit, then `refresh_weights(...,
                device=True)` (csrc/repack.hip: one launch, no host copy); and at the end (or alone: --refresh-only) the
                host and device refresh of 1, 4, 5 and 6 stages (refreshN_alt / refreshN_device_alt) and one whole six-stage
@@ -82,7 +84,7 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
 
 Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--srf-only] [--backbone-only]
-        [--shallow-only] [--frames 20 5]
+        [--shallow-only] [--lstm-only] [--frames 20 5]
 """
 import argparse
 import ctypes as C
@@ -99,6 +101,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from iip_uavsal_saliency_amd import UAVSal, losses, ops, synth, train      # noqa: E402
+from iip_uavsal_saliency_amd import UAVSAL_LSTM                            # noqa: E402
 from iip_uavsal_saliency_amd import _lib as L                              # noqa: E402
 from iip_uavsal_saliency_amd import packing as P                           # noqa: E402
 from iip_uavsal_saliency_amd.weights import WeightCache                    # noqa: E402
@@ -798,6 +801,121 @@ def shallow_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
         q.grad = None
 
 
+def lstm_phases(res, m, x, cb, y_gaze, iters, repeats):
+    """the phases of the ConvLSTM backward (train.lstm_backward, csrc/train_lstm.hip), added to `res`; `m` is the ConvTWA model
+    of the other phases, a `UAVSAL_LSTM` with the same synthetic weights is built beside it.  `lstm_backward` alone with and
+    without `grad_x`; its launches alone from the tensors the walk hands out: the recompute of `cc` (two convs), `uavsal_lstm_scan`
+    and ONE `uavsal_lstm_gate_bwd` with both carries (ms and operand bytes / time as a fraction of 8 TB/s: 3 C floats read per frame and
+    C written, and 13 C read and 5 C written, per pixel), one carry conv, the T-step loop (gate kernel + carry conv per step: `loop_ms`,
+    and per step), `grad_x`'s conv, `uavsal_conv3_wgrad` at [1024,512,3,3] (shares, TFLOP/s); and, alternated in the same run with every
+    run listed (`_all_ms`: the spread), the ("rnn",) step and the ten-stage Adam iteration with device refresh of both models."""
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    T = x.shape[0]
+    ml = UAVSAL_LSTM(time_dims=m.time_dims)
+    synth.load_synth_weights(ml, 0)
+    ml = ml.to(dev).eval()
+    rc = ml.rnn.cell_list[0].rnn_conv
+    cache = WeightCache(torch.device(dev), ml._wshared.setdefault(str(torch.device(dev)), {}))
+    taps = {}
+    out, _ = ml(x, cb, None, taps=taps)
+    x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
+    pred = out.detach().requires_grad_(True)
+    g_y = torch.autograd.grad(losses.loss_fu(pred, y_gaze), pred)[0]
+    grad_h = train.decoder_input_grad(ml.conv_out_st, h_seq, g_y, cache=cache, y=out)
+    w = rc.weight.detach()
+    gw = torch.empty_like(rc.weight)
+    parts = {}
+    _, _, g0, gc0 = train.lstm_backward(x_seq, h_seq, None, None, w, grad_h, need_x_grad=True, out=gw, cache=cache, module=rc, parts=parts)
+    cc, cs, dcc = parts["cc"], parts["c_seq"], parts["dcc"]
+    hh, ww = cc.shape[1:3]
+    xn, hn = x_seq.permute(0, 2, 3, 1), h_seq.permute(0, 2, 3, 1)
+    hprev = torch.cat([torch.zeros_like(hn[:1]), hn[:T - 1]], 0).contiguous()
+    cat = torch.cat([xn, hprev], 3)
+    Gn = grad_h.permute(0, 2, 3, 1)
+    ch, ccar = g0.permute(0, 2, 3, 1).contiguous(), gc0.permute(0, 2, 3, 1).contiguous()
+    zero = torch.zeros_like(ccar)
+    d1, co1 = torch.empty_like(cc[:1]), torch.empty_like(ccar)
+
+    def recompute():
+        a = train._conv(lib, cache, xn, rc, 1024, 9, wslice=(0, 256))
+        return train._conv(lib, cache, hprev, rc, 1024, 9, wslice=(256, 512), res=a)
+
+    def loop():
+        carry = None
+        for t in range(T - 1, -1, -1):
+            train.lstm_gate_bwd(Gn[t:t + 1], carry, co1 if carry is not None else None, cc[t:t + 1], cs[t:t + 1],
+                                cs[t - 1:t] if t else zero, dcc=dcc[t:t + 1], carry_c_out=co1)
+            carry = train._conv(lib, cache, dcc[t:t + 1], rc, 256, 9, wslice=(256, 512), transposed=True)
+    cases = {"lstm_backward": lambda: train.lstm_backward(x_seq, h_seq, None, None, w, grad_h, out=gw, cache=cache, module=rc),
+             "lstm_backward_x": lambda: train.lstm_backward(x_seq, h_seq, None, None, w, grad_h, need_x_grad=True, out=gw, cache=cache, module=rc),
+             "lstm_cc": recompute,
+             "lstm_scan": lambda: train.lstm_scan(cc, None),
+             "lstm_gate": lambda: train.lstm_gate_bwd(Gn[:1], ch, ccar, cc[:1], cs[:1], zero, dcc=d1, carry_c_out=co1),
+             "lstm_carry_conv": lambda: train._conv(lib, cache, dcc[:1], rc, 256, 9, wslice=(256, 512), transposed=True),
+             "lstm_loop": loop,
+             "lstm_grad_x": lambda: train._conv(lib, cache, dcc, rc, 256, 9, wslice=(0, 256), transposed=True),
+             "lstm_wgrad": lambda: train.conv3_wgrad(dcc, cat, out=gw)}
+    for k, fn in cases.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, 4 * iters if k in ("lstm_scan", "lstm_gate", "lstm_carry_conv") else iters, repeats)
+    px = hh * ww
+    res["lstm_loop_per_step_ms"] = res["lstm_loop_ms"] / T
+    res["lstm_scan_of_8TBs"] = 4.0 * 256 * 4 * T * px / (res["lstm_scan_ms"] * 1e-3) / 8e12
+    res["lstm_gate_of_8TBs"] = 18.0 * 256 * 4 * px / (res["lstm_gate_ms"] * 1e-3) / 8e12
+    flop = 2.0 * 1024 * 4608 * T * px
+    gd = L.Conv3WgradDesc()
+    gd.n_img, gd.H, gd.W, gd.Co, gd.Ci = T, hh, ww, 1024, 512
+    res["lstm_wgrad_shares"] = int(lib.uavsal_conv3_wgrad_shares(C.byref(gd)))
+    res["lstm_wgrad_tflops"] = flop / (res["lstm_wgrad_ms"] * 1e-3) / 1e12
+    res["lstm_cc_tflops"] = flop / (res["lstm_cc_ms"] * 1e-3) / 1e12
+    res["lstm_grad_x_tflops"] = 0.5 * flop / (res["lstm_grad_x_ms"] * 1e-3) / 1e12
+    res["lstm_carry_conv_tflops"] = 0.5 * flop / T / (res["lstm_carry_conv_ms"] * 1e-3) / 1e12
+    del parts, cc, cs, dcc, cat
+    kw10 = dict(decoder=True, fuse=True, fust=True, ctx=True, nets=True, st=True, srf=True, backbone=True, shallow=True)
+
+    def boxes_of(mm):
+        return ((mm.rnn, mm.conv_out_st, mm.fucbst_layer, mm.fust_layer, mm.fucb_layer, mm.cxt_cb_prior) + tuple(train.prior_nets(mm).values())
+                + (mm.st_layer,) + tuple(train.srf_head(mm)) + tuple(train.backbone_blocks(mm)) + tuple(train.shallow_blocks(mm)))
+
+    def stepper(mm, **kw):
+        w_ = mm.rnn.cell_list[0].rnn_conv.weight
+
+        def run():
+            w_.grad = None
+            train.recurrence_step(mm, x, cb, None, y_gaze, **kw)
+        return run
+
+    def iteration(mm, **kw):
+        boxes = boxes_of(mm)
+        opt = torch.optim.Adam([q for b in boxes for q in b.parameters()], lr=1e-4, betas=(0.9, 0.999), weight_decay=5e-5)
+
+        def run():
+            opt.zero_grad()
+            train.recurrence_step(mm, x, cb, None, y_gaze, **kw10, **kw)
+            opt.step()
+            mm.refresh_weights(*boxes, device=True, fused_t=True)
+        return run
+    runs = {"step_twa": stepper(m), "step_lstm": stepper(ml, lstm=True),
+            "iter10_device_twa": iteration(m), "iter10_device_lstm": iteration(ml, lstm=True)}
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # alternated in the same run, every run listed
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    runs["step_lstm"]()
+    torch.cuda.synchronize()
+    res["step_lstm_peak_MB"] = torch.cuda.max_memory_allocated(dev) / 1e6
+    for mm in (m, ml):
+        for q in mm.parameters():
+            q.grad = None
+
+
 def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
     """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
     from iip_uavsal_saliency_amd import repack
@@ -855,7 +973,7 @@ def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
 
 
 def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False, backbone_only=False,
-          shallow_only=False):
+          shallow_only=False, lstm_only=False):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
@@ -890,6 +1008,10 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False,
     if shallow_only:
         res = {"T": T}
         shallow_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+        return res
+    if lstm_only:
+        res = {"T": T}
+        lstm_phases(res, m, x, cb, y_gaze, iters, repeats)
         return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -1014,11 +1136,13 @@ def main():
     ap.add_argument("--srf-only", action="store_true", help="only the phases of the eighth stage (srf_phases)")
     ap.add_argument("--backbone-only", action="store_true", help="only the phases of the ninth stage (backbone_phases)")
     ap.add_argument("--shallow-only", action="store_true", help="only the phases of the tenth stage (shallow_phases)")
+    ap.add_argument("--lstm-only", action="store_true", help="only the phases of the ConvLSTM backward (lstm_phases)")
     ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
     out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
-           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only, a.backbone_only, a.shallow_only)
+           "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only, a.backbone_only, a.shallow_only,
+                           a.lstm_only)
                      for T in a.frames]}
     print(json.dumps(out))
 
