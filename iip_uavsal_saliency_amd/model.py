@@ -295,7 +295,7 @@ class UAVSal(nn.Module):
     def refresh_weights(self, *modules, device=False, fused_t=False):
         """After an optimiser step on the parameters of `modules` (e.g. `model.rnn`, `model.conv_out_st`, `model.fucbst_layer`):
         repack every packed copy of their weights -- conv weights in every layout in use, the Winograd transforms, the
-        transposed forms of train.py, and for the decoder and the fusion block their BatchNorm folds and statistics and their
+        transposed forms of train/, and for the decoder and the fusion block their BatchNorm folds and statistics and their
         depthwise entries (the one inside a projection GEMM's loader is the same entry) -- INTO THE EXISTING DEVICE
         TENSORS, and take the parameters' new version counters as the packed state, so that the next call neither drops nor
         rebuilds a launch plan (plans hold the tensors' addresses).  Only the named modules are repacked.  If any OTHER

@@ -384,7 +384,7 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
                    model_size: Optional[tuple] = None, frame_layout: str = "CHW", bgr: bool = False,
                    gaze_layout: Optional[str] = None, criterion=None, prepare=None, stages=("rnn",), refresh="host"):
     """The inner loop of the reference's `train` phase for one video (Demo_Train_Test.py:105-153), for the stage this package
-    trains: the ConvTWA recurrence `model.rnn` (train.py).  Arguments, groups, skip rule, carried detached state and returned
+    trains: the ConvTWA recurrence `model.rnn` (train/).  Arguments, groups, skip rule, carried detached state and returned
     aggregates are `validate_video`'s (one loop serves both); every group that runs does
     `optimizer.zero_grad()`, `train.recurrence_step(...)`, `optimizer.step()`, `model.refresh_weights(model.rnn)`.
     `optimizer` is the caller's `torch.optim` object over `model.rnn.parameters()`; the reference uses
@@ -428,15 +428,7 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     stages = tuple(stages)
     if refresh not in ("host", "device"):
         raise ValueError("refresh must be 'host' or 'device', got %r" % (refresh,))
-    allowed = [("rnn",), ("rnn", "decoder"), ("rnn", "fuse"), ("rnn", "decoder", "fuse"), ("rnn", "fuse", "fust"),
-               ("rnn", "decoder", "fuse", "fust")]
-    allowed += [s + ("ctx",) for s in allowed if "fuse" in s]
-    allowed += [s + ("nets",) for s in allowed if "fuse" in s]
-    allowed += [s + ("st",) for s in allowed if "fuse" in s and ("fust" in s or not getattr(model, "num_cb", 0))]
-    allowed += [s + ("srf",) for s in allowed if "st" in s]
-    allowed += [s + ("backbone",) for s in allowed if "srf" in s]
-    allowed += [s + ("shallow",) for s in allowed if "backbone" in s]
-    if stages not in allowed:
+    if not _train.stages_allowed(model, stages):
         raise ValueError("stages must be 'rnn' followed by any of 'decoder', 'fuse' in that order, and 'fust' last behind "
                          "'fuse' (then 'ctx', then 'nets', behind 'fuse' too; 'st' the very last, behind 'fuse' and, in a "
                          "model with priors, 'fust'; only 'srf' may follow 'st', only 'backbone' 'srf', only 'shallow' 'backbone'), got %r" % (stages,))
@@ -451,25 +443,8 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
         if lstm:                                          # the ConvLSTM carries (h, c), as in validate_video
             state = [(state[0].detach(), state[1].detach())]
         optimizer.step()
-        mods = [model.rnn] + ([model.conv_out_st] if "decoder" in kw else [])
-        if "fuse" in kw:
-            mods.append(model.fucbst_layer if model.num_cb else model.fust_layer)
-        if "fust" in kw:
-            mods.append(model.fust_layer)
-        if "ctx" in kw:
-            mods.append(model.fucb_layer)
-            if getattr(model, "use_context_prior", False):
-                mods.append(model.cxt_cb_prior)
-        if "nets" in kw:
-            mods.extend(_train.prior_nets(model).values())
-        if "st" in kw:
-            mods.append(model.st_layer)
-        if "srf" in kw:
-            mods.extend(_train.srf_head(model))
-        if "backbone" in kw:
-            mods.extend(_train.backbone_blocks(model))
+        mods = _train.stage_modules(model, kw)
         if "shallow" in kw:
-            mods.extend(_train.shallow_blocks(model))
             model.refresh_weights(*mods, device=refresh == "device", fused_t=True)
         elif refresh == "device":
             model.refresh_weights(*mods, device=True)

@@ -123,7 +123,7 @@ class WeightCache:
     def conv_t(self, conv, wslice, layout):
         """The weights of the TRANSPOSED conv of `conv` (input channels `wslice`), packed for `layout`: input and output channels
         swapped and the taps flipped, `Wt[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx]` -- the conv that carries a gradient with
-        respect to `conv`'s output back to its input (train.py)."""
+        respect to `conv`'s output back to its input (train/)."""
         def make():
             w = _weight([conv], wslice).transpose(0, 1).flip(2, 3)
             return self._up(P.pack_conv_weight(w, layout))[0]

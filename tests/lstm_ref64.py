@@ -1,4 +1,4 @@
-"""Float64 restatement of the ConvLSTM slice of train.py -- the cell of reference model_convlstm.py:111-126 (bias = False, one
+"""Float64 restatement of the ConvLSTM slice of train/recurrence.py -- the cell of reference model_convlstm.py:111-126 (bias = False, one
 layer), back-propagation through time as `train.lstm_backward` walks it, the two kernels of csrc/train_lstm.hip -- written with
 torch's own operators, the seeded inputs of the tests, and per-element bounds in the convention of tests/plan_ref64.py:
 

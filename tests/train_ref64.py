@@ -1,4 +1,4 @@
-"""Float64 restatement of the trainable slice of train.py -- the ConvTWA cell, back-propagation through time, the decoder
+"""Float64 restatement of the trainable slice of train/ -- the ConvTWA cell, back-propagation through time, the decoder
 conv_out_st + sigmoid and its input gradient -- written with torch's own operators, the seeded inputs of the tests, and the
 per-element bounds of the three kernels of csrc/train.hip in the convention of tests/plan_ref64.py:
 
