@@ -397,6 +397,33 @@ SKINNY_UNIT, SKINNY_SHARES = 128, 1024       # UAVSAL_SKINNY_UNIT, UAVSAL_SKINNY
 SKINNY_MAX_NARROW, SKINNY_MAX_WIDE = 32, 192
 SHALLOW_DESC_TYPES = [SkinnyWgradDesc]      # sized by uavsal_shallow_sizeof_desc (csrc/train_shallow.hip)
 
+class BnStatsDesc(C.Structure):
+    _fields_ = [("u", _f), ("ld", C.c_int32), ("gamma", _f), ("beta", _f), ("running_mean", _f), ("running_var", _f),
+                ("eps", C.c_double), ("momentum", C.c_double), ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("mu", _f), ("var", _f), ("r", _f), ("s", _f), ("b", _f),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
+
+
+class BnApplyDesc(C.Structure):
+    _fields_ = [("u", _f), ("ld", C.c_int32), ("s", _f), ("b", _f), ("dot_w", _f), ("out", _f),
+                ("n_pix", C.c_int64), ("C", C.c_int32), ("act", C.c_int32)]
+
+
+class BnBwdDesc(C.Structure):
+    _fields_ = [("g", _f), ("ldg", C.c_int32), ("g_pix", _f), ("g_chan", _f), ("u", _f), ("ld", C.c_int32),
+                ("s", _f), ("b", _f), ("mu", _f), ("r", _f), ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("sums", C.c_void_p),
+                ("g_gamma", _f), ("g_beta", _f), ("g_w", _f), ("gu", _f),
+                ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("act", C.c_int32),
+                ("accumulate", C.c_int32)]
+
+
+class DwWgradDesc(C.Structure):
+    _fields_ = [("g", _f), ("ldg", C.c_int32), ("e", _f), ("lde", C.c_int32), ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("out", _f), ("n_img", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("accumulate", C.c_int32)]
+
+
+BN_DESC_TYPES = [BnStatsDesc, BnApplyDesc, BnBwdDesc, DwWgradDesc]      # sized by uavsal_bn_sizeof_desc (csrc/train_bn.hip)
+
 REPACK_MAX_SRC = 4            # UAVSAL_REPACK_MAX_SRC: weights / BatchNorms side by side in one entry (csrc/repack.hip)
 REPACK_CONV, REPACK_WINO, REPACK_FOLD, REPACK_DW, REPACK_COPY, REPACK_COPY_T = range(6)
 REPACK_LAYOUT = {"f32": 0, "f32k32": 0, "f16x3": 1, "f16x3i": 2, "f16x3j": 3, "bf16": 4, "bf16x3": 5}
@@ -507,6 +534,17 @@ SYMBOLS = [
     ("uavsal_skinny_wgrad_shares", C.c_int, [C.POINTER(SkinnyWgradDesc)]),
     ("uavsal_skinny_wgrad", C.c_int, [C.POINTER(SkinnyWgradDesc), C.c_void_p]),
     ("uavsal_shallow_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_bn_slabs", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("uavsal_bn_slab_rows", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("uavsal_bn_stats_workspace_bytes", C.c_int64, [C.POINTER(BnStatsDesc)]),
+    ("uavsal_bn_stats", C.c_int, [C.POINTER(BnStatsDesc), C.c_void_p]),
+    ("uavsal_bn_apply", C.c_int, [C.POINTER(BnApplyDesc), C.c_void_p]),
+    ("uavsal_bn_bwd_workspace_bytes", C.c_int64, [C.POINTER(BnBwdDesc)]),
+    ("uavsal_bn_bwd_sums", C.c_int, [C.POINTER(BnBwdDesc), C.c_void_p]),
+    ("uavsal_bn_bwd_apply", C.c_int, [C.POINTER(BnBwdDesc), C.c_void_p]),
+    ("uavsal_dw_wgrad_workspace_bytes", C.c_int64, [C.POINTER(DwWgradDesc)]),
+    ("uavsal_dw_wgrad", C.c_int, [C.POINTER(DwWgradDesc), C.c_void_p]),
+    ("uavsal_bn_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_repack", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("uavsal_repack_sizeof_desc", C.c_int, []),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
@@ -593,7 +631,8 @@ def load():
                           (lib.uavsal_block_sizeof_desc, BLOCK_DESC_TYPES), (lib.uavsal_ctx_sizeof_desc, CTX_DESC_TYPES),
                           (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES),
                           (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES), (lib.uavsal_srf_sizeof_desc, SRF_DESC_TYPES),
-                          (lib.uavsal_shallow_sizeof_desc, SHALLOW_DESC_TYPES), (lib.uavsal_lstm_sizeof_desc, LSTM_DESC_TYPES)):
+                          (lib.uavsal_shallow_sizeof_desc, SHALLOW_DESC_TYPES), (lib.uavsal_lstm_sizeof_desc, LSTM_DESC_TYPES),
+                          (lib.uavsal_bn_sizeof_desc, BN_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

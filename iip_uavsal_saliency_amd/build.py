@@ -12,7 +12,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG, "libuavsal_hip.so")
-SOURCES = ["conv_gemm.hip", "conv_gemm_k32.hip", "dwproj.hip", "dw_conv.hip", "fused_ir.hip", "fused_mid.hip", "glue.hip", "letterbox.hip", "loss.hip", "overlay.hip", "post.hip", "plan.hip", "prior.hip", "repack.hip", "score.hip", "train.hip", "train_block.hip", "train_ctx.hip", "train_decoder.hip", "train_lstm.hip", "train_nets.hip", "train_shallow.hip", "train_srf.hip", "train_st.hip", "winograd.hip"]
+SOURCES = ["conv_gemm.hip", "conv_gemm_k32.hip", "dwproj.hip", "dw_conv.hip", "fused_ir.hip", "fused_mid.hip", "glue.hip", "letterbox.hip", "loss.hip", "overlay.hip", "post.hip", "plan.hip", "prior.hip", "repack.hip", "score.hip", "train.hip", "train_block.hip", "train_bn.hip", "train_ctx.hip", "train_decoder.hip", "train_lstm.hip", "train_nets.hip", "train_shallow.hip", "train_srf.hip", "train_st.hip", "winograd.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
 FLAGS += os.environ.get("UAVSAL_EXTRA_HIPCC_FLAGS", "").split()        # e.g. -DUAVSAL_PROBE for tools/gemm_probe2.py
 

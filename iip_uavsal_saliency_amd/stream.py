@@ -382,7 +382,8 @@ def validate_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
 def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob_prior: torch.Tensor,
                    fix_map: torch.Tensor, fix_loc: torch.Tensor, optimizer, batch_size: int = 4,
                    model_size: Optional[tuple] = None, frame_layout: str = "CHW", bgr: bool = False,
-                   gaze_layout: Optional[str] = None, criterion=None, prepare=None, stages=("rnn",), refresh="host"):
+                   gaze_layout: Optional[str] = None, criterion=None, prepare=None, stages=("rnn",), refresh="host",
+                   batch_stats=()):
     """The inner loop of the reference's `train` phase for one video (Demo_Train_Test.py:105-153), for the stage this package
     trains: the ConvTWA recurrence `model.rnn` (train/).  Arguments, groups, skip rule, carried detached state and returned
     aggregates are `validate_video`'s (one loop serves both); every group that runs does
@@ -421,7 +422,11 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     them on the GPU (`model.refresh_weights(..., device=True)`: the same bytes, no copy through the host).
     A `UAVSAL_LSTM` model (`rnn_type == "lstm"`) is trained the same way: the step is `recurrence_step(..., lstm=True)`
     (`train.lstm_backward`), the carried state is `[(h.detach(), c.detach())]` as in `validate_video`, and `stages`, their
-    order rules and `refresh` are unchanged -- `"rnn"` is then the ConvLSTM's `[1024,512,3,3]` weight."""
+    order rules and `refresh` are unchanged -- `"rnn"` is then the ConvLSTM's `[1024,512,3,3]` weight.
+    `batch_stats=("decoder",)` (needs `"decoder"` in `stages`): the keyword is passed through to `recurrence_step`, which then
+    runs the decoder's BatchNorms on the statistics of each group and moves their running statistics, as the reference's
+    `train` phase does; `model.conv_out_st` is put into training mode for the steps and its mode restored afterwards (the
+    model itself stays in `eval()`).  `validate_video` stays on the running statistics, as the reference's `val` phase does."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
@@ -433,6 +438,15 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
                          "'fuse' (then 'ctx', then 'nets', behind 'fuse' too; 'st' the very last, behind 'fuse' and, in a "
                          "model with priors, 'fust'; only 'srf' may follow 'st', only 'backbone' 'srf', only 'shallow' 'backbone'), got %r" % (stages,))
     kw = {s: True for s in stages[1:]}
+    batch_stats = (batch_stats,) if isinstance(batch_stats, str) else tuple(batch_stats)
+    if batch_stats:
+        for name in batch_stats:
+            if name not in _train.BATCH_STATS:
+                raise NotImplementedError("batch_stats covers %r only; the BatchNorms of stage %r stay on their running "
+                                          "statistics" % (_train.BATCH_STATS, name))
+        if "decoder" not in stages:
+            raise ValueError("batch_stats=('decoder',) needs 'decoder' in stages, got %r" % (stages,))
+        kw["batch_stats"] = batch_stats                   # (without it the call keeps the keywords it always had)
     lstm = getattr(model, "rnn_type", "twa") == "lstm"
     if lstm:
         kw["lstm"] = True                                 # (a ConvTWA model's call keeps the keywords it always had)
@@ -451,8 +465,15 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
         else:
             model.refresh_weights(*mods)                  # (no keyword: a model-like object without `device=` keeps working)
         return loss, state
-    return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,
-                             bgr, gaze_layout, prepare, step)
+    was = model.conv_out_st.training if batch_stats else None
+    try:
+        if batch_stats:
+            model.conv_out_st.train()
+        return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,
+                                 bgr, gaze_layout, prepare, step)
+    finally:
+        if batch_stats:
+            model.conv_out_st.train(was)
 
 
 class RequestPipeline:

@@ -18,6 +18,10 @@ stage is a keyword of the step; its module tells what it trains, what it needs a
     9  features[8:18]            backbone   backbone.py     csrc/train_block.hip (`tails32`: csrc/train_decoder.hip)
     10 features[2:8]             shallow    backbone.py     csrc/train_shallow.hip
 
+`batch_stats=("decoder",)` runs the decoder's BatchNorms on the statistics of the batch instead (bn.py, decoder.py:
+csrc/train_bn.hip), the first stage for which the reference's `model.train()` behaviour exists; every other stage's
+BatchNorms stay on their running statistics.
+
 `STAGES` below is the same list as data: what each keyword needs and which modules it refreshes.  `_common.py` holds what the
 stages share.  The imports run one way: block <- ctx <- {nets, st}, st <- srf, block <- backbone; the step combines them here.
 Apart from the launches named above everything is one `uavsal_conv_gemm` / `uavsal_dw3x3` call each, routed by the library's
@@ -37,8 +41,10 @@ from .block import (BLOCK_PARAMS, _block_backward, _block_parts, _block_recomput
                     _param_grad_parts, block_backward, block_input_grad, block_param_grads, ir_bwd, ir_bwd_dil, ir_bwd_s2, ir_sums,
                     ir_sums_dil, ir_sums_s2)
 from .ctx import PRIOR_PATH_BLOCKS, bilinear_bwd, fust_output_grad, prior_path_backward, prior_path_blocks, tsum_bwd  # noqa: F401
-from .decoder import (DECODER_PARAMS, _decoder_parts, dec_bwd, dec_sums, decoder_backward, decoder_input_grad,  # noqa: F401
-                      decoder_param_grads)
+from . import bn  # noqa: F401
+from .bn import bn_apply, bn_bwd_apply, bn_bwd_sums, bn_stats, dw_wgrad  # noqa: F401
+from .decoder import (DECODER_PARAMS, _decoder_parts, dec_bwd, dec_sums, decoder_backward, decoder_backward_batch,  # noqa: F401
+                      decoder_forward_batch, decoder_input_grad, decoder_param_grads)
 from .nets import (PRIOR_NETS, _narrow_parts, frame_sum, ir_narrow_grads, narrow_block_param_grads, prior_net_backward,  # noqa: F401
                    prior_nets)
 from .recurrence import lstm_backward, lstm_gate_bwd, lstm_scan, twa_backward, twa_gate_bwd, twa_wgrad  # noqa: F401
@@ -98,6 +104,9 @@ STAGES = (
 )
 
 
+BATCH_STATS = ("decoder",)       # the stages whose BatchNorms `recurrence_step(batch_stats=...)` can run on batch statistics
+
+
 def stages_allowed(model, stages):
     """Whether `stages` is a tuple `stream.finetune_video` trains: `"rnn"` first, then names of `STAGES` in its order, none
     twice, each with what it `needs`."""
@@ -117,7 +126,7 @@ def _grads_of(module):
 
 
 def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False,
-                    st=False, srf=False, backbone=False, shallow=False, lstm=False):
+                    st=False, srf=False, backbone=False, shallow=False, lstm=False, batch_stats=()):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -134,7 +143,22 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     any launch): `in_state` is None or `[(h, c)]`, the forward runs through the plan as it always did, and `lstm_backward`
     stands where `twa_backward` stands, setting -- or adding to -- the `.grad` of the `[1024,512,3,3]` `rnn_conv.weight`; every
     other keyword works unchanged behind it.  Returns `(loss, out, [h_last.detach(), c_last.detach()])`, the forward's
-    contract for this model; refresh `model.rnn` as usual.  Without the keyword a `UAVSAL_LSTM` model raises, as it always did."""
+    contract for this model; refresh `model.rnn` as usual.  Without the keyword a `UAVSAL_LSTM` model raises, as it always did.
+    `batch_stats=("decoder",)` (opt-in; the default `()` runs the launches it ran and returns the bits it returned; needs
+    `decoder=True`): the decoder runs as the reference's `train()` runs it, its BatchNorms on the statistics of the batch
+    (`BATCH_STATS`).  The model stays in eval mode and `model.conv_out_st.train()` has been called -- a configuration torch
+    itself defines; anything else raises a `RuntimeError` that names what is missing, before any launch, and any other stage
+    name in the tuple a `NotImplementedError` that names it.  The plan runs as always (a child in training mode changes
+    nothing in it: the plan and the weight cache read the running statistics where they lie), its own prediction is dropped,
+    and `out` and the loss come from `decoder_forward_batch` on the `rnn` tap, which also moves the decoder's running
+    statistics; `decoder_backward_batch` sets -- or adds to -- the nine `.grad`s and hands its `grad_h` to the recurrence
+    unchanged.  The returned `out` is the batch-statistics prediction.  Afterwards
+    `model.refresh_weights(model.rnn, model.conv_out_st)` refolds the eval-mode packed forms from the moved statistics."""
+    batch_stats = (batch_stats,) if isinstance(batch_stats, str) else tuple(batch_stats)
+    for name in batch_stats:
+        if name not in BATCH_STATS:
+            raise NotImplementedError("batch_stats covers %r only; the BatchNorms of stage %r stay on their running statistics"
+                                      % (BATCH_STATS, name))
     criterion = criterion or _losses.loss_fu
     is_lstm = getattr(model, "rnn_type", "twa") != "twa"
     if is_lstm and not lstm:
@@ -149,6 +173,12 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
         raise RuntimeError("recurrence_step needs model.eval(): only the recurrence is trained, every BatchNorm stays folded")
     if model.precision != "f32":
         raise RuntimeError("recurrence_step supports precision 'f32' only, got %r" % (model.precision,))
+    if batch_stats:
+        if not decoder:
+            raise RuntimeError("batch_stats=('decoder',) needs decoder=True: the batch statistics belong to the trained decoder")
+        if not model.conv_out_st.training:
+            raise RuntimeError("batch_stats=('decoder',) needs model.conv_out_st.train() (under model.eval()): the decoder's "
+                               "BatchNorms are in eval mode")
     if not torch.is_tensor(x) or not x.is_cuda or not torch.is_tensor(y_gaze) or not y_gaze.is_cuda:
         raise RuntimeError("recurrence_step needs tensors on the MI355X (cuda) device; there is no CPU fallback")
     rc = model.rnn.cell_list[0].rnn_conv
@@ -157,6 +187,10 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if fust or ctx or nets:
         taps["cb192"] = None                                         # (likewise)
     out, h_last = model(x, cb, in_state, taps=taps)
+    if batch_stats:                                                  # the plan's own prediction is dropped
+        cache = WeightCache(x.device, model._wshared.setdefault(str(torch.device(x.device)), {}))
+        out, saved = decoder_forward_batch(model.conv_out_st, taps["rnn"].contiguous(memory_format=torch.channels_last),
+                                           cache=cache)
     pred = out.detach().requires_grad_(True)
     with torch.enable_grad():
         loss = criterion(pred, y_gaze)
@@ -165,7 +199,10 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     cache = WeightCache(dev, model._wshared.setdefault(str(torch.device(dev)), {}))
     cl = torch.channels_last
     h_seq, x_seq = taps["rnn"].contiguous(memory_format=cl), taps["prefuse"].contiguous(memory_format=cl)
-    if decoder:
+    if decoder and batch_stats:
+        grads, acc = _grads_of(model.conv_out_st)
+        grad_h, _ = decoder_backward_batch(model.conv_out_st, h_seq, g_y, saved=saved, grads=grads, accumulate=acc, cache=cache)
+    elif decoder:
         grads, acc = _grads_of(model.conv_out_st)
         grad_h, _ = decoder_backward(model.conv_out_st, h_seq, g_y, cache=cache, y=out, grads=grads, accumulate=acc)
     else:

@@ -2,7 +2,10 @@
 the second stage, trained (`decoder_backward`, `decoder_param_grads`; csrc/train_decoder.hip: `uavsal_pix_gemm`,
 `uavsal_dec_sums`, `uavsal_dec_finish`), its BatchNorms on their running statistics.
 `recurrence_step(decoder=True)`: the decoder's nine parameters' `.grad` are set as well, or added to, and the recurrence
-receives that path's `grad_h`; afterwards call `model.refresh_weights(model.rnn, model.conv_out_st)`."""
+receives that path's `grad_h`; afterwards call `model.refresh_weights(model.rnn, model.conv_out_st)`.
+`decoder_forward_batch` / `decoder_backward_batch` (csrc/train_bn.hip, train/bn.py) are the same block in TRAINING mode: the
+BatchNorms on the statistics of the batch, the gradient through those statistics, the running statistics moved;
+`recurrence_step(decoder=True, batch_stats=("decoder",))` with `model.conv_out_st.train()` under `model.eval()`."""
 import ctypes as C
 
 import torch
@@ -209,4 +212,125 @@ def decoder_backward(block, h_seq, grad_out, cache=None, y=None, parts=None, gra
                                     accumulate=accumulate)
         if parts is not None:
             parts.update(e=e, d=dd, y=y, ga=ga)
+    return g.permute(0, 3, 1, 2), grads
+
+
+# ---------------------------------------------------------------------------------------------- batch statistics (training mode)
+_BATCH_REFUSAL = ("decoder_forward_batch / decoder_backward_batch run the decoder's BatchNorms on BATCH statistics: call "
+                  "block.train() (model.conv_out_st.train() under model.eval()); a block in eval mode goes through the eval-mode "
+                  "functions decoder_backward, decoder_input_grad and decoder_param_grads")
+
+
+def _decoder_parts_batch(block, who):
+    seq = block.conv
+    if getattr(block, "expand_ratio", 0) == 1 or len(seq) != 4 or seq[2].weight.shape[0] != 1:
+        raise RuntimeError("%s takes model.conv_out_st (expand 1x1, depthwise 3x3, projection to one channel)" % who)
+    bns = (seq[0][1], seq[1][1], seq[3])
+    if not block.training or not all(b.training for b in bns):
+        raise RuntimeError(_BATCH_REFUSAL)
+    if not all(b.track_running_stats and b.affine and b.running_mean is not None for b in bns):
+        raise RuntimeError("%s needs affine BatchNorms that track their running statistics" % who)
+    return seq[0][0], bns[0], seq[1][0], bns[1], seq[2], bns[2]
+
+
+def _dw_raw(lib, x, w9):
+    """The raw depthwise 3x3 of the dense NHWC `x` with the tap-major weights `w9`: `uavsal_dw3x3` with unit scale, zero bias
+    and no activation."""
+    T, hh, ww, c = x.shape
+    out = torch.empty_like(x)
+    one, zero = torch.ones(c, dtype=torch.float32, device=x.device), torch.zeros(c, dtype=torch.float32, device=x.device)
+    q = L.DwDesc()
+    q.inp, q.ldi, q.w9c, q.scale, q.bias = x.data_ptr(), c, w9.data_ptr(), one.data_ptr(), zero.data_ptr()
+    q.out, q.ldo = out.data_ptr(), c
+    q.n_img, q.H, q.W, q.C, q.stride, q.dilation, q.act = T, hh, ww, c, 1, 1, L.ACT_NONE
+    L.check(lib.uavsal_dw3x3(C.byref(q), _stream(x)), "uavsal_dw3x3")
+    return out
+
+
+def decoder_forward_batch(block, h_seq, update_running=True, parts=None, cache=None):
+    """The decoder `block` = `model.conv_out_st` + sigmoid in TRAINING mode, torch's rules for `nn.BatchNorm2d`: every
+    BatchNorm normalises with the statistics of all `T*h*w` pixels of `h_seq` `[T,256,h,w]` together.  Returns
+    `(y [T,1,h,w], saved)`; `saved` holds what `decoder_backward_batch` needs: the raw `u1 = W1 h`, `u2 = dw3x3(Wd, e)`,
+    `u3 = w3 . d` and `e = ReLU6(BN1(u1))` (dense NHWC; `d` is never stored: the projection reads `u2`) and the three
+    `bn.BnFold`s `f1`, `f2`, `f3` (batch mean, biased variance, r and the fold s, b).  `update_running` (default): the running
+    statistics of the three BatchNorms move on the device as torch moves them (momentum, unbiased variance) and
+    `num_batches_tracked` goes up by one -- afterwards `model.refresh_weights(model.conv_out_st)` refolds the eval-mode packed
+    forms from them.  Launches: the 256 -> 1536 GEMM, then per BatchNorm `uavsal_bn_stats` (two) and `uavsal_bn_apply` (one),
+    with `uavsal_dw3x3` between the first two; no synchronisation.  A block in eval mode raises.  `parts` receives `saved`."""
+    from . import bn as B
+    lib = L.load()
+    pw, bn1, dwc, bn2, pl, bn3 = _decoder_parts_batch(block, "decoder_forward_batch")
+    h = _nhwc(h_seq, "h_seq", pw.weight.shape[1])
+    T, hh, ww, _ = h.shape
+    dev, hid = h.device, pw.weight.shape[0]
+    if update_running and any(b.momentum is None for b in (bn1, bn2, bn3)):
+        raise RuntimeError("decoder_forward_batch: momentum=None (the cumulative average) is not covered")
+
+    def stats(u, b):
+        run = (b.running_mean, b.running_var) if update_running else (None, None)
+        f = B.bn_stats(u, b.weight, b.bias, b.eps, *run, momentum=b.momentum)
+        if update_running:
+            b.num_batches_tracked.add_(1)
+        return f
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        u1 = _conv(lib, cache, h, pw, hid, 1)
+        f1 = stats(u1, bn1)
+        e = B.bn_apply(u1, f1, "relu6")
+        u2 = _dw_raw(lib, e, cache.depthwise(dwc, bn2)[0])
+        f2 = stats(u2, bn2)
+        u3 = B.bn_apply(u2, f2, "relu6", dot_w=pl.weight.detach().reshape(-1))
+        f3 = stats(u3, bn3)
+        y = B.bn_apply(u3, f3, "sigmoid")
+    saved = dict(u1=u1, e=e, u2=u2, u3=u3, f1=f1, f2=f2, f3=f3)
+    if parts is not None:
+        parts.update(saved)
+    return y.view(T, 1, hh, ww), saved
+
+
+def decoder_backward_batch(block, h_seq, grad_out, saved=None, grads=None, accumulate=False, parts=None, cache=None):
+    """The backward of `decoder_forward_batch`: returns `(grad_h [T,256,h,w], grads)`, `grads` keyed by the nine names of
+    `DECODER_PARAMS`, the values `torch.autograd` gives for the reference's `dwBlock` in `.train()` mode + sigmoid -- the
+    gradient flows through the batch statistics: per BatchNorm `g_u = s (g_a - d beta / P - xh d gamma / P)` -- written into
+    `grads`, or with `accumulate` added to it, as `decoder_backward` does.  `grad_out` `[T,1,h,w]` = d loss / d y; `saved`:
+    what the forward returned for this `h_seq` (default: the forward is run again WITHOUT moving the running statistics).
+    BN3, then BN2, then BN1: `uavsal_bn_bwd_sums` and `uavsal_bn_bwd_apply` each (the adjoint of the projection is formed
+    inside BN2's launches, which also give W3's gradient), `uavsal_dw_wgrad` and the flipped `uavsal_dw3x3` between BN2 and
+    BN1, `uavsal_pix_gemm` for W1 and one transposed GEMM for `grad_h`.  The ReLU6 masks and xh come from the stored raw
+    `u1`, `u2`.  A block in eval mode raises.  `parts` receives `g_u1`, `g_u2`, `g_u3`, `g_e` (dense NHWC)."""
+    from . import bn as B
+    lib = L.load()
+    pw, bn1, dwc, bn2, pl, bn3 = _decoder_parts_batch(block, "decoder_backward_batch")
+    h = _nhwc(h_seq, "h_seq", pw.weight.shape[1])
+    T, hh, ww, _ = h.shape
+    if (not torch.is_tensor(grad_out) or not grad_out.is_cuda or grad_out.dtype != torch.float32
+            or tuple(grad_out.shape) != (T, 1, hh, ww)):
+        raise RuntimeError("grad_out must be a float32 cuda tensor [%d,1,%d,%d]" % (T, hh, ww))
+    dev, hid = h.device, pw.weight.shape[0]
+    params, grads = _decoder_slots(block, grads, accumulate)          # raises before anything is launched
+    if any(q.device != dev or not q.is_contiguous() for q in params.values()):
+        raise RuntimeError("the decoder's parameters must be dense tensors on the device of `h_seq`")
+    N = DECODER_PARAMS
+    with torch.cuda.device(dev):
+        cache = cache or WeightCache(dev, {})
+        if saved is None:
+            _, saved = decoder_forward_batch(block, h_seq, update_running=False, cache=cache)
+        u1, e, u2, u3, f1, f2, f3 = (saved[k] for k in ("u1", "e", "u2", "u3", "f1", "f2", "f3"))
+        if tuple(u1.shape) != (T, hh, ww, hid) or tuple(u3.shape) != (T, hh, ww, 1):
+            raise RuntimeError("saved does not belong to this h_seq")
+        gy = grad_out.detach().contiguous().view(T, hh, ww, 1)
+        w3 = pl.weight.detach().reshape(-1)
+        s3 = B.bn_bwd_sums(gy, u3, f3, "sigmoid", g_weight=grads[N[7]], g_bias=grads[N[8]], accumulate=accumulate)
+        g_u3 = B.bn_bwd_apply(gy, u3, f3, s3, "sigmoid")
+        g2 = (g_u3, w3)
+        s2 = B.bn_bwd_sums(g2, u2, f2, "relu6", g_weight=grads[N[4]], g_bias=grads[N[5]], g_w=grads[N[6]], accumulate=accumulate)
+        g_u2 = B.bn_bwd_apply(g2, u2, f2, s2, "relu6")
+        B.dw_wgrad(g_u2, e, out=grads[N[3]], accumulate=accumulate)
+        g_e = _dw_raw(lib, g_u2, cache.depthwise(dwc, bn2)[0].flip(0).contiguous())
+        s1 = B.bn_bwd_sums(g_e, u1, f1, "relu6", g_weight=grads[N[1]], g_bias=grads[N[2]], accumulate=accumulate)
+        g_u1 = B.bn_bwd_apply(g_e, u1, f1, s1, "relu6")
+        pix_gemm(g_u1, h, out=grads[N[0]], accumulate=accumulate)
+        g = _conv(lib, cache, g_u1, pw, pw.weight.shape[1], 1, transposed=True)
+        if parts is not None:
+            parts.update(g_u1=g_u1, g_u2=g_u2, g_u3=g_u3, g_e=g_e)
     return g.permute(0, 3, 1, 2), grads

@@ -1279,6 +1279,101 @@ int uavsal_skinny_wgrad_shares(const uavsal_skinny_wgrad_desc* d);  /* K shares 
 int uavsal_skinny_wgrad(const uavsal_skinny_wgrad_desc* d, uavsal_stream_t stream);
 int uavsal_shallow_sizeof_desc(int which);    /* 0 skinny_wgrad (uavsal_srf_sizeof_desc is closed at 3) */
 
+/* ---- BatchNorm on BATCH statistics (training mode) and the decoder built on it (csrc/train_bn.hip) -----------------------
+ * torch's rules for nn.BatchNorm2d in training mode.  For one BatchNorm over u [P][C], P = n_img * H * W pixels of ALL frames
+ * of the call together, rows `ld` floats apart (a channel slice is read in place), C % 4 == 0 or C == 1 (else UAVSAL_ESHAPE):
+ *     mu = mean_p u,  var = mean_p (u - mu)^2 (biased),  r = 1 / sqrt(var + eps),  xh = (u - mu) r,  a = gamma xh + beta
+ * and with g = d loss / d act(a), g_a = g act'(a):
+ *     d beta = sum_p g_a,  d gamma = sum_p g_a xh,  d loss / d u = gamma r (g_a - d beta / P - xh d gamma / P).
+ * The running statistics move as running_mean <- (1 - m) running_mean + m mu, running_var <- (1 - m) running_var +
+ * m var P / (P - 1).  The kernels work from the FOLD s = gamma r, b = beta - mu s: a = fma(u, s, b) in fp32 -- every kernel
+ * below forms a by that one fused multiply-add, so a mask or a sigmoid recomputed in the backward is the forward's -- and
+ * xh = fl(fl(u - mu) r) from the fp32 mu, r.  Nothing divides by gamma: a channel with gamma = 0 has g_u = 0 and a non-zero
+ * d gamma.
+ *
+ * The reductions share one geometry.  A lane owns 4 consecutive channels of a pixel (16-byte accesses; C == 1: one), lc lanes
+ * side by side (the smallest power of two >= C / 4, at most 64), the 256 / lc pixel lanes of a workgroup take the pixels of a
+ * SLAB in turn (pixel lane i: the slab's pixels i, i + 256 / lc, ...).  Slabs are whole picture rows counted through all
+ * frames: rows per slab = max(ceil(512 / W), ceil(n_img H / 256)) (uavsal_bn_slab_rows), slabs = ceil(n_img H / rows per slab)
+ * (uavsal_bn_slabs): a function of the shape alone.  Order of every sum: a thread adds its pixels in pixel order in double;
+ * the pixel lanes of a channel are added in pixel-lane order in double; the finish launch adds the slabs in slab order in
+ * double and rounds once.  No atomics, no host round trip, no synchronisation: two calls return the same bits.
+ *
+ * uavsal_bn_stats: sum u and sum u^2 (the products exact in double) -> mu = S1 / P, var = max(S2 / P - mu^2, 0) in double;
+ *   writes mu, var, r, s, b [C] fp32, each rounded once from double, and -- running_mean / running_var not NULL -- blends the
+ *   running statistics in place in double, rounded once (P >= 2 then, else UAVSAL_ESHAPE).  ws: uavsal_bn_stats_workspace_bytes
+ *   = slabs * 2 * C doubles, [slab][2][C].  TWO launches.
+ * uavsal_bn_apply: out[p][c] = act(fma(u, s, b)), dense [n_pix][C]; act none / ReLU6 / sigmoid (apply_act: 1 / (1 + expf(-a))).
+ *   dot_w != NULL (C % 4 == 0): out[p] = sum_c dot_w[c] act(...)[p][c] instead, dense [n_pix] (the decoder's projection to one
+ *   channel; the activated tensor is not stored): a wave per pixel, lane l adds its channels 4 l + 256 j, j = 0, 1, ... (the
+ *   four of a load in channel order) to one fp32 accumulator by fused multiply-adds, the 64 lanes meet in a butterfly
+ *   (xor 32, 16, ..., 1).  ONE launch.
+ * uavsal_bn_bwd_sums: g [P][C] rows ldg apart, or (g == NULL) the rank-one g[p][c] = fl(g_pix[p] g_chan[c]) -- the adjoint of a
+ *   projection to one channel, formed in the launch instead of being stored.  g_a = g 1[0 < a < 6] (ReLU6), g fl(y fl(1 - y)),
+ *   y = act(a) (sigmoid), g (none).  Accumulates g_a and g_a xh (and, rank-one, g_pix act(a): the projection's weight
+ *   gradient); the finish writes `sums` [2][C] doubles = d beta, d gamma (kept for uavsal_bn_bwd_apply) and, each where the
+ *   pointer is not NULL, g_beta, g_gamma, g_w [C], rounded once, overwritten or (`accumulate`) added to.
+ *   ws: uavsal_bn_bwd_workspace_bytes = slabs * 3 * C doubles, [slab][2 or 3][C].  TWO launches.
+ * uavsal_bn_bwd_apply: gu[p][c] = fl(s fma(-xh, c2, fl(g_a - c1))), c1 = fl(sums[c] / P), c2 = fl(sums[C + c] / P), g_a and
+ *   xh formed as in uavsal_bn_bwd_sums; dense [P][C].  The same descriptor.  ONE launch.
+ * uavsal_dw_wgrad: out[c][ky][kx] = sum_p g[p][c] e[p + (ky-1, kx-1)][c], zero outside the picture, never across frames (the
+ *   halo is masked by the row inside ITS frame), C % 4 == 0; nine sums per channel in double per slab, the geometry and order
+ *   above; out [C][3][3] rounded once, overwritten or (`accumulate`) added to.  ws: slabs * 9 * C doubles.  TWO launches.
+ * The raw depthwise conv of the decoder and its transpose are uavsal_dw3x3 with unit scale, zero bias and no activation, the
+ * transpose with the taps flipped.
+ * UAVSAL_EALIGN: a 4-wide tensor or its pitch not 16-byte aligned, a workspace not 8-byte aligned; UAVSAL_EINVAL: a missing
+ * pointer, a size <= 0, a pitch below C, a workspace too small, eps < 0 or momentum outside [0, 1].
+ */
+typedef struct uavsal_bn_stats_desc {
+    const float* u;  int32_t ld;
+    const float* gamma;  const float* beta;         /* [C] */
+    float* running_mean;  float* running_var;       /* [C], updated in place; NULL: left alone */
+    double eps, momentum;
+    double* ws;  int64_t ws_bytes;
+    float* mu;  float* var;  float* r;  float* s;  float* b;     /* [C] each */
+    int32_t n_img, H, W, C;
+} uavsal_bn_stats_desc;
+
+typedef struct uavsal_bn_apply_desc {
+    const float* u;  int32_t ld;
+    const float* s;  const float* b;                /* [C] */
+    const float* dot_w;                             /* NULL, or [C]: the dot over the channels */
+    float* out;                                     /* dense [n_pix][C], or [n_pix] with dot_w */
+    int64_t n_pix;  int32_t C, act;
+} uavsal_bn_apply_desc;
+
+typedef struct uavsal_bn_bwd_desc {
+    const float* g;  int32_t ldg;                   /* [P] rows of C floats, or NULL: */
+    const float* g_pix;  const float* g_chan;       /* [P], [C]: g[p][c] = g_pix[p] g_chan[c] */
+    const float* u;  int32_t ld;
+    const float* s;  const float* b;  const float* mu;  const float* r;     /* uavsal_bn_stats's */
+    double* ws;  int64_t ws_bytes;                  /* bwd_sums only */
+    double* sums;                                   /* [2][C]: bwd_sums writes, bwd_apply reads */
+    float* g_gamma;  float* g_beta;  float* g_w;    /* [C] each or NULL (bwd_sums) */
+    float* gu;                                      /* dense [P][C] (bwd_apply) */
+    int32_t n_img, H, W, C, act, accumulate;
+} uavsal_bn_bwd_desc;
+
+typedef struct uavsal_dw_wgrad_desc {
+    const float* g;  int32_t ldg;
+    const float* e;  int32_t lde;
+    double* ws;  int64_t ws_bytes;
+    float* out;                                     /* [C][3][3] */
+    int32_t n_img, H, W, C, accumulate;
+} uavsal_dw_wgrad_desc;
+
+int uavsal_bn_slabs(int n_img, int H, int W);       /* slabs of every reduction above for that shape (no launch); 0: refused */
+int uavsal_bn_slab_rows(int n_img, int H, int W);   /* picture rows per slab */
+int64_t uavsal_bn_stats_workspace_bytes(const uavsal_bn_stats_desc* d);
+int uavsal_bn_stats(const uavsal_bn_stats_desc* d, uavsal_stream_t stream);
+int uavsal_bn_apply(const uavsal_bn_apply_desc* d, uavsal_stream_t stream);
+int64_t uavsal_bn_bwd_workspace_bytes(const uavsal_bn_bwd_desc* d);
+int uavsal_bn_bwd_sums(const uavsal_bn_bwd_desc* d, uavsal_stream_t stream);
+int uavsal_bn_bwd_apply(const uavsal_bn_bwd_desc* d, uavsal_stream_t stream);
+int64_t uavsal_dw_wgrad_workspace_bytes(const uavsal_dw_wgrad_desc* d);
+int uavsal_dw_wgrad(const uavsal_dw_wgrad_desc* d, uavsal_stream_t stream);
+int uavsal_bn_sizeof_desc(int which);         /* 0 bn_stats, 1 bn_apply, 2 bn_bwd, 3 dw_wgrad (additions: UAVSAL_ABI_VERSION stays 20) */
+
 /* ---- repacking refreshed weights on the device (csrc/repack.hip) ---------------------------------------------------------
  * After an optimiser step the packed copies of a module's weights are remade FROM the fp32 parameters and buffers where they
  * lie INTO the packed device tensors that exist (launch plans hold their addresses): the bytes packing.py / weights.py make

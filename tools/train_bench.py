@@ -916,6 +916,106 @@ def lstm_phases(res, m, x, cb, y_gaze, iters, repeats):
             q.grad = None
 
 
+def decoder_bn_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
+    """the phases of the decoder on BATCH statistics (train.decoder_forward_batch / decoder_backward_batch, csrc/train_bn.hip),
+    added to `res`: the two batch functions alone; every launch of theirs alone from the tensors the walk hands out (`bn_*_ms`
+    and, for the memory-bound ones, the bytes the launch must move over its time as a fraction of 8 TB/s: `*_of_8TBs`; a
+    1536-channel tensor at T frames of 45 x 80 is T * 22.1 MB); and, alternated in the same run with every run listed
+    (`_all_ms`: the spread), the two-stage step ("rnn", "decoder") without the keyword and with `batch_stats=("decoder",)`,
+    each followed by the device refresh of both stages as a training loop follows it (`iter_dec*`: a step on batch statistics
+    moves the running statistics, so a forward WITHOUT the refresh behind it drops and rebuilds the plans -- no loop does that,
+    and a step timed alone would time the rebuild), the refresh alone, the step without the keyword alone (`step_dec_ms`, timed
+    before any batch step ran), and the peak memory of either iteration."""
+    from iip_uavsal_saliency_amd.train import bn as B
+    lib = L.load()
+    dev = x.device
+    cl = torch.channels_last
+    blk = m.conv_out_st
+    taps = {}
+    m(x, cb, None, taps=taps)
+    h_seq = taps["rnn"].contiguous(memory_format=cl)
+    hn = h_seq.permute(0, 2, 3, 1)
+    T, hh, ww, _ = hn.shape
+    blk.train()
+    y, sv = train.decoder_forward_batch(blk, h_seq, update_running=False, cache=cache)
+    pred = y.detach().requires_grad_(True)
+    g_y = torch.autograd.grad(losses.loss_fu(pred, y_gaze), pred)[0]
+    parts = {}
+    _, grads = train.decoder_backward_batch(blk, h_seq, g_y, saved=sv, parts=parts, cache=cache)
+    pw, bn1, dwc, bn2, pl, bn3 = train.decoder._decoder_parts_batch(blk, "train_bench")
+    u1, e, u2, u3, f1, f2, f3 = (sv[k] for k in ("u1", "e", "u2", "u3", "f1", "f2", "f3"))
+    g_u1, g_u2, g_u3, g_e = (parts[k] for k in ("g_u1", "g_u2", "g_u3", "g_e"))
+    gy = g_y.contiguous().view(T, hh, ww, 1)
+    w3 = pl.weight.detach().reshape(-1)
+    w9 = cache.depthwise(dwc, bn2)[0]
+    s3 = B.bn_bwd_sums(gy, u3, f3, "sigmoid")
+    s2 = B.bn_bwd_sums((g_u3, w3), u2, f2, "relu6")
+    s1 = B.bn_bwd_sums(g_e, u1, f1, "relu6")
+    big = 1536.0 * 4 * T * hh * ww                              # bytes of one 1536-channel tensor
+    launches = {                                               # name: (call, 1536-channel tensors moved; 0: not memory bound / tiny)
+        "bn_gemm_u1": (lambda: train._conv(lib, cache, hn, pw, 1536, 1), 0),
+        "bn_stats1": (lambda: B.bn_stats(u1, bn1.weight, bn1.bias, bn1.eps), 1),
+        "bn_apply1": (lambda: B.bn_apply(u1, f1, "relu6"), 2),
+        "bn_dw_raw": (lambda: train.decoder._dw_raw(lib, e, w9), 2),
+        "bn_stats2": (lambda: B.bn_stats(u2, bn2.weight, bn2.bias, bn2.eps), 1),
+        "bn_apply_dot": (lambda: B.bn_apply(u2, f2, "relu6", dot_w=w3), 1),
+        "bn_stats3": (lambda: B.bn_stats(u3, bn3.weight, bn3.bias, bn3.eps), 0),
+        "bn_apply3": (lambda: B.bn_apply(u3, f3, "sigmoid"), 0),
+        "bn_bwd_sums3": (lambda: B.bn_bwd_sums(gy, u3, f3, "sigmoid"), 0),
+        "bn_bwd_apply3": (lambda: B.bn_bwd_apply(gy, u3, f3, s3, "sigmoid"), 0),
+        "bn_bwd_sums2": (lambda: B.bn_bwd_sums((g_u3, w3), u2, f2, "relu6"), 1),
+        "bn_bwd_apply2": (lambda: B.bn_bwd_apply((g_u3, w3), u2, f2, s2, "relu6"), 2),
+        "bn_dw_wgrad": (lambda: B.dw_wgrad(g_u2, e, out=grads[train.DECODER_PARAMS[3]]), 2),
+        "bn_dw_raw_t": (lambda: train.decoder._dw_raw(lib, g_u2, w9.flip(0).contiguous()), 2),
+        "bn_bwd_sums1": (lambda: B.bn_bwd_sums(g_e, u1, f1, "relu6"), 2),
+        "bn_bwd_apply1": (lambda: B.bn_bwd_apply(g_e, u1, f1, s1, "relu6"), 3),
+        "bn_pix_gemm": (lambda: train.pix_gemm(g_u1, hn, out=grads[train.DECODER_PARAMS[0]]), 0),
+        "bn_gemm_grad_h": (lambda: train._conv(lib, cache, g_u1, pw, 256, 1, transposed=True), 0)}
+    for k, (fn, tensors) in launches.items():
+        res[k + "_ms"] = 1e3 * best_of(fn, iters, repeats)
+        if tensors:
+            res[k + "_of_8TBs"] = tensors * big / (res[k + "_ms"] * 1e-3) / 8e12
+    res["bn_slabs"], res["bn_slab_rows"] = B.slabs(T, hh, ww)
+    res["bn_tensor_MB"] = big / 1e6
+    res["dec_forward_batch_ms"] = 1e3 * best_of(lambda: train.decoder_forward_batch(blk, h_seq, update_running=False, cache=cache), iters, repeats)
+    res["dec_forward_batch_running_ms"] = 1e3 * best_of(lambda: train.decoder_forward_batch(blk, h_seq, cache=cache), iters, repeats)
+    res["dec_backward_batch_ms"] = 1e3 * best_of(lambda: train.decoder_backward_batch(blk, h_seq, g_y, saved=sv, grads=grads, cache=cache), iters, repeats)
+    blk.eval()
+    res["dec_backward_eval_ms"] = 1e3 * best_of(lambda: train.decoder_backward(blk, h_seq, g_y, cache=cache, grads=grads), iters, repeats)
+    del parts, sv, u1, e, u2, g_u1, g_u2, g_e
+    trained = list(m.rnn.parameters()) + list(blk.parameters())
+
+    def stepper(batch, refresh=True):
+        def run():
+            for q in trained:
+                q.grad = None
+            blk.train(batch)
+            train.recurrence_step(m, x, cb, None, y_gaze, decoder=True, **({"batch_stats": ("decoder",)} if batch else {}))
+            blk.eval()
+            if refresh:
+                m.refresh_weights(m.rnn, blk, device=True)
+        return run
+    res["step_dec_ms"] = 1e3 * best_of(stepper(False, refresh=False), iters, repeats)
+    runs = {"iter_dec": stepper(False), "iter_dec_batch": stepper(True)}
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # alternated in the same run, every run listed
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = 1e3 * min(v), [1e3 * t for t in v]
+    for k, fn in runs.items():
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        fn()
+        torch.cuda.synchronize()
+        res[k + "_peak_MB"] = torch.cuda.max_memory_allocated(dev) / 1e6
+    res["refresh_dec_device_ms"] = 1e3 * best_of(lambda: m.refresh_weights(m.rnn, blk, device=True), iters, repeats)
+    for q in trained:
+        q.grad = None
+
+
 def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
     """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
     from iip_uavsal_saliency_amd import repack
@@ -973,7 +1073,7 @@ def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
 
 
 def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False, backbone_only=False,
-          shallow_only=False, lstm_only=False):
+          shallow_only=False, lstm_only=False, decoder_bn_only=False):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
@@ -1012,6 +1112,10 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False,
     if lstm_only:
         res = {"T": T}
         lstm_phases(res, m, x, cb, y_gaze, iters, repeats)
+        return res
+    if decoder_bn_only:
+        res = {"T": T}
+        decoder_bn_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
         return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -1137,12 +1241,14 @@ def main():
     ap.add_argument("--backbone-only", action="store_true", help="only the phases of the ninth stage (backbone_phases)")
     ap.add_argument("--shallow-only", action="store_true", help="only the phases of the tenth stage (shallow_phases)")
     ap.add_argument("--lstm-only", action="store_true", help="only the phases of the ConvLSTM backward (lstm_phases)")
+    ap.add_argument("--decoder-bn-only", action="store_true",
+                    help="only the phases of the decoder on batch statistics (decoder_bn_phases)")
     ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
     out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
            "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only, a.backbone_only, a.shallow_only,
-                           a.lstm_only)
+                           a.lstm_only, a.decoder_bn_only)
                      for T in a.frames]}
     print(json.dumps(out))
 
