@@ -20,6 +20,12 @@ static inline int uavsal_launch_status() {
 }
 
 static inline bool uavsal_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+static inline bool al16(const void* p) { return uavsal_aligned16(p); }
+static inline bool al8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }
+static inline bool al4(const void* p) { return (((uintptr_t)p) & 3u) == 0; }
+
+// four consecutive floats at a 16-byte aligned address
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // The frame-repeat forms of the conv launch (conv_gemm.hip), for the plan engine (plan.hip) only: not part of the C ABI.
 // uavsal_conv_repeat_pair: 1 when `pw` (a 1x1 expand) and `dw` (the depthwise -> projection launch that reads pw's output)

@@ -18,7 +18,7 @@ namespace pixgemm {
 constexpr int kTile = 128, kStep = 32, kRow = 160;
 constexpr int kTargetWGs = 1024;
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+using ::ld4;
 
 // D of the wave's MFMA tile (i, j), register r: row m = wm + i * 32 + (r & 3) + 8 (r >> 2) + 4 (lane >> 5),
 // column n = wn + j * 32 + (lane & 31), with wm = (wave & 1) * 64, wn = (wave >> 1) * 64.

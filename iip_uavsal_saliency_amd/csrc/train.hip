@@ -235,7 +235,6 @@ __global__ __launch_bounds__(256) void dec_bwd_kernel(const DecK p) {
     }
 }
 
-bool al16(const void* p) { return uavsal_aligned16(p); }
 
 }  // namespace
 

@@ -14,18 +14,24 @@
 //    doubles per lane).  The waves meet in LDS in wave order and the workgroup writes one partial per sum.  Behind the
 //    hidden channel groups the grid holds ceil(Co / 256) more workgroups per slab that sum go the same way.  Workspace
 //    [slab][11 * Ch + Co] doubles.  No atomics; the slab size depends on the shape alone.
+//    uavsal_ir_sums_dil (a dilated depthwise conv: the SRF-Net head) and uavsal_ir_sums_s2 (stride 2: the multi-prior path and
+//    the backbone) are the SAME kernel, ir_sums_kernel, with another tap policy (csrc/train_sums.h: where the nine taps of e
+//    of an output pixel live): the same slabs, channel groups, double accumulators, wave order and workspace, so
+//    uavsal_ir_finish takes any of the three.  With stride 2 a slab is whole OUTPUT rows; the waves take its output pixels
+//    in turn for S2 and Gd, then the input pixels of the rows 2 oy and 2 oy + 1 for S1.  The stride-1, dilation-1
+//    instantiation carries no dilation: no multiply, no kernel argument.
 //
 // 3. uavsal_ir_finish: a thread per channel sums the slabs in slab order in double and writes the seven small gradients,
 //    each rounded once.
 #include "common.h"
-#include "pix_gemm_tile.h"
+#include "train_sums.h"
 
 namespace {
 
-using pixgemm::ld4;
-constexpr int kGroup = 256;                  // channels of one workgroup of the sums: 64 lanes x 4
+using sums::kGroup; using sums::put;
 constexpr int kNS = UAVSAL_IR_NSUM;          // 11 sums per hidden channel: S2, Gd[9], S1
-constexpr int kSlabPixels = 512, kMaxSlabs = 256;
+constexpr int kSlabPixels = 512;             // pixels of a slab of output rows (stride 1) ...
+constexpr int kSlabInputPixels = 256;        // ... and of the input rows behind a slab of output rows (stride 2)
 
 // ------------------------------------------------------------------------------------------------ ga from gd
 struct BwdK {
@@ -103,23 +109,29 @@ __global__ __launch_bounds__(256) void ir_bwd_kernel(const BwdK p) {
 }
 
 // ------------------------------------------------------------------------------------------------ channel sums
+// The kernel arguments.  SumK is all the stride-1, dilation-1 instantiation gets; the other two append what their taps need.
 struct SumK {
     const float *gd, *d, *e, *ga, *go;
     double* ws;
-    long long rows;             // n_img * H
-    int H, W, Ch, Co, ldgo, slab_rows, slabs, cgroups;
+    long long rows;             // n_img * (output rows of an image)
+    int H, W, Ch, Co, ldgo, slab_rows, slabs, cgroups;          // H, W: of e and ga
 };
+struct SumDilK : SumK { int dil; };
+struct SumS2K : SumK { int Ho, Wo; };                           // of gd, d and go
 
-__global__ __launch_bounds__(256) void ir_sums_kernel(const SumK p) {
+template <class Taps, class K>
+__global__ __launch_bounds__(256) void ir_sums_kernel(const K p) {
     __shared__ double red[4 * kGroup];
+    constexpr bool kS2 = Taps::kStride == 2;
     const int slab = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long r0 = (long long)slab * p.slab_rows;
     long long r1 = r0 + p.slab_rows;
     if (r1 > p.rows) r1 = p.rows;
-    const long long q0 = r0 * p.W, q1 = r1 * p.W;              // global pixels of the slab
+    int Wo = p.W;
+    if constexpr (kS2) Wo = p.Wo;
+    const long long q0 = r0 * Wo, q1 = r1 * Wo;                // global OUTPUT pixels of the slab
     double* o = p.ws + (long long)slab * ((long long)kNS * p.Ch + p.Co);      // ws [slab][kNS][Ch], then S3 [Co]
-    const int t = threadIdx.x;
 
     if ((int)blockIdx.y >= p.cgroups) {                        // uniform over the workgroup: S3 of one group of output channels
         const int m0 = ((int)blockIdx.y - p.cgroups) * kGroup;
@@ -131,11 +143,7 @@ __global__ __launch_bounds__(256) void ir_sums_kernel(const SumK p) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) a3[u] += (double)gv[u];
             }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = a3[u];
-        __syncthreads();
-        if (m0 + t < p.Co)
-            o[(long long)kNS * p.Ch + m0 + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
+        sums::wave_meet(red, a3, o + (long long)kNS * p.Ch + m0, p.Co - m0);
         return;
     }
 
@@ -148,64 +156,133 @@ __global__ __launch_bounds__(256) void ir_sums_kernel(const SumK p) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) acc[j][u] = 0.0;
 
-    if (live)
-        for (long long q = q0 + wave; q < q1; q += 4) {
-            const long long row = q / p.W;
-            const int x = (int)(q - row * p.W);
-            const int yy = (int)(row % p.H);                   // the row inside ITS frame: no frame sees its neighbour
+    if (live) {
+        for (long long q = q0 + wave; q < q1; q += 4) {        // S2 and Gd (stride 1: and S1): the slab's output pixels
+            const Taps taps(p, q, c);
             const f32x4 dv = ld4(p.d + q * p.Ch + c);
             const f32x4 gv = ld4(p.gd + q * p.Ch + c);
-            const f32x4 av = ld4(p.ga + q * p.Ch + c);
-            f32x4 d2;
+            if constexpr (!kS2) {
+                const f32x4 av = ld4(p.ga + q * p.Ch + c);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) d2[u] = (dv[u] > 0.f && dv[u] < 6.f) ? gv[u] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc[0][u] += (double)d2[u];
-                acc[10][u] += (double)av[u];
+                for (int u = 0; u < 4; ++u) acc[10][u] += (double)av[u];
             }
+            sums::pixel_sums(taps, dv, gv, acc);
+        }
+        if constexpr (kS2) {
+            // S1: the input rows 2 oy and 2 oy + 1 of every output row of the slab (each input row belongs to one output row)
+            const long long j0 = r0 * 2 * p.W, j1 = r1 * 2 * p.W;
+            for (long long j = j0 + wave; j < j1; j += 4) {
+                const long long vr = j / p.W;                  // 2 * (output row) + (0 | 1)
+                const int x = (int)(j - vr * p.W);
+                const long long row = vr >> 1;
+                const long long n = row / p.Ho;
+                const int y = 2 * (int)(row - n * p.Ho) + (int)(vr & 1);
+                if (y >= p.H) continue;                        // an odd H: the last output row has one input row
+                const f32x4 av = ld4(p.ga + ((n * p.H + y) * p.W + x) * p.Ch + c);
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int iy = yy + ky - 1;
-                if (iy < 0 || iy >= p.H) continue;
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int ix = x + kx - 1;
-                    if (ix < 0 || ix >= p.W) continue;
-                    const f32x4 ev = ld4(p.e + (q + (long long)(ky - 1) * p.W + (kx - 1)) * p.Ch + c);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) acc[1 + ky * 3 + kx][u] += (double)d2[u] * (double)ev[u];
-                }
+                for (int u = 0; u < 4; ++u) acc[10][u] += (double)av[u];
             }
         }
-    // the four waves meet in wave order
-#pragma unroll
-    for (int j = 0; j < kNS; ++j) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = acc[j][u];
-        __syncthreads();
-        if (cg * kGroup + t < p.Ch)
-            o[(long long)j * p.Ch + cg * kGroup + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
-        __syncthreads();
     }
+#pragma unroll
+    for (int j = 0; j < kNS; ++j) sums::wave_meet(red, acc[j], o + (long long)j * p.Ch + cg * kGroup, p.Ch - cg * kGroup);
 }
 
 // the hidden widths taken: multiples of 64, or with the descriptor's ch16 of 16 (the kernel itself needs Ch % 4 == 0 only)
 inline int ch_step(int ch16) { return ch16 ? 16 : 64; }
 
-bool sums_plan(const uavsal_ir_sums_desc* d, SumK& k) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || (d->Ch % ch_step(d->ch16)) || (d->Co % 4)) return false;
-    k.cgroups = (d->Ch + kGroup - 1) / kGroup;
-    if ((long long)d->H * d->W > 0x7fffffffll || k.cgroups + (d->Co + kGroup - 1) / kGroup > 65535) return false;
-    k.H = d->H; k.W = d->W; k.Ch = d->Ch; k.Co = d->Co;
-    k.rows = (long long)d->n_img * d->H;
-    long long sr = (kSlabPixels + d->W - 1) / d->W;            // rows of about kSlabPixels pixels ...
-    const long long cap = (k.rows + kMaxSlabs - 1) / kMaxSlabs; // ... but at most kMaxSlabs slabs
-    if (sr < cap) sr = cap;
-    if (sr > 0x7fffffffll) return false;
-    k.slab_rows = (int)sr;
-    k.slabs = (int)((k.rows + sr - 1) / sr);
-    return true;
+// What the three entry points (uavsal_ir_sums, _s2, _dil) hand the one launcher: their descriptor's common fields, and
+// which taps.  ok: the descriptor was not null.
+enum SumsKind { kUnit, kStride2, kDilated };
+struct SumsCall {
+    bool ok;
+    SumsKind kind;
+    const float *gd, *d, *e, *ga, *go;
+    double* ws;
+    int64_t ws_bytes;
+    int n_img, H, W, Ch, Co, ldgo, ch_mod, dil;
+};
+
+template <class Desc>
+SumsCall sums_call(const Desc* d, SumsKind kind) {
+    SumsCall c = {};
+    if (!d) return c;
+    c.ok = true; c.kind = kind;
+    c.gd = d->gd; c.d = d->d; c.e = d->e; c.ga = d->ga; c.go = d->go; c.ldgo = d->ldgo; c.ws = d->ws; c.ws_bytes = d->ws_bytes;
+    c.n_img = d->n_img; c.H = d->H; c.W = d->W; c.Ch = d->Ch; c.Co = d->Co; c.ch_mod = 64; c.dil = 1;
+    return c;
+}
+SumsCall sums_call(const uavsal_ir_sums_desc* d) {
+    SumsCall c = sums_call(d, kUnit);
+    if (d) c.ch_mod = ch_step(d->ch16);
+    return c;
+}
+SumsCall sums_call(const uavsal_ir_sums_s2_desc* d) {
+    SumsCall c = sums_call(d, kStride2);
+    if (d) c.ch_mod = ch_step(d->ch16);     // the opt-in of uavsal_ir_sums_desc
+    return c;
+}
+SumsCall sums_call(const uavsal_ir_sums_dil_desc* d) {          // no ch16: Ch % 64
+    SumsCall c = sums_call(d, kDilated);
+    if (d) c.dil = d->dil;
+    return c;
+}
+
+// The slab plan, a function of the shape alone (the dilation is not part of it).  Stride 1: rows of about kSlabPixels pixels.
+// Stride 2: OUTPUT rows whose two input rows hold about kSlabInputPixels, and at most 0x3fffffff of them.
+bool sums_plan(const SumsCall& c, SumS2K& k) {
+    if (!c.ok || c.n_img <= 0 || c.H <= 0 || c.W <= 0 || c.Ch <= 0 || c.Co <= 0 || (c.Ch % c.ch_mod) || (c.Co % 4)) return false;
+    k.cgroups = (c.Ch + kGroup - 1) / kGroup;
+    if ((long long)c.H * c.W > 0x7fffffffll || k.cgroups + (c.Co + kGroup - 1) / kGroup > 65535) return false;
+    const bool s2 = c.kind == kStride2;
+    k.H = c.H; k.W = c.W; k.Ch = c.Ch; k.Co = c.Co;
+    k.Ho = s2 ? (c.H - 1) / 2 + 1 : c.H; k.Wo = s2 ? (c.W - 1) / 2 + 1 : c.W;
+    k.rows = (long long)c.n_img * k.Ho;
+    return s2 ? sums::slab_rule(k.rows, 2ll * c.W, kSlabInputPixels, k.slab_rows, k.slabs, 0x3fffffffll)
+              : sums::slab_rule(k.rows, c.W, kSlabPixels, k.slab_rows, k.slabs);
+}
+
+int sums_slabs(const SumsCall& c) {
+    SumS2K k;
+    return sums_plan(c, k) ? k.slabs : 0;
+}
+
+int sums_slab_rows(const SumsCall& c) {
+    SumS2K k;
+    return sums_plan(c, k) ? k.slab_rows : 0;
+}
+
+int64_t sums_workspace_bytes(const SumsCall& c) {
+    SumS2K k;
+    if (!sums_plan(c, k)) return 0;
+    return (int64_t)k.slabs * ((int64_t)kNS * k.Ch + k.Co) * (int64_t)sizeof(double);
+}
+
+int sums_launch(const SumsCall& c, uavsal_stream_t stream) {
+    if (!c.ok || !c.gd || !c.d || !c.e || !c.ga || !c.go || !c.ws) return UAVSAL_EINVAL;
+    if (c.n_img <= 0 || c.H <= 0 || c.W <= 0 || c.Ch <= 0 || c.Co <= 0 || c.dil < 1) return UAVSAL_EINVAL;
+    if (c.Ch % c.ch_mod) return UAVSAL_ESHAPE;
+    if ((c.Co & 3) || (c.ldgo & 3)) return UAVSAL_EALIGN;
+    if (c.ldgo < c.Co) return UAVSAL_EINVAL;
+    SumS2K k;
+    if (!sums_plan(c, k)) return UAVSAL_ESHAPE;
+    if (c.kind == kDilated && (long long)c.dil * 2 > 0x7fffffffll / ((long long)c.W + 1)) return UAVSAL_ESHAPE;
+    if (c.ws_bytes < sums_workspace_bytes(c)) return UAVSAL_EINVAL;
+    if (!al16(c.gd) || !al16(c.d) || !al16(c.e) || !al16(c.ga) || !al16(c.go) || !al8(c.ws)) return UAVSAL_EALIGN;
+    k.gd = c.gd; k.d = c.d; k.e = c.e; k.ga = c.ga; k.go = c.go; k.ldgo = c.ldgo; k.ws = c.ws;
+    const dim3 grid((unsigned)k.slabs, (unsigned)(k.cgroups + (k.Co + kGroup - 1) / kGroup));
+    const hipStream_t s = (hipStream_t)stream;
+    if (c.kind == kStride2) {
+        hipLaunchKernelGGL((ir_sums_kernel<sums::Stride2Taps, SumS2K>), grid, dim3(256), 0, s, k);
+    } else if (c.kind == kDilated) {
+        SumDilK kd;
+        static_cast<SumK&>(kd) = k;
+        kd.dil = c.dil;
+        hipLaunchKernelGGL((ir_sums_kernel<sums::Stride1Taps<true>, SumDilK>), grid, dim3(256), 0, s, kd);
+    } else {
+        hipLaunchKernelGGL((ir_sums_kernel<sums::Stride1Taps<false>, SumK>), grid, dim3(256), 0, s, static_cast<const SumK&>(k));
+    }
+    return uavsal_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------ finalise
@@ -215,11 +292,6 @@ struct FinK {
     float *g_gamma1, *g_beta1, *g_wd, *g_gamma2, *g_beta2, *g_gamma3, *g_beta3;
     int Ch, Co, slabs, accumulate;
 };
-
-__device__ __forceinline__ void put(float* o, double v, int accumulate) {
-    if (accumulate) v += (double)*o;
-    *o = (float)v;
-}
 
 __global__ __launch_bounds__(256) void ir_finish_kernel(const FinK k) {
     const long long stride = (long long)kNS * k.Ch + k.Co;
@@ -253,10 +325,6 @@ __global__ __launch_bounds__(256) void ir_finish_kernel(const FinK k) {
     }
 }
 
-bool al16(const void* p) { return uavsal_aligned16(p); }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 
 extern "C" int uavsal_block_sizeof_desc(int which) {
@@ -281,37 +349,21 @@ extern "C" int uavsal_ir_bwd(const uavsal_ir_bwd_desc* d, uavsal_stream_t stream
     return uavsal_launch_status();
 }
 
-extern "C" int uavsal_ir_sums_slabs(const uavsal_ir_sums_desc* d) {
-    SumK k;
-    return sums_plan(d, k) ? k.slabs : 0;
-}
+// The three channel-sums launches and their queries: one kernel, one launcher (sums_launch above), three tap policies.
+extern "C" int uavsal_ir_sums_slabs(const uavsal_ir_sums_desc* d) { return sums_slabs(sums_call(d)); }
+extern "C" int uavsal_ir_sums_slab_rows(const uavsal_ir_sums_desc* d) { return sums_slab_rows(sums_call(d)); }
+extern "C" int64_t uavsal_ir_sums_workspace_bytes(const uavsal_ir_sums_desc* d) { return sums_workspace_bytes(sums_call(d)); }
+extern "C" int uavsal_ir_sums(const uavsal_ir_sums_desc* d, uavsal_stream_t stream) { return sums_launch(sums_call(d), stream); }
 
-extern "C" int uavsal_ir_sums_slab_rows(const uavsal_ir_sums_desc* d) {
-    SumK k;
-    return sums_plan(d, k) ? k.slab_rows : 0;
-}
+extern "C" int uavsal_ir_sums_s2_slabs(const uavsal_ir_sums_s2_desc* d) { return sums_slabs(sums_call(d)); }
+extern "C" int uavsal_ir_sums_s2_slab_rows(const uavsal_ir_sums_s2_desc* d) { return sums_slab_rows(sums_call(d)); }
+extern "C" int64_t uavsal_ir_sums_s2_workspace_bytes(const uavsal_ir_sums_s2_desc* d) { return sums_workspace_bytes(sums_call(d)); }
+extern "C" int uavsal_ir_sums_s2(const uavsal_ir_sums_s2_desc* d, uavsal_stream_t stream) { return sums_launch(sums_call(d), stream); }
 
-extern "C" int64_t uavsal_ir_sums_workspace_bytes(const uavsal_ir_sums_desc* d) {
-    SumK k;
-    if (!sums_plan(d, k)) return 0;
-    return (int64_t)k.slabs * ((int64_t)kNS * k.Ch + k.Co) * (int64_t)sizeof(double);
-}
-
-extern "C" int uavsal_ir_sums(const uavsal_ir_sums_desc* d, uavsal_stream_t stream) {
-    if (!d || !d->gd || !d->d || !d->e || !d->ga || !d->go || !d->ws) return UAVSAL_EINVAL;
-    if (d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0) return UAVSAL_EINVAL;
-    if (d->Ch % ch_step(d->ch16)) return UAVSAL_ESHAPE;
-    if ((d->Co & 3) || (d->ldgo & 3)) return UAVSAL_EALIGN;
-    if (d->ldgo < d->Co) return UAVSAL_EINVAL;
-    SumK k;
-    if (!sums_plan(d, k)) return UAVSAL_ESHAPE;
-    if (d->ws_bytes < uavsal_ir_sums_workspace_bytes(d)) return UAVSAL_EINVAL;
-    if (!al16(d->gd) || !al16(d->d) || !al16(d->e) || !al16(d->ga) || !al16(d->go) || !al8(d->ws)) return UAVSAL_EALIGN;
-    k.gd = d->gd; k.d = d->d; k.e = d->e; k.ga = d->ga; k.go = d->go; k.ldgo = d->ldgo; k.ws = d->ws;
-    hipLaunchKernelGGL(ir_sums_kernel, dim3((unsigned)k.slabs, (unsigned)(k.cgroups + (k.Co + kGroup - 1) / kGroup)), dim3(256), 0,
-                       (hipStream_t)stream, k);
-    return uavsal_launch_status();
-}
+extern "C" int uavsal_ir_sums_dil_slabs(const uavsal_ir_sums_dil_desc* d) { return sums_slabs(sums_call(d)); }
+extern "C" int uavsal_ir_sums_dil_slab_rows(const uavsal_ir_sums_dil_desc* d) { return sums_slab_rows(sums_call(d)); }
+extern "C" int64_t uavsal_ir_sums_dil_workspace_bytes(const uavsal_ir_sums_dil_desc* d) { return sums_workspace_bytes(sums_call(d)); }
+extern "C" int uavsal_ir_sums_dil(const uavsal_ir_sums_dil_desc* d, uavsal_stream_t stream) { return sums_launch(sums_call(d), stream); }
 
 static int ir_finish(const uavsal_ir_finish_desc* d, uavsal_stream_t stream, int ch16) {
     if (!d || !d->ws || !d->rowdot1 || !d->rowdot3 || !d->wd || !d->s2 || !d->r1 || !d->mu1 || !d->r2 || !d->mu2 || !d->r3 ||

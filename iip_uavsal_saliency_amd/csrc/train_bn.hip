@@ -6,7 +6,7 @@
 // loads; C == 1: one channel, vec = 1), `lc` lanes -- the smallest power of two >= C / vec, at most 64 -- stand side by side on
 // one pixel (a wave reads 1 KB of a 256-channel row), and the 256 / lc pixel lanes of a workgroup take the pixels of the
 // workgroup's slab in turn.  A workgroup owns one group of lc * vec channels and one slab of whole picture rows, counted
-// through all frames (the rule of uavsal_dec_sums: about 512 pixels, at most 256 slabs: a function of the shape alone).  A
+// through all frames (sums::slab_rule of csrc/train_sums.h: about 512 pixels, at most 256 slabs: a function of the shape alone).  A
 // thread adds its products in double; the pixel lanes of a channel meet in LDS and are added in pixel-lane order; one partial
 // per sum, slab and channel goes to the workspace [slab][sum][C].  A finish launch, a thread per channel, adds the slabs in
 // slab order and rounds once.  No atomics: two calls return the same bits.
@@ -20,10 +20,12 @@
 // 4. uavsal_bn_bwd_apply: g_u = s (g_a - d beta / P - xh d gamma / P), element-wise.
 // 5. uavsal_dw_wgrad: the nine sums per channel of a depthwise 3x3's weight gradient (two launches).
 #include "common.h"
+#include "train_sums.h"
 
 namespace {
 
-constexpr int kSlabPixels = 512, kMaxSlabs = 256;
+using sums::put;
+constexpr int kSlabPixels = 512;             // pixels of a slab
 constexpr int kThreads = 256;
 
 template <int V> struct Vec { float v[V]; };
@@ -83,13 +85,7 @@ bool geo_plan(int n_img, int H, int W, int C, Geo& g) {
     g.lc = lc; g.pl = kThreads / lc; g.cgc = lc * g.vec;
     g.cgs = (C + g.cgc - 1) / g.cgc;
     if (g.cgs > 65535) return false;
-    long long sr = (kSlabPixels + W - 1) / W;                  // rows of about kSlabPixels pixels ...
-    const long long cap = (g.rows + kMaxSlabs - 1) / kMaxSlabs; // ... but at most kMaxSlabs slabs
-    if (sr < cap) sr = cap;
-    if (sr > 0x7fffffffll) return false;
-    g.slab_rows = (int)sr;
-    g.slabs = (int)((g.rows + sr - 1) / sr);
-    return true;
+    return sums::slab_rule(g.rows, W, kSlabPixels, g.slab_rows, g.slabs);
 }
 
 // The pixel lanes of a channel meet in pixel-lane order: red holds kThreads * 4 doubles; `o` points at this slab's and this
@@ -269,11 +265,6 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_sums_kernel(const BwdK k) {
     if (k.ns == 3) slab_reduce<V>(red, a2, active, g, cg, o + 2 * g.C);      // uniform over the launch
 }
 
-__device__ __forceinline__ void put(float* o, double v, int accumulate) {
-    if (accumulate) v += (double)*o;
-    *o = (float)v;
-}
-
 __global__ __launch_bounds__(kThreads) void bn_bwd_finish_kernel(const BwdK k) {
     const int C = k.g.C;
     const int c = blockIdx.x * kThreads + threadIdx.x;
@@ -387,9 +378,6 @@ __global__ __launch_bounds__(kThreads) void dw_wgrad_finish_kernel(const DwK k) 
     for (int j = 0; j < 9; ++j) put(k.out + (long long)c * 9 + j, s[j], k.accumulate);
 }
 
-bool al16(const void* p) { return uavsal_aligned16(p); }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 // a tensor read `vec` floats at a time: the pointer and the pitch
 bool alv(const void* p, int ld, int vec) { return vec == 1 ? al4(p) : (al16(p) && !(ld & 3)); }
 bool blocks_ok(long long total, unsigned& blocks) {

@@ -17,18 +17,12 @@
 //
 // And, for the path when it is TRAINED (train.prior_path_backward):
 //
-// 4. uavsal_ir_sums_s2: uavsal_ir_sums (csrc/train_block.hip) for a depthwise 3x3 with stride 2, into the same workspace
-//    [slab][11 * Ch + Co], so that uavsal_ir_finish serves both.  The layout of ir_sums_kernel: a workgroup owns a channel
-//    group of 256 (the lanes behind Ch idle) and a slab of whole OUTPUT rows counted through all images; its four waves take
-//    the slab's output pixels in turn for S2 and Gd (e at (2 oy - 1 + ky, 2 ox - 1 + kx) of the output row's own image, every
-//    tap guarded), then the input pixels of the rows 2 oy and 2 oy + 1 -- each input row belongs to one output row -- for S1.
-//    Behind the hidden channel groups ceil(Co / 256) workgroups per slab sum go over the output pixels.  Double
-//    accumulators, the waves meet in LDS in wave order, no atomics; the slab size depends on the shape alone.
+// 4. uavsal_ir_sums_s2 lives in csrc/train_block.hip: ir_sums_kernel with the stride-2 tap policy of csrc/train_sums.h,
+//    into the same workspace [slab][11 * Ch + Co], so that uavsal_ir_finish serves both; only its descriptor's size is
+//    answered here (uavsal_mp_sizeof_desc).
 #include "common.h"
 
 namespace {
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // ------------------------------------------------------------------------------------------------ ga from gd, stride 2
 struct S2K {
@@ -176,125 +170,6 @@ __global__ __launch_bounds__(256) void tsum_bwd_kernel(const TbK p) {
     *reinterpret_cast<f32x4*>(p.out + ((size_t)n * p.HW + pix) * p.ldo + c) = av + gv;
 }
 
-// ------------------------------------------------------------------------------------------------ channel sums, stride 2
-constexpr int kGroup = 256;                  // channels of one workgroup of the sums: 64 lanes x 4
-constexpr int kNS = UAVSAL_IR_NSUM;          // 11 sums per hidden channel: S2, Gd[9], S1 (the workspace of uavsal_ir_sums)
-constexpr int kSlabInputPixels = 256, kMaxSlabs = 256;
-
-struct Sum2K {
-    const float *gd, *d, *e, *ga, *go;
-    double* ws;
-    long long rows;             // n_img * Ho: output rows counted through all images
-    int H, W, Ho, Wo, Ch, Co, ldgo, slab_rows, slabs, cgroups;
-};
-
-__global__ __launch_bounds__(256) void ir_sums_s2_kernel(const Sum2K p) {
-    __shared__ double red[4 * kGroup];
-    const int slab = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long r0 = (long long)slab * p.slab_rows;
-    long long r1 = r0 + p.slab_rows;
-    if (r1 > p.rows) r1 = p.rows;
-    const long long q0 = r0 * p.Wo, q1 = r1 * p.Wo;            // global OUTPUT pixels of the slab
-    double* o = p.ws + (long long)slab * ((long long)kNS * p.Ch + p.Co);      // ws [slab][kNS][Ch], then S3 [Co]
-    const int t = threadIdx.x;
-
-    if ((int)blockIdx.y >= p.cgroups) {                        // uniform over the workgroup: S3 of one group of output channels
-        const int m0 = ((int)blockIdx.y - p.cgroups) * kGroup;
-        const int m = m0 + lane * 4;
-        double a3[4] = {0.0, 0.0, 0.0, 0.0};
-        if (m < p.Co)
-            for (long long q = q0 + wave; q < q1; q += 4) {
-                const f32x4 gv = ld4(p.go + q * p.ldgo + m);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a3[u] += (double)gv[u];
-            }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = a3[u];
-        __syncthreads();
-        if (m0 + t < p.Co)
-            o[(long long)kNS * p.Ch + m0 + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
-        return;
-    }
-
-    const int cg = blockIdx.y;
-    const int c = cg * kGroup + lane * 4;
-    const bool live = c < p.Ch;                                // Ch % 4 == 0: a lane's four channels are all inside or all outside
-    double acc[kNS][4];
-#pragma unroll
-    for (int j = 0; j < kNS; ++j)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[j][u] = 0.0;
-
-    if (live) {
-        for (long long q = q0 + wave; q < q1; q += 4) {        // S2 and Gd: the slab's output pixels
-            const long long row = q / p.Wo;
-            const int ox = (int)(q - row * p.Wo);
-            const long long n = row / p.Ho;
-            const int oy = (int)(row - n * p.Ho);
-            const f32x4 dv = ld4(p.d + q * p.Ch + c);
-            const f32x4 gv = ld4(p.gd + q * p.Ch + c);
-            f32x4 d2;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) d2[u] = (dv[u] > 0.f && dv[u] < 6.f) ? gv[u] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[0][u] += (double)d2[u];
-            const float* eimg = p.e + n * p.H * p.W * p.Ch + c;          // the input image of THIS output row
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int iy = 2 * oy - 1 + ky;                // -1 at the top, H below an odd H's last output row
-                if (iy < 0 || iy >= p.H) continue;
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int ix = 2 * ox - 1 + kx;
-                    if (ix < 0 || ix >= p.W) continue;
-                    const f32x4 ev = ld4(eimg + ((long long)iy * p.W + ix) * p.Ch);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) acc[1 + ky * 3 + kx][u] += (double)d2[u] * (double)ev[u];
-                }
-            }
-        }
-        // S1: the input rows 2 oy and 2 oy + 1 of every output row of the slab (each input row belongs to one output row)
-        const long long j0 = r0 * 2 * p.W, j1 = r1 * 2 * p.W;
-        for (long long j = j0 + wave; j < j1; j += 4) {
-            const long long vr = j / p.W;                      // 2 * (output row) + (0 | 1)
-            const int x = (int)(j - vr * p.W);
-            const long long row = vr >> 1;
-            const long long n = row / p.Ho;
-            const int y = 2 * (int)(row - n * p.Ho) + (int)(vr & 1);
-            if (y >= p.H) continue;                            // an odd H: the last output row has one input row
-            const f32x4 av = ld4(p.ga + ((n * p.H + y) * p.W + x) * p.Ch + c);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[10][u] += (double)av[u];
-        }
-    }
-    // the four waves meet in wave order
-#pragma unroll
-    for (int j = 0; j < kNS; ++j) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = acc[j][u];
-        __syncthreads();
-        if (cg * kGroup + t < p.Ch)
-            o[(long long)j * p.Ch + cg * kGroup + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
-        __syncthreads();
-    }
-}
-
-bool sums2_plan(const uavsal_ir_sums_s2_desc* d, Sum2K& k) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || (d->Ch % (d->ch16 ? 16 : 64)) || (d->Co % 4)) return false;
-    k.cgroups = (d->Ch + kGroup - 1) / kGroup;
-    if ((long long)d->H * d->W > 0x7fffffffll || k.cgroups + (d->Co + kGroup - 1) / kGroup > 65535) return false;
-    k.H = d->H; k.W = d->W; k.Ho = (d->H - 1) / 2 + 1; k.Wo = (d->W - 1) / 2 + 1; k.Ch = d->Ch; k.Co = d->Co;
-    k.rows = (long long)d->n_img * k.Ho;
-    long long sr = (kSlabInputPixels + 2ll * d->W - 1) / (2ll * d->W);   // output rows whose input rows hold about kSlabInputPixels ...
-    const long long cap = (k.rows + kMaxSlabs - 1) / kMaxSlabs;          // ... but at most kMaxSlabs slabs
-    if (sr < cap) sr = cap;
-    if (sr > 0x3fffffffll) return false;
-    k.slab_rows = (int)sr;
-    k.slabs = (int)((k.rows + sr - 1) / sr);
-    return true;
-}
-
 inline int grid_for(long long total, unsigned* nblk) {
     const long long b = (total + 255) / 256;
     if (b <= 0 || b > 0x7fffffffLL) return UAVSAL_ESHAPE;
@@ -328,40 +203,6 @@ extern "C" int uavsal_ir_bwd_s2(const uavsal_ir_bwd_s2_desc* d, uavsal_stream_t 
 }
 
 extern "C" int uavsal_mp_sizeof_desc(int which) { return which == 0 ? (int)sizeof(uavsal_ir_sums_s2_desc) : -1; }
-
-extern "C" int uavsal_ir_sums_s2_slabs(const uavsal_ir_sums_s2_desc* d) {
-    Sum2K k;
-    return sums2_plan(d, k) ? k.slabs : 0;
-}
-
-extern "C" int uavsal_ir_sums_s2_slab_rows(const uavsal_ir_sums_s2_desc* d) {
-    Sum2K k;
-    return sums2_plan(d, k) ? k.slab_rows : 0;
-}
-
-extern "C" int64_t uavsal_ir_sums_s2_workspace_bytes(const uavsal_ir_sums_s2_desc* d) {
-    Sum2K k;
-    if (!sums2_plan(d, k)) return 0;
-    return (int64_t)k.slabs * ((int64_t)kNS * k.Ch + k.Co) * (int64_t)sizeof(double);
-}
-
-extern "C" int uavsal_ir_sums_s2(const uavsal_ir_sums_s2_desc* d, uavsal_stream_t stream) {
-    if (!d || !d->gd || !d->d || !d->e || !d->ga || !d->go || !d->ws) return UAVSAL_EINVAL;
-    if (d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0) return UAVSAL_EINVAL;
-    if (d->Ch % (d->ch16 ? 16 : 64)) return UAVSAL_ESHAPE;     // ch16: the opt-in of uavsal_ir_sums_desc (the kernel needs Ch % 4 == 0 only)
-    if ((d->Co & 3) || (d->ldgo & 3)) return UAVSAL_EALIGN;
-    if (d->ldgo < d->Co) return UAVSAL_EINVAL;
-    Sum2K k;
-    if (!sums2_plan(d, k)) return UAVSAL_ESHAPE;
-    if (d->ws_bytes < uavsal_ir_sums_s2_workspace_bytes(d)) return UAVSAL_EINVAL;
-    if (!uavsal_aligned16(d->gd) || !uavsal_aligned16(d->d) || !uavsal_aligned16(d->e) || !uavsal_aligned16(d->ga) ||
-        !uavsal_aligned16(d->go) || (reinterpret_cast<uintptr_t>(d->ws) & 7u))
-        return UAVSAL_EALIGN;
-    k.gd = d->gd; k.d = d->d; k.e = d->e; k.ga = d->ga; k.go = d->go; k.ldgo = d->ldgo; k.ws = d->ws;
-    hipLaunchKernelGGL(ir_sums_s2_kernel, dim3((unsigned)k.slabs, (unsigned)(k.cgroups + (k.Co + kGroup - 1) / kGroup)), dim3(256),
-                       0, (hipStream_t)stream, k);
-    return uavsal_launch_status();
-}
 
 extern "C" int uavsal_bilinear_ac_bwd(const uavsal_bilinear_bwd_desc* d, uavsal_stream_t stream) {
     if (!d || !d->gout || !d->gin) return UAVSAL_EINVAL;

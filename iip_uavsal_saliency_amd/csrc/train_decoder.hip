@@ -27,13 +27,14 @@
 //    sums G3 of ALL channels itself (sum_c w3[c] G3[c]: per thread its channels in order, then the fixed tree).
 #include "common.h"
 #include "pix_gemm_tile.h"
+#include "train_sums.h"
 
 namespace {
 
-using pixgemm::kTile; using pixgemm::kStep; using pixgemm::kRow; using pixgemm::ld4;
-constexpr int kGroup = 256;                  // channels of one workgroup of the sums: 64 lanes x 4
+using pixgemm::kTile; using pixgemm::kStep; using pixgemm::kRow;
+using sums::kGroup; using sums::put;
 constexpr int kNS = UAVSAL_DEC_NSUM;         // 12 sums per channel: G3, S2, Gd[9], S1
-constexpr int kSlabPixels = 512, kMaxSlabs = 256;
+constexpr int kSlabPixels = 512;             // pixels of a slab
 
 // ------------------------------------------------------------------------------------------------ pixel GEMM
 struct PgK {
@@ -292,14 +293,7 @@ __global__ __launch_bounds__(256) void dec_sums_kernel(const SumK p) {
     // the four waves meet in wave order; ws [slab][kNS][C] doubles, then S3 of the slab behind the kNS * C
     double* o = p.ws + (long long)slab * ((long long)kNS * p.C + 1);
 #pragma unroll
-    for (int j = 0; j < kNS; ++j) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = acc[j][u];
-        __syncthreads();
-        const int t = threadIdx.x;
-        o[(long long)j * p.C + cg * kGroup + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
-        __syncthreads();
-    }
+    for (int j = 0; j < kNS; ++j) sums::wave_meet(red, acc[j], o + (long long)j * p.C + cg * kGroup, kGroup);     // C % kGroup == 0
     if (cg == 0) {
         if (lane == 0) red[wave] = a3;
         __syncthreads();
@@ -312,13 +306,7 @@ bool sums_plan(const uavsal_dec_sums_desc* d, SumK& k) {
     if ((long long)d->H * d->W > 0x7fffffffll || d->C / kGroup > 65535) return false;
     k.H = d->H; k.W = d->W; k.C = d->C;
     k.rows = (long long)d->n_img * d->H;
-    long long sr = (kSlabPixels + d->W - 1) / d->W;            // rows of about kSlabPixels pixels ...
-    const long long cap = (k.rows + kMaxSlabs - 1) / kMaxSlabs; // ... but at most kMaxSlabs slabs
-    if (sr < cap) sr = cap;
-    if (sr > 0x7fffffffll) return false;
-    k.slab_rows = (int)sr;
-    k.slabs = (int)((k.rows + sr - 1) / sr);
-    return true;
+    return sums::slab_rule(k.rows, d->W, kSlabPixels, k.slab_rows, k.slabs);
 }
 
 // ------------------------------------------------------------------------------------------------ finalise
@@ -328,11 +316,6 @@ struct FinK {
     float *g_gamma1, *g_beta1, *g_wd, *g_gamma2, *g_beta2, *g_w3, *g_gamma3, *g_beta3;
     int C, slabs, accumulate;
 };
-
-__device__ __forceinline__ void put(float* o, double v, int accumulate) {
-    if (accumulate) v += (double)*o;
-    *o = (float)v;
-}
 
 __global__ __launch_bounds__(256) void dec_finish_kernel(const FinK k) {
     __shared__ double red[256];
@@ -376,10 +359,6 @@ __global__ __launch_bounds__(256) void dec_finish_kernel(const FinK k) {
         put(k.g_gamma3, (double)k.r3[0] * (red[0] - (double)k.mu3[0] * S3), k.accumulate);
     }
 }
-
-bool al16(const void* p) { return uavsal_aligned16(p); }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 }  // namespace
 

@@ -19,7 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // s = sigmoid(z), sp = s (1 - s)
@@ -119,7 +118,6 @@ __global__ __launch_bounds__(256) void lstm_gate_bwd_kernel(const GateK k) {
     st4(k.co + o, co);
 }
 
-bool al16(const void* p) { return uavsal_aligned16(p); }
 
 }  // namespace
 

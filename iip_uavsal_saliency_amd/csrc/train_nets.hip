@@ -3,14 +3,14 @@
 // carries the output gradient of a net that ran on ONE frame.  include/uavsal_hip.h states the formulas.
 //
 // 1. uavsal_ir_narrow_grads: everything the nine gradients need, in ONE launch.  A workgroup owns a slab of whole picture
-//    rows counted through all images (the rule of sums_plan in csrc/train_block.hip with about 256 pixels: at most 256 slabs, a
+//    rows counted through all images (sums::slab_rule of csrc/train_sums.h with about 256 pixels: at most 256 slabs, a
 //    function of the shape alone) and writes one partial per output into `ws` [slab][...] doubles.  The outputs of one block
 //    are at most 64 x 120 + 120 x 20 + 11 x 120 + 64 numbers and the maps are the 45 x 80 prior maps: the stage is bound by
 //    its launches, so the products run as VALU FMAs out of LDS, not on the matrix cores -- a 16-row MFMA tile would be a
 //    third padding at Ch = 48 and the operands would need a transposing stage for five pixels' worth of arithmetic.
 //    a. the eleven sums per hidden channel (S2, Gd[9], S1) and S3: a lane owns four channels and every 256 / (Ch / 4)-th
 //       (S3: 16th) pixel of the slab, forms delta2 in fp32 as uavsal_ir_bwd does and adds every product to a double accumulator, exactly the
-//       per-pixel arithmetic of ir_sums_kernel; the pixel lanes meet in LDS in lane order.
+//       per-pixel arithmetic of ir_sums_kernel (sums::pixel_sums); the pixel lanes meet in LDS in lane order.
 //    b. G1 = ga x x and G3 = go x d: the slab goes through LDS in chunks of UAVSAL_NARROW_CHUNK pixels; a lane owns a 4 x 4
 //       tile of G1 and two 4 x 4 tiles of G3, accumulates a chunk in fp32 (fmaf, pixel order) and carries it to double
 //       accumulators between chunks (the convention of pix_gemm_tile.h).  144 accumulator registers, no scratch.
@@ -20,15 +20,15 @@
 // 3. uavsal_frame_sum: out[p][c] = sum_n a[n][p][c], frames in frame order in double, rounded once.
 // No atomics anywhere: two calls return the same bits.
 #include "common.h"
-#include "pix_gemm_tile.h"
+#include "train_sums.h"
 
 namespace {
 
-using pixgemm::ld4;
+using sums::put;
 constexpr int kNS = UAVSAL_IR_NSUM;                    // 11 sums per hidden channel: S2, Gd[9], S1
 constexpr int kP = UAVSAL_NARROW_CHUNK;                // pixels of one fp32 chunk
 constexpr int kCo = 64, kMaxCh = 128, kMaxCin = 32;
-constexpr int kSlabPixels = 256, kMaxSlabs = 256;
+constexpr int kSlabPixels = 256;                       // pixels of a slab (1. above)
 
 struct NarK {
     const float *x, *e, *d, *gd, *ga, *go;
@@ -62,33 +62,13 @@ __global__ __launch_bounds__(256) void ir_narrow_kernel(const NarK p) {
             for (int u = 0; u < 4; ++u) acc[j][u] = 0.0;
         if (pl < lanes)
             for (long long q = q0 + pl; q < q1; q += lanes) {
-                const long long row = q / p.W;
-                const int x = (int)(q - row * p.W);
-                const int yy = (int)(row % p.H);               // the row inside ITS image: no image sees its neighbour
+                const sums::Stride1Taps<false> taps(p, q, c);
                 const f32x4 dv = ld4(p.d + q * Ch + c);
                 const f32x4 gv = ld4(p.gd + q * Ch + c);
                 const f32x4 av = ld4(p.ga + q * Ch + c);
-                f32x4 d2;
 #pragma unroll
-                for (int u = 0; u < 4; ++u) d2[u] = (dv[u] > 0.f && dv[u] < 6.f) ? gv[u] : 0.f;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    acc[0][u] += (double)d2[u];
-                    acc[10][u] += (double)av[u];
-                }
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    const int iy = yy + ky - 1;
-                    if (iy < 0 || iy >= p.H) continue;
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const int ix = x + kx - 1;
-                        if (ix < 0 || ix >= p.W) continue;
-                        const f32x4 ev = ld4(p.e + (q + (long long)(ky - 1) * p.W + (kx - 1)) * Ch + c);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) acc[1 + ky * 3 + kx][u] += (double)d2[u] * (double)ev[u];
-                    }
-                }
+                for (int u = 0; u < 4; ++u) acc[10][u] += (double)av[u];
+                sums::pixel_sums(taps, dv, gv, acc);
             }
 #pragma unroll
         for (int j = 0; j < kNS; ++j) {                        // the pixel lanes meet in lane order (lanes * Ch <= 1024 doubles)
@@ -218,13 +198,7 @@ bool narrow_plan(const uavsal_ir_narrow_desc* d, NarK& k) {
     if ((long long)d->H * d->W > 0x7fffffffll) return false;
     k.H = d->H; k.W = d->W; k.Cin = d->Cin; k.Ch = d->Ch;
     k.rows = (long long)d->n_img * d->H;
-    long long sr = (kSlabPixels + d->W - 1) / d->W;            // rows of about kSlabPixels pixels ...
-    const long long cap = (k.rows + kMaxSlabs - 1) / kMaxSlabs; // ... but at most kMaxSlabs slabs
-    if (sr < cap) sr = cap;
-    if (sr > 0x7fffffffll) return false;
-    k.slab_rows = (int)sr;
-    k.slabs = (int)((k.rows + sr - 1) / sr);
-    return true;
+    return sums::slab_rule(k.rows, d->W, kSlabPixels, k.slab_rows, k.slabs);
 }
 
 // ------------------------------------------------------------------------------------------------ finalise
@@ -234,11 +208,6 @@ struct NarFinK {
     float *g_w1, *g_gamma1, *g_beta1, *g_wd, *g_gamma2, *g_beta2, *g_w3, *g_gamma3, *g_beta3;
     int Cin, Ch, slabs, accumulate;
 };
-
-__device__ __forceinline__ void put(float* o, double v, int accumulate) {
-    if (accumulate) v += (double)*o;
-    *o = (float)v;
-}
 
 __global__ __launch_bounds__(128) void ir_narrow_finish_kernel(const NarFinK k) {
     __shared__ double prod[kMaxCh];
@@ -321,10 +290,6 @@ __global__ __launch_bounds__(256) void frame_sum_kernel(const FsK k) {
     }
     *reinterpret_cast<f32x4*>(k.out + pix * k.ldo + c) = (f32x4){(float)s[0], (float)s[1], (float)s[2], (float)s[3]};
 }
-
-bool al16(const void* p) { return uavsal_aligned16(p); }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 }  // namespace
 

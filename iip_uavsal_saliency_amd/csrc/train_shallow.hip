@@ -162,10 +162,6 @@ void sk_launch(int tiles, dim3 grid, hipStream_t stream, const SkK& k) {
     }
 }
 
-bool al16(const void* p) { return uavsal_aligned16(p); }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 
 extern "C" int uavsal_shallow_sizeof_desc(int which) { return which == 0 ? (int)sizeof(uavsal_skinny_wgrad_desc) : -1; }

@@ -17,17 +17,14 @@
 //    12 x 20 map neighbouring pixels share no tap, so there is no halo to reuse; the launch reads at most 18 + 1 and writes
 //    1 x C x 4 bytes per pixel on a 1/32-scale map.
 //
-// 3. uavsal_ir_sums_dil: ir_sums_kernel (csrc/train_block.hip) with the taps of e at dil (ky-1, kx-1): the same slabs,
-//    channel groups, double accumulators, wave order and workspace layout, so uavsal_ir_finish takes the workspace as is.
+// 3. uavsal_ir_sums_dil lives in csrc/train_block.hip: ir_sums_kernel with the taps of e at dil (ky-1, kx-1) (the dilated
+//    tap policy of csrc/train_sums.h); only its descriptor's size is answered here.
 #include "common.h"
 #include "pix_gemm_tile.h"
 
 namespace {
 
-using pixgemm::kTile; using pixgemm::ld4;
-constexpr int kGroup = 256;                  // channels of one workgroup of the sums: 64 lanes x 4
-constexpr int kNS = UAVSAL_IR_NSUM;          // 11 sums per hidden channel: S2, Gd[9], S1
-constexpr int kSlabPixels = 512, kMaxSlabs = 256;
+using pixgemm::kTile;
 
 // ------------------------------------------------------------------------------------------------ weight gradient
 struct C3K {
@@ -157,114 +154,6 @@ __global__ __launch_bounds__(256) void ir_bwd_dil_kernel(const BwdK p) {
     *reinterpret_cast<f32x4*>(p.ga + q * p.C + c) = v;
 }
 
-// ------------------------------------------------------------------------------------------------ channel sums, dilated
-struct SumK {
-    const float *gd, *d, *e, *ga, *go;
-    double* ws;
-    long long rows;             // n_img * H
-    int H, W, Ch, Co, ldgo, slab_rows, slabs, cgroups, dil;
-};
-
-__global__ __launch_bounds__(256) void ir_sums_dil_kernel(const SumK p) {
-    __shared__ double red[4 * kGroup];
-    const int slab = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long r0 = (long long)slab * p.slab_rows;
-    long long r1 = r0 + p.slab_rows;
-    if (r1 > p.rows) r1 = p.rows;
-    const long long q0 = r0 * p.W, q1 = r1 * p.W;              // global pixels of the slab
-    double* o = p.ws + (long long)slab * ((long long)kNS * p.Ch + p.Co);      // ws [slab][kNS][Ch], then S3 [Co]
-    const int t = threadIdx.x;
-
-    if ((int)blockIdx.y >= p.cgroups) {                        // uniform over the workgroup: S3 of one group of output channels
-        const int m0 = ((int)blockIdx.y - p.cgroups) * kGroup;
-        const int m = m0 + lane * 4;
-        double a3[4] = {0.0, 0.0, 0.0, 0.0};
-        if (m < p.Co)
-            for (long long q = q0 + wave; q < q1; q += 4) {
-                const f32x4 gv = ld4(p.go + q * p.ldgo + m);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a3[u] += (double)gv[u];
-            }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = a3[u];
-        __syncthreads();
-        if (m0 + t < p.Co)
-            o[(long long)kNS * p.Ch + m0 + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
-        return;
-    }
-
-    const int cg = blockIdx.y;
-    const int c = cg * kGroup + lane * 4;
-    const bool live = c < p.Ch;                                // Ch % 64 == 0: a lane's four channels are all inside or all outside
-    double acc[kNS][4];
-#pragma unroll
-    for (int j = 0; j < kNS; ++j)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[j][u] = 0.0;
-
-    if (live)
-        for (long long q = q0 + wave; q < q1; q += 4) {
-            const long long row = q / p.W;
-            const int x = (int)(q - row * p.W);
-            const int yy = (int)(row % p.H);                   // the row inside ITS frame: no frame sees its neighbour
-            const f32x4 dv = ld4(p.d + q * p.Ch + c);
-            const f32x4 gv = ld4(p.gd + q * p.Ch + c);
-            const f32x4 av = ld4(p.ga + q * p.Ch + c);
-            f32x4 d2;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) d2[u] = (dv[u] > 0.f && dv[u] < 6.f) ? gv[u] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc[0][u] += (double)d2[u];
-                acc[10][u] += (double)av[u];
-            }
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int iy = yy + (ky - 1) * p.dil;
-                if (iy < 0 || iy >= p.H) continue;
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int ix = x + (kx - 1) * p.dil;
-                    if (ix < 0 || ix >= p.W) continue;
-                    const f32x4 ev = ld4(p.e + (q + (long long)(ky - 1) * p.dil * p.W + (kx - 1) * p.dil) * p.Ch + c);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) acc[1 + ky * 3 + kx][u] += (double)d2[u] * (double)ev[u];
-                }
-            }
-        }
-    // the four waves meet in wave order
-#pragma unroll
-    for (int j = 0; j < kNS; ++j) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) red[wave * kGroup + lane * 4 + u] = acc[j][u];
-        __syncthreads();
-        if (cg * kGroup + t < p.Ch)
-            o[(long long)j * p.Ch + cg * kGroup + t] = ((red[t] + red[kGroup + t]) + red[2 * kGroup + t]) + red[3 * kGroup + t];
-        __syncthreads();
-    }
-}
-
-// the slabs of uavsal_ir_sums (csrc/train_block.hip): the same function of the shape
-bool sums_plan(const uavsal_ir_sums_dil_desc* d, SumK& k) {
-    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || (d->Ch % 64) || (d->Co % 4)) return false;
-    k.cgroups = (d->Ch + kGroup - 1) / kGroup;
-    if ((long long)d->H * d->W > 0x7fffffffll || k.cgroups + (d->Co + kGroup - 1) / kGroup > 65535) return false;
-    k.H = d->H; k.W = d->W; k.Ch = d->Ch; k.Co = d->Co;
-    k.rows = (long long)d->n_img * d->H;
-    long long sr = (kSlabPixels + d->W - 1) / d->W;            // rows of about kSlabPixels pixels ...
-    const long long cap = (k.rows + kMaxSlabs - 1) / kMaxSlabs; // ... but at most kMaxSlabs slabs
-    if (sr < cap) sr = cap;
-    if (sr > 0x7fffffffll) return false;
-    k.slab_rows = (int)sr;
-    k.slabs = (int)((k.rows + sr - 1) / sr);
-    return true;
-}
-
-bool al16(const void* p) { return uavsal_aligned16(p); }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 
 extern "C" int uavsal_srf_sizeof_desc(int which) {
@@ -317,38 +206,5 @@ extern "C" int uavsal_ir_bwd_dil(const uavsal_ir_bwd_dil_desc* d, uavsal_stream_
     const long long blocks = (k.total + 255) / 256;
     if (blocks > 0x7fffffffll) return UAVSAL_ESHAPE;
     hipLaunchKernelGGL(ir_bwd_dil_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, k);
-    return uavsal_launch_status();
-}
-
-extern "C" int uavsal_ir_sums_dil_slabs(const uavsal_ir_sums_dil_desc* d) {
-    SumK k;
-    return sums_plan(d, k) ? k.slabs : 0;
-}
-
-extern "C" int uavsal_ir_sums_dil_slab_rows(const uavsal_ir_sums_dil_desc* d) {
-    SumK k;
-    return sums_plan(d, k) ? k.slab_rows : 0;
-}
-
-extern "C" int64_t uavsal_ir_sums_dil_workspace_bytes(const uavsal_ir_sums_dil_desc* d) {
-    SumK k;
-    if (!sums_plan(d, k)) return 0;
-    return (int64_t)k.slabs * ((int64_t)kNS * k.Ch + k.Co) * (int64_t)sizeof(double);
-}
-
-extern "C" int uavsal_ir_sums_dil(const uavsal_ir_sums_dil_desc* d, uavsal_stream_t stream) {
-    if (!d || !d->gd || !d->d || !d->e || !d->ga || !d->go || !d->ws) return UAVSAL_EINVAL;
-    if (d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->Ch <= 0 || d->Co <= 0 || d->dil < 1) return UAVSAL_EINVAL;
-    if (d->Ch % 64) return UAVSAL_ESHAPE;
-    if ((d->Co & 3) || (d->ldgo & 3)) return UAVSAL_EALIGN;
-    if (d->ldgo < d->Co) return UAVSAL_EINVAL;
-    SumK k;
-    if (!sums_plan(d, k)) return UAVSAL_ESHAPE;
-    if ((long long)d->dil * 2 > 0x7fffffffll / ((long long)d->W + 1)) return UAVSAL_ESHAPE;
-    if (d->ws_bytes < uavsal_ir_sums_dil_workspace_bytes(d)) return UAVSAL_EINVAL;
-    if (!al16(d->gd) || !al16(d->d) || !al16(d->e) || !al16(d->ga) || !al16(d->go) || !al8(d->ws)) return UAVSAL_EALIGN;
-    k.gd = d->gd; k.d = d->d; k.e = d->e; k.ga = d->ga; k.go = d->go; k.ldgo = d->ldgo; k.ws = d->ws; k.dil = d->dil;
-    hipLaunchKernelGGL(ir_sums_dil_kernel, dim3((unsigned)k.slabs, (unsigned)(k.cgroups + (k.Co + kGroup - 1) / kGroup)), dim3(256), 0,
-                       (hipStream_t)stream, k);
     return uavsal_launch_status();
 }

@@ -13,14 +13,14 @@
 //    thread per four channels of a pixel; it gathers the at most six terms of frames j - 1, j, j + 1 of ITS sequence in a
 //    fixed order in double.
 #include "common.h"
+#include "train_sums.h"
 
 namespace {
 
+using sums::put;
 constexpr int kCG = 32;                      // channels of one workgroup of the sums: 8 lanes x 4
 constexpr int kPixLanes = 32;                // pixels of one pass: 256 threads / 8
-constexpr int kSlabPixels = 512, kMaxSlabs = 256;
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+constexpr int kSlabPixels = 512;             // pixels of a slab
 
 // ------------------------------------------------------------------------------------------------ gp and S
 struct SumK {
@@ -68,13 +68,7 @@ bool sums_plan(const uavsal_cbr_sums_desc* d, SumK& k) {
     if ((long long)d->H * d->W > 0x7fffffffll || d->C / kCG > 65535) return false;
     k.W = d->W; k.C = d->C;
     k.rows = (long long)d->n_img * d->H;
-    long long sr = (kSlabPixels + d->W - 1) / d->W;            // rows of about kSlabPixels pixels ...
-    const long long cap = (k.rows + kMaxSlabs - 1) / kMaxSlabs; // ... but at most kMaxSlabs slabs
-    if (sr < cap) sr = cap;
-    if (sr > 0x7fffffffll) return false;
-    k.slab_rows = (int)sr;
-    k.slabs = (int)((k.rows + sr - 1) / sr);
-    return true;
+    return sums::slab_rule(k.rows, d->W, kSlabPixels, k.slab_rows, k.slabs);
 }
 
 // ------------------------------------------------------------------------------------------------ finalise
@@ -84,11 +78,6 @@ struct FinK {
     float *g_gamma, *g_beta;
     int C, slabs, accumulate;
 };
-
-__device__ __forceinline__ void put(float* o, double v, int accumulate) {
-    if (accumulate) v += (double)*o;
-    *o = (float)v;
-}
 
 __global__ __launch_bounds__(256) void cbr_finish_kernel(const FinK k) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -146,10 +135,6 @@ __global__ __launch_bounds__(256) void tdiff_bwd_kernel(const TbK p) {
     for (int u = 0; u < 4; ++u) v[u] = (rv[u] > 0.f && rv[u] < 6.f) ? (float)s[u] : 0.f;
     *reinterpret_cast<f32x4*>(p.out + row * p.ldo + c) = v;
 }
-
-bool al16(const void* p) { return uavsal_aligned16(p); }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 }  // namespace
 

@@ -1,8 +1,9 @@
 """The backward of a general inverted-residual block (`dwBlock`, `model_feature.InvertedResidual`), which every stage in front
 of the recurrence goes through: trained (`block_backward`, `block_param_grads`; csrc/train_block.hip: `uavsal_ir_bwd`,
 `uavsal_ir_sums`, `uavsal_ir_finish`, and `uavsal_pix_gemm` for both 1x1 weight gradients) or frozen (`block_input_grad`), with
-the stride-2 launches of csrc/train_ctx.hip (`uavsal_ir_bwd_s2`, `uavsal_ir_sums_s2`), the dilated ones of csrc/train_srf.hip
-(`uavsal_ir_bwd_dil`, `uavsal_ir_sums_dil`) and the Ch % 16 opt-in of csrc/train_shallow.hip.
+the stride-2 launches (`uavsal_ir_bwd_s2` of csrc/train_ctx.hip, `uavsal_ir_sums_s2`), the dilated ones (`uavsal_ir_bwd_dil` of
+csrc/train_srf.hip, `uavsal_ir_sums_dil`; the three sums are one kernel in csrc/train_block.hip) and the Ch % 16 opt-in of
+csrc/train_shallow.hip.
 The third stage is one such block, the fusion block that produces the recurrence's input (`fuse_block`:
 `model.fucbst_layer[0]`, or `model.fust_layer[0]` without priors).  `recurrence_step(fuse=True)`: the recurrence's backward
 also returns the gradient of its input, which `block_backward` carries to that block's nine parameters (`.grad` set, or added
@@ -95,23 +96,93 @@ def _block_slots(block, out, accumulate):
     return params, _grad_slots({n: params[n] for n in BLOCK_PARAMS}, out, accumulate, "out")
 
 
+# What each launch says when `gd`, `d`, `e` (and `ga`) do not fit each other: `gd` and `d` on the output grid of the depthwise
+# conv, `e` and `ga` on its input grid, all on one device.
+_GRID_MSG = {
+    "ir_bwd": "gd, d, e must be dense float32 NHWC cuda tensors of one shape",
+    "ir_bwd_s2": "gd and d must be [n,(H-1)//2+1,(W-1)//2+1,C] for e [n,H,W,C], on one device",
+    "ir_bwd_dil": "gd, d, e must have one shape on one device",
+    "ir_sums": "gd, d, e, ga must be dense float32 NHWC cuda tensors of one shape on one device",
+    "ir_sums_s2": "gd and d must be [n,(H-1)//2+1,(W-1)//2+1,Ch] for e and ga [n,H,W,Ch], on one device",
+    "ir_sums_dil": "gd, d, e, ga must have one shape on one device",
+}
+
+
+def _ir_grid(stem, stride, fields, gd, d, e, ga=None):
+    """The checks the six launches share -> `(n, ho, wo, c)`, the shape of `gd` and `d` for `e` (and `ga`) `[n,h,w,c]` and a
+    depthwise conv of `stride`; `fields["dil"]`, where the launch has a dilation, is checked behind them."""
+    ts = (gd, d, e) if ga is None else (gd, d, e, ga)
+    _dense_nhwc(stem, "gd, d, e" if ga is None else "gd, d, e, ga", *ts)
+    n, hh, ww, c = e.shape
+    grid = (n, (hh - 1) // stride + 1, (ww - 1) // stride + 1, c)
+    if (tuple(gd.shape) != grid or tuple(d.shape) != grid or (ga is not None and ga.shape != e.shape)
+            or any(t.device != e.device for t in ts)):
+        raise RuntimeError("%s: %s" % (stem, _GRID_MSG[stem]))
+    dil = fields.get("dil", 1)
+    if not isinstance(dil, int) or dil < 1:
+        raise RuntimeError("%s: the dilation must be an integer >= 1, got %r" % (stem, dil))
+    return grid
+
+
+def _ir_bwd(desc, stem, stride, gd, d, e, wd9, s2, **fields):
+    """`ir_bwd`, `ir_bwd_s2` and `ir_bwd_dil`: `desc` the descriptor class, `stem` the function's name (its symbol is
+    `uavsal_<stem>`), `stride` that of the `gd` / `d` grid; `fields`: what the descriptor holds besides (`dil`)."""
+    lib = L.load()
+    n, _, _, c = _ir_grid(stem, stride, fields, gd, d, e)
+    for name, t, m in (("wd9", wd9, 9 * c), ("s2", s2, c)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == e.device and t.is_contiguous() and t.numel() >= m):
+            raise RuntimeError("%s: %s must be a dense float32 tensor of at least %d elements on the device of e" % (stem, name, m))
+    ga = torch.empty_like(e)
+    k = desc()
+    k.gd, k.d, k.e, k.wd9, k.s2, k.ga = gd.data_ptr(), d.data_ptr(), e.data_ptr(), wd9.data_ptr(), s2.data_ptr(), ga.data_ptr()
+    k.n_img, k.H, k.W, k.C = n, e.shape[1], e.shape[2], c
+    for f, v in fields.items():
+        setattr(k, f, v)
+    L.check(getattr(lib, "uavsal_" + stem)(C.byref(k), _stream(e)), "uavsal_" + stem)
+    return ga
+
+
+def _ir_sums(desc, stem, stride, gd, d, e, ga, go, **fields):
+    """`ir_sums`, `ir_sums_s2` and `ir_sums_dil`: the arguments of `_ir_bwd`; `fields`: `ch16` or `dil`."""
+    lib = L.load()
+    n, ho, wo, c = _ir_grid(stem, stride, fields, gd, d, e, ga)
+    if not torch.is_tensor(go) or go.dtype != torch.float32 or go.device != e.device:
+        raise RuntimeError("%s: go must be a float32 tensor on the device of e" % stem)
+    gp, ldgo, *gs = _nhwc_view(go)
+    if gs[:3] != [n, ho, wo]:
+        raise RuntimeError("%s: go must cover the pixels of %s" % (stem, "e" if stride == 1 else "d"))
+    k = desc()
+    k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
+    k.n_img, k.H, k.W, k.Ch, k.Co = n, e.shape[1], e.shape[2], c, gs[3]
+    for f, v in fields.items():
+        setattr(k, f, v)
+    symbol = "uavsal_" + stem
+    nbytes = int(getattr(lib, symbol + "_workspace_bytes")(C.byref(k)))
+    if nbytes <= 0:
+        L.check(-3, symbol)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
+    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
+    L.check(getattr(lib, symbol)(C.byref(k), _stream(e)), symbol)
+    return ws, int(getattr(lib, symbol + "_slabs")(C.byref(k)))
+
+
 def ir_bwd(gd, d, e, wd9, s2):
     """`uavsal_ir_bwd` on the current stream: `gd`, `d`, `e` dense NHWC `[T,h,w,C]`, the tap-major depthwise weights and the
     folded scale of the depthwise BatchNorm on the device -> `ga` = d loss / d a1, dense NHWC."""
-    lib = L.load()
-    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
-                for t in (gd, d, e)) or gd.shape != d.shape or e.shape != d.shape):
-        raise RuntimeError("ir_bwd: gd, d, e must be dense float32 NHWC cuda tensors of one shape")
-    T, hh, ww, c = e.shape
-    for name, t, n in (("wd9", wd9, 9 * c), ("s2", s2, c)):
-        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == e.device and t.is_contiguous() and t.numel() >= n):
-            raise RuntimeError("ir_bwd: %s must be a dense float32 tensor of at least %d elements on the device of e" % (name, n))
-    ga = torch.empty_like(e)
-    k = L.IrBwdDesc()
-    k.gd, k.d, k.e, k.wd9, k.s2, k.ga = gd.data_ptr(), d.data_ptr(), e.data_ptr(), wd9.data_ptr(), s2.data_ptr(), ga.data_ptr()
-    k.n_img, k.H, k.W, k.C = T, hh, ww, c
-    L.check(lib.uavsal_ir_bwd(C.byref(k), _stream(e)), "uavsal_ir_bwd")
-    return ga
+    return _ir_bwd(L.IrBwdDesc, "ir_bwd", 1, gd, d, e, wd9, s2)
+
+
+def ir_bwd_s2(gd, d, e, wd9, s2):
+    """`uavsal_ir_bwd_s2` on the current stream: `ir_bwd` for a depthwise 3x3 with stride 2.  `gd`, `d` dense NHWC
+    `[n,Ho,Wo,C]` with `Ho = (H-1)//2+1`, `Wo = (W-1)//2+1`, `e` dense NHWC `[n,H,W,C]`, the tap-major depthwise weights and
+    the folded scale of the depthwise BatchNorm on the device -> `ga` = d loss / d a1, dense NHWC like `e`."""
+    return _ir_bwd(L.IrBwdS2Desc, "ir_bwd_s2", 2, gd, d, e, wd9, s2)
+
+
+def ir_bwd_dil(gd, d, e, wd9, s2, dil):
+    """`uavsal_ir_bwd_dil` on the current stream: `ir_bwd` for a depthwise 3x3 with stride 1 and dilation `dil` >= 1 (the ASPP
+    branches of the SRF-Net head): `gd`, `d`, `e` dense NHWC `[T,h,w,C]` -> `ga` = d loss / d a1, dense NHWC."""
+    return _ir_bwd(L.IrBwdDilDesc, "ir_bwd_dil", 1, gd, d, e, wd9, s2, dil=dil)
 
 
 def ir_sums(gd, d, e, ga, go, ch16=False):
@@ -119,103 +190,21 @@ def ir_sums(gd, d, e, ga, go, ch16=False):
     include/uavsal_hip.h) that `uavsal_ir_finish` takes.  `gd`, `d`, `e`, `ga` dense NHWC `[T,h,w,Ch]`; `go` an NHWC view
     `[T,h,w,Co]` of the same pixels (a channel slice is read in place).  `ch16=True`: any Ch % 16 == 0 is taken, not only
     Ch % 64 == 0 (the descriptor's opt-in; `ir_finish(..., ch16=True)` takes the workspace)."""
-    lib = L.load()
-    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
-                for t in (gd, d, e, ga)) or not all(t.shape == e.shape and t.device == e.device for t in (gd, d, ga))):
-        raise RuntimeError("ir_sums: gd, d, e, ga must be dense float32 NHWC cuda tensors of one shape on one device")
-    T, hh, ww, c = e.shape
-    if not torch.is_tensor(go) or go.dtype != torch.float32 or go.device != e.device:
-        raise RuntimeError("ir_sums: go must be a float32 tensor on the device of e")
-    gp, ldgo, *gs = _nhwc_view(go)
-    if gs[:3] != [T, hh, ww]:
-        raise RuntimeError("ir_sums: go must cover the pixels of e")
-    k = L.IrSumsDesc()
-    k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
-    k.n_img, k.H, k.W, k.Ch, k.Co, k.ch16 = T, hh, ww, c, gs[3], int(bool(ch16))
-    nbytes = int(lib.uavsal_ir_sums_workspace_bytes(C.byref(k)))
-    if nbytes <= 0:
-        L.check(-3, "uavsal_ir_sums")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
-    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
-    L.check(lib.uavsal_ir_sums(C.byref(k), _stream(e)), "uavsal_ir_sums")
-    return ws, int(lib.uavsal_ir_sums_slabs(C.byref(k)))
+    return _ir_sums(L.IrSumsDesc, "ir_sums", 1, gd, d, e, ga, go, ch16=int(bool(ch16)))
 
 
 def ir_sums_s2(gd, d, e, ga, go, ch16=False):
     """`uavsal_ir_sums_s2` on the current stream -> `(ws, slabs)`: `ir_sums` for a depthwise 3x3 with stride 2, in the same
     workspace layout.  `e`, `ga` dense NHWC `[n,H,W,Ch]`; `gd`, `d` dense NHWC `[n,Ho,Wo,Ch]` with `Ho = (H-1)//2+1`,
     `Wo = (W-1)//2+1`; `go` an NHWC view `[n,Ho,Wo,Co]` (a channel slice is read in place).  `ch16`: as in `ir_sums`."""
-    lib = L.load()
-    _dense_nhwc("ir_sums_s2", "gd, d, e, ga", gd, d, e, ga)
-    n, hh, ww, c = e.shape
-    ho, wo = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
-    if (ga.shape != e.shape or gd.shape != d.shape or tuple(d.shape) != (n, ho, wo, c)
-            or any(t.device != e.device for t in (gd, d, ga))):
-        raise RuntimeError("ir_sums_s2: gd and d must be [n,(H-1)//2+1,(W-1)//2+1,Ch] for e and ga [n,H,W,Ch], on one device")
-    if not torch.is_tensor(go) or go.dtype != torch.float32 or go.device != e.device:
-        raise RuntimeError("ir_sums_s2: go must be a float32 tensor on the device of e")
-    gp, ldgo, *gs = _nhwc_view(go)
-    if gs[:3] != [n, ho, wo]:
-        raise RuntimeError("ir_sums_s2: go must cover the pixels of d")
-    k = L.IrSumsS2Desc()
-    k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
-    k.n_img, k.H, k.W, k.Ch, k.Co, k.ch16 = n, hh, ww, c, gs[3], int(bool(ch16))
-    nbytes = int(lib.uavsal_ir_sums_s2_workspace_bytes(C.byref(k)))
-    if nbytes <= 0:
-        L.check(-3, "uavsal_ir_sums_s2")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
-    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
-    L.check(lib.uavsal_ir_sums_s2(C.byref(k), _stream(e)), "uavsal_ir_sums_s2")
-    return ws, int(lib.uavsal_ir_sums_s2_slabs(C.byref(k)))
-
-
-def ir_bwd_dil(gd, d, e, wd9, s2, dil):
-    """`uavsal_ir_bwd_dil` on the current stream: `ir_bwd` for a depthwise 3x3 with stride 1 and dilation `dil` >= 1 (the ASPP
-    branches of the SRF-Net head): `gd`, `d`, `e` dense NHWC `[T,h,w,C]` -> `ga` = d loss / d a1, dense NHWC."""
-    lib = L.load()
-    _dense_nhwc("ir_bwd_dil", "gd, d, e", gd, d, e)
-    if gd.shape != d.shape or e.shape != d.shape or any(t.device != e.device for t in (gd, d)):
-        raise RuntimeError("ir_bwd_dil: gd, d, e must have one shape on one device")
-    if not isinstance(dil, int) or dil < 1:
-        raise RuntimeError("ir_bwd_dil: the dilation must be an integer >= 1, got %r" % (dil,))
-    T, hh, ww, c = e.shape
-    for name, t, n in (("wd9", wd9, 9 * c), ("s2", s2, c)):
-        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == e.device and t.is_contiguous() and t.numel() >= n):
-            raise RuntimeError("ir_bwd_dil: %s must be a dense float32 tensor of at least %d elements on the device of e" % (name, n))
-    ga = torch.empty_like(e)
-    k = L.IrBwdDilDesc()
-    k.gd, k.d, k.e, k.wd9, k.s2, k.ga = gd.data_ptr(), d.data_ptr(), e.data_ptr(), wd9.data_ptr(), s2.data_ptr(), ga.data_ptr()
-    k.n_img, k.H, k.W, k.C, k.dil = T, hh, ww, c, dil
-    L.check(lib.uavsal_ir_bwd_dil(C.byref(k), _stream(e)), "uavsal_ir_bwd_dil")
-    return ga
+    return _ir_sums(L.IrSumsS2Desc, "ir_sums_s2", 2, gd, d, e, ga, go, ch16=int(bool(ch16)))
 
 
 def ir_sums_dil(gd, d, e, ga, go, dil):
     """`uavsal_ir_sums_dil` on the current stream -> `(ws, slabs)`: `ir_sums` for a depthwise 3x3 with stride 1 and dilation
     `dil` >= 1, in the same workspace layout.  `gd`, `d`, `e`, `ga` dense NHWC `[T,h,w,Ch]`; `go` an NHWC view `[T,h,w,Co]` of
     the same pixels (a channel slice is read in place)."""
-    lib = L.load()
-    _dense_nhwc("ir_sums_dil", "gd, d, e, ga", gd, d, e, ga)
-    if not all(t.shape == e.shape and t.device == e.device for t in (gd, d, ga)):
-        raise RuntimeError("ir_sums_dil: gd, d, e, ga must have one shape on one device")
-    if not isinstance(dil, int) or dil < 1:
-        raise RuntimeError("ir_sums_dil: the dilation must be an integer >= 1, got %r" % (dil,))
-    T, hh, ww, c = e.shape
-    if not torch.is_tensor(go) or go.dtype != torch.float32 or go.device != e.device:
-        raise RuntimeError("ir_sums_dil: go must be a float32 tensor on the device of e")
-    gp, ldgo, *gs = _nhwc_view(go)
-    if gs[:3] != [T, hh, ww]:
-        raise RuntimeError("ir_sums_dil: go must cover the pixels of e")
-    k = L.IrSumsDilDesc()
-    k.gd, k.d, k.e, k.ga, k.go, k.ldgo = gd.data_ptr(), d.data_ptr(), e.data_ptr(), ga.data_ptr(), gp, ldgo
-    k.n_img, k.H, k.W, k.Ch, k.Co, k.dil = T, hh, ww, c, gs[3], dil
-    nbytes = int(lib.uavsal_ir_sums_dil_workspace_bytes(C.byref(k)))
-    if nbytes <= 0:
-        L.check(-3, "uavsal_ir_sums_dil")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=e.device)
-    k.ws, k.ws_bytes = ws.data_ptr(), nbytes
-    L.check(lib.uavsal_ir_sums_dil(C.byref(k), _stream(e)), "uavsal_ir_sums_dil")
-    return ws, int(lib.uavsal_ir_sums_dil_slabs(C.byref(k)))
+    return _ir_sums(L.IrSumsDilDesc, "ir_sums_dil", 1, gd, d, e, ga, go, dil=dil)
 
 
 def _takes_pix_gemm(lib, M, N, K):
@@ -284,12 +273,8 @@ def block_param_grads(block, x, e, d, grad_out, gd=None, ga=None, cache=None, ou
                 skinny_wgrad(a, b, **kw)
             else:
                 pix_gemm(a, b, tails32=backbone or shallow, **kw)
-        if dil > 1:
-            ws, slabs = ir_sums_dil(gd, d, e, ga, go, dil)
-        elif shallow:
-            ws, slabs = (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go, ch16=True)
-        else:
-            ws, slabs = (ir_sums if stride == 1 else ir_sums_s2)(gd, d, e, ga, go)
+        sums, kw = (ir_sums_dil, dict(dil=dil)) if dil > 1 else (ir_sums if stride == 1 else ir_sums_s2, dict(ch16=shallow))
+        ws, slabs = sums(gd, d, e, ga, go, **kw)
         k = L.IrFinishDesc()
         k.ws, k.ws_bytes, k.rowdot1, k.rowdot3 = ws.data_ptr(), ws.numel() * 8, rd1.data_ptr(), rd3.data_ptr()
         k.wd, k.s2 = dwc.weight.data_ptr(), s2.data_ptr()
@@ -362,26 +347,6 @@ def _block_backward(block, x, grad_out, need_x_grad, cache, parts, grads, accumu
         if parts is not None:
             parts.update(pt)
     return (g.permute(0, 3, 1, 2) if need_x_grad else None), grads
-
-
-def ir_bwd_s2(gd, d, e, wd9, s2):
-    """`uavsal_ir_bwd_s2` on the current stream: `ir_bwd` for a depthwise 3x3 with stride 2.  `gd`, `d` dense NHWC
-    `[n,Ho,Wo,C]` with `Ho = (H-1)//2+1`, `Wo = (W-1)//2+1`, `e` dense NHWC `[n,H,W,C]`, the tap-major depthwise weights and
-    the folded scale of the depthwise BatchNorm on the device -> `ga` = d loss / d a1, dense NHWC like `e`."""
-    lib = L.load()
-    _dense_nhwc("ir_bwd_s2", "gd, d, e", gd, d, e)
-    n, hh, ww, c = e.shape
-    if gd.shape != d.shape or tuple(d.shape) != (n, (hh - 1) // 2 + 1, (ww - 1) // 2 + 1, c) or d.device != e.device or gd.device != e.device:
-        raise RuntimeError("ir_bwd_s2: gd and d must be [n,(H-1)//2+1,(W-1)//2+1,C] for e [n,H,W,C], on one device")
-    for name, t, m in (("wd9", wd9, 9 * c), ("s2", s2, c)):
-        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == e.device and t.is_contiguous() and t.numel() >= m):
-            raise RuntimeError("ir_bwd_s2: %s must be a dense float32 tensor of at least %d elements on the device of e" % (name, m))
-    ga = torch.empty_like(e)
-    k = L.IrBwdS2Desc()
-    k.gd, k.d, k.e, k.wd9, k.s2, k.ga = gd.data_ptr(), d.data_ptr(), e.data_ptr(), wd9.data_ptr(), s2.data_ptr(), ga.data_ptr()
-    k.n_img, k.H, k.W, k.C = n, hh, ww, c
-    L.check(lib.uavsal_ir_bwd_s2(C.byref(k), _stream(e)), "uavsal_ir_bwd_s2")
-    return ga
 
 
 def _input_grad_parts(block):

@@ -184,6 +184,27 @@ def test_ir_bwd_dil_and_ir_sums_dil_against_float64(ch, dil, h, w, n):
                2 * SF.ir_bwd_dil_bound(*args[:5], 1) + 1e-300, "ir_bwd_dil at dilation 1 against ir_bwd " + tag)
 
 
+# (n, H, W, Ch, Co), slabs: one slab and one channel group; 36 rows at 26 rows per slab are two slabs, the second partial, and
+# Ch = 320 leaves the second channel group mostly idle
+@pytest.mark.parametrize("n,h,w,ch,co,slabs_want", [(2, 5, 7, 64, 64, 1), (3, 12, 20, 320, 128, 2)])
+def test_ir_sums_dil_at_dilation_1_has_the_bits_of_ir_sums(n, h, w, ch, co, slabs_want):
+    """The instantiations of the channel-sums kernel share one order of additions: at dilation 1 the dilated launch reads
+    the taps of the undilated one, so its workspace is the same bytes, slab for slab."""
+    rs = np.random.RandomState(1000 * ch + n * h * w)
+    gd, ga = (torch.from_numpy((rs.standard_normal((n, h, w, ch)) / (h * w)).astype(np.float32)).to(DEV) for _ in range(2))
+    d, e = (torch.from_numpy((-1.0 + 8.0 * rs.random_sample((n, h, w, ch))).clip(0, 6).astype(np.float32)).to(DEV) for _ in range(2))
+    go = torch.from_numpy((rs.standard_normal((n, h, w, co)) / (h * w)).astype(np.float32)).to(DEV)
+    k = _lib.IrSumsDesc()
+    k.n_img, k.H, k.W, k.Ch, k.Co = n, h, w, ch, co
+    assert int(_lib.load().uavsal_ir_sums_slabs(C.byref(k))) == slabs_want
+    ws, slabs = train.ir_sums(gd, d, e, ga, go)
+    ws1, slabs1 = train.ir_sums_dil(gd, d, e, ga, go, 1)
+    assert slabs == slabs1 == slabs_want
+    assert ws.numel() == ws1.numel() == slabs * (_lib.IR_NSUM * ch + co)
+    assert bool(torch.isfinite(ws).all()) and float(ws.abs().max()) > 0.0
+    assert torch.equal(ws.view(torch.int64).cpu(), ws1.view(torch.int64).cpu())
+
+
 # ------------------------------------------------------------------------------------------------ 3. the pixel GEMM's new shapes
 @pytest.mark.parametrize("M,N", SF.GEMM_NEW_SHAPES + SF.GEMM_OLD_SHAPES)
 def test_pix_gemm_shapes_of_the_head(M, N):
