@@ -424,6 +424,14 @@ class DwWgradDesc(C.Structure):
 
 BN_DESC_TYPES = [BnStatsDesc, BnApplyDesc, BnBwdDesc, DwWgradDesc]      # sized by uavsal_bn_sizeof_desc (csrc/train_bn.hip)
 
+
+class BnApplyResDesc(C.Structure):
+    _fields_ = [("u", _f), ("ld", C.c_int32), ("s", _f), ("b", _f), ("res", _f), ("ldr", C.c_int32), ("out", _f),
+                ("n_pix", C.c_int64), ("C", C.c_int32), ("act", C.c_int32)]
+
+
+BLOCK_BN_DESC_TYPES = [BnApplyResDesc]      # sized by uavsal_block_bn_sizeof_desc (csrc/train_bn.hip)
+
 REPACK_MAX_SRC = 4            # UAVSAL_REPACK_MAX_SRC: weights / BatchNorms side by side in one entry (csrc/repack.hip)
 REPACK_CONV, REPACK_WINO, REPACK_FOLD, REPACK_DW, REPACK_COPY, REPACK_COPY_T = range(6)
 REPACK_LAYOUT = {"f32": 0, "f32k32": 0, "f16x3": 1, "f16x3i": 2, "f16x3j": 3, "bf16": 4, "bf16x3": 5}
@@ -545,6 +553,8 @@ SYMBOLS = [
     ("uavsal_dw_wgrad_workspace_bytes", C.c_int64, [C.POINTER(DwWgradDesc)]),
     ("uavsal_dw_wgrad", C.c_int, [C.POINTER(DwWgradDesc), C.c_void_p]),
     ("uavsal_bn_sizeof_desc", C.c_int, [C.c_int]),
+    ("uavsal_bn_apply_res", C.c_int, [C.POINTER(BnApplyResDesc), C.c_void_p]),
+    ("uavsal_block_bn_sizeof_desc", C.c_int, [C.c_int]),
     ("uavsal_repack", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("uavsal_repack_sizeof_desc", C.c_int, []),
     ("uavsal_guard", C.c_int, [C.POINTER(GuardDesc), C.c_void_p]),
@@ -632,7 +642,7 @@ def load():
                           (lib.uavsal_mp_sizeof_desc, MP_DESC_TYPES), (lib.uavsal_nets_sizeof_desc, NETS_DESC_TYPES),
                           (lib.uavsal_st_sizeof_desc, ST_DESC_TYPES), (lib.uavsal_srf_sizeof_desc, SRF_DESC_TYPES),
                           (lib.uavsal_shallow_sizeof_desc, SHALLOW_DESC_TYPES), (lib.uavsal_lstm_sizeof_desc, LSTM_DESC_TYPES),
-                          (lib.uavsal_bn_sizeof_desc, BN_DESC_TYPES)):
+                          (lib.uavsal_bn_sizeof_desc, BN_DESC_TYPES), (lib.uavsal_block_bn_sizeof_desc, BLOCK_BN_DESC_TYPES)):
         for i, t in enumerate(types):
             if sizeof(i) != C.sizeof(t):
                 raise RuntimeError("descriptor %s: ctypes size %d != C size %d" % (t.__name__, C.sizeof(t), sizeof(i)))

@@ -14,7 +14,8 @@
 // 1. uavsal_bn_stats: sum u, sum u^2 -> mu, var, r, s = gamma r, b = beta - mu s, and the running statistics blended in double
 //    in place (two launches).
 // 2. uavsal_bn_apply: out = act(fma(u, s, b)) element-wise; with dot_w: out[p] = sum_c dot_w[c] act(...)[p][c], a wave per
-//    pixel (the decoder's projection to one channel: d is never stored).
+//    pixel (the decoder's projection to one channel: d is never stored).  uavsal_bn_apply_res: out = act(fma(u, s, b)) + res,
+//    the last BatchNorm of an inverted-residual block with its residual (train.block_forward_batch).
 // 3. uavsal_bn_bwd_sums: sum g_a, sum g_a xh (and, for a rank-one gradient g[p][c] = g_pix[p] g_chan[c], sum g_pix act(a): the
 //    weight gradient of the projection that made it) -> d beta, d gamma (two launches).
 // 4. uavsal_bn_bwd_apply: g_u = s (g_a - d beta / P - xh d gamma / P), element-wise.
@@ -189,6 +190,26 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const ApplyK k) {
 #pragma unroll
     for (int u = 0; u < V; ++u) o.v[u] = apply_act(bn_pre(x.v[u], s.v[u], b.v[u]), k.act);
     stv<V>(k.out + p * k.C + c, o);
+}
+
+// out = act(fma(u, s, b)) + res: bn_apply_kernel's items (a lane owns four channels of a pixel), `res` rows ldr apart
+struct ApplyResK {
+    const float *u, *s, *b, *res;
+    float* out;
+    long long total;
+    int C, CV, ld, ldr, act;
+};
+
+__global__ __launch_bounds__(kThreads) void bn_apply_res_kernel(const ApplyResK k) {
+    const long long item = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (item >= k.total) return;
+    const int c = (int)(item % k.CV) * 4;
+    const long long p = item / k.CV;
+    const Vec<4> x = ldv<4>(k.u + p * k.ld + c), s = ldv<4>(k.s + c), b = ldv<4>(k.b + c), r = ldv<4>(k.res + p * k.ldr + c);
+    Vec<4> o;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) o.v[u] = apply_act(bn_pre(x.v[u], s.v[u], b.v[u]), k.act) + r.v[u];
+    stv<4>(k.out + p * k.C + c, o);
 }
 
 // a wave per pixel: lane l adds its channels 4 l + 256 j (j = 0, 1, ...; the four of a load in channel order) to ONE fp32
@@ -455,6 +476,25 @@ extern "C" int uavsal_bn_apply(const uavsal_bn_apply_desc* d, uavsal_stream_t st
     if (!blocks_ok(k.total, blocks)) return UAVSAL_ESHAPE;
     if (vec == 4) hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, k);
     else hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, k);
+    return uavsal_launch_status();
+}
+
+extern "C" int uavsal_block_bn_sizeof_desc(int which) { return which == 0 ? (int)sizeof(uavsal_bn_apply_res_desc) : -1; }
+
+extern "C" int uavsal_bn_apply_res(const uavsal_bn_apply_res_desc* d, uavsal_stream_t stream) {
+    if (!d || !d->u || !d->s || !d->b || !d->res || !d->out) return UAVSAL_EINVAL;
+    if (d->n_pix <= 0 || d->C <= 0 || d->ld < d->C || d->ldr < d->C) return UAVSAL_EINVAL;
+    if (d->act != UAVSAL_ACT_NONE && d->act != UAVSAL_ACT_RELU6 && d->act != UAVSAL_ACT_SIGMOID) return UAVSAL_EINVAL;
+    if (d->C & 3) return UAVSAL_ESHAPE;
+    if (!alv(d->u, d->ld, 4) || !alv(d->res, d->ldr, 4) || !al16(d->s) || !al16(d->b) || !al16(d->out)) return UAVSAL_EALIGN;
+    ApplyResK k;
+    k.u = d->u; k.s = d->s; k.b = d->b; k.res = d->res; k.out = d->out; k.C = d->C; k.CV = d->C / 4;
+    k.ld = d->ld; k.ldr = d->ldr; k.act = d->act;
+    if (d->n_pix > 0x7fffffffffffffffll / k.CV) return UAVSAL_ESHAPE;
+    k.total = d->n_pix * k.CV;
+    unsigned blocks;
+    if (!blocks_ok(k.total, blocks)) return UAVSAL_ESHAPE;
+    hipLaunchKernelGGL(bn_apply_res_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, k);
     return uavsal_launch_status();
 }
 

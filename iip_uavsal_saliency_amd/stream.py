@@ -383,7 +383,7 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
                    fix_map: torch.Tensor, fix_loc: torch.Tensor, optimizer, batch_size: int = 4,
                    model_size: Optional[tuple] = None, frame_layout: str = "CHW", bgr: bool = False,
                    gaze_layout: Optional[str] = None, criterion=None, prepare=None, stages=("rnn",), refresh="host",
-                   batch_stats=()):
+                   batch_stats=(), block_stats=()):
     """The inner loop of the reference's `train` phase for one video (Demo_Train_Test.py:105-153), for the stage this package
     trains: the ConvTWA recurrence `model.rnn` (train/).  Arguments, groups, skip rule, carried detached state and returned
     aggregates are `validate_video`'s (one loop serves both); every group that runs does
@@ -426,7 +426,10 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
     `batch_stats=("decoder",)` (needs `"decoder"` in `stages`): the keyword is passed through to `recurrence_step`, which then
     runs the decoder's BatchNorms on the statistics of each group and moves their running statistics, as the reference's
     `train` phase does; `model.conv_out_st` is put into training mode for the steps and its mode restored afterwards (the
-    model itself stays in `eval()`).  `validate_video` stays on the running statistics, as the reference's `val` phase does."""
+    model itself stays in `eval()`).  `validate_video` stays on the running statistics, as the reference's `val` phase does.
+    `block_stats=("fuse",)` (needs `"fuse"` in `stages`; combines with `batch_stats`): likewise for the fusion block in front of
+    the recurrence -- the keyword is passed through to `recurrence_step`, the block's container (`train.fuse_container`) is put
+    into training mode for the steps and its mode restored afterwards, also when a step raises."""
     from . import losses as _losses
     from . import train as _train
     criterion = criterion or _losses.loss_fu
@@ -447,6 +450,15 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
         if "decoder" not in stages:
             raise ValueError("batch_stats=('decoder',) needs 'decoder' in stages, got %r" % (stages,))
         kw["batch_stats"] = batch_stats                   # (without it the call keeps the keywords it always had)
+    block_stats = (block_stats,) if isinstance(block_stats, str) else tuple(block_stats)
+    if block_stats:
+        for name in block_stats:
+            if name not in _train.BLOCK_STATS:
+                raise NotImplementedError("block_stats covers %r only; the BatchNorms of stage %r stay on their running "
+                                          "statistics" % (_train.BLOCK_STATS, name))
+        if "fuse" not in stages:
+            raise ValueError("block_stats=('fuse',) needs 'fuse' in stages, got %r" % (stages,))
+        kw["block_stats"] = block_stats                   # (likewise)
     lstm = getattr(model, "rnn_type", "twa") == "lstm"
     if lstm:
         kw["lstm"] = True                                 # (a ConvTWA model's call keeps the keywords it always had)
@@ -466,14 +478,20 @@ def finetune_video(model, frames_u8: torch.Tensor, gauss_prior: torch.Tensor, ob
             model.refresh_weights(*mods)                  # (no keyword: a model-like object without `device=` keeps working)
         return loss, state
     was = model.conv_out_st.training if batch_stats else None
+    box = _train.fuse_container(model) if block_stats else None
+    box_was = [(m, m.training) for m in box.modules()] if block_stats else []
     try:
         if batch_stats:
             model.conv_out_st.train()
+        if block_stats:
+            box.train()
         return _gaze_groups_loop(model, frames_u8, gauss_prior, ob_prior, fix_map, fix_loc, batch_size, model_size, frame_layout,
                                  bgr, gaze_layout, prepare, step)
     finally:
         if batch_stats:
             model.conv_out_st.train(was)
+        for m, mode in box_was:
+            m.training = mode
 
 
 class RequestPipeline:

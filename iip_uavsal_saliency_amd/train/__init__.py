@@ -20,7 +20,13 @@ stage is a keyword of the step; its module tells what it trains, what it needs a
 
 `batch_stats=("decoder",)` runs the decoder's BatchNorms on the statistics of the batch instead (bn.py, decoder.py:
 csrc/train_bn.hip), the first stage for which the reference's `model.train()` behaviour exists; every other stage's
-BatchNorms stay on their running statistics.
+BatchNorms stay on their running statistics.  `block_stats=("fuse",)` does the same for the fusion block in FRONT of the
+recurrence (block_bn.py: `block_forward_batch` / `block_backward_batch`, `uavsal_bn_apply_res`), whose new output the recurrence
+and the decoder then run on again outside the plan (recurrence.py: `twa_forward` / `lstm_forward`):
+
+    keyword                      stage          module          what runs outside the plan
+    batch_stats=("decoder",)     conv_out_st    decoder.py      the decoder on the plan's `rnn` tap
+    block_stats=("fuse",)        fusion block   block_bn.py     the block on its input tap, the recurrence, the decoder
 
 `STAGES` below is the same list as data: what each keyword needs and which modules it refreshes.  `_common.py` holds what the
 stages share.  The imports run one way: block <- ctx <- {nets, st}, st <- srf, block <- backbone; the step combines them here.
@@ -31,6 +37,7 @@ from typing import Callable, NamedTuple, Optional
 
 import torch
 
+from .. import _lib as _L
 from .. import losses as _losses
 from ..weights import WeightCache
 from ._common import HID, _conv, _param_grad_tensors, conv3_wgrad, pix_gemm, skinny_wgrad  # noqa: F401
@@ -40,14 +47,16 @@ from .backbone import (BACKBONE_C4, BACKBONE_END, BACKBONE_FIRST, BACKBONE_PARAM
 from .block import (BLOCK_PARAMS, _block_backward, _block_parts, _block_recompute, _input_grad, _input_grad_parts,  # noqa: F401
                     _param_grad_parts, block_backward, block_input_grad, block_param_grads, ir_bwd, ir_bwd_dil, ir_bwd_s2, ir_sums,
                     ir_sums_dil, ir_sums_s2)
+from .block_bn import block_backward_batch, block_forward_batch  # noqa: F401
 from .ctx import PRIOR_PATH_BLOCKS, bilinear_bwd, fust_output_grad, prior_path_backward, prior_path_blocks, tsum_bwd  # noqa: F401
 from . import bn  # noqa: F401
 from .bn import bn_apply, bn_bwd_apply, bn_bwd_sums, bn_stats, dw_wgrad  # noqa: F401
-from .decoder import (DECODER_PARAMS, _decoder_parts, dec_bwd, dec_sums, decoder_backward, decoder_backward_batch,  # noqa: F401
+from .decoder import (DECODER_PARAMS, _decoder_parts, _decoder_recompute, dec_bwd, dec_sums, decoder_backward, decoder_backward_batch,  # noqa: F401
                       decoder_forward_batch, decoder_input_grad, decoder_param_grads)
 from .nets import (PRIOR_NETS, _narrow_parts, frame_sum, ir_narrow_grads, narrow_block_param_grads, prior_net_backward,  # noqa: F401
                    prior_nets)
-from .recurrence import lstm_backward, lstm_gate_bwd, lstm_scan, twa_backward, twa_gate_bwd, twa_wgrad  # noqa: F401
+from .recurrence import (lstm_backward, lstm_forward, lstm_gate_bwd, lstm_scan, twa_backward, twa_forward, twa_gate_bwd,  # noqa: F401
+                         twa_wgrad)
 from .srf import SRF_HEAD, SRF_HEAD_BLOCKS, SRF_HEAD_PARAMS, conv3_backward, srf_head, srf_head_backward  # noqa: F401
 from .st import (ST_BLOCK_PARAMS, ST_BLOCK_PARTS, ST_CBR_PARAMS, _cbr_backward, cbr_backward, cbr_sums, st_block_backward,  # noqa: F401
                  tdiff_bwd)
@@ -105,6 +114,17 @@ STAGES = (
 
 
 BATCH_STATS = ("decoder",)       # the stages whose BatchNorms `recurrence_step(batch_stats=...)` can run on batch statistics
+BLOCK_STATS = ("fuse",)          # the stages in FRONT of the recurrence that `recurrence_step(block_stats=...)` can run that way
+
+
+def fuse_container(model):
+    """The module that holds `fuse_block(model)`'s block: what `.train()` is called on for `block_stats=("fuse",)` and what
+    `model.refresh_weights` takes afterwards."""
+    return model.fucbst_layer if model.num_cb else model.fust_layer
+
+
+def _names(value):
+    return (value,) if isinstance(value, str) else tuple(value)
 
 
 def stages_allowed(model, stages):
@@ -126,7 +146,7 @@ def _grads_of(module):
 
 
 def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=False, fuse=False, fust=False, ctx=False, nets=False,
-                    st=False, srf=False, backbone=False, shallow=False, lstm=False, batch_stats=()):
+                    st=False, srf=False, backbone=False, shallow=False, lstm=False, batch_stats=(), block_stats=()):
     """One training step's forward and backward for the recurrence: `model(x, cb, in_state)` through the launch plan, the
     criterion (default `losses.loss_fu`) and its gradient, the decoder's input gradient and `twa_backward`.  Ends with
     `model.rnn.cell_list[0].rnn_conv.weight.grad` set -- or added to when it already exists, as `loss.backward()` would --
@@ -153,8 +173,25 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     and `out` and the loss come from `decoder_forward_batch` on the `rnn` tap, which also moves the decoder's running
     statistics; `decoder_backward_batch` sets -- or adds to -- the nine `.grad`s and hands its `grad_h` to the recurrence
     unchanged.  The returned `out` is the batch-statistics prediction.  Afterwards
-    `model.refresh_weights(model.rnn, model.conv_out_st)` refolds the eval-mode packed forms from the moved statistics."""
-    batch_stats = (batch_stats,) if isinstance(batch_stats, str) else tuple(batch_stats)
+    `model.refresh_weights(model.rnn, model.conv_out_st)` refolds the eval-mode packed forms from the moved statistics.
+    `block_stats=("fuse",)` (opt-in, a keyword of its own because it names a stage in FRONT of the recurrence; the default `()`
+    runs the launches it ran and returns the bits it returned; needs `fuse=True`; combines freely with `batch_stats`): the
+    fusion block `fuse_block(model)` runs as the reference's `train()` runs it (`BLOCK_STATS`).  The model stays in eval mode
+    and the block's container (`fuse_container(model)`: `model.fucbst_layer`, or `model.fust_layer` without priors) has been
+    put into `.train()`; anything else raises a `RuntimeError` that names what is missing, before any launch, and any other
+    name in the tuple a `NotImplementedError` that names it.  The plan runs as always and delivers the block's input tap;
+    `block_forward_batch` gives the new `prefuse` and moves the block's running statistics; `twa_forward` (`lstm=True`:
+    `lstm_forward`) gives the new history and state from it; the decoder runs on that history, in eval mode by the forward's
+    own launches or, under `batch_stats=("decoder",)`, through `decoder_forward_batch`.  The plan's own `prefuse`, `rnn`,
+    prediction and state are dropped: `out`, the loss and the returned state are the rerun's.  The backward runs as always on
+    the new tensors, `block_backward_batch` standing where `block_backward` stands; the `grad_x` it returns feeds the stages
+    behind it (`fust`, `ctx`, `nets`, `st`, ...) unchanged -- they stay in eval mode.  Afterwards
+    `model.refresh_weights(model.rnn, fuse_container(model))` refolds the block's eval-mode packed forms."""
+    batch_stats, block_stats = _names(batch_stats), _names(block_stats)
+    for name in block_stats:
+        if name not in BLOCK_STATS:
+            raise NotImplementedError("block_stats covers %r only; the BatchNorms of stage %r stay on their running statistics"
+                                      % (BLOCK_STATS, name))
     for name in batch_stats:
         if name not in BATCH_STATS:
             raise NotImplementedError("batch_stats covers %r only; the BatchNorms of stage %r stay on their running statistics"
@@ -179,6 +216,13 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
         if not model.conv_out_st.training:
             raise RuntimeError("batch_stats=('decoder',) needs model.conv_out_st.train() (under model.eval()): the decoder's "
                                "BatchNorms are in eval mode")
+    if block_stats:
+        if not fuse:
+            raise RuntimeError("block_stats=('fuse',) needs fuse=True: the batch statistics belong to the trained fusion block")
+        box = fuse_container(model)
+        if not box.training or not fuse_block(model)[0].training:
+            raise RuntimeError("block_stats=('fuse',) needs model.%s.train() (under model.eval()): the fusion block's BatchNorms "
+                               "are in eval mode" % ("fucbst_layer" if model.num_cb else "fust_layer"))
     if not torch.is_tensor(x) or not x.is_cuda or not torch.is_tensor(y_gaze) or not y_gaze.is_cuda:
         raise RuntimeError("recurrence_step needs tensors on the MI355X (cuda) device; there is no CPU fallback")
     rc = model.rnn.cell_list[0].rnn_conv
@@ -187,18 +231,32 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
     if fust or ctx or nets:
         taps["cb192"] = None                                         # (likewise)
     out, h_last = model(x, cb, in_state, taps=taps)
+    dev = x.device
+    cache = WeightCache(dev, model._wshared.setdefault(str(torch.device(dev)), {}))
+    cl = torch.channels_last
+    h0 = None if in_state is None else in_state[0]
+    if lstm:
+        h0, c0 = (None, None) if h0 is None else h0
+    if block_stats:                                                  # the plan's own prefuse, rnn, prediction and state are dropped
+        fu = taps[src].contiguous(memory_format=cl)
+        x_seq, blk_saved = block_forward_batch(blk, fu, cache=cache)
+        if lstm:
+            h_seq, c_last = lstm_forward(x_seq, h0, c0, rc.weight.detach(), cache=cache, module=rc)
+            h_last = [h_seq[-1:].contiguous(), c_last.contiguous()]
+        else:
+            h_seq = twa_forward(x_seq, h0, rc.weight.detach(), cache=cache, module=rc)
+            h_last = [h_seq[-1:].contiguous()]
+        if not batch_stats:                                          # the eval-mode decoder by the forward's own launches
+            y = _decoder_recompute(_L.load(), cache, model.conv_out_st, h_seq.permute(0, 2, 3, 1), None)[2]
+            out = y.view(y.shape[0], 1, y.shape[1], y.shape[2])
+    else:
+        h_seq, x_seq = taps["rnn"].contiguous(memory_format=cl), taps["prefuse"].contiguous(memory_format=cl)
     if batch_stats:                                                  # the plan's own prediction is dropped
-        cache = WeightCache(x.device, model._wshared.setdefault(str(torch.device(x.device)), {}))
-        out, saved = decoder_forward_batch(model.conv_out_st, taps["rnn"].contiguous(memory_format=torch.channels_last),
-                                           cache=cache)
+        out, saved = decoder_forward_batch(model.conv_out_st, h_seq, cache=cache)
     pred = out.detach().requires_grad_(True)
     with torch.enable_grad():
         loss = criterion(pred, y_gaze)
         (g_y,) = torch.autograd.grad(loss, pred)
-    dev = x.device
-    cache = WeightCache(dev, model._wshared.setdefault(str(torch.device(dev)), {}))
-    cl = torch.channels_last
-    h_seq, x_seq = taps["rnn"].contiguous(memory_format=cl), taps["prefuse"].contiguous(memory_format=cl)
     if decoder and batch_stats:
         grads, acc = _grads_of(model.conv_out_st)
         grad_h, _ = decoder_backward_batch(model.conv_out_st, h_seq, g_y, saved=saved, grads=grads, accumulate=acc, cache=cache)
@@ -207,13 +265,11 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
         grad_h, _ = decoder_backward(model.conv_out_st, h_seq, g_y, cache=cache, y=out, grads=grads, accumulate=acc)
     else:
         grad_h = decoder_input_grad(model.conv_out_st, h_seq, g_y, cache=cache, y=out)
-    h0 = None if in_state is None else in_state[0]
     w = rc.weight
     had = w.grad is not None
     if not had:
         w.grad = torch.empty_like(w, memory_format=torch.contiguous_format)
     if lstm:
-        h0, c0 = (None, None) if h0 is None else h0
         _, grad_x, _, _ = lstm_backward(x_seq, h_seq, h0, c0, w.detach(), grad_h, need_x_grad=bool(fuse), out=w.grad,
                                         accumulate=had, cache=cache, module=rc)
     else:
@@ -221,9 +277,13 @@ def recurrence_step(model, x, cb, in_state, y_gaze, criterion=None, decoder=Fals
                                     cache=cache, module=rc)
     if fuse:
         grads, acc = _grads_of(blk)
-        fu = taps[src].contiguous(memory_format=cl)
-        grad_fu, _ = block_backward(blk, fu, grad_x, need_x_grad=bool(fust or ctx or nets or st), cache=cache, grads=grads,
-                                    accumulate=acc)
+        if block_stats:
+            grad_fu, _ = block_backward_batch(blk, fu, grad_x, saved=blk_saved, need_x_grad=bool(fust or ctx or nets or st),
+                                              cache=cache, grads=grads, accumulate=acc)
+        else:
+            fu = taps[src].contiguous(memory_format=cl)
+            grad_fu, _ = block_backward(blk, fu, grad_x, need_x_grad=bool(fust or ctx or nets or st), cache=cache, grads=grads,
+                                        accumulate=acc)
         g_cb, g_st = None, grad_fu                                   # (without priors the fuse stage IS fust_layer[0])
         if ctx:
             pg = {n: _grads_of(b) for n, b in prior_path_blocks(model).items()}

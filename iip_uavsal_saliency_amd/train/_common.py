@@ -29,30 +29,39 @@ def _nhwc(t, name, c=None):
     return v.contiguous()
 
 
-def _conv(lib, cache, x, conv, cout, taps, wslice=None, transposed=False, bn=None, act=L.ACT_NONE, res=None, tscale=None):
+def _conv(lib, cache, x, conv, cout, taps, wslice=None, transposed=False, bn=None, act=L.ACT_NONE, res=None, tscale=None,
+          epi=L.EPI_AFFINE, aux=None, out=None, out2=None, gate_interleave=0):
     """One `uavsal_conv_gemm` launch on the current stream (no synchronisation): `x` NHWC, the weights of `conv` (or of its
     transposed conv; `tscale`: with the folded scale of that BatchNorm in its rows) from `cache` in the layout the route of
-    this launch takes."""
+    this launch takes.  `epi` with `aux` (and `out2`): a step of the recurrence as the launch's epilogue (`UAVSAL_EPI_TWA`:
+    `res` = x_t, `aux` = the hoisted W_x half; `UAVSAL_EPI_LSTM`: `res` = c_{t-1}, `out2` = c_t, the weights' gate rows
+    interleaved, `gate_interleave` = the hidden size); `out`: a dense NHWC tensor to write instead of a new one."""
     ap, lda, n, h, w, cin = _nhwc_view(x)
-    out = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.device)
     d = L.ConvDesc()
     d.a, d.lda, d.a_img_stride = ap, lda, h * w
-    d.out, d.ldc, d.o_img_stride = out.data_ptr(), cout, h * w
+    d.out, d.ldc, d.o_img_stride = out.data_ptr(), out.shape[3], h * w
     if bn is not None:
         s, b = cache.affine(bn, cout)
         d.scale, d.bias = s.data_ptr(), b.data_ptr()
     if res is not None:
         rp, ldr, *_ = _nhwc_view(res)
         d.res, d.ldr, d.r_img_stride = rp, ldr, h * w
+    if aux is not None:
+        xp, ldx, *_ = _nhwc_view(aux)
+        d.aux, d.ldx, d.x_img_stride = xp, ldx, h * w
+    if out2 is not None:
+        d.out2, d.ld2 = out2.data_ptr(), out2.shape[3]
     d.n_img, d.H, d.W, d.Cin, d.Cout, d.taps = n, h, w, cin, cout, taps
-    d.prec, d.act, d.epi, d.tile = L.PREC["f32"], act, L.EPI_AFFINE, 0
+    d.prec, d.act, d.epi, d.tile = L.PREC["f32"], act, epi, 0
     d.w = 1 << 20
     rt = L.conv_route(lib, d)
     layout = P.conv_weight_layout("f32", False, False, rt.tile, 3 if taps == 9 else 1)
     if tscale is not None:
         wp = cache.conv_t_scaled(conv, tscale, layout)
     else:
-        wp = cache.conv_t(conv, wslice, layout) if transposed else cache.conv(conv, wslice, 0, layout)
+        wp = cache.conv_t(conv, wslice, layout) if transposed else cache.conv(conv, wslice, gate_interleave, layout)
     d.w = wp.data_ptr()
     L.check(lib.uavsal_conv_gemm(C.byref(d), _stream(x)), "uavsal_conv_gemm")
     return out

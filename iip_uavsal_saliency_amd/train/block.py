@@ -33,14 +33,22 @@ _PARTS_RULES = {
                            + _BLOCK_SHAPE, None)),
     "block_backward": ("block_backward", (1,), False, (64, 64, 128), False,
                        ("a dwBlock with an expand conv, stride 1 and dilation 1 " + _BLOCK_SHAPE, None)),
+    "block_batch": ("block_forward_batch / block_backward_batch", (1,), False, (64, 64, 128), False,
+                    ("a dwBlock with an expand conv, stride 1 and dilation 1 " + _BLOCK_SHAPE, None)),
     "backbone": ("the backbone backward", (1, 2), False, (32, 64, 32), True, _FEATURES_SHAPE),
     "shallow": ("the shallow backward", (1, 2), False, (8, 16, 8), True, _FEATURES_SHAPE),
 }
 
 
+_BATCH_REFUSAL = ("block_forward_batch / block_backward_batch run the block's BatchNorms on BATCH statistics: call block.train() "
+                  "(its container's .train() under model.eval()); a block in eval mode goes through the eval-mode functions "
+                  "block_backward / block_input_grad")
+
+
 def _checked_parts(block, kind):
     """`(pw, pwbn, dwc, dwbn, pl, plbn)` of an inverted-residual `block` that the row `kind` of `_PARTS_RULES` takes, or a
-    RuntimeError.  The special cases of `block_param_grads` are its row's alone (`own`)."""
+    RuntimeError.  The special cases of `block_param_grads` are its row's alone (`own`).  The row "block_batch" (block_bn.py)
+    takes the shapes of "block_backward" in TRAINING mode, with affine BatchNorms that track their statistics."""
     noun, strides, dilated, (mod_in, mod_hid, mod_out), named, (what, what_strides) = _PARTS_RULES[kind]
     own = kind == "block_param_grads"
     seq = getattr(block, "conv", None)
@@ -67,7 +75,13 @@ def _checked_parts(block, kind):
                               cin, hid, cout))
     if own and stride == 2 and block.use_res_connect:
         raise RuntimeError("block_param_grads: a block with stride 2 has no residual")
-    if block.training:
+    if kind == "block_batch":
+        bns = (pwbn, dwbn, plbn)
+        if not block.training or not all(b.training for b in bns):
+            raise RuntimeError(_BATCH_REFUSAL)
+        if not all(b.track_running_stats and b.affine and b.running_mean is not None for b in bns):
+            raise RuntimeError("%s needs affine BatchNorms that track their running statistics" % noun)
+    elif block.training:
         raise RuntimeError("the block's BatchNorms use their running statistics: call model.eval()")
     return pw, pwbn, dwc, dwbn, pl, plbn
 

@@ -2,9 +2,9 @@
 kernels of csrc/train_bn.hip (`uavsal_bn_stats`, `uavsal_bn_apply`, `uavsal_bn_bwd_sums`, `uavsal_bn_bwd_apply`,
 `uavsal_dw_wgrad`; include/uavsal_hip.h states the formulas and the order of every sum).  Teacher-forced on given tensors,
 as `st.cbr_sums` is; `decoder.decoder_forward_batch` / `decoder_backward_batch` compose them into the decoder's training-mode
-forward and backward, and the later stages can be composed from them the same way.  `u` is an NHWC view `[n,h,w,C]` (a channel
-slice is read in place), `C % 4 == 0` or `C == 1`; the statistics run over all `n*h*w` pixels of the call.  Every call runs
-on the current stream without synchronisation; two calls return the same bits."""
+forward and backward, and block_bn.py an inverted-residual block's (`uavsal_bn_apply_res`: `bn_apply(res=)`).  `u` is an NHWC
+view `[n,h,w,C]` (a channel slice is read in place), `C % 4 == 0` or `C == 1`; the statistics run over all `n*h*w` pixels of
+the call.  Every call runs on the current stream without synchronisation; two calls return the same bits."""
 import ctypes as C
 from typing import NamedTuple
 
@@ -90,12 +90,28 @@ def bn_stats(u, weight, bias, eps, running_mean=None, running_var=None, momentum
     return BnFold(*out.unbind(0))
 
 
-def bn_apply(u, fold, act=None, dot_w=None):
+def bn_apply(u, fold, act=None, dot_w=None, res=None):
     """`uavsal_bn_apply`: `act(s u + b)` as a dense NHWC tensor `[n,h,w,C]`; with `dot_w` `[C]` the dot of that tensor with
-    `dot_w` over the channels instead, dense `[n,h,w,1]` (the activated tensor is not stored).  One launch."""
+    `dot_w` over the channels instead, dense `[n,h,w,1]` (the activated tensor is not stored).  `res` (an NHWC view like `u`,
+    `C % 4 == 0`; not with `dot_w`): `uavsal_bn_apply_res`, `act(s u + b) + res`, the sum rounded once more -- the residual
+    of an inverted-residual block behind its last BatchNorm.  One launch."""
     lib = L.load()
     up, ld, n, hh, ww, c = _view(u, "u")
     dev = u.device
+    if res is not None:
+        if dot_w is not None:
+            raise RuntimeError("bn_apply: res and dot_w do not combine")
+        rp, ldr, *rs = _view(res, "res")
+        if rs != [n, hh, ww, c] or res.device != dev:
+            raise RuntimeError("res must be [%d,%d,%d,%d] on the device of u" % (n, hh, ww, c))
+        q = L.BnApplyResDesc()
+        q.u, q.ld, q.s, q.b = up, ld, _vec(fold.s, "fold.s", c, dev), _vec(fold.b, "fold.b", c, dev)
+        q.res, q.ldr = rp, ldr
+        out = torch.empty((n, hh, ww, c), dtype=torch.float32, device=dev)
+        q.out, q.n_pix, q.C, q.act = out.data_ptr(), n * hh * ww, c, _act(act)
+        with torch.cuda.device(dev):
+            L.check(lib.uavsal_bn_apply_res(C.byref(q), _stream(u)), "uavsal_bn_apply_res")
+        return out
     k = L.BnApplyDesc()
     k.u, k.ld, k.s, k.b = up, ld, _vec(fold.s, "fold.s", c, dev), _vec(fold.b, "fold.b", c, dev)
     if dot_w is not None:

@@ -248,3 +248,75 @@ def lstm_backward(x_seq, h_seq, h0, c0, weight, grad_h, need_x_grad=False, out=N
         if parts is not None:
             parts.update(cc=cc, c_seq=cs, dcc=dcc)
     return gw, (dx.permute(0, 3, 1, 2) if need_x_grad else None), carry.permute(0, 3, 1, 2), cbuf.permute(0, 3, 1, 2)
+
+
+# ---------------------------------------------------------------------------------------------- the forward from a given input
+def _state(s, name, hh, ww, dev):
+    """A carried state `[1,256,h,w]` as a dense NHWC tensor; None: zeros."""
+    if s is None:
+        return torch.zeros((1, hh, ww, HID), dtype=torch.float32, device=dev)
+    s = _nhwc(s, name, HID).contiguous()
+    if tuple(s.shape) != (1, hh, ww, HID) or s.device != dev:
+        raise RuntimeError("%s must be [1,256,%d,%d] on the device of x_seq" % (name, hh, ww))
+    return s
+
+
+def _forward_args(x_seq, weight, rows, what):
+    x = _nhwc(x_seq, "x_seq", HID)
+    if (not torch.is_tensor(weight) or tuple(weight.shape) != (rows, 2 * HID, 3, 3) or weight.dtype != torch.float32
+            or weight.device != x.device):
+        raise RuntimeError("weight must be the float32 [%d,512,3,3] %s weight on the device" % (rows, what))
+    return x
+
+
+def twa_forward(x_seq, h0, weight, cache=None, module=None):
+    """The ConvTWA recurrence forward from a GIVEN input sequence, outside the launch plan: `x_seq` `[T,256,h,w]`, `h0`
+    `[1,256,h,w]` (None = zeros), `weight` `[256,512,3,3]` -> `h_seq` `[T,256,h,w]` (channels-last),
+    `h_t = i_t x_t + (1 - i_t) h_{t-1}`, `i_t = sigmoid(conv3x3(W, cat[x_t, h_{t-1}]))`.  What a stage in FRONT of the
+    recurrence needs once its output is no longer the plan's (`recurrence_step(block_stats=...)`).  No new kernel: one batched
+    3x3 `uavsal_conv_gemm` of all frames with the W_x half (the hoisted `aux`), then per step one `uavsal_conv_gemm` of
+    `h_{t-1}` with the W_h half whose epilogue is the step (`UAVSAL_EPI_TWA`), written straight into `h_seq[t]`.  Both go the
+    DIRECT implicit-GEMM route, the tile `uavsal_conv_route` gives each launch -- never a Winograd route, whatever the launch
+    plan takes for its steps -- so the result is within rounding of the plan's `rnn` tap and need not be its bits.  `cache` + `module`: take
+    the packed forms from a `WeightCache` under the id of `module` (the conv that owns `weight`), the entries the plan's
+    direct route uses; default: packed on the host for this call.  No synchronisation; two calls return the same bits."""
+    lib = L.load()
+    x = _forward_args(x_seq, weight, HID, "ConvTWA")
+    T, hh, ww, _ = x.shape
+    dev = x.device
+    with torch.cuda.device(dev):
+        hprev = _state(h0, "h0", hh, ww, dev)
+        if cache is None or module is None:
+            cache, module = WeightCache(dev, {}), types.SimpleNamespace(weight=weight)
+        aux = _conv(lib, cache, x, module, HID, 9, wslice=(0, HID))      # W_x * x_t of all frames: the steps' `aux`
+        h_seq = torch.empty((T, hh, ww, HID), dtype=torch.float32, device=dev)
+        for t in range(T):
+            _conv(lib, cache, hprev, module, HID, 9, wslice=(HID, 2 * HID), epi=L.EPI_TWA, res=x[t:t + 1], aux=aux[t:t + 1],
+                  out=h_seq[t:t + 1])
+            hprev = h_seq[t:t + 1]
+    return h_seq.permute(0, 3, 1, 2)
+
+
+def lstm_forward(x_seq, h0, c0, weight, cache=None, module=None):
+    """`twa_forward` for the ConvLSTM of `UAVSAL_LSTM` (model_convlstm.py:111-126, no bias): `h0`, `c0` `[1,256,h,w]` (None =
+    zeros), `weight` `[1024,512,3,3]` (rows gate * 256 + c, gates i, f, o, g) -> `(h_seq [T,256,h,w], c_last [1,256,h,w])`,
+    `c_t = f c_{t-1} + i g`, `h_t = o tanh(c_t)`.  The hoisted W_x conv writes the gate-interleaved pre-activations (column
+    4 c + gate, `WeightCache.conv(gate_interleave=256)`), and each step is one `uavsal_conv_gemm` 256 -> 1024 of `h_{t-1}` with
+    the `UAVSAL_EPI_LSTM` epilogue, which writes `h_t` into `h_seq[t]` and `c_t` into one of two cell-state maps that take turns.  The direct route, as the plan's
+    own ConvLSTM steps."""
+    lib = L.load()
+    x = _forward_args(x_seq, weight, 4 * HID, "ConvLSTM")
+    T, hh, ww, _ = x.shape
+    dev = x.device
+    with torch.cuda.device(dev):
+        hprev, cprev = _state(h0, "h0", hh, ww, dev), _state(c0, "c0", hh, ww, dev)
+        if cache is None or module is None:
+            cache, module = WeightCache(dev, {}), types.SimpleNamespace(weight=weight)
+        aux = _conv(lib, cache, x, module, 4 * HID, 9, wslice=(0, HID), gate_interleave=HID)
+        h_seq = torch.empty((T, hh, ww, HID), dtype=torch.float32, device=dev)
+        cs = (torch.empty_like(cprev), torch.empty_like(cprev))      # c_t and c_{t-1} take turns in two maps, whatever T (c0 is only read)
+        for t in range(T):
+            _conv(lib, cache, hprev, module, 4 * HID, 9, wslice=(HID, 2 * HID), epi=L.EPI_LSTM, res=cprev, aux=aux[t:t + 1],
+                  out=h_seq[t:t + 1], out2=cs[t % 2], gate_interleave=HID)
+            hprev, cprev = h_seq[t:t + 1], cs[t % 2]
+    return h_seq.permute(0, 3, 1, 2), cprev.permute(0, 3, 1, 2)

@@ -1374,6 +1374,22 @@ int64_t uavsal_dw_wgrad_workspace_bytes(const uavsal_dw_wgrad_desc* d);
 int uavsal_dw_wgrad(const uavsal_dw_wgrad_desc* d, uavsal_stream_t stream);
 int uavsal_bn_sizeof_desc(int which);         /* 0 bn_stats, 1 bn_apply, 2 bn_bwd, 3 dw_wgrad (additions: UAVSAL_ABI_VERSION stays 20) */
 
+/* uavsal_bn_apply_res (csrc/train_bn.hip): out[p][c] = fl(act(fma(u, s, b)) + res[p][c]), dense [n_pix][C] -- the last
+ * BatchNorm of an inverted-residual block in training mode with the block's residual (train.block_forward_batch): the
+ * pre-activation is uavsal_bn_apply's one fused multiply-add, the sum one more rounding.  `res` is an NHWC view with its own
+ * pitch ldr >= C (a channel slice is read in place).  C % 4 == 0: a lane owns four channels of a pixel, 16-byte accesses, the
+ * item order of uavsal_bn_apply.  ONE launch; element-wise, so two calls return the same bits.  Errors as uavsal_bn_apply. */
+typedef struct uavsal_bn_apply_res_desc {
+    const float* u;  int32_t ld;
+    const float* s;  const float* b;                /* [C] */
+    const float* res;  int32_t ldr;                 /* [n_pix] rows of C floats, ldr apart */
+    float* out;                                     /* dense [n_pix][C] */
+    int64_t n_pix;  int32_t C, act;
+} uavsal_bn_apply_res_desc;
+
+int uavsal_bn_apply_res(const uavsal_bn_apply_res_desc* d, uavsal_stream_t stream);
+int uavsal_block_bn_sizeof_desc(int which);   /* 0 bn_apply_res; uavsal_bn_sizeof_desc's list stays closed (UAVSAL_ABI_VERSION stays 20) */
+
 /* ---- repacking refreshed weights on the device (csrc/repack.hip) ---------------------------------------------------------
  * After an optimiser step the packed copies of a module's weights are remade FROM the fp32 parameters and buffers where they
  * lie INTO the packed device tensors that exist (launch plans hold their addresses): the bytes packing.py / weights.py make

@@ -73,6 +73,8 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
                Alone: --shallow-only;
   lstm         the second model, `UAVSAL_LSTM`, trained through `recurrence_step(lstm=True)`: `lstm_phases`' docstring.
                Only with --lstm-only (a second model is built for it);
+  fuse_bn      the fusion block on batch statistics, `recurrence_step(block_stats=("fuse",))`: `fuse_bn_phases`' docstring.
+               Only with --fuse-bn-only (medians with every window listed);
   refresh pairs beside every refresh case above its `_device` twin: the same in-place edit, then `refresh_weights(...,
                device=True)` (csrc/repack.hip: one launch, no host copy); and at the end (or alone: --refresh-only) the
                host and device refresh of 1, 4, 5 and 6 stages (refreshN_alt / refreshN_device_alt) and one whole six-stage
@@ -84,7 +86,7 @@ At 360x640 frames (45x80 maps), one sequence of T = 20 (the reference's batch_si
 Each is a host clock around `--iters` back-to-back calls ending in a synchronise, best of `--repeats`.
 
 Usage:  python tools/train_bench.py [--iters 10] [--repeats 3] [--skip-eager] [--refresh-only] [--st-only] [--srf-only] [--backbone-only]
-        [--shallow-only] [--lstm-only] [--frames 20 5]
+        [--shallow-only] [--lstm-only] [--decoder-bn-only] [--fuse-bn-only] [--frames 20 5]
 """
 import argparse
 import ctypes as C
@@ -1016,6 +1018,115 @@ def decoder_bn_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
         q.grad = None
 
 
+def _median(v):
+    v = sorted(v)
+    return 0.5 * (v[(len(v) - 1) // 2] + v[len(v) // 2])
+
+
+def fuse_bn_phases(res, m, x, cb, y_gaze, cache, iters, repeats):
+    """the phases of the fusion block on BATCH statistics (train.block_forward_batch / block_backward_batch, train.twa_forward;
+    csrc/train_bn.hip: uavsal_bn_apply_res), added to `res`.  Every figure is the MEDIAN of `--repeats` windows of `--iters`
+    back-to-back calls ending in a synchronise, with every window listed (`_all_ms`: the spread): the two block functions and
+    `twa_forward` alone on the plan's own taps (`lstm_forward`: a second model, `lstm_forward_ms`); `uavsal_bn_apply_res` alone at
+    256 channels beside `uavsal_bn_apply` (`*_of_8TBs`: the bytes the launch must move over its time as a fraction of 8 TB/s);
+    the eval-mode `block_backward` beside them; and, alternated in the same run, one iteration -- the three-stage step
+    ("rnn", "decoder", "fuse") followed by the device refresh of the three stages, as a training loop follows it (a step on
+    batch statistics moves the running statistics, so a forward WITHOUT the refresh behind it drops and rebuilds the plans) --
+    without a keyword (`iter_fuse`), with `block_stats=("fuse",)` (`iter_fuse_block`) and with `batch_stats=("decoder",)` as well
+    (`iter_fuse_both`), the step without the keywords alone (`step_fuse3_ms`, timed before any batch step ran), and the peak
+    memory of each iteration."""
+    from iip_uavsal_saliency_amd.train import bn as B
+    dev = x.device
+    cl = torch.channels_last
+    blk, src = train.fuse_block(m)
+    box = train.fuse_container(m)
+    dec, rc = m.conv_out_st, m.rnn.cell_list[0].rnn_conv
+    taps = {src: None}
+    m(x, cb, None, taps=taps)
+    fu = taps[src].contiguous(memory_format=cl)
+    x_seq = taps["prefuse"].contiguous(memory_format=cl)
+    T, _, hh, ww = fu.shape
+
+    def timed(key, fn):
+        per_call(fn, 2)
+        v = [1e3 * per_call(fn, iters) for _ in range(repeats)]
+        res[key + "_ms"], res[key + "_all_ms"] = _median(v), v
+    box.train()
+    out, sv = train.block_forward_batch(blk, fu, update_running=False, cache=cache)
+    go = torch.randn_like(out) / (hh * ww)
+    grads = train.block_backward_batch(blk, fu, go, saved=sv, cache=cache)[1]
+    timed("block_forward_batch", lambda: train.block_forward_batch(blk, fu, update_running=False, cache=cache))
+    timed("block_forward_batch_running", lambda: train.block_forward_batch(blk, fu, cache=cache))
+    timed("block_backward_batch", lambda: train.block_backward_batch(blk, fu, go, saved=sv, grads=grads, cache=cache))
+    f3, u3 = sv["f3"], sv["u3"]
+    resid = x_seq.permute(0, 2, 3, 1)
+    small = 256.0 * 4 * T * hh * ww                              # bytes of one 256-channel tensor
+    timed("bn_apply_res256", lambda: B.bn_apply(u3, f3, None, res=resid))
+    timed("bn_apply256", lambda: B.bn_apply(u3, f3, None))
+    res["bn_apply_res256_of_8TBs"] = 3 * small / (res["bn_apply_res256_ms"] * 1e-3) / 8e12
+    res["bn_apply256_of_8TBs"] = 2 * small / (res["bn_apply256_ms"] * 1e-3) / 8e12
+    del sv, f3, u3
+    box.eval()
+    timed("block_backward_eval", lambda: train.block_backward(blk, fu, go, cache=cache, grads=grads))
+    timed("twa_forward", lambda: train.twa_forward(x_seq, None, rc.weight.detach(), cache=cache, module=rc))
+    mine = train.twa_forward(x_seq, None, rc.weight.detach(), cache=cache, module=rc)
+    res["twa_forward_vs_plan_max_abs"] = float((mine - taps["rnn"]).abs().max())
+    res["twa_forward_vs_plan_rel_l2"] = float((mine - taps["rnn"]).norm() / taps["rnn"].norm())
+    del mine
+    trained = list(m.rnn.parameters()) + list(dec.parameters()) + list(box.parameters())
+
+    def stepper(block, batch, refresh=True):
+        kw = dict(decoder=True, fuse=True)
+        if block:
+            kw["block_stats"] = ("fuse",)
+        if batch:
+            kw["batch_stats"] = ("decoder",)
+
+        def run():
+            for q in trained:
+                q.grad = None
+            box.train(block)
+            dec.train(batch)
+            train.recurrence_step(m, x, cb, None, y_gaze, **kw)
+            box.eval()
+            dec.eval()
+            if refresh:
+                m.refresh_weights(m.rnn, dec, box, device=True)
+        return run
+    timed("step_fuse3", stepper(False, False, refresh=False))
+    runs = {"iter_fuse": stepper(False, False), "iter_fuse_block": stepper(True, False), "iter_fuse_both": stepper(True, True)}
+    for fn in runs.values():
+        per_call(fn, 2)
+    alt = {k: [] for k in runs}                               # alternated in the same run, every run listed
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            alt[k].append(1e3 * per_call(fn, iters))
+    for k, v in alt.items():
+        res[k + "_ms"], res[k + "_all_ms"] = _median(v), v
+    for k, fn in runs.items():
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        fn()
+        torch.cuda.synchronize()
+        res[k + "_peak_MB"] = torch.cuda.max_memory_allocated(dev) / 1e6
+    timed("refresh_fuse3_device", lambda: m.refresh_weights(m.rnn, dec, box, device=True))
+    for q in trained:
+        q.grad = None
+    # the ConvLSTM forward: the second model, its own plan's prefuse tap
+    ml = UAVSAL_LSTM(time_dims=m.time_dims)
+    synth.load_synth_weights(ml, 0)
+    ml = ml.to(dev).eval()
+    tl = {}
+    ml(x, cb, None, taps=tl)
+    xl = tl["prefuse"].contiguous(memory_format=cl)
+    rl = ml.rnn.cell_list[0].rnn_conv
+    lcache = WeightCache(torch.device(dev), ml._wshared.setdefault(str(torch.device(dev)), {}))
+    timed("lstm_forward", lambda: train.lstm_forward(xl, None, None, rl.weight.detach(), cache=lcache, module=rl))
+    hl = train.lstm_forward(xl, None, None, rl.weight.detach(), cache=lcache, module=rl)[0]
+    res["lstm_forward_vs_plan_max_abs"] = float((hl - tl["rnn"]).abs().max())
+    res["lstm_forward_vs_plan_rel_l2"] = float((hl - tl["rnn"]).norm() / tl["rnn"].norm())
+
+
 def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
     """host and device refresh of 1, 4, 5 and 6 stages and one whole six-stage iteration with either, added to `res`"""
     from iip_uavsal_saliency_amd import repack
@@ -1073,7 +1184,7 @@ def refresh_phases(res, m, x, cb, y_gaze, iters, repeats):
 
 
 def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False, srf_only=False, backbone_only=False,
-          shallow_only=False, lstm_only=False, decoder_bn_only=False):
+          shallow_only=False, lstm_only=False, decoder_bn_only=False, fuse_bn_only=False):
     H, W, h, w = 360, 640, 45, 80
     m = UAVSal(time_dims=5 if T % 5 == 0 else 4)            # (--frames 8: two chunks of four)
     synth.load_synth_weights(m, 0)
@@ -1116,6 +1227,10 @@ def bench(T, iters, repeats, dev, skip_eager, refresh_only=False, st_only=False,
     if decoder_bn_only:
         res = {"T": T}
         decoder_bn_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
+        return res
+    if fuse_bn_only:
+        res = {"T": T}
+        fuse_bn_phases(res, m, x, cb, y_gaze, cache, iters, repeats)
         return res
     cl = torch.channels_last
     x_seq, h_seq = taps["prefuse"].contiguous(memory_format=cl), taps["rnn"].contiguous(memory_format=cl)
@@ -1243,12 +1358,14 @@ def main():
     ap.add_argument("--lstm-only", action="store_true", help="only the phases of the ConvLSTM backward (lstm_phases)")
     ap.add_argument("--decoder-bn-only", action="store_true",
                     help="only the phases of the decoder on batch statistics (decoder_bn_phases)")
+    ap.add_argument("--fuse-bn-only", action="store_true",
+                    help="only the phases of the fusion block on batch statistics (fuse_bn_phases)")
     ap.add_argument("--frames", type=int, nargs="+", default=[20, 5], help="sequence lengths to run (multiples of 5, or of 4)")
     a = ap.parse_args()
     dev = "cuda:0"
     out = {"device": torch.cuda.get_device_name(0), "map": [45, 80],
            "cases": [bench(T, a.iters, a.repeats, dev, a.skip_eager, a.refresh_only, a.st_only, a.srf_only, a.backbone_only, a.shallow_only,
-                           a.lstm_only, a.decoder_bn_only)
+                           a.lstm_only, a.decoder_bn_only, a.fuse_bn_only)
                      for T in a.frames]}
     print(json.dumps(out))
 
